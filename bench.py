@@ -18,14 +18,20 @@ Workloads (BASELINE.json configs; the names C1..C5 are SURVEY.md section 8's):
       With --gpus N > 1 the sequences are split over the ranks (parallel.ShardedCovs; 3 ms of work: a functional path, not a
       scaling benchmark).
   c5  configs[4]: N=2048, L=128, d=16, num_levels=6, fp32, SignatureRBF, full Gram.
-One step = one complete evaluation with the inputs already resident in HBM and the result left in HBM.  Prints ONE JSON line
-on rank 0: the driver's contract fields + `roofline` (what binds the dominant kernel -- `bound`, `issue_frac`, `alu_frac` --, the
+One step = one complete evaluation with the inputs already resident in HBM and the result left in HBM; --steps is the number
+of timed steps and `ms_per_step` the wall time of one.  Rank 0 prints ONE strict-JSON line under 2 KB, the headline of the
+full record, so that a reader keeping only the end of the output can parse it.  --record FILE writes the full record: the
+driver's contract fields + `roofline` (what binds the dominant kernel -- `bound`, `issue_frac`, `alu_frac` --, the
 pair-stream fraction of SURVEY 8(d) as `stream_frac`, the kernel's HIP-event time on the library's stream, the HBM traffic
 measured by two rocprofv3 --pmc passes of this very command), `clock_ghz` (the shader clock during the timed region, sampled
 on the device), `cpu_baseline` (the oracle's op-for-op restatement of the reference's TF graph on the host cores, bounded
 sample), `rel_err` (a sub-sample of the timed output against the oracle, outside the timed region),
 `end_to_end_ms_host_pointers` (the same evaluation from and to host memory: H2D + compute + D2H) and, on the default
-single-GPU line, `secondary`: the other single-GPU configurations (c2 through the pair recursion, c2 at order 5, c2 RBF, c3, c3 with increments, c3 with SignatureLinear, c5), 3 warm-up + 10 steps each.
+single-GPU line, `secondary`: the other single-GPU configurations (c2 through the pair recursion, c2 at order 5, c2 RBF, c3, c3 with increments, c3 with SignatureLinear, c5), 3 warm-up + 10 steps each
+(measured only when --record asks for the record).
+--dump-outputs DIR writes what the last timed step computed (K; or Kzz, Kzx, Kxx_diag for c3) as DIR/<name>.npy in the
+workload's float type, below 64 MB in all: an array above its share is a seeded sample of its rows, <name>_rows.npy the
+row indices.  The inputs are seeded, so two builds run with the same arguments can be compared array for array.
 
 --gpus N > 1 without a torchrun environment launches the N ranks itself (python -m torch.distributed.run, one process per
 GPU, rendezvous on 127.0.0.1) and fails when the node has fewer than N GPUs: a line with "n_gpus": N was computed by N ranks,
@@ -227,6 +233,61 @@ def cpu_baseline(cfg, base, increments, budget_s=10.0, numpy_leg=True):
     return res
 
 
+DUMP_BYTES = 48 << 20            # --dump-outputs: all arrays together stay below 64 MB
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """--dump-outputs: writes {name: tensor} as dirname/<name>.npy in the tensor's own float type, DUMP_BYTES in all.  The arrays
+    are taken smallest first, each up to an equal share of what the ones before it left; an array larger than its share is
+    written as a fixed, seeded sample of its rows (first axis, ascending), the row indices beside it as <name>_rows.npy
+    (float64), so that two builds given the same arguments can be compared entry for entry."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BYTES
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].numel() * kv[1].element_size())
+    for i, (name, a) in enumerate(todo):
+        a = a.detach()
+        if a.dtype not in (torch.float32, torch.float64):
+            raise TypeError("%s: %s is not float32 / float64" % (name, a.dtype))
+        share = left // (len(todo) - i)
+        if a.numel() * a.element_size() > share:
+            row = a[0].numel() * a.element_size()
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], share // (row + 8), replace=False))
+            a = a[torch.as_tensor(rows, device=a.device)]
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+            left -= rows.size * 8
+        np.save(os.path.join(dirname, name + ".npy"), a.cpu().numpy())
+        left -= a.numel() * a.element_size()
+
+
+def strict(obj):
+    """obj with every non-finite float replaced by None: the printed line is strict JSON."""
+    if isinstance(obj, float):
+        return obj if math.isfinite(obj) else None
+    if isinstance(obj, dict):
+        return {k: strict(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return [strict(v) for v in obj]
+    return obj
+
+
+def result_line(res):
+    """The one line bench.py prints: the headline of the full record (--record), short enough to survive a reader that keeps
+    only the last two kilobytes of the output."""
+    rf = res["roofline"]
+    line = {k: res.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                    "vs_baseline", "dtype", "data", "rel_err", "clock_ghz", "end_to_end_ms_host_pointers",
+                                    "verify_max_abs_diff_vs_single_rank") if k in res}
+    line["config"] = {"name": res["config"]["name"], "workload": res["config"]["workload"]}
+    line["roofline"] = {k: rf[k] for k in ("bound", "achieved", "peak", "unit", "frac", "stream_frac", "issue_frac", "alu_frac", "kernel",
+                                           "kernel_ms_per_launch", "launches_per_step")}
+    if res.get("cpu_baseline"):
+        line["cpu_baseline"] = {k: res["cpu_baseline"].get(k) for k in ("value", "unit", "cores", "kind", "implementation")}
+    if res.get("ranks_seen"):
+        line["ranks_seen"] = {k: res["ranks_seen"][k] for k in ("world_size", "backend", "launched_by")}
+    return line
+
+
 def rel_err(got, want):
     got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
     return float((np.abs(got - want) / (np.abs(want) + 1e-6 * np.abs(want).max())).max())
@@ -388,9 +449,9 @@ FP64_MATRIX_PEAK_TFLOPS = 78.6          # MI355X_MICROARCH.md: dense float64 MFM
 
 
 def run_workload(cfg, base, increments, steps, warmup, dev, rank=0, world=1, chunks=4, weak=False, checks=True, host_e2e=True,
-                 traffic="measure", lattice=False, order=1, issue_src="measure"):
+                 traffic="measure", lattice=False, order=1, issue_src="measure", dump_dir=None):
     """Times `steps` evaluations of one BASELINE configuration on this rank's device (inputs resident in HBM) and returns the
-    bench-line fields on rank 0 (None elsewhere)."""
+    bench-line fields on rank 0 (None elsewhere).  dump_dir: rank 0 writes the last timed step's result there (dump_outputs)."""
     import torch
     import torch.distributed as dist
     from gpsig_amd import _lib, kernels, parallel
@@ -485,6 +546,8 @@ def run_workload(cfg, base, increments, steps, warmup, dev, rank=0, world=1, chu
         if checks and n_gpus > 1:
             pass
         return None
+    if dump_dir:
+        dump_outputs(dump_dir, dict(zip(("Kzz", "Kzx", "Kxx_diag"), out)) if T else {"K": out})
 
     pairs = float(T) * N if T else float(N) * N                    # entries delivered per step
     value = pairs * steps / dt
@@ -956,7 +1019,14 @@ def main(argv=None):
     ap.add_argument("--no-traffic", action="store_true", help="do not run the two rocprofv3 --pmc passes (roofline.traffic falls back to profiles/hbm_traffic.json)")
     ap.add_argument("--timed-loop-only", action="store_true", help="warm-up + timed steps and nothing else (what the --pmc passes run)")
     ap.add_argument("--rendezvous-check", action="store_true", help="start the ranks, gather ranks_seen, print it; no evaluation (CPU-testable)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (a seeded sample of rows where it exceeds the size cap)")
+    ap.add_argument("--record", metavar="FILE", default=None,
+                    help="write the full record (roofline detail, clock, ranks and, on the default single-GPU line, the secondary "
+                         "configurations) to FILE as JSON; stdout carries its headline")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     argv = list(sys.argv[1:] if argv is None else argv)
 
     backend = os.environ.get("GPSIG_BENCH_BACKEND", "nccl")       # "gloo": functional check of the N > 1 path on a box with fewer GPUs
@@ -1031,14 +1101,18 @@ def main(argv=None):
     res = run_workload(cfg, base, args.increments, args.steps, args.warmup, dev, rank, world, chunks=args.chunks, weak=args.weak,
                        checks=not lean, host_e2e=not lean, lattice=args.lattice,
                        traffic="off" if lean else ("static" if (args.no_traffic or args.lattice) else "measure"),
-                       issue_src="off" if (lean or args.no_traffic) else "measure")
+                       issue_src="off" if (lean or args.no_traffic) else "measure", dump_dir=args.dump_outputs)
     if rank == 0:
         res["ranks_seen"] = seen
         if cpu is not None:
             res["cpu_baseline"] = cpu
-        if n_gpus == 1 and args.config is None and args.base is None and not args.increments and not args.no_secondary and not lean and not args.lattice:
-            res["secondary"] = secondary_lines(dev)
-        print(json.dumps(res))
+        if args.record:
+            if (n_gpus == 1 and args.config is None and args.base is None and not args.increments and not args.no_secondary and not lean
+                    and not args.lattice):
+                res["secondary"] = secondary_lines(dev)
+            with open(args.record, "w") as f:
+                json.dump(strict(res), f, allow_nan=False)
+        print(json.dumps(strict(result_line(res)), allow_nan=False))
     if world > 1:
         dist.destroy_process_group()
 

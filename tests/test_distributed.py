@@ -394,3 +394,48 @@ def test_bench_rank_launch_command():
     cmd = mod.rank_launch_command(8, ["--gpus", "8", "--steps", "5"])
     assert cmd[:3] == [sys.executable, "-m", "torch.distributed.run"] and "--nproc-per-node=8" in cmd and "127.0.0.1" in cmd
     assert cmd[-4:] == ["--gpus", "8", "--steps", "5"] and cmd[-5].endswith("bench.py")
+
+
+def _bench_module():
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_bench_dump_outputs_is_capped_seeded_and_exact(tmp_path):
+    """--dump-outputs: arrays within the cap are written whole, larger ones as the same seeded sample of rows every time, their
+    own float type, under 64 MB in all (c3's three covariances and c2's Gram)."""
+    import torch
+    mod = _bench_module()
+    g = torch.Generator().manual_seed(0)
+    cases = {"c3": {"Kzz": torch.randn(512, 512, dtype=torch.float64, generator=g), "Kzx": torch.randn(512, 16384, dtype=torch.float64, generator=g),
+                    "Kxx_diag": torch.randn(16384, dtype=torch.float64, generator=g)},
+             "c2": {"K": torch.randn(4096, 4096, dtype=torch.float64, generator=g)},
+             "c5": {"K": torch.randn(2048, 2048, dtype=torch.float32, generator=g)}}
+    for name, arrays in cases.items():
+        dumps = []
+        for run in range(2):
+            d = tmp_path / ("%s_%d" % (name, run))
+            mod.dump_outputs(str(d), arrays)
+            size = sum(f.stat().st_size for f in d.iterdir())
+            assert size < 64e6
+            got = {f.name[:-4]: np.load(f) for f in d.iterdir()}
+            assert (size > 32e6) == any(k.endswith("_rows") for k in got)         # a sample fills most of the cap
+            dumps.append(got)
+            for key, a in arrays.items():
+                want = a.numpy()
+                if key + "_rows" in got:
+                    rows = got[key + "_rows"]
+                    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0)
+                    want = want[rows.astype(np.int64)]
+                assert got[key].dtype == want.dtype
+                np.testing.assert_array_equal(got[key], want)
+        assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+
+
+def test_bench_takes_at_least_one_timed_step():
+    rc, line, err = _run_bench(["--steps", "0", "--no-cpu-baseline"], {})
+    assert rc != 0 and line is None and "--steps" in err

@@ -4,6 +4,7 @@ import json
 import os
 import subprocess
 import sys
+import tempfile
 import time
 
 import pytest
@@ -13,11 +14,28 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bench(args, env_extra=None, timeout=1500):
+    """The full record bench.py writes with --record, after checking the one line it prints: the last line of stdout, strict JSON,
+    under 2 KB, the record's headline."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(env_extra or {})
-    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, capture_output=True, text=True, timeout=timeout)
-    assert pr.returncode == 0, pr.stderr[-3000:]
-    return json.loads([ln for ln in pr.stdout.splitlines() if ln.startswith("{")][-1])
+    with tempfile.TemporaryDirectory() as tmp:
+        rec = os.path.join(tmp, "record.json")
+        pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--record", rec], env=env, capture_output=True, text=True,
+                            timeout=timeout)
+        assert pr.returncode == 0, pr.stderr[-3000:]
+        with open(rec) as f:
+            record = json.load(f, parse_constant=_no_constant)
+    out = pr.stdout.splitlines()
+    assert [ln for ln in out if ln.startswith("{")] == out[-1:] and len(out[-1]) < 2048, pr.stdout[-3000:]
+    line = json.loads(out[-1], parse_constant=_no_constant)
+    for k in ("value", "ms_per_step", "steps", "warmup", "n_gpus", "rel_err"):
+        assert line[k] == record[k], k
+    assert line["roofline"]["bound"] == record["roofline"]["bound"]
+    return record
+
+
+def _no_constant(name):
+    raise ValueError("not strict JSON: " + name)
 
 
 def test_two_ranks_started_by_bench_itself():
@@ -34,6 +52,39 @@ def test_two_ranks_started_by_bench_itself():
     pr = line["per_rank"]
     assert [t["rank"] for t in pr["ranks"]] == [0, 1] and all(t["compute_ms"] > 0 and t["chunks"] == 4 for t in pr["ranks"])
     assert pr["compute_max_over_min"] >= 1.0 and pr["symmetrise_ms_rank0"] > 0 and pr["ranks"][1]["symmetrise_ms"] == 0.0
+
+
+@pytest.mark.parametrize("cfg", ["c2", "c3"])
+def test_dump_outputs_is_the_timed_result(cfg):
+    """--dump-outputs DIR after --steps 3: the line counts three timed steps, and DIR holds the last step's arrays (c2's Gram as a seeded
+    sample of its rows; c3's Kzz, Kzx sampled, Kxx-diag) under 64 MB, equal to the library's evaluation of the same seeded inputs."""
+    import importlib.util
+    import numpy as np
+    import torch
+    from gpsig_amd import kernels
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    with tempfile.TemporaryDirectory() as tmp:
+        line = _bench(["--config", cfg, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-traffic", "--dump-outputs", tmp])
+        assert sum(os.path.getsize(os.path.join(tmp, f)) for f in os.listdir(tmp)) < 64e6
+        got = {f[:-4]: np.load(os.path.join(tmp, f)) for f in os.listdir(tmp)}
+    assert line["steps"] == 3 and line["warmup"] == 1
+    w = bench.WORKLOADS[cfg]
+    dev = torch.device("cuda:0")
+    X = torch.as_tensor(bench.make_inputs(w), device=dev)
+    kern = (kernels.SignatureLinear if w["base"] == "linear" else kernels.SignatureRBF)(w["L"] * w["d"], w["d"], w["M"], lengthscales=bench.lengthscales(w))
+    if w["T"]:
+        Z = torch.as_tensor(bench.make_tensors(w, False), device=dev)
+        want = dict(zip(("Kzz", "Kzx", "Kxx_diag"), (a.cpu().numpy() for a in kern.K_tens_n_seq_covs(Z, X))))
+    else:
+        want = {"K": kern.K(X).cpu().numpy()}
+    assert sorted(got) == sorted(list(want) + [k + "_rows" for k in want if want[k].nbytes > 32e6])
+    for k, a in want.items():
+        if k + "_rows" in got:
+            a = a[got[k + "_rows"].astype(np.int64)]
+        assert got[k].dtype == np.float64 and got[k].shape == a.shape
+        assert np.abs(got[k] - a).max() <= 1e-12 * np.abs(a).max(), k
 
 
 def test_clock_probe_reads_a_plausible_shader_clock():
