@@ -87,6 +87,8 @@ _KERNEL_FUNCS = {
 }
 _PLAIN = {
     "gpsig_abi_version": ([], C.c_int),
+    "gpsig_spectral_cross": ([_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp], C.c_int),
+    "gpsig_spectral_cross_grad": ([_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "gpsig_lr_state_destroy": ([_vp], None),
     "gpsig_lr_state_sizes": ([_vp, _vp, C.POINTER(_i32), C.POINTER(_i32)], C.c_int),
     "gpsig_lr_state_export": ([_vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),

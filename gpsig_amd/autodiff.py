@@ -800,6 +800,42 @@ class _LrSeqFeatures(torch.autograd.Function):
         return gX.to(ctx.dt[0]), gS.to(ctx.dt[1]), gWh.to(ctx.dt[2]), gp0, None, None, None
 
 
+_SPECTRAL_FAMILY = {"rbf": 0, "exp": 1, "mixed": 2}
+
+
+class _SpectralCross(torch.autograd.Function):
+    """SignatureSpectral's kappa(P, S) (kernels.py:921-942) for points P (n, d) and landmarks S (c, d) -> (n, c), by gpsig_spectral_cross; the
+    reverse pass by gpsig_spectral_cross_grad: d points, d landmarks, d alpha, d omega, d gamma, the parameters read from device memory.
+    What base_kernel_matrix computes for this family without the (n, c, d) difference tensor per component under autograd; the same
+    convention at zero distance (_SqrtZeroGrad)."""
+
+    @staticmethod
+    def forward(ctx, P, S, alpha, omega, gamma, family):
+        Pd, Sd, a, o, g = (_c(t) for t in (P, S, alpha, omega, gamma))
+        n, d = Pd.shape
+        cc, Q = Sd.shape[0], a.shape[0]
+        out = torch.empty((n, cc), dtype=torch.float64, device=Pd.device)
+        lc = _ctx_for(Pd)
+        lc.check(lc._lib.gpsig_spectral_cross(lc._h, Q, _SPECTRAL_FAMILY[family], d, _ptr(Pd), n, _ptr(Sd), cc, _ptr(a), _ptr(o), _ptr(g),
+                                              _ptr(out)))
+        ctx.family = family
+        ctx.dt = tuple(t.dtype for t in (P, S, alpha, omega, gamma))
+        ctx.save_for_backward(Pd, Sd, a, o, g)
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        Pd, Sd, a, o, g = ctx.saved_tensors
+        n, d = Pd.shape
+        cc, Q = Sd.shape[0], a.shape[0]
+        G = _c(G)
+        gP, gS, ga, go, gg = (torch.empty_like(t) for t in (Pd, Sd, a, o, g))
+        lc = _ctx_for(Pd)
+        lc.check(lc._lib.gpsig_spectral_cross_grad(lc._h, Q, _SPECTRAL_FAMILY[ctx.family], d, _ptr(Pd), n, _ptr(Sd), cc, _ptr(a), _ptr(o),
+                                                   _ptr(g), _ptr(G), _ptr(gP), _ptr(gS), _ptr(ga), _ptr(go), _ptr(gg)))
+        return tuple(t.to(dt) for t, dt in zip((gP, gS, ga, go, gg), ctx.dt)) + (None,)
+
+
 class _LowRankScope:
     """One low-rank evaluation: landmarks gathered from the evaluation's scaled points, their whitening, and the level features of
     every input asked for (kept per tensor: Kzz, Kzx and Kxx of one call share them)."""
@@ -811,7 +847,7 @@ class _LowRankScope:
             raise ValueError("the low-rank draw indexes %d points, the evaluation has %d" % (int(idx.max()) + 1, pool.shape[0]))
         self.mod = mod
         self.S = pool[idx]                                                                          # low_rank_calculations.py:47-48 (tf.gather: differentiable)
-        W = mod._kappa(self.S, self.S) + torch.diag(jd)                                             # :51-52
+        W = self._cross(self.S) + torch.diag(jd)                                                    # :51-52
         ev, U = torch.linalg.eigh(W)                                                                # :55
         # an eigenvector is fixed up to sign; the level >= 2 features depend on it through the projections of coordinate pairs: the
         # component of largest magnitude is taken positive (the library's and the checker's convention; constant under autograd)
@@ -821,8 +857,16 @@ class _LowRankScope:
         self.Wh = U * sgn[None, :] / torch.sqrt(ev + JITTER)[None, :]                               # :56-57, :60
         self._seq, self._tens = {}, {}
 
+    def _cross(self, pts):
+        """kappa(pts, landmarks): SignatureSpectral's through the HIP op (_SpectralCross) for CUDA tensors unless the module option
+        ``lr_hip`` is False; torch ops (_kappa) otherwise -- the in-tree checker of that op."""
+        mod = self.mod
+        if mod.kern._base == "spectral" and getattr(mod, "lr_hip", True) and pts.is_cuda:
+            return _SpectralCross.apply(pts, self.S, positive(mod.raw_alpha), positive(mod.raw_omega), positive(mod.raw_sgamma), mod.kern.family)
+        return mod._kappa(pts, self.S)
+
     def _nys(self, pts):
-        return self.mod._kappa(pts, self.S) @ self.Wh                                               # :59-61
+        return self._cross(pts) @ self.Wh                                                           # :59-61
 
     def seq(self, Xs):
         """signature_algs.py:162-192 (with :191 summing P, as evidently intended).  (N, L, d') -> [(N, 1), (N, c), (N, r), ...].

@@ -465,7 +465,6 @@ void lr_state_dev(const gpsig_lr_state* st, LrDev* D) {
 int lr_check(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr) {
     if (!lr) return fail(c, GPSIG_ERR_INVALID, "lowrank descriptor is NULL");
     if (p->dtype != GPSIG_F64) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for float64 only");
-    if (p->base_kernel == GPSIG_BASE_SPECTRAL) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is not built for the spectral base kernel");
     if (p->order != 1 && p->num_levels > 1) return fail(c, GPSIG_ERR_UNSUPPORTED, "Low-rank mode not implemented for order higher than 1.");
     if (lr->num_components < 1 || lr->rank_bound < 1) return fail(c, GPSIG_ERR_INVALID, "num_components and rank_bound must be positive");
     if (lr->num_sketches != p->num_levels - 1) return fail(c, GPSIG_ERR_INVALID, "need one sketch per level 2..num_levels");
@@ -2689,6 +2688,8 @@ int gpsig_lr_seq_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowra
     double* phi = static_cast<double*>(dPhi);
     double p0, p1;
     base_p(p, &p0, &p1);
+    const double* spec;                  // BASE_SPECTRAL: its parameter table (p0 = Q, p1 = family), read by the spectral instances
+    CHK(spectral_table(c, p, &spec));
     // One kernel, one workgroup per sequence, intermediates in LDS (lr_fused_kernel.hpp) when a sequence's three arrays fit
     const size_t fused_lds = lr_fused_lds_bytes(cc, r, d_eff, L, c->lr_fused_pad);
     if (c->lr_fused != 0 && fused_lds <= LR_FUSED_MAX_LDS && M - 1 <= LR_FUSED_MAX_SKETCHES) {
@@ -2700,6 +2701,7 @@ int gpsig_lr_seq_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowra
         for (int i = 0; i < D.nsk; ++i) A.sk[i] = LrFusedSketch{D.colptr[i], D.ent[i]};
         A.Phi = phi; A.F = F;
         A.lp = lr_fused_stride(L, c->lr_fused_pad);
+        A.spec = spec;
         A.rows_b = cc > r ? cc : r;
         if (d_eff > A.rows_b) A.rows_b = d_eff;
         const unsigned grid = unsigned(N < (int64_t(1) << 20) ? N : (int64_t(1) << 20));
@@ -2719,9 +2721,15 @@ int gpsig_lr_seq_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowra
     CHK(ensure(c, B_LR6, sizeof(double) * size_t(N) * (l > 0 ? l : 1) * wmax + 8, &Pb));
     if (N <= 0) return finish(c);
     // Nystrom features (low_rank_calculations.py:59-60): kappa(X, S) then the whitening GEMM on the matrix cores
-    hipLaunchKernelGGL(lr_seq_cross_kernel<double>, dim3(grid_for(N * L * cc)), dim3(256), 0, c->stream, static_cast<const double*>(dX),
-                       N, int(L), s, D.S, cc, int(p->base_kernel), p0, p1, static_cast<double*>(kxs));
-    HIPCHK(c, hipGetLastError());
+    if (p->base_kernel == GPSIG_BASE_SPECTRAL) {
+        const int rc = lr_seq_cross_spectral_launch(c->stream, static_cast<const double*>(dX), N, int(L), s, D.S, cc, int(p0), int(p1), spec,
+                                                    static_cast<double*>(kxs));
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral Nystrom cross kernel: %s", hipGetErrorString(hipError_t(rc)));
+    } else {
+        hipLaunchKernelGGL(lr_seq_cross_kernel<double>, dim3(grid_for(N * L * cc)), dim3(256), 0, c->stream, static_cast<const double*>(dX),
+                           N, int(L), s, D.S, cc, int(p->base_kernel), p0, p1, static_cast<double*>(kxs));
+        HIPCHK(c, hipGetLastError());
+    }
     // feat = kxs (NL, c) * Wh (c, c) = kxs * (Wh^T)^T : pass B = Wh^T, i.e. read Wh column-wise -> upload is row-major Wh, so
     // B[j][k] must be Wh[k][j]: use the transposed copy made below
     void* wht;
@@ -2795,6 +2803,8 @@ int gpsig_lr_tens_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowr
     if (T <= 0) return finish(c);
     double p0, p1;
     base_p(p, &p0, &p1);
+    const double* spec;
+    CHK(spectral_table(c, p, &spec));
     if (c->lr_fused != 0 && lr_tens_fused_lds_bytes(cc, r, d_eff, lt, E) <= 64 * 1024 && M - 1 <= LR_FUSED_MAX_SKETCHES && T <= 0x7fffffff) {
         LrTensFusedArgs A;
         A.Z = static_cast<const double*>(dZ); A.T = T; A.lt = lt; A.E = E; A.P = s; A.S = D.S; A.Wh = D.Wh;
@@ -2802,6 +2812,7 @@ int gpsig_lr_tens_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowr
         for (int i = 0; i < LR_FUSED_MAX_SKETCHES; ++i) A.sk[i] = LrFusedSketch{nullptr, nullptr};
         for (int i = 0; i < D.nsk; ++i) A.sk[i] = LrFusedSketch{D.colptr[i], D.ent[i]};
         A.Phi = phi; A.F = F;
+        A.spec = spec;
         const int rc = lr_tens_fused_launch(c->stream, A);
         if (rc != 0) return fail(c, GPSIG_ERR_HIP, "fused low-rank tensor feature kernel: %s", hipGetErrorString(hipError_t(rc)));
         CHK(out_done(c, Phi, dPhi, sizeof(double) * size_t(T) * F));
@@ -2825,9 +2836,15 @@ int gpsig_lr_tens_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowr
         HIPCHK(c, hipMemcpyAsync(wht, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, c->stream));
         CHK(host_sync(c));
     }
-    hipLaunchKernelGGL(lr_tens_cross_kernel<double>, dim3(grid_for(rows * cc)), dim3(256), 0, c->stream, static_cast<const double*>(dZ), rows,
-                       s, D.S, cc, int(p->base_kernel), p0, p1, static_cast<double*>(kxs));
-    HIPCHK(c, hipGetLastError());
+    if (p->base_kernel == GPSIG_BASE_SPECTRAL) {
+        const int rc = lr_tens_cross_spectral_launch(c->stream, static_cast<const double*>(dZ), rows, s, D.S, cc, int(p0), int(p1), spec,
+                                                     static_cast<double*>(kxs));
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral Nystrom cross kernel: %s", hipGetErrorString(hipError_t(rc)));
+    } else {
+        hipLaunchKernelGGL(lr_tens_cross_kernel<double>, dim3(grid_for(rows * cc)), dim3(256), 0, c->stream, static_cast<const double*>(dZ), rows,
+                           s, D.S, cc, int(p->base_kernel), p0, p1, static_cast<double*>(kxs));
+        HIPCHK(c, hipGetLastError());
+    }
     CHK(lr_gemm(c, static_cast<const double*>(kxs), static_cast<const double*>(wht), rows, cc, cc, cc, cc, static_cast<double*>(feat), cc));
     // increments: F(z[.,1]) - F(z[.,0]) (kernels.py:304); rows are ((k*T + t)*E + e): a "time difference" over e with L = E
     if (increments) {

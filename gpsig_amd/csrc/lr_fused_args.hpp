@@ -33,6 +33,7 @@ struct LrFusedArgs {
     double* Phi; int F;
     int lp;                 // row stride of the LDS arrays, in doubles (odd, > number of time steps rounded up to 64)
     int rows_b;             // rows of the two work arrays: max(c, r, d_eff)
+    const double* spec;     // BASE_SPECTRAL: spectral_table()'s device table (p0 = Q, p1 = family); the spectral instances only
 };
 
 inline int lr_fused_stride(int L, int pad) { return (L + 63) / 64 * 64 + pad; }
@@ -53,6 +54,7 @@ struct LrTensFusedArgs {
     double p0, p1;
     LrFusedSketch sk[LR_FUSED_MAX_SKETCHES];
     double* Phi; int F;
+    const double* spec;     // BASE_SPECTRAL table, as LrFusedArgs::spec
 };
 inline size_t lr_tens_fused_lds_bytes(int c, int r, int d_eff, int lt, int E) {
     const size_t rows = size_t(lt) * E, w = size_t(c > r ? c : r);
@@ -71,5 +73,15 @@ int lr_fused2_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid);
 
 // lr_fused_inst.hip: launches the kernel on `stream` with `grid` workgroups; returns the hipError_t of the launch
 int lr_fused_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, int variant);
+
+// lr_spectral_inst.hip: the same kernels with SignatureSpectral's kappa in phase 1 (A.kind == BASE_SPECTRAL; the launchers above hand over)
+int lr_fused_spectral_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, size_t lds);
+int lr_fused2_spectral_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, size_t lds);
+int lr_tens_fused_spectral_launch(hipStream_t stream, const LrTensFusedArgs& A, size_t lds);
+// ... and the multi-pass route's Nystrom cross matrices (lowrank_kernels.hpp: lr_seq_cross_kernel / lr_tens_cross_kernel)
+int lr_seq_cross_spectral_launch(hipStream_t stream, const double* X, int64_t N, int L, ScaleParams P, const double* S, int c, int Q, int family,
+                                 const double* spec, double* out);
+int lr_tens_cross_spectral_launch(hipStream_t stream, const double* Z, int64_t rows, ScaleParams P, const double* S, int c, int Q, int family,
+                                  const double* spec, double* out);
 
 }  // namespace gpsig

@@ -18,6 +18,7 @@ int launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, size_t lds) 
 
 int lr_fused_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, int variant) {
     const size_t lds = sizeof(double) * size_t(A.lp) * (size_t(A.c) + 2 * size_t(A.rows_b));
+    if (A.kind == BASE_SPECTRAL) return lr_fused_spectral_launch(stream, A, grid, lds);
     // BASELINE configs[2]'s sequences (L=50, c=r=50, 'sqrt'), same box: 256 threads / 4 entries per batch 4.32 ms, 256 / 8 3.84,
     // 512 / 4 2.71, 512 / 8 2.57, 1024 / 4 3.09, 1024 / 8 4.01 (profiles/r02_lowrank.txt)
     switch (variant) {
@@ -30,6 +31,7 @@ int lr_fused_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, int
 
 int lr_fused2_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid) {
     const size_t lds = sizeof(double) * size_t(A.lp) * 2 * size_t(A.rows_b);
+    if (A.kind == BASE_SPECTRAL) return lr_fused2_spectral_launch(stream, A, grid, lds);
     auto kern = lr_seq_features_fused2_kernel<512, 8>;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
@@ -41,7 +43,35 @@ int lr_fused2_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid) {
 
 int lr_tens_fused_launch(hipStream_t stream, const LrTensFusedArgs& A) {
     const size_t lds = lr_tens_fused_lds_bytes(A.c, A.r, A.P.d_eff(), A.lt, A.E);
+    if (A.kind == BASE_SPECTRAL) return lr_tens_fused_spectral_launch(stream, A, lds);
     hipLaunchKernelGGL(lr_tens_features_fused_kernel, dim3(unsigned(A.T)), dim3(LR_TENS_THREADS), lds, stream, A);
+    return int(hipGetLastError());
+}
+
+// ---- SignatureSpectral: the same kernels with its kappa in phase 1, one instance each (the family's phase 1 -- Q components of 3d
+// multiply-adds, an exp and a cos per pair -- is not worth a variant search of its own)
+int lr_fused_spectral_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, size_t lds) {
+    auto kern = lr_seq_features_fused_spectral_kernel<512, 8>;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+        if (e != hipSuccess) return int(e);
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, A);
+    return int(hipGetLastError());
+}
+
+int lr_fused2_spectral_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, size_t lds) {
+    auto kern = lr_seq_features_fused2_spectral_kernel<512, 8>;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+        if (e != hipSuccess) return int(e);
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, A);
+    return int(hipGetLastError());
+}
+
+int lr_tens_fused_spectral_launch(hipStream_t stream, const LrTensFusedArgs& A, size_t lds) {
+    hipLaunchKernelGGL(lr_tens_features_fused_spectral_kernel, dim3(unsigned(A.T)), dim3(LR_TENS_THREADS), lds, stream, A);
     return int(hipGetLastError());
 }
 

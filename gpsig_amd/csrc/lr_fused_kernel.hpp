@@ -25,6 +25,7 @@
 #include "aux_kernels.hpp"
 #include "lr_fused_args.hpp"
 #include "seq_core.hpp"
+#include "spectral_pair.hpp"
 
 namespace gpsig {
 
@@ -34,8 +35,11 @@ namespace gpsig {
 // two workgroups per CU.  The repeated-squaring helper round 4 added to base_eval cost it ONE register and with it a workgroup per CU: BASELINE
 // configs[2] in low-rank mode 2.8 -> 4.6 ms, unnoticed until the round's last bench.  The library pow is out of line everywhere since
 // (seq_core.hpp: poly_pow_general); tests/test_abi.py reads the compiler's report for this kernel.)
-template <int THREADS, int UNROLL>
-__global__ __launch_bounds__(THREADS) void lr_seq_features_fused_kernel(LrFusedArgs A) {
+// Phase 1 of the spectral instances (SPEC): SignatureSpectral's kappa takes the coordinates of x - S_i, not (<x,S_i>, |x|^2, |S_i|^2);
+// the landmark row and the parameter table are wave-uniform (constant address space, as S and Wh).  The run-time family switch of
+// base_eval stays out of them and the spectral arithmetic out of the others (occupancy steps, above).
+template <int THREADS, int UNROLL, bool SPEC>
+__device__ __forceinline__ void lr_seq_features_fused_body(const LrFusedArgs& A) {
     extern __shared__ double lr_lds[];
     const int lp = A.lp, c = A.c, r = A.r, L = A.L;
     double* const U = lr_lds;                               // [c][lp]
@@ -65,6 +69,13 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_fused_kernel(LrFusedA
                 for (int fe = 0; fe < d_eff; ++fe) { const double x = bufB[fe * lp + t]; xs = fma(x, x, xs); }
                 for (int i = wave; i < c; i += NW) {
                     const lr_const_ptr<double> Si = lr_as_const(A.S) + size_t(i) * d_eff;
+                    if constexpr (SPEC) {
+                        const lr_const_ptr<double> tab = lr_as_const(A.spec);
+                        const int Q = int(A.p0);
+                        bufA[i * lp + t] = spectral_pair(tab, tab + Q, tab + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff,
+                                                         [&](int f) { return bufB[f * lp + t]; }, [&](int f) { return Si[f]; });
+                        continue;
+                    }
                     double ip = 0.0, ss = 0.0;
                     for (int fe = 0; fe < d_eff; ++fe) {
                         const double y = Si[fe];
@@ -159,6 +170,11 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_fused_kernel(LrFusedA
     }
 }
 
+template <int THREADS, int UNROLL>
+__global__ __launch_bounds__(THREADS) void lr_seq_features_fused_kernel(LrFusedArgs A) { lr_seq_features_fused_body<THREADS, UNROLL, false>(A); }
+template <int THREADS, int UNROLL>
+__global__ __launch_bounds__(THREADS) void lr_seq_features_fused_spectral_kernel(LrFusedArgs A) { lr_seq_features_fused_body<THREADS, UNROLL, true>(A); }
+
 // ---- the same with TWO arrays in LDS instead of three --------------------------------------------------------------------
 // For sequences of at most 64 time steps and at most LR_FUSED2_COLS output columns per wavefront, a wavefront keeps the columns it
 // produces in REGISTERS until every wavefront of the workgroup has finished reading the array they replace, and writes them in
@@ -167,8 +183,8 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_fused_kernel(LrFusedA
 // wavefronts again to hide the scalar-load latency of the sketch entries and the phases in which one wavefront works.
 //   W holds: the scaled observations (transposed) -> kxs -> E_2 (running sums of U) -> P_2 -> E_3 -> ...;  U: feat -> U.
 constexpr int LR_FUSED2_COLS = 8;
-template <int THREADS, int UNROLL>
-__global__ __launch_bounds__(THREADS) void lr_seq_features_fused2_kernel(LrFusedArgs A) {
+template <int THREADS, int UNROLL, bool SPEC>
+__device__ __forceinline__ void lr_seq_features_fused2_body(const LrFusedArgs& A) {
     extern __shared__ double lr_lds[];
     const int lp = A.lp, c = A.c, r = A.r, L = A.L;
     double* const U = lr_lds;                               // [max(c, d_eff)][lp]
@@ -195,6 +211,13 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_fused2_kernel(LrFused
             for (int fe = 0; fe < d_eff; ++fe) { const double x = U[fe * lp + t]; xs = fma(x, x, xs); }
             for (int i = wave; i < c; i += NW) {
                 const lr_const_ptr<double> Si = lr_as_const(A.S) + size_t(i) * d_eff;
+                if constexpr (SPEC) {
+                    const lr_const_ptr<double> tab = lr_as_const(A.spec);
+                    const int Q = int(A.p0);
+                    W[i * lp + t] = spectral_pair(tab, tab + Q, tab + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff,
+                                                  [&](int f) { return U[f * lp + t]; }, [&](int f) { return Si[f]; });
+                    continue;
+                }
                 double ip = 0.0, ss = 0.0;
                 for (int fe = 0; fe < d_eff; ++fe) {
                     const double y = Si[fe];
@@ -291,6 +314,11 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_fused2_kernel(LrFused
     }
 }
 
+template <int THREADS, int UNROLL>
+__global__ __launch_bounds__(THREADS) void lr_seq_features_fused2_kernel(LrFusedArgs A) { lr_seq_features_fused2_body<THREADS, UNROLL, false>(A); }
+template <int THREADS, int UNROLL>
+__global__ __launch_bounds__(THREADS) void lr_seq_features_fused2_spectral_kernel(LrFusedArgs A) { lr_seq_features_fused2_body<THREADS, UNROLL, true>(A); }
+
 // ---- inducing tensors ---------------------------------------------------------------------------------------------------
 // One workgroup per tensor t.  Rows (k, e) of the tensor's lt * E components: scaled (kernels.py:367-398), kappa against the
 // landmarks (low_rank_calculations.py:59), whitened (:60), differenced over e for incremental tensors (kernels.py:304); then
@@ -298,7 +326,8 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_fused2_kernel(LrFused
 // column.  The sketches' entries come from L2 (they are the same for every tensor).  A few hundred multiply-adds per thread:
 // the point is one launch instead of about twenty.
 constexpr int LR_TENS_THREADS = 128;
-__global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_fused_kernel(LrTensFusedArgs A) {
+template <bool SPEC>
+__device__ __forceinline__ void lr_tens_features_fused_body(const LrTensFusedArgs& A) {
     extern __shared__ double lr_lds[];
     const int c = A.c, r = A.r, lt = A.lt, E = A.E, d_eff = A.P.d_eff();
     const int rows = lt * E, w = c > r ? c : r;
@@ -324,6 +353,12 @@ __global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_fused_kernel
     __syncthreads();
     for (int q = threadIdx.x; q < rows * c; q += LR_TENS_THREADS) {
         const int row = q / c, i = q - row * c;
+        if constexpr (SPEC) {
+            const int Q = int(A.p0);
+            kx[q] = spectral_pair(A.spec, A.spec + Q, A.spec + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff,
+                                  [&](int f) { return zs[row * d_eff + f]; }, [&](int f) { return A.S[size_t(i) * d_eff + f]; });
+            continue;
+        }
         double ip = 0.0, xs = 0.0, ss = 0.0;
         for (int fe = 0; fe < d_eff; ++fe) {
             const double x = zs[row * d_eff + fe], y = A.S[size_t(i) * d_eff + fe];
@@ -371,5 +406,8 @@ __global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_fused_kernel
         __syncthreads();                             // R (Ra / Rb) is rewritten by the next level's chain
     }
 }
+
+__global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_fused_kernel(LrTensFusedArgs A) { lr_tens_features_fused_body<false>(A); }
+__global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_fused_spectral_kernel(LrTensFusedArgs A) { lr_tens_features_fused_body<true>(A); }
 
 }  // namespace gpsig

@@ -8,7 +8,7 @@ every method is numpy-in / numpy-out (host pointers) or torch-CUDA-in / torch-CU
 pointers, asynchronous on the current stream).
 
 float32 inputs are computed in float32 where the float32 kernels are built, else by the float64 kernels and rounded.
-Not built (raise NotImplementedError, never a silent CPU fallback): ``SignatureSpectral`` in low-rank mode.  Training (gradients): ``gpsig_amd.autodiff``.
+Training (gradients): ``gpsig_amd.autodiff``.
 """
 import ctypes as C
 
@@ -936,8 +936,6 @@ class SignatureSpectral(SignatureKernel):
         if self.num_lags > 0:
             # the reference stores its (Q, d) scale matrix in self.gamma, overwriting the lag weights of kernels.py:82 (:913)
             raise NotImplementedError("SignatureSpectral with num_lags > 0: the reference overwrites the lag weights (kernels.py:82 vs :913)")
-        if self.low_rank:
-            raise NotImplementedError("SignatureSpectral in low-rank mode is not built")
         self.family = {0: 'rbf', 1: 'exp', 2: 'mixed'}[self._FAMILIES[family]]                               # :909-914
         self.Q = int(Q)
         self.alpha = np.exp(np.random.randn(self.Q))                                                         # :919

@@ -353,6 +353,17 @@ int gpsig_lr_seq_features_dev(gpsig_ctx* ctx, const gpsig_params* p, int32_t num
 int gpsig_lr_seq_features_grad(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
                                const gpsig_sketch* sketches, const void* X, int64_t N, int32_t L, const double* S, const double* Wh,
                                const void* dPhi, void* gX, double* gS, double* gWh, double* g_base);
+/* SignatureSpectral's Nystrom cross matrix for the TRAINING path (kernels.py:921-942, low_rank_calculations.py:59): K (n, c) = kappa(P, S)
+ * for points P (n, d) and landmarks S (c, d), the parameters alpha (Q), omega (Q, d), gamma (Q, d) read from DEVICE memory (they change at
+ * every optimiser step: no trip through the host), family 0 = rbf, 1 = exp, 2 = mixed; 1 <= Q <= 64, d <= 32.  Device pointers, device-pointer
+ * mode; asynchronous on the context's stream.
+ * _grad: G = dL/dK (n, c) -> dP (n, d), dS (c, d), dalpha (Q), domega (Q, d), dgamma (Q, d), overwritten; deterministic (partial sums
+ * combined in a fixed order).  The exponential envelope's sqrt has derivative 0 at zero distance (a point paired with itself). */
+int gpsig_spectral_cross(gpsig_ctx* ctx, int32_t Q, int32_t family, int32_t d, const double* P, int64_t n, const double* S, int32_t c,
+                         const double* alpha, const double* omega, const double* gamma, double* K);
+int gpsig_spectral_cross_grad(gpsig_ctx* ctx, int32_t Q, int32_t family, int32_t d, const double* P, int64_t n, const double* S, int32_t c,
+                              const double* alpha, const double* omega, const double* gamma, const double* G, double* dP, double* dS,
+                              double* dalpha, double* domega, double* dgamma);
 /* SignatureKernel._K_seq_lr_feat (kernels.py:239-261): Nystrom_map + signature_kern_first_order_lr_feature.  Phi: (N, F). */
 int gpsig_lr_seq_features(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L, void* Phi);
 /* SignatureKernel._K_tens_lr_feat (kernels.py:285-311): Nystrom_map + tensor_kern_lr_feature.  Phi: (T, F). */

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Low-rank mode (gpsig/low_rank_calculations.py, signature_algs.py:162-222, kernels.py:236-311) at the benchmark shapes.
 
-    python tools/bench_lr.py [--config c3|c2] [--base rbf|linear] [--components 50] [--rank 50] [--sparsity sqrt] [--fused 1|0]
+    python tools/bench_lr.py [--config c3|c2] [--base rbf|linear|spectral] [--Q 5] [--family rbf|exp|mixed] [--components 50] [--rank 50]
+                             [--sparsity sqrt] [--fused 1|0]
 
 c3: the SVGP inducing-tensor path of BASELINE configs[2] in low-rank mode -- K_tens_n_seq_covs(Z, X), T=512, N=16384, L=50, d=6, M=4.
 c2: K(X) at BASELINE configs[1]'s shape, N=4096, L=64, d=8, M=5.
 Inputs resident in HBM, random objects (landmarks, whitening, sketches) drawn once outside the timed region and handed in, as
 the parity tests do; `with_draw` is the same evaluation with a fresh draw per call (landmark gather, rocSOLVER eigendecomposition,
 host-side sketches: what the reference does per TF session run).  Per-stage times are wall-clock around synchronised C-ABI calls.
+SignatureSpectral: alpha = 1, omega = 0.1, gamma = 1 / sqrt(d) (the RBF run's lengthscale), the same data and seeds as the RBF run.
 Prints one JSON line; --verify compares a sub-sample with the oracle's restatement given the same random objects.
 """
 import argparse
@@ -27,7 +29,9 @@ SHAPES = {"c3": dict(N=16384, L=50, d=6, M=4, T=512), "c2": dict(N=4096, L=64, d
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c3", choices=sorted(SHAPES))
-    ap.add_argument("--base", default="rbf", choices=["rbf", "linear"])
+    ap.add_argument("--base", default="rbf", choices=["rbf", "linear", "spectral"])
+    ap.add_argument("--Q", type=int, default=5)
+    ap.add_argument("--family", default="rbf", choices=["rbf", "exp", "mixed"])
     ap.add_argument("--components", type=int, default=50)
     ap.add_argument("--rank", type=int, default=None)
     ap.add_argument("--sparsity", default="sqrt", choices=["sqrt", "log", "lin"])
@@ -49,7 +53,12 @@ def main():
     Z = torch.as_tensor(Zh, device=dev) if T else None
     cls = kernels.SignatureLinear if args.base == "linear" else kernels.SignatureRBF
     ls = 1.0 if args.base == "linear" else float(np.sqrt(d))
-    kern = cls(L * d, d, M, lengthscales=ls, low_rank=True, num_components=args.components, rank_bound=args.rank, sparsity=args.sparsity)
+    lr_kw = dict(low_rank=True, num_components=args.components, rank_bound=args.rank, sparsity=args.sparsity)
+    if args.base == "spectral":
+        kern = kernels.SignatureSpectral(L * d, d, M, family=args.family, Q=args.Q, **lr_kw)
+        kern.alpha, kern.omega, kern.gamma = np.ones(args.Q), np.full((args.Q, d), 0.1), np.full((args.Q, d), 1 / ls)
+    else:
+        kern = cls(L * d, d, M, lengthscales=ls, **lr_kw)
     kern.rng = np.random.default_rng(3)
     ctx = _lib.context(0, torch.cuda.current_stream(dev).cuda_stream)
     ctx.set_option("lr_fused", args.fused)
@@ -112,7 +121,7 @@ def main():
     kern.device_draw = True
     l = L - 1
     res = {"what": f"low-rank mode, {args.config} shape: " + (f"K_tens_n_seq_covs, T={T} inducing tensors, " if T else "K(X), ") +
-                   f"N={N}, L={L}, d={d}, num_levels={M}, Signature{'Linear' if args.base == 'linear' else 'RBF'}, fp64, "
+                   f"N={N}, L={L}, d={d}, num_levels={M}, {type(kern).__name__}" + (f" (Q={args.Q}, {args.family})" if args.base == "spectral" else "") + ", fp64, "
                    f"num_components={args.components}, rank_bound={args.rank or args.components}, sparsity={args.sparsity}",
            "ms_per_evaluation": ms, "entries_per_s": pairs / (ms * 1e-3), "ms_with_fresh_draw": ms_fresh, "ms_draw_on_device": ms_draw, "ms_draw_on_host_round2": ms_draw_host, "stages": stages,
            "fused_feature_kernel": bool(args.fused), "feature_width": F, "sketch_nnz_per_level": nnz,
@@ -122,7 +131,11 @@ def main():
     res["seq_features_lds_GBps"] = res["seq_features_lds_bytes"] / (ms_seq * 1e-3) / 1e9
     if args.verify:
         from oracle import sigkern_oracle as O
-        ko = O.SignatureKernelOracle(L * d, d, M, base=args.base, lengthscales=ls)
+        if args.base == "spectral":
+            ko = O.SignatureKernelOracle(L * d, d, M, base="spectral", lengthscales=None,
+                                         base_params=dict(alpha=kern.alpha, omega=kern.omega, gamma=kern.gamma, family=kern.family))
+        else:
+            ko = O.SignatureKernelOracle(L * d, d, M, base=args.base, lengthscales=ls)
         lo = O.LowRankOracle(ko, sth.landmarks, sth.jitter_diag, sth.sketches)
         ns, ts = 20, 12
         if T:
