@@ -271,7 +271,8 @@ SeqLaunchFn seq_launcher_ho(int mode, const SeqHOConfig& c, bool f32) {
 
 namespace {
 
-int check_params(gpsig_ctx* c, const gpsig_params* p) {
+// low_rank: the low-rank entry points, whose float32 forms carry the spectral base kernel too
+int check_params(gpsig_ctx* c, const gpsig_params* p, bool low_rank = false) {
     if (!c) return GPSIG_ERR_INVALID;
     if (!p) return fail(c, GPSIG_ERR_INVALID, "params is NULL");
     if (p->dtype != GPSIG_F64 && p->dtype != GPSIG_F32) return fail(c, GPSIG_ERR_INVALID, "unknown dtype %d", p->dtype);
@@ -288,7 +289,7 @@ int check_params(gpsig_ctx* c, const gpsig_params* p) {
             return fail(c, GPSIG_ERR_INVALID, "spectral kernel: base_table must hold alpha[Q], omega[Q][d], gamma[Q][d]");
         if (p->lengthscales || p->num_lags != 0)
             return fail(c, GPSIG_ERR_INVALID, "spectral kernel: lengthscales must be NULL and num_lags 0 (kernels.py:907, :82 vs :913)");
-        if (p->dtype != GPSIG_F64) return fail(c, GPSIG_ERR_UNSUPPORTED, "the spectral base kernel is built for float64 only");
+        if (p->dtype != GPSIG_F64 && !low_rank) return fail(c, GPSIG_ERR_UNSUPPORTED, "the spectral base kernel is built for float64 only (low-rank mode apart)");
     }
     if (p->order < 1 || p->order > p->num_levels) return fail(c, GPSIG_ERR_INVALID, "order=%d outside [1, num_levels]", p->order);
     if (!p->variances) return fail(c, GPSIG_ERR_INVALID, "variances is NULL");
@@ -384,15 +385,19 @@ int upload_weights(gpsig_ctx* c, const gpsig_params* p, const double** w) {
 #define ENTER(c, p)                         \
     CHK(check_params((c), (p)));            \
     HIPCHK((c), hipSetDevice((c)->device));
+#define ENTER_LR(c, p)                      \
+    CHK(check_params((c), (p), true));      \
+    HIPCHK((c), hipSetDevice((c)->device));
 
 
-// ---- low-rank mode (float64) ---------------------------------------------------------------------------
+// ---- low-rank mode (float64; float32 features and Grams from a float64 state) --------------------------------------------------
 struct LrDev {                 // device copies of a gpsig_lowrank
     const double* S; const double* Wh;
     int c, r, nsk;
     std::vector<const int32_t*> colptr, i1, i2;
     std::vector<const double*> val;
     std::vector<const LrEntry*> ent;        // the same entries packed (value, i1, i2) for the fused feature kernel
+    std::vector<int64_t> nent;              // entries of ent[i] that may be read (nnz; the capacity for a device-drawn state)
     std::vector<int> k1, k2;
 };
 
@@ -456,7 +461,7 @@ void lr_state_dev(const gpsig_lr_state* st, LrDev* D) {
     D->S = st->S; D->Wh = st->Wh;
     for (int i = 0; i < st->nsk; ++i) {
         D->colptr.push_back(st->sk[i].colptr); D->i1.push_back(st->sk[i].i1); D->i2.push_back(st->sk[i].i2);
-        D->val.push_back(st->sk[i].val); D->ent.push_back(st->sk[i].ent);
+        D->val.push_back(st->sk[i].val); D->ent.push_back(st->sk[i].ent); D->nent.push_back(st->sk[i].cap);
         D->k1.push_back(st->sk[i].k1); D->k2.push_back(st->sk[i].k2);
     }
 }
@@ -464,7 +469,7 @@ void lr_state_dev(const gpsig_lr_state* st, LrDev* D) {
 
 int lr_check(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr) {
     if (!lr) return fail(c, GPSIG_ERR_INVALID, "lowrank descriptor is NULL");
-    if (p->dtype != GPSIG_F64) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for float64 only");
+    if (p->dtype != GPSIG_F64 && p->dtype != GPSIG_F32) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for float64 and float32");
     if (p->order != 1 && p->num_levels > 1) return fail(c, GPSIG_ERR_UNSUPPORTED, "Low-rank mode not implemented for order higher than 1.");
     if (lr->num_components < 1 || lr->rank_bound < 1) return fail(c, GPSIG_ERR_INVALID, "num_components and rank_bound must be positive");
     if (lr->num_sketches != p->num_levels - 1) return fail(c, GPSIG_ERR_INVALID, "need one sketch per level 2..num_levels");
@@ -562,6 +567,7 @@ int lr_upload(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, int 
             for (int64_t e = 0; e < sk.nnz; ++e) packed[size_t(e)] = LrEntry{sk.val[e], sk.i1[e], sk.i2[e]};
         }
         D->ent.push_back(reinterpret_cast<const LrEntry*>(place(packed.data(), sizeof(LrEntry) * size_t(sk.nnz), 16)));
+        D->nent.push_back(sk.nnz);
         D->k1.push_back(sk.k1); D->k2.push_back(sk.k2);
     }
     if (!cached) {
@@ -609,6 +615,220 @@ int lr_level_offsets(gpsig_ctx* c, int M, int cc, int r, const int32_t** dev_off
     }
     *dev_off = static_cast<const int32_t*>(d);
     return GPSIG_OK;
+}
+
+// ---- low-rank mode, float32 calls.  The state (landmarks, whitening, projections) stays float64 -- drawn and whitened in float64 --;
+// what the float32 feature kernels read of it, and the spectral table, are narrowed on the device once per call into B_LRF32.
+int lr_gemm(gpsig_ctx* c, const float* A, const float* B, int64_t N1, int64_t N2, int K, int64_t lda, int64_t ldb, float* C_, int64_t ldc) {
+    if (N1 <= 0 || N2 <= 0) return GPSIG_OK;
+    dim3 grid((unsigned)((N2 + GEMM_BN - 1) / GEMM_BN), (unsigned)((N1 + GEMM_BM - 1) / GEMM_BM));
+    hipLaunchKernelGGL(gemm_abt_f32_tiled_kernel, grid, dim3(256), 0, c->stream, A, B, N1, N2, K, lda, ldb, C_, ldc);
+    HIPCHK(c, hipGetLastError());
+    return GPSIG_OK;
+}
+
+struct LrDevF32 { const float* S; const float* Wh; const float* spec; const LrEntryF32* ent[LR_FUSED_MAX_SKETCHES]; };
+
+int lr_narrow(gpsig_ctx* c, const gpsig_params* p, const LrDev& D, int d_eff, const double* spec, LrDevF32* F) {
+    const int64_t nS = int64_t(D.c) * d_eff, nW = int64_t(D.c) * D.c;
+    const int64_t nspec = spec ? int64_t(p->base_params[0]) * (1 + 2 * SPECTRAL_STRIDE) : 0;
+    auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
+    size_t bytes = up16(sizeof(float) * nS) + up16(sizeof(float) * nW) + up16(sizeof(float) * nspec);
+    for (int i = 0; i < D.nsk; ++i) bytes += sizeof(LrEntryF32) * size_t(D.nent[i]) + 16;
+    void* base;
+    CHK(ensure(c, B_LRF32, bytes + 16, &base));
+    char* b = static_cast<char*>(base);
+    float* S = reinterpret_cast<float*>(b); b += up16(sizeof(float) * nS);
+    float* Wh = reinterpret_cast<float*>(b); b += up16(sizeof(float) * nW);
+    float* sp = reinterpret_cast<float*>(b); b += up16(sizeof(float) * nspec);
+    int rc = lr_narrow_launch(c->stream, D.S, nS, S);
+    if (rc == 0) rc = lr_narrow_launch(c->stream, D.Wh, nW, Wh);
+    if (rc == 0 && spec) rc = lr_narrow_launch(c->stream, spec, nspec, sp);
+    for (int i = 0; i < D.nsk && rc == 0; ++i) {
+        LrEntryF32* e = reinterpret_cast<LrEntryF32*>(b);
+        rc = lr_narrow_entries_launch(c->stream, D.ent[i], D.nent[i], e);
+        F->ent[i] = e;
+        b += sizeof(LrEntryF32) * size_t(D.nent[i]) + 16;
+    }
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "narrowing the low-rank state to float32: %s", hipGetErrorString(hipError_t(rc)));
+    F->S = S; F->Wh = Wh; F->spec = spec ? sp : nullptr;
+    return GPSIG_OK;
+}
+
+// gpsig_lr_seq_features for float32 sequences: the fused kernels only (lr_fused != 0 and the float32 footprint within LDS); elsewhere
+// UNSUPPORTED, and the Python layer computes the call in float64 and rounds it
+int lr_seq_features_f32(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L, void* Phi) {
+    const int M = p->num_levels;
+    ScaleParams s;
+    CHK(scale_params(c, p, true, &s));
+    const int d_eff = s.d_eff();
+    const int cc = lr->num_components, r = lr->rank_bound;
+    const bool two = c->lr_fused == 1 && lr_fused2_ok(cc, r, L);
+    const size_t lds = two ? lr_fused2_lds_bytes_f32(cc, r, d_eff, L, c->lr_fused_pad) : lr_fused_lds_bytes_f32(cc, r, d_eff, L, c->lr_fused_pad);
+    if (c->lr_fused == 0 || lds > LR_FUSED_MAX_LDS || M - 1 > LR_FUSED_MAX_SKETCHES)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "float32 low-rank features are built for the fused kernels only (lr_fused != 0, %zu bytes of LDS)", lds);
+    LrDev D;
+    CHK(lr_upload(c, p, lr, d_eff, &D));
+    const int F = 1 + cc + (M - 1) * r;
+    const void* dX;
+    CHK(in_dev(c, B_IN0, X, sizeof(float) * size_t(N) * L * p->num_features, &dX));
+    void* dPhi;
+    CHK(out_dev(c, B_OUT0, Phi, sizeof(float) * size_t(N) * F, &dPhi));
+    if (N <= 0) return finish(c);
+    double p0, p1;
+    base_p(p, &p0, &p1);
+    const double* spec;
+    CHK(spectral_table(c, p, &spec));
+    LrDevF32 G;
+    CHK(lr_narrow(c, p, D, d_eff, spec, &G));
+    LrFusedArgsF32 A;
+    A.X = static_cast<const float*>(dX); A.N = N; A.L = L; A.P = s; A.S = G.S; A.Wh = G.Wh;
+    A.c = cc; A.r = r; A.M = M; A.difference = p->difference; A.kind = int(p->base_kernel); A.p0 = float(p0); A.p1 = float(p1);
+    for (int i = 0; i < LR_FUSED_MAX_SKETCHES; ++i) A.sk[i] = LrFusedSketchF32{nullptr, nullptr};
+    for (int i = 0; i < D.nsk; ++i) A.sk[i] = LrFusedSketchF32{D.colptr[i], G.ent[i]};
+    A.Phi = static_cast<float*>(dPhi); A.F = F;
+    A.lp = lr_fused_stride(L, c->lr_fused_pad);
+    A.spec = G.spec;
+    A.rows_b = cc > r ? cc : r;
+    if (d_eff > A.rows_b) A.rows_b = d_eff;
+    const unsigned grid = unsigned(N < (int64_t(1) << 20) ? N : (int64_t(1) << 20));
+    const int rc = lr_fused_f32_launch(c->stream, A, grid, two);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "fused float32 low-rank feature kernel: %s", hipGetErrorString(hipError_t(rc)));
+    CHK(out_done(c, Phi, dPhi, sizeof(float) * size_t(N) * F));
+    return finish(c);
+}
+
+// gpsig_lr_tens_features for float32 tensors: the fused kernel only, as above
+int lr_tens_features_f32(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* Z, int64_t T, int32_t increments, void* Phi) {
+    const int M = p->num_levels, lt = M * (M + 1) / 2, E = increments ? 2 : 1;
+    ScaleParams s;
+    CHK(scale_params(c, p, true, &s));
+    const int d_eff = s.d_eff();
+    const int cc = lr->num_components, r = lr->rank_bound;
+    const size_t lds = lr_tens_fused_lds_bytes_f32(cc, r, d_eff, lt, E);
+    if (c->lr_fused == 0 || lds > 64 * 1024 || M - 1 > LR_FUSED_MAX_SKETCHES || T > 0x7fffffff)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "float32 low-rank tensor features are built for the fused kernel only (lr_fused != 0, %zu bytes of LDS)", lds);
+    LrDev D;
+    CHK(lr_upload(c, p, lr, d_eff, &D));
+    const int F = 1 + cc + (M - 1) * r;
+    const void* dZ;
+    CHK(in_dev(c, B_IN0, Z, sizeof(float) * size_t(lt) * T * E * d_eff, &dZ));
+    void* dPhi;
+    CHK(out_dev(c, B_OUT0, Phi, sizeof(float) * size_t(T) * F, &dPhi));
+    if (T <= 0) return finish(c);
+    double p0, p1;
+    base_p(p, &p0, &p1);
+    const double* spec;
+    CHK(spectral_table(c, p, &spec));
+    LrDevF32 G;
+    CHK(lr_narrow(c, p, D, d_eff, spec, &G));
+    LrTensFusedArgsF32 A;
+    A.Z = static_cast<const float*>(dZ); A.T = T; A.lt = lt; A.E = E; A.P = s; A.S = G.S; A.Wh = G.Wh;
+    A.c = cc; A.r = r; A.M = M; A.kind = int(p->base_kernel); A.p0 = float(p0); A.p1 = float(p1);
+    for (int i = 0; i < LR_FUSED_MAX_SKETCHES; ++i) A.sk[i] = LrFusedSketchF32{nullptr, nullptr};
+    for (int i = 0; i < D.nsk; ++i) A.sk[i] = LrFusedSketchF32{D.colptr[i], G.ent[i]};
+    A.Phi = static_cast<float*>(dPhi); A.F = F;
+    A.spec = G.spec;
+    const int rc = lr_tens_fused_f32_launch(c->stream, A);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "fused float32 low-rank tensor feature kernel: %s", hipGetErrorString(hipError_t(rc)));
+    CHK(out_done(c, Phi, dPhi, sizeof(float) * size_t(T) * F));
+    return finish(c);
+}
+
+// low-rank Gram products (gpsig_lr_kernel / gpsig_lr_kernel_diag) in the features' float type: factors, scaling and the GEMM in T, level
+// weights and jitter from their float64 host values
+template <typename T>
+int lr_kernel_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* PhiA, const void* PhiB, int64_t N1, int64_t N2,
+                int32_t normalize_a, int32_t normalize_b, int32_t return_levels, void* out) {
+    const int M = p->num_levels, M1 = M + 1, cc = lr->num_components, r = lr->rank_bound;
+    const bool sym = PhiB == nullptr;
+    if (sym) N2 = N1;
+    const int32_t* off;
+    int F;
+    CHK(lr_level_offsets(c, M, cc, r, &off, &F));
+    const void *dA, *dB;
+    CHK(in_dev(c, B_IN0, PhiA, sizeof(T) * size_t(N1) * F, &dA));
+    if (sym) dB = dA; else CHK(in_dev(c, B_IN1, PhiB, sizeof(T) * size_t(N2) * F, &dB));
+    const size_t ob = sizeof(T) * size_t(N1) * N2 * (return_levels ? M1 : 1);
+    void* dout;
+    CHK(out_dev(c, B_OUT0, out, ob, &dout));
+    const double* w;
+    CHK(upload_weights(c, p, &w));
+    void *fa, *fb, *sa, *sb;
+    CHK(ensure(c, B_LR2, sizeof(T) * size_t(N1) * M1 + 8, &fa));
+    CHK(ensure(c, B_LR3, sizeof(T) * size_t(N2) * M1 + 8, &fb));
+    CHK(ensure(c, B_LR4, sizeof(T) * size_t(N1) * F + 8, &sa));
+    CHK(ensure(c, B_LR5, sizeof(T) * size_t(N2) * F + 8, &sb));
+    if (N1 <= 0 || N2 <= 0) return finish(c);
+    // per-row level factors: A side carries sigma*variances, both sides 1/sqrt(|Phi_m|^2 + jitter) when normalising
+    hipLaunchKernelGGL(lr_level_factors_kernel<T>, dim3(grid_for(N1 * M1)), dim3(256), 0, c->stream, static_cast<const T*>(dA), N1,
+                       int64_t(F), M1, off, w, p->jitter, int(normalize_a != 0), static_cast<T*>(fa));
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(lr_level_factors_kernel<T>, dim3(grid_for(N2 * M1)), dim3(256), 0, c->stream, static_cast<const T*>(dB), N2,
+                       int64_t(F), M1, off, static_cast<const double*>(nullptr), p->jitter, int((sym ? normalize_a : normalize_b) != 0),
+                       static_cast<T*>(fb));
+    HIPCHK(c, hipGetLastError());
+    const bool jit_diag = sym && normalize_a;         // kernels.py:431
+    if (!return_levels) {
+        hipLaunchKernelGGL(lr_scale_factors_kernel<T>, dim3(grid_for(N1 * F)), dim3(256), 0, c->stream, static_cast<const T*>(dA), N1,
+                           int64_t(F), M1, off, static_cast<const T*>(fa), -1, static_cast<T*>(sa), int64_t(F));
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(lr_scale_factors_kernel<T>, dim3(grid_for(N2 * F)), dim3(256), 0, c->stream, static_cast<const T*>(dB), N2,
+                           int64_t(F), M1, off, static_cast<const T*>(fb), -1, static_cast<T*>(sb), int64_t(F));
+        HIPCHK(c, hipGetLastError());
+        CHK(lr_gemm(c, static_cast<const T*>(sa), static_cast<const T*>(sb), N1, N2, F, F, F, static_cast<T*>(dout), N2));
+        if (jit_diag) {
+            hipLaunchKernelGGL(lr_add_jitter_diag_kernel<T>, dim3(grid_for(N1)), dim3(256), 0, c->stream, static_cast<T*>(dout), N1, M1,
+                               static_cast<const T*>(fa), static_cast<const T*>(fb), p->jitter, -1);
+            HIPCHK(c, hipGetLastError());
+        }
+    } else {
+        std::vector<int32_t> hoff(M1 + 1);
+        hoff[0] = 0; hoff[1] = 1;
+        if (M >= 1) hoff[2] = 1 + cc;
+        for (int m = 2; m <= M; ++m) hoff[m + 1] = hoff[m] + r;
+        for (int m = 0; m <= M; ++m) {
+            const int wdt = hoff[m + 1] - hoff[m];
+            hipLaunchKernelGGL(lr_scale_factors_kernel<T>, dim3(grid_for(N1 * wdt)), dim3(256), 0, c->stream, static_cast<const T*>(dA),
+                               N1, int64_t(F), M1, off, static_cast<const T*>(fa), m, static_cast<T*>(sa), int64_t(wdt));
+            HIPCHK(c, hipGetLastError());
+            hipLaunchKernelGGL(lr_scale_factors_kernel<T>, dim3(grid_for(N2 * wdt)), dim3(256), 0, c->stream, static_cast<const T*>(dB),
+                               N2, int64_t(F), M1, off, static_cast<const T*>(fb), m, static_cast<T*>(sb), int64_t(wdt));
+            HIPCHK(c, hipGetLastError());
+            T* om = static_cast<T*>(dout) + size_t(m) * N1 * N2;
+            CHK(lr_gemm(c, static_cast<const T*>(sa), static_cast<const T*>(sb), N1, N2, wdt, wdt, wdt, om, N2));
+            if (jit_diag) {
+                hipLaunchKernelGGL(lr_add_jitter_diag_kernel<T>, dim3(grid_for(N1)), dim3(256), 0, c->stream, om, N1, M1,
+                                   static_cast<const T*>(fa), static_cast<const T*>(fb), p->jitter, m);
+                HIPCHK(c, hipGetLastError());
+            }
+        }
+    }
+    CHK(out_done(c, out, dout, ob));
+    return finish(c);
+}
+
+template <typename T>
+int lr_kernel_diag_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* Phi, int64_t N, int32_t return_levels,
+                     void* out) {
+    const int M = p->num_levels, M1 = M + 1;
+    const int32_t* off;
+    int F;
+    CHK(lr_level_offsets(c, M, lr->num_components, lr->rank_bound, &off, &F));
+    const void* dP;
+    CHK(in_dev(c, B_IN0, Phi, sizeof(T) * size_t(N) * F, &dP));
+    const size_t ob = sizeof(T) * size_t(N) * (return_levels ? M1 : 1);
+    void* dout;
+    CHK(out_dev(c, B_OUT0, out, ob, &dout));
+    const double* w;
+    CHK(upload_weights(c, p, &w));
+    if (N > 0) {
+        hipLaunchKernelGGL(lr_level_diag_kernel<T>, dim3(grid_for(N * M1)), dim3(256), 0, c->stream, static_cast<const T*>(dP), N,
+                           int64_t(F), M1, off, w, int(return_levels != 0), static_cast<T*>(dout));
+        HIPCHK(c, hipGetLastError());
+    }
+    CHK(out_done(c, out, dout, ob));
+    return finish(c);
 }
 
 constexpr size_t TIMING_MAX_EVENTS = 8192;
@@ -2576,8 +2796,9 @@ int gpsig_kernel_K_seq_n_seq_covs(gpsig_ctx* c, const gpsig_params* p, const voi
 
 int gpsig_lr_gather_points(gpsig_ctx* c, const gpsig_params* p, const void* X, int64_t N, int32_t L, const int64_t* idx, int64_t R,
                            double* out_host) {
-    ENTER(c, p);
-    if (p->dtype != GPSIG_F64) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for float64 only");
+    ENTER_LR(c, p);
+    if (p->dtype != GPSIG_F64 && p->dtype != GPSIG_F32) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for float64 and float32");
+    const bool f32 = p->dtype == GPSIG_F32;      // float32 points, gathered into float64 landmarks (each value widened, then scaled)
     if (!idx || !out_host || R < 0) return fail(c, GPSIG_ERR_INVALID, "bad landmark request");
     for (int64_t k = 0; k < R; ++k)
         if (idx[k] < 0 || idx[k] >= N * L) return fail(c, GPSIG_ERR_INVALID, "landmark index out of range");
@@ -2585,14 +2806,18 @@ int gpsig_lr_gather_points(gpsig_ctx* c, const gpsig_params* p, const void* X, i
     CHK(scale_params(c, p, true, &s));
     const int d_eff = s.d_eff();
     const void* dX;
-    CHK(in_dev(c, B_IN0, X, sizeof(double) * size_t(N) * L * p->num_features, &dX));
+    CHK(in_dev(c, B_IN0, X, (f32 ? sizeof(float) : sizeof(double)) * size_t(N) * L * p->num_features, &dX));
     void *didx, *dout;
     CHK(ensure(c, B_LR2, sizeof(int64_t) * size_t(R) + 8, &didx));
     CHK(ensure(c, B_LR3, sizeof(double) * size_t(R) * d_eff + 8, &dout));
     if (R > 0) {
         HIPCHK(c, hipMemcpyAsync(didx, idx, sizeof(int64_t) * size_t(R), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(lr_gather_points_kernel<double>, dim3(grid_for(R * d_eff)), dim3(256), 0, c->stream,
-                           static_cast<const double*>(dX), L, s, static_cast<const int64_t*>(didx), R, static_cast<double*>(dout));
+        if (f32)
+            hipLaunchKernelGGL(lr_gather_points_f32_kernel, dim3(grid_for(R * d_eff)), dim3(256), 0, c->stream,
+                               static_cast<const float*>(dX), L, s, static_cast<const int64_t*>(didx), R, static_cast<double*>(dout));
+        else
+            hipLaunchKernelGGL(lr_gather_points_kernel<double>, dim3(grid_for(R * d_eff)), dim3(256), 0, c->stream,
+                               static_cast<const double*>(dX), L, s, static_cast<const int64_t*>(didx), R, static_cast<double*>(dout));
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(out_host, dout, sizeof(double) * size_t(R) * d_eff, hipMemcpyDeviceToHost, c->stream));
     }
@@ -2670,8 +2895,9 @@ int gpsig_lr_whitening(gpsig_ctx* c, const gpsig_params* p, const double* S_host
 }
 
 int gpsig_lr_seq_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L, void* Phi) {
-    ENTER(c, p);
+    ENTER_LR(c, p);
     CHK(lr_check(c, p, lr));
+    if (p->dtype == GPSIG_F32) return lr_seq_features_f32(c, p, lr, X, N, L, Phi);
     const int M = p->num_levels;
     ScaleParams s;
     CHK(scale_params(c, p, true, &s));
@@ -2785,8 +3011,9 @@ int gpsig_lr_seq_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowra
 
 int gpsig_lr_tens_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* Z, int64_t T, int32_t increments,
                            void* Phi) {
-    ENTER(c, p);
+    ENTER_LR(c, p);
     CHK(lr_check(c, p, lr));
+    if (p->dtype == GPSIG_F32) return lr_tens_features_f32(c, p, lr, Z, T, increments, Phi);
     const int M = p->num_levels, lt = M * (M + 1) / 2, E = increments ? 2 : 1;
     ScaleParams s;
     CHK(scale_params(c, p, true, &s));
@@ -2885,109 +3112,29 @@ int gpsig_lr_tens_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowr
 
 int gpsig_lr_kernel(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* PhiA, const void* PhiB, int64_t N1, int64_t N2,
                     int32_t normalize_a, int32_t normalize_b, int32_t return_levels, void* out) {
-    ENTER(c, p);
+    ENTER_LR(c, p);
     if (!lr) return fail(c, GPSIG_ERR_INVALID, "lowrank descriptor is NULL");
-    if (p->dtype != GPSIG_F64) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for float64 only");
-    const int M = p->num_levels, M1 = M + 1, cc = lr->num_components, r = lr->rank_bound;
-    const bool sym = PhiB == nullptr;
-    if (sym) N2 = N1;
-    const int32_t* off;
-    int F;
-    CHK(lr_level_offsets(c, M, cc, r, &off, &F));
-    const void *dA, *dB;
-    CHK(in_dev(c, B_IN0, PhiA, sizeof(double) * size_t(N1) * F, &dA));
-    if (sym) dB = dA; else CHK(in_dev(c, B_IN1, PhiB, sizeof(double) * size_t(N2) * F, &dB));
-    const size_t ob = sizeof(double) * size_t(N1) * N2 * (return_levels ? M1 : 1);
-    void* dout;
-    CHK(out_dev(c, B_OUT0, out, ob, &dout));
-    const double* w;
-    CHK(upload_weights(c, p, &w));
-    void *fa, *fb, *sa, *sb;
-    CHK(ensure(c, B_LR2, sizeof(double) * size_t(N1) * M1 + 8, &fa));
-    CHK(ensure(c, B_LR3, sizeof(double) * size_t(N2) * M1 + 8, &fb));
-    CHK(ensure(c, B_LR4, sizeof(double) * size_t(N1) * F + 8, &sa));
-    CHK(ensure(c, B_LR5, sizeof(double) * size_t(N2) * F + 8, &sb));
-    if (N1 <= 0 || N2 <= 0) return finish(c);
-    // per-row level factors: A side carries sigma*variances, both sides 1/sqrt(|Phi_m|^2 + jitter) when normalising
-    hipLaunchKernelGGL(lr_level_factors_kernel<double>, dim3(grid_for(N1 * M1)), dim3(256), 0, c->stream, static_cast<const double*>(dA), N1,
-                       int64_t(F), M1, off, w, p->jitter, int(normalize_a != 0), static_cast<double*>(fa));
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(lr_level_factors_kernel<double>, dim3(grid_for(N2 * M1)), dim3(256), 0, c->stream, static_cast<const double*>(dB), N2,
-                       int64_t(F), M1, off, static_cast<const double*>(nullptr), p->jitter, int((sym ? normalize_a : normalize_b) != 0),
-                       static_cast<double*>(fb));
-    HIPCHK(c, hipGetLastError());
-    const bool jit_diag = sym && normalize_a;         // kernels.py:431
-    if (!return_levels) {
-        hipLaunchKernelGGL(lr_scale_factors_kernel<double>, dim3(grid_for(N1 * F)), dim3(256), 0, c->stream, static_cast<const double*>(dA), N1,
-                           int64_t(F), M1, off, static_cast<const double*>(fa), -1, static_cast<double*>(sa), int64_t(F));
-        HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(lr_scale_factors_kernel<double>, dim3(grid_for(N2 * F)), dim3(256), 0, c->stream, static_cast<const double*>(dB), N2,
-                           int64_t(F), M1, off, static_cast<const double*>(fb), -1, static_cast<double*>(sb), int64_t(F));
-        HIPCHK(c, hipGetLastError());
-        CHK(lr_gemm(c, static_cast<const double*>(sa), static_cast<const double*>(sb), N1, N2, F, F, F, static_cast<double*>(dout), N2));
-        if (jit_diag) {
-            hipLaunchKernelGGL(lr_add_jitter_diag_kernel<double>, dim3(grid_for(N1)), dim3(256), 0, c->stream, static_cast<double*>(dout), N1, M1,
-                               static_cast<const double*>(fa), static_cast<const double*>(fb), p->jitter, -1);
-            HIPCHK(c, hipGetLastError());
-        }
-    } else {
-        std::vector<int32_t> hoff(M1 + 1);
-        hoff[0] = 0; hoff[1] = 1;
-        if (M >= 1) hoff[2] = 1 + cc;
-        for (int m = 2; m <= M; ++m) hoff[m + 1] = hoff[m] + r;
-        for (int m = 0; m <= M; ++m) {
-            const int wdt = hoff[m + 1] - hoff[m];
-            hipLaunchKernelGGL(lr_scale_factors_kernel<double>, dim3(grid_for(N1 * wdt)), dim3(256), 0, c->stream, static_cast<const double*>(dA),
-                               N1, int64_t(F), M1, off, static_cast<const double*>(fa), m, static_cast<double*>(sa), int64_t(wdt));
-            HIPCHK(c, hipGetLastError());
-            hipLaunchKernelGGL(lr_scale_factors_kernel<double>, dim3(grid_for(N2 * wdt)), dim3(256), 0, c->stream, static_cast<const double*>(dB),
-                               N2, int64_t(F), M1, off, static_cast<const double*>(fb), m, static_cast<double*>(sb), int64_t(wdt));
-            HIPCHK(c, hipGetLastError());
-            double* om = static_cast<double*>(dout) + size_t(m) * N1 * N2;
-            CHK(lr_gemm(c, static_cast<const double*>(sa), static_cast<const double*>(sb), N1, N2, wdt, wdt, wdt, om, N2));
-            if (jit_diag) {
-                hipLaunchKernelGGL(lr_add_jitter_diag_kernel<double>, dim3(grid_for(N1)), dim3(256), 0, c->stream, om, N1, M1,
-                                   static_cast<const double*>(fa), static_cast<const double*>(fb), p->jitter, m);
-                HIPCHK(c, hipGetLastError());
-            }
-        }
-    }
-    CHK(out_done(c, out, dout, ob));
-    return finish(c);
+    if (p->dtype == GPSIG_F32) return lr_kernel_t<float>(c, p, lr, PhiA, PhiB, N1, N2, normalize_a, normalize_b, return_levels, out);
+    if (p->dtype != GPSIG_F64) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for float64 and float32");
+    return lr_kernel_t<double>(c, p, lr, PhiA, PhiB, N1, N2, normalize_a, normalize_b, return_levels, out);
 }
 
 int gpsig_lr_kernel_diag(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* Phi, int64_t N, int32_t return_levels,
                          void* out) {
-    ENTER(c, p);
+    ENTER_LR(c, p);
     if (!lr) return fail(c, GPSIG_ERR_INVALID, "lowrank descriptor is NULL");
-    if (p->dtype != GPSIG_F64) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for float64 only");
-    const int M = p->num_levels, M1 = M + 1;
-    const int32_t* off;
-    int F;
-    CHK(lr_level_offsets(c, M, lr->num_components, lr->rank_bound, &off, &F));
-    const void* dP;
-    CHK(in_dev(c, B_IN0, Phi, sizeof(double) * size_t(N) * F, &dP));
-    const size_t ob = sizeof(double) * size_t(N) * (return_levels ? M1 : 1);
-    void* dout;
-    CHK(out_dev(c, B_OUT0, out, ob, &dout));
-    const double* w;
-    CHK(upload_weights(c, p, &w));
-    if (N > 0) {
-        hipLaunchKernelGGL(lr_level_diag_kernel<double>, dim3(grid_for(N * M1)), dim3(256), 0, c->stream, static_cast<const double*>(dP), N,
-                           int64_t(F), M1, off, w, int(return_levels != 0), static_cast<double*>(dout));
-        HIPCHK(c, hipGetLastError());
-    }
-    CHK(out_done(c, out, dout, ob));
-    return finish(c);
+    if (p->dtype == GPSIG_F32) return lr_kernel_diag_t<float>(c, p, lr, Phi, N, return_levels, out);
+    if (p->dtype != GPSIG_F64) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for float64 and float32");
+    return lr_kernel_diag_t<double>(c, p, lr, Phi, N, return_levels, out);
 }
 
 int gpsig_lr_draw(gpsig_ctx* c, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t sparsity, uint64_t seed,
                   const void* X, int64_t N, int32_t L, const void* X2, int64_t N2, int32_t L2, const void* Z, int64_t T, int32_t increments,
                   gpsig_lr_state** inout) {
-    ENTER(c, p);
+    ENTER_LR(c, p);
     using namespace gpsig;
     if (!inout) return fail(c, GPSIG_ERR_INVALID, "null state slot");
-    if (p->dtype != GPSIG_F64) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for float64 only");
+    if (p->dtype != GPSIG_F64 && p->dtype != GPSIG_F32) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for float64 and float32");
     if (c->ptr_mode != GPSIG_PTR_DEVICE) return fail(c, GPSIG_ERR_INVALID, "gpsig_lr_draw takes device pointers (the host-side draw is gpsig_amd/low_rank.py)");
     if (num_components < 1 || rank_bound < 1 || sparsity < 0 || sparsity > 2) return fail(c, GPSIG_ERR_INVALID, "bad low-rank sizes");
     if (num_components > LR_DRAW_MAX || rank_bound > LR_DRAW_MAX) return fail(c, GPSIG_ERR_UNSUPPORTED, "the device-side draw takes at most %d components / rank bound", LR_DRAW_MAX);
@@ -3020,9 +3167,15 @@ int gpsig_lr_draw(gpsig_ctx* c, const gpsig_params* p, int32_t num_components, i
     HIPCHK(c, hipMemsetAsync(st->info, 0, sizeof(int) * 4, c->stream));
     hipLaunchKernelGGL(lr_draw_indices_kernel, dim3(1), dim3(64), 0, c->stream, total, cc, key, uint32_t(LRS_LANDMARKS), st->idx);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(lr_gather_landmarks_kernel, dim3(grid_for(int64_t(cc) * d_eff)), dim3(256), 0, c->stream, st->idx, cc,
-                       static_cast<const double*>(Z), ztot, static_cast<const double*>(X), X ? N : 0, int(L), static_cast<const double*>(X2),
-                       X2 ? N2 : 0, int(L2), s, key, p->jitter, st->S, st->jd);
+    // float32 points: the landmarks are gathered widened to float64, and everything below is the float64 draw of the widened points
+    if (p->dtype == GPSIG_F32)
+        hipLaunchKernelGGL(lr_gather_landmarks_f32_kernel, dim3(grid_for(int64_t(cc) * d_eff)), dim3(256), 0, c->stream, st->idx, cc,
+                           static_cast<const float*>(Z), ztot, static_cast<const float*>(X), X ? N : 0, int(L), static_cast<const float*>(X2),
+                           X2 ? N2 : 0, int(L2), s, key, p->jitter, st->S, st->jd);
+    else
+        hipLaunchKernelGGL(lr_gather_landmarks_kernel, dim3(grid_for(int64_t(cc) * d_eff)), dim3(256), 0, c->stream, st->idx, cc,
+                           static_cast<const double*>(Z), ztot, static_cast<const double*>(X), X ? N : 0, int(L), static_cast<const double*>(X2),
+                           X2 ? N2 : 0, int(L2), s, key, p->jitter, st->S, st->jd);
     HIPCHK(c, hipGetLastError());
     // the projections depend on the seed only: they are drawn on a side stream while the main one decomposes the landmark Gram
     if (!c->side_stream) {

@@ -32,12 +32,13 @@ struct ScaleParams {
 
 // x~[n][t][fe]: observation t of sequence n after add_lags_to_sequences (gpsig/lags.py:41-63), division by
 // the lengthscales (kernels.py:357-358) and the lag weights gamma (kernels.py:360-361).  fe = lag * d_in + f.
-template <typename T>
-__device__ __forceinline__ T scaled_point(const T* __restrict__ Xn, int L, int t, int fe, const ScaleParams& P) {
+// In: the stored type of the points (float32 points are widened value by value when T is double: the result is that of the widened array)
+template <typename T, typename In = T>
+__device__ __forceinline__ T scaled_point(const In* __restrict__ Xn, int L, int t, int fe, const ScaleParams& P) {
     const int lag = fe / P.d_in, f = fe - lag * P.d_in;
     T v;
     if (lag == 0) {
-        v = Xn[int64_t(t) * P.d_in + f];
+        v = T(Xn[int64_t(t) * P.d_in + f]);
     } else {
         // lin_interp (gpsig/lags.py:7-38): left = the last grid time not later than the query (+jitter)
         const T denom = T(L - 1);
@@ -46,7 +47,7 @@ __device__ __forceinline__ T scaled_point(const T* __restrict__ Xn, int L, int t
         for (int i = L - 1; i >= 0; --i)
             if (!(T(i) / denom - tq > T(P.jitter))) { left = i; break; }  // lags.py:20-22
         const int right = left + 1 < L ? left + 1 : L - 1;              // lags.py:23 (never out of range for lags > 0)
-        const T xl = Xn[int64_t(left) * P.d_in + f], xr = Xn[int64_t(right) * P.d_in + f];
+        const T xl = T(Xn[int64_t(left) * P.d_in + f]), xr = T(Xn[int64_t(right) * P.d_in + f]);
         const T tl = T(left) / denom, tr = T(right) / denom;
         v = xl + (tq - tl) * (xr - xl) / (tr - tl);                     // lags.py:33
     }

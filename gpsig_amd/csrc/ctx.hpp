@@ -33,6 +33,7 @@ enum BufId {
     B_GR7B, B_TW0, B_TW1, B_TW2,
     B_SF0, B_SF1, B_SF2, B_SF3, B_SF4, B_SF5,                               // explicit level features (sig_feat_kernel.hpp): both sides, partial products, level diagonals                              // weighted tensor-vs-sequence sums: partial factor gradients; level arrays of the fallback
     B_SPEC,                                                    // spectral base-kernel table
+    B_LRF32,                                                   // low-rank mode, float32 calls: the state and the spectral table narrowed to float32
     B_TQ,                                                      // item counters of the Kzx tile kernel's persistent launch
     B_STASH,                                                   // what the fused reverse kernel needs of the forward recursion (gpsig_seq_gram_levels_stash)
     B_WD0, B_WD1, B_WD2, B_WD3, B_WD4, B_WD5, B_WD6, B_WD7, B_WD8, B_WD9, B_WD10,   // wide state spaces (wide_api.hip): augmented rows, kernel-argument chunks, their adjoints, lattice states

@@ -29,6 +29,21 @@ __global__ void lr_gather_points_kernel(const T* __restrict__ X, int L, ScalePar
     }
 }
 
+// The same from float32 points into float64 landmarks: each coordinate is widened before it is scaled, so the result is bitwise that of
+// lr_gather_points_kernel<double> on the widened array (the low-rank state is float64 whatever the points' type)
+__global__ void lr_gather_points_f32_kernel(const float* __restrict__ X, int L, ScaleParams P, const int64_t* __restrict__ idx, int64_t R,
+                                            double* __restrict__ out) {
+    const int d_eff = P.d_eff();
+    const int64_t total = R * d_eff;
+    for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < total; i += int64_t(gridDim.x) * blockDim.x) {
+        const int fe = int(i % d_eff);
+        const int64_t r = i / d_eff;
+        const int64_t n = idx[r] / L;
+        const int t = int(idx[r] % L);
+        out[i] = scaled_point<double, float>(X + n * int64_t(L) * P.d_in, L, t, fe, P);
+    }
+}
+
 // Base-kernel matrix of already scaled points: out[a][b] = kappa(A[a], B[b]); A (na, d), B (nb, d).
 template <typename T>
 __global__ void base_kernel_matrix_kernel(const T* __restrict__ A, const T* __restrict__ B, int64_t na, int64_t nb, int d, int kind,
@@ -359,6 +374,73 @@ __global__ __launch_bounds__(256, 2) void gemm_abt_f64_tiled_kernel(const double
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int64_t i = tile_i + wr * 64 + m * 16 + lk + 4 * r, j = tile_j + wc * 64 + n * 16 + li;
+                if (i < N1 && j < N2) C[i * ldc + j] = acc[m][n][r];
+            }
+}
+
+// The float32 product (low-rank Grams of float32 features): the same 128 x 128 tiles on v_mfma_f32_16x16x4_f32 -- exact float32 (a k-ordered
+// fmaf chain per output), at the float32 vector rate.  Operand maps as the float64 form (lane l: A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15]);
+// the C/D map is the standard one, NOT the float64 instruction's: result r of lane l is D[4 (l >> 4) + r][l & 15].  Rows padded to 17 floats.
+typedef float mfma_f32x4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256, 2) void gemm_abt_f32_tiled_kernel(const float* __restrict__ A, const float* __restrict__ B, int64_t N1,
+                                                                   int64_t N2, int K, int64_t lda, int64_t ldb, float* __restrict__ C,
+                                                                   int64_t ldc) {
+    __shared__ float As[GEMM_BM * GEMM_LDK];
+    __shared__ float Bs[GEMM_BN * GEMM_LDK];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wr = wave >> 1, wc = wave & 1;
+    const int li = lane & 15, lk = lane >> 4;
+    const int64_t tile_i = int64_t(blockIdx.y) * GEMM_BM, tile_j = int64_t(blockIdx.x) * GEMM_BN;
+    const int srow = tid >> 1, scol = (tid & 1) * 8;
+    const int64_t ai = tile_i + srow, bj = tile_j + srow;
+    const float* arow = A + (ai < N1 ? ai : 0) * lda;
+    const float* brow = B + (bj < N2 ? bj : 0) * ldb;
+    const bool aok = ai < N1, bok = bj < N2;
+    float pa[8], pb[8];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int k = k0 + scol + e;
+            pa[e] = (aok && k < K) ? arow[k] : 0.0f;
+            pb[e] = (bok && k < K) ? brow[k] : 0.0f;
+        }
+    };
+    mfma_f32x4 acc[4][4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc[m][n] = mfma_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    fetch(0);
+    for (int k0 = 0; k0 < K; k0 += GEMM_BK) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            As[srow * GEMM_LDK + scol + e] = pa[e];
+            Bs[srow * GEMM_LDK + scol + e] = pb[e];
+        }
+        __syncthreads();
+        if (k0 + GEMM_BK < K) fetch(k0 + GEMM_BK);
+#pragma unroll
+        for (int kk = 0; kk < GEMM_BK; kk += 4) {
+            float av[4], bv[4];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                av[m] = As[(wr * 64 + m * 16 + li) * GEMM_LDK + kk + lk];
+                bv[m] = Bs[(wc * 64 + m * 16 + li) * GEMM_LDK + kk + lk];
+            }
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m], bv[n], acc[m][n], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t i = tile_i + wr * 64 + m * 16 + 4 * lk + r, j = tile_j + wc * 64 + n * 16 + li;
                 if (i < N1 && j < N2) C[i * ldc + j] = acc[m][n][r];
             }
 }

@@ -110,9 +110,12 @@ static __global__ void __launch_bounds__(64) lr_draw_indices_kernel(int64_t tota
 
 // The landmark candidates are, in this order: the scaled components of Z (ztot rows of d_eff), the scaled observations of X (n1 * l1
 // rows), those of X2 (kernels.py:444-446, :562-563).  S[k][fe] = candidate idx[k];  jd[k] = jitter * uniform (low_rank_calculations.py:52).
-static __global__ void lr_gather_landmarks_kernel(const int64_t* __restrict__ idx, int c, const double* __restrict__ Z, int64_t ztot,
-                                                  const double* __restrict__ X, int64_t n1, int l1, const double* __restrict__ X2, int64_t n2, int l2,
-                                                  ScaleParams P, PhiloxKey key, double jitter, double* __restrict__ S, double* __restrict__ jd) {
+// In: the points' stored type.  Float32 points are widened value by value before any arithmetic, so the landmarks (and everything drawn from
+// them) are bitwise those of the same points widened to float64.
+template <typename In>
+__device__ __forceinline__ void lr_gather_landmarks_body(const int64_t* __restrict__ idx, int c, const In* __restrict__ Z, int64_t ztot,
+                                                         const In* __restrict__ X, int64_t n1, int l1, const In* __restrict__ X2, int64_t n2, int l2,
+                                                         const ScaleParams& P, PhiloxKey key, double jitter, double* __restrict__ S, double* __restrict__ jd) {
     const int d_eff = P.d_eff();
     const int64_t total = int64_t(c) * d_eff;
     for (int64_t e = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; e < total; e += int64_t(gridDim.x) * blockDim.x) {
@@ -121,7 +124,7 @@ static __global__ void lr_gather_landmarks_kernel(const int64_t* __restrict__ id
         double v;
         if (q < ztot) {                                                              // kernels.py:367-398 on one component
             const int lag = fe / P.d_in, f = fe - lag * P.d_in;
-            v = Z[q * d_eff + fe];
+            v = double(Z[q * d_eff + fe]);
             if (P.has_ls) {
                 v = v / P.lsv(f);
                 if (P.num_lags > 0) v = v * P.gamma[lag];
@@ -131,9 +134,9 @@ static __global__ void lr_gather_landmarks_kernel(const int64_t* __restrict__ id
             const bool first = q < n1 * l1;
             if (!first) q -= n1 * l1;
             const int l = first ? l1 : l2;
-            const double* A = first ? X : X2;
+            const In* A = first ? X : X2;
             const int64_t n = q / l;
-            v = scaled_point<double>(A + n * int64_t(l) * P.d_in, l, int(q - n * l), fe, P);
+            v = scaled_point<double, In>(A + n * int64_t(l) * P.d_in, l, int(q - n * l), fe, P);
         }
         S[e] = v;
         if (fe == 0) {
@@ -142,6 +145,16 @@ static __global__ void lr_gather_landmarks_kernel(const int64_t* __restrict__ id
             jd[k] = jitter * philox_u01(w[0], w[1]);
         }
     }
+}
+static __global__ void lr_gather_landmarks_kernel(const int64_t* __restrict__ idx, int c, const double* __restrict__ Z, int64_t ztot,
+                                                  const double* __restrict__ X, int64_t n1, int l1, const double* __restrict__ X2, int64_t n2, int l2,
+                                                  ScaleParams P, PhiloxKey key, double jitter, double* __restrict__ S, double* __restrict__ jd) {
+    lr_gather_landmarks_body<double>(idx, c, Z, ztot, X, n1, l1, X2, n2, l2, P, key, jitter, S, jd);
+}
+static __global__ void lr_gather_landmarks_f32_kernel(const int64_t* __restrict__ idx, int c, const float* __restrict__ Z, int64_t ztot,
+                                                      const float* __restrict__ X, int64_t n1, int l1, const float* __restrict__ X2, int64_t n2, int l2,
+                                                      ScaleParams P, PhiloxKey key, double jitter, double* __restrict__ S, double* __restrict__ jd) {
+    lr_gather_landmarks_body<float>(idx, c, Z, ztot, X, n1, l1, X2, n2, l2, P, key, jitter, S, jd);
 }
 
 // ---- symmetric eigendecomposition, n <= 64, one workgroup: cyclic Jacobi with a round-robin ordering ------------------------------

@@ -23,6 +23,7 @@ constexpr int LR_FUSED_MAX_SKETCHES = 7;            // levels 2 .. 8
 constexpr size_t LR_FUSED_MAX_LDS = 156 * 1024;     // of the 160 KB a CU has (one workgroup per CU at that size)
 
 struct LrFusedArgs {
+    using value_type = double;
     const double* X; int64_t N; int L;
     ScaleParams P;
     const double* S;        // landmarks (c, d_eff), scaled points
@@ -47,6 +48,7 @@ inline size_t lr_fused_lds_bytes(int c, int r, int d_eff, int L, int pad = 1) {
 // Feature map of inducing tensors (gpsig/kernels.py:285-311 _K_tens_lr_feat, signature_algs.py:194-222 tensor_kern_lr_feature),
 // one workgroup per tensor: its lt * E components are whitened and chained through the sketches in LDS.
 struct LrTensFusedArgs {
+    using value_type = double;
     const double* Z; int64_t T; int lt, E;      // Z (lt, T, E, d_eff) as the caller gives it
     ScaleParams P;
     const double* S; const double* Wh;
@@ -73,6 +75,48 @@ int lr_fused2_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid);
 
 // lr_fused_inst.hip: launches the kernel on `stream` with `grid` workgroups; returns the hipError_t of the launch
 int lr_fused_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, int variant);
+
+// ---- float32 forms (lr_fused_inst.hip: lr_seq_features_fused{,2}{,_spectral}_f32_kernel, lr_tens_features_fused{,_spectral}_f32_kernel).
+// The same bodies on float: points, landmarks, whitening, sketch values, spectral table and features in float32, phase 1 on the hardware
+// transcendentals.  The state stays float64 (drawn and whitened in float64); lr_narrow_launch converts what the kernels read once per call.
+struct LrEntryF32 { float val; int32_t i1, i2, pad; };  // 16 bytes as LrEntry: one s_load_dwordx4 per entry
+struct LrFusedSketchF32 { const int32_t* colptr; const LrEntryF32* ent; };
+
+struct LrFusedArgsF32 {
+    using value_type = float;
+    const float* X; int64_t N; int L;
+    ScaleParams P;
+    const float* S;
+    const float* Wh;
+    int c, r, M, difference, kind;
+    float p0, p1;
+    LrFusedSketchF32 sk[LR_FUSED_MAX_SKETCHES];
+    float* Phi; int F;
+    int lp;                 // row stride of the LDS arrays, in floats (odd)
+    int rows_b;
+    const float* spec;      // the spectral table in float32 (same layout as spectral_table()'s)
+};
+struct LrTensFusedArgsF32 {
+    using value_type = float;
+    const float* Z; int64_t T; int lt, E;
+    ScaleParams P;
+    const float* S; const float* Wh;
+    int c, r, M, kind;
+    float p0, p1;
+    LrFusedSketchF32 sk[LR_FUSED_MAX_SKETCHES];
+    float* Phi; int F;
+    const float* spec;
+};
+inline size_t lr_fused_lds_bytes_f32(int c, int r, int d_eff, int L, int pad = 1) { return lr_fused_lds_bytes(c, r, d_eff, L, pad) / 2; }
+inline size_t lr_fused2_lds_bytes_f32(int c, int r, int d_eff, int L, int pad = 1) { return lr_fused2_lds_bytes(c, r, d_eff, L, pad) / 2; }
+inline size_t lr_tens_fused_lds_bytes_f32(int c, int r, int d_eff, int lt, int E) { return lr_tens_fused_lds_bytes(c, r, d_eff, lt, E) / 2; }
+// the kind / spectral switch as the float64 launchers; fused2 where lr_fused2_ok, else the three-array form (one instance each: 512 threads,
+// 8 entries per scalar-load batch)
+int lr_fused_f32_launch(hipStream_t stream, const LrFusedArgsF32& A, unsigned grid, bool two_arrays);
+int lr_tens_fused_f32_launch(hipStream_t stream, const LrTensFusedArgsF32& A);
+// out[i] = float(in[i]) for n values, and the sketch entries (value narrowed, indices copied); returns the hipError_t of the launch
+int lr_narrow_launch(hipStream_t stream, const double* in, int64_t n, float* out);
+int lr_narrow_entries_launch(hipStream_t stream, const LrEntry* in, int64_t n, LrEntryF32* out);
 
 // lr_spectral_inst.hip: the same kernels with SignatureSpectral's kappa in phase 1 (A.kind == BASE_SPECTRAL; the launchers above hand over)
 int lr_fused_spectral_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, size_t lds);

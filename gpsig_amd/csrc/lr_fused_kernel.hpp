@@ -38,13 +38,61 @@ namespace gpsig {
 // Phase 1 of the spectral instances (SPEC): SignatureSpectral's kappa takes the coordinates of x - S_i, not (<x,S_i>, |x|^2, |S_i|^2);
 // the landmark row and the parameter table are wave-uniform (constant address space, as S and Wh).  The run-time family switch of
 // base_eval stays out of them and the spectral arithmetic out of the others (occupancy steps, above).
-template <int THREADS, int UNROLL, bool SPEC>
-__device__ __forceinline__ void lr_seq_features_fused_body(const LrFusedArgs& A) {
-    extern __shared__ double lr_lds[];
+// The bodies are templates on the argument block (LrFusedArgs: float64, LrFusedArgsF32: float32); T is its element type.
+// The dynamic LDS array of each element type has its own name (one translation unit holds both).
+template <typename T> __device__ __forceinline__ T* lr_dyn_lds();
+template <> __device__ __forceinline__ double* lr_dyn_lds<double>() { extern __shared__ double lr_lds[]; return lr_lds; }
+template <> __device__ __forceinline__ float* lr_dyn_lds<float>() { extern __shared__ float lr_lds_f32[]; return lr_lds_f32; }
+
+// SignatureSpectral's kappa in float32 (spectral_pair's arithmetic): exp on v_exp_f32 (kexp), cos on v_cos_f32, whose argument is in
+// revolutions -- cos(2 pi w2) = v_cos_f32(w2) -- and which loses accuracy away from zero: the phase is reduced first, w2 - rint(w2) in
+// [-1/2, 1/2] (exact in float32), so the error does not grow with the phase beyond that of w2 itself.
+template <typename TP, class FX, class FY>
+__device__ __forceinline__ float spectral_pair_f32(TP alpha, TP omega, TP gamma, int ld, int Q, int family, int d, FX&& xf, FY&& yf) {
+    float acc = 0.0f;
+    for (int q = 0; q < Q; ++q) {
+        float w1 = 0.0f, w2 = 0.0f;
+        for (int f = 0; f < d; ++f) {
+            const float diff = xf(f) - yf(f);
+            const float gd = gamma[q * ld + f] * diff;
+            w1 = fmaf(gd, gd, w1);
+            w2 = fmaf(omega[q * ld + f], diff, w2);
+        }
+        const float env = spectral_gauss(family, q, Q) ? kexp(-w1 / 2) : kexp(-sqrtf(w1) / 2);
+        acc = fmaf(alpha[q] * env, __builtin_amdgcn_cosf(w2 - rintf(w2)), acc);
+    }
+    return acc;
+}
+
+// kappa(x, S_i) for the families of base_eval in float32 (the float64 bodies keep their inline (<x,S_i>, |x|^2, |S_i|^2) form).  The distance
+// families (RBF, Matern) from the coordinate differences -- landmarks are points, so x == S_i occurs, and |x|^2 + |S_i|^2 - 2 <x,S_i> cancels there to a float32
+// rounding of |x|^2, which the square root of the Matern kernels lifts to ~1e-3.  x(fe) and s(fe) give the coordinates.
+GPSIG_HD bool lr_dist_kind(int kind) { return kind == BASE_RBF || kind == BASE_MATERN12 || kind == BASE_MATERN32 || kind == BASE_MATERN52; }
+template <class FX, class FS>
+__device__ __forceinline__ float lr_kappa_f32(int kind, float p0, float p1, int d_eff, float xs, FX&& x, FS&& s) {
+    using T = float;
+    if (lr_dist_kind(kind)) {
+        T dd = T(0);
+        for (int fe = 0; fe < d_eff; ++fe) { const T df = x(fe) - s(fe); dd = fma(df, df, dd); }
+        return base_eval<T>(kind, T(0), dd, T(0), p0, p1);              // dist = fma(-2, 0, dd + 0) = dd
+    }
+    T ip = T(0), ss = T(0);
+    for (int fe = 0; fe < d_eff; ++fe) {
+        const T y = s(fe);
+        ip = fma(x(fe), y, ip);
+        ss = fma(y, y, ss);
+    }
+    return base_eval<T>(kind, ip, xs, ss, p0, p1);
+}
+
+template <int THREADS, int UNROLL, bool SPEC, typename Args>
+__device__ __forceinline__ void lr_seq_features_fused_body(const Args& A) {
+    using T = typename Args::value_type;
+    T* const lr_lds = lr_dyn_lds<T>();
     const int lp = A.lp, c = A.c, r = A.r, L = A.L;
-    double* const U = lr_lds;                               // [c][lp]
-    double* bufA = U + size_t(c) * lp;                      // [rows_b][lp]
-    double* bufB = bufA + size_t(A.rows_b) * lp;            // [rows_b][lp]
+    T* const U = lr_lds;                                    // [c][lp]
+    T* bufA = U + size_t(c) * lp;                           // [rows_b][lp]
+    T* bufB = bufA + size_t(A.rows_b) * lp;                 // [rows_b][lp]
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr int NW = THREADS / 64;
@@ -53,36 +101,45 @@ __device__ __forceinline__ void lr_seq_features_fused_body(const LrFusedArgs& A)
     const int nchunk = (L + 63) / 64;
 
     for (int64_t n = blockIdx.x; n < A.N; n += gridDim.x) {
-        const double* Xn = A.X + n * int64_t(L) * A.P.d_in;
-        double* phi = A.Phi + n * int64_t(A.F);
+        const T* Xn = A.X + n * int64_t(L) * A.P.d_in;
+        T* phi = A.Phi + n * int64_t(A.F);
         // ---- phase 0: scaled observations, bufB[fe][t]
         for (int q = threadIdx.x; q < L * d_eff; q += THREADS) {
             const int t = q / d_eff, fe = q - t * d_eff;
-            bufB[fe * lp + t] = scaled_point<double>(Xn, L, t, fe, A.P);
+            bufB[fe * lp + t] = scaled_point<T>(Xn, L, t, fe, A.P);
         }
         __syncthreads();
         // ---- phase 1: kxs, bufA[i][t]
         for (int ch = 0; ch < nchunk; ++ch) {
             const int t = ch * 64 + lane;
             if (t < L) {
-                double xs = 0.0;
-                for (int fe = 0; fe < d_eff; ++fe) { const double x = bufB[fe * lp + t]; xs = fma(x, x, xs); }
+                T xs = T(0);
+                for (int fe = 0; fe < d_eff; ++fe) { const T x = bufB[fe * lp + t]; xs = fma(x, x, xs); }
                 for (int i = wave; i < c; i += NW) {
-                    const lr_const_ptr<double> Si = lr_as_const(A.S) + size_t(i) * d_eff;
+                    const lr_const_ptr<T> Si = lr_as_const(A.S) + size_t(i) * d_eff;
                     if constexpr (SPEC) {
-                        const lr_const_ptr<double> tab = lr_as_const(A.spec);
+                        const lr_const_ptr<T> tab = lr_as_const(A.spec);
                         const int Q = int(A.p0);
-                        bufA[i * lp + t] = spectral_pair(tab, tab + Q, tab + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff,
-                                                         [&](int f) { return bufB[f * lp + t]; }, [&](int f) { return Si[f]; });
+                        if constexpr (sizeof(T) == sizeof(float))
+                            bufA[i * lp + t] = spectral_pair_f32(tab, tab + Q, tab + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff,
+                                                                 [&](int f) { return bufB[f * lp + t]; }, [&](int f) { return Si[f]; });
+                        else
+                            bufA[i * lp + t] = spectral_pair(tab, tab + Q, tab + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff,
+                                                             [&](int f) { return bufB[f * lp + t]; }, [&](int f) { return Si[f]; });
                         continue;
                     }
-                    double ip = 0.0, ss = 0.0;
+                    if constexpr (sizeof(T) == sizeof(float)) {
+                        bufA[i * lp + t] = lr_kappa_f32(A.kind, A.p0, A.p1, d_eff, xs, [&](int f) { return bufB[f * lp + t]; },
+                                                        [&](int f) { return Si[f]; });
+                        continue;
+                    }
+                    T ip = T(0), ss = T(0);
                     for (int fe = 0; fe < d_eff; ++fe) {
-                        const double y = Si[fe];
+                        const T y = Si[fe];
                         ip = fma(bufB[fe * lp + t], y, ip);
                         ss = fma(y, y, ss);
                     }
-                    bufA[i * lp + t] = base_eval<double>(A.kind, ip, xs, ss, A.p0, A.p1);
+                    bufA[i * lp + t] = base_eval<T>(A.kind, ip, xs, ss, A.p0, A.p1);
                 }
             }
         }
@@ -91,9 +148,9 @@ __device__ __forceinline__ void lr_seq_features_fused_body(const LrFusedArgs& A)
         for (int ch = 0; ch < nchunk; ++ch) {
             const int t = ch * 64 + lane;
             if (t < L) {
-                const lr_const_ptr<double> Wh = lr_as_const(A.Wh);
+                const lr_const_ptr<T> Wh = lr_as_const(A.Wh);
                 for (int j = wave; j < c; j += NW) {
-                    double acc = 0.0;
+                    T acc = T(0);
 #pragma unroll 4
                     for (int i = 0; i < c; ++i) acc = fma(bufA[i * lp + t], Wh[size_t(i) * c + j], acc);
                     bufB[j * lp + t] = acc;
@@ -106,43 +163,43 @@ __device__ __forceinline__ void lr_seq_features_fused_body(const LrFusedArgs& A)
             const int t = ch * 64 + lane;
             if (t < l) {
                 for (int j = wave; j < c; j += NW) {
-                    const double f0 = bufB[j * lp + t];
+                    const T f0 = bufB[j * lp + t];
                     U[j * lp + t] = A.difference ? bufB[j * lp + t + 1] - f0 : f0;
                 }
             }
         }
         __syncthreads();
         // ---- level 1 and the exclusive running sums for level 2: thread = column
-        if (threadIdx.x == 0) phi[0] = 1.0;
+        if (threadIdx.x == 0) phi[0] = T(1);
         for (int j = threadIdx.x; j < c; j += THREADS) {
-            double run = 0.0;
-            const double* u = U + size_t(j) * lp;
-            double* e = bufA + size_t(j) * lp;
+            T run = T(0);
+            const T* u = U + size_t(j) * lp;
+            T* e = bufA + size_t(j) * lp;
             const bool more = A.M >= 2;
 #pragma unroll 8
             for (int t = 0; t < l; ++t) {
-                const double v = u[t];
+                const T v = u[t];
                 if (more) e[t] = run;
                 run += v;
             }
             phi[1 + j] = run;                                                                   // signature_algs.py:182
         }
         __syncthreads();
-        double* cur = bufA;
-        double* nxt = bufB;
+        T* cur = bufA;
+        T* nxt = bufB;
         for (int lev = 2; lev <= A.M; ++lev) {
             const lr_const_ptr<int32_t> colptr = lr_as_const(A.sk[lev - 2].colptr);
-            const lr_const_ptr<LrEntry> ent = lr_as_const(A.sk[lev - 2].ent);
+            const auto ent = lr_as_const(A.sk[lev - 2].ent);
             // P_lev[t][j] = sum_e val * U[t][i1] * E[t][i2]                                   low_rank_calculations.py:64-193
             for (int j = wave; j < r; j += NW) {
                 const int e0 = colptr[j], e1 = colptr[j + 1];
                 for (int ch = 0; ch < nchunk; ++ch) {
                     const int t = ch * 64 + lane;
                     const int tt = t < l ? t : 0;                 // idle lanes read a valid address
-                    double acc = 0.0;
+                    T acc = T(0);
 #pragma unroll UNROLL
                     for (int e = e0; e < e1; ++e) {
-                        const double val = ent[e].val;            // (member by member: an address-space-4 struct has no copy constructor)
+                        const T val = ent[e].val;            // (member by member: an address-space-4 struct has no copy constructor)
                         const int i1 = ent[e].i1, i2 = ent[e].i2;
                         acc = fma(val * U[i1 * lp + tt], cur[i2 * lp + tt], acc);
                     }
@@ -153,18 +210,18 @@ __device__ __forceinline__ void lr_seq_features_fused_body(const LrFusedArgs& A)
             const int off = 1 + c + (lev - 2) * r;
             const bool more = lev < A.M;
             for (int j = threadIdx.x; j < r; j += THREADS) {
-                double run = 0.0;
-                double* e = nxt + size_t(j) * lp;
+                T run = T(0);
+                T* e = nxt + size_t(j) * lp;
 #pragma unroll 8
                 for (int t = 0; t < l; ++t) {
-                    const double v = e[t];
+                    const T v = e[t];
                     if (more) e[t] = run;                                                       // signature_algs.py:186
                     run += v;
                 }
                 phi[off + j] = run;                                                             // :191
             }
             __syncthreads();
-            double* tmp = cur; cur = nxt; nxt = tmp;
+            T* tmp = cur; cur = nxt; nxt = tmp;
         }
         // cur / nxt are read again by the next sequence's phase 0 (bufB) only after the barrier above
     }
@@ -174,6 +231,10 @@ template <int THREADS, int UNROLL>
 __global__ __launch_bounds__(THREADS) void lr_seq_features_fused_kernel(LrFusedArgs A) { lr_seq_features_fused_body<THREADS, UNROLL, false>(A); }
 template <int THREADS, int UNROLL>
 __global__ __launch_bounds__(THREADS) void lr_seq_features_fused_spectral_kernel(LrFusedArgs A) { lr_seq_features_fused_body<THREADS, UNROLL, true>(A); }
+template <int THREADS, int UNROLL>
+__global__ __launch_bounds__(THREADS) void lr_seq_features_fused_f32_kernel(LrFusedArgsF32 A) { lr_seq_features_fused_body<THREADS, UNROLL, false>(A); }
+template <int THREADS, int UNROLL>
+__global__ __launch_bounds__(THREADS) void lr_seq_features_fused_spectral_f32_kernel(LrFusedArgsF32 A) { lr_seq_features_fused_body<THREADS, UNROLL, true>(A); }
 
 // ---- the same with TWO arrays in LDS instead of three --------------------------------------------------------------------
 // For sequences of at most 64 time steps and at most LR_FUSED2_COLS output columns per wavefront, a wavefront keeps the columns it
@@ -183,12 +244,13 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_fused_spectral_kernel
 // wavefronts again to hide the scalar-load latency of the sketch entries and the phases in which one wavefront works.
 //   W holds: the scaled observations (transposed) -> kxs -> E_2 (running sums of U) -> P_2 -> E_3 -> ...;  U: feat -> U.
 constexpr int LR_FUSED2_COLS = 8;
-template <int THREADS, int UNROLL, bool SPEC>
-__device__ __forceinline__ void lr_seq_features_fused2_body(const LrFusedArgs& A) {
-    extern __shared__ double lr_lds[];
+template <int THREADS, int UNROLL, bool SPEC, typename Args>
+__device__ __forceinline__ void lr_seq_features_fused2_body(const Args& A) {
+    using T = typename Args::value_type;
+    T* const lr_lds = lr_dyn_lds<T>();
     const int lp = A.lp, c = A.c, r = A.r, L = A.L;
-    double* const U = lr_lds;                               // [max(c, d_eff)][lp]
-    double* const W = U + size_t(A.rows_b) * lp;            // [rows_b][lp]
+    T* const U = lr_lds;                                    // [max(c, d_eff)][lp]
+    T* const W = U + size_t(A.rows_b) * lp;                 // [rows_b][lp]
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr int NW = THREADS / 64;
@@ -197,46 +259,54 @@ __device__ __forceinline__ void lr_seq_features_fused2_body(const LrFusedArgs& A
     const int t = lane, tt = t < l ? t : 0;
 
     for (int64_t n = blockIdx.x; n < A.N; n += gridDim.x) {
-        const double* Xn = A.X + n * int64_t(L) * A.P.d_in;
-        double* phi = A.Phi + n * int64_t(A.F);
+        const T* Xn = A.X + n * int64_t(L) * A.P.d_in;
+        T* phi = A.Phi + n * int64_t(A.F);
         // ---- scaled observations, U[fe][t]
         for (int q = threadIdx.x; q < L * d_eff; q += THREADS) {
             const int tq = q / d_eff, fe = q - tq * d_eff;
-            U[fe * lp + tq] = scaled_point<double>(Xn, L, tq, fe, A.P);
+            U[fe * lp + tq] = scaled_point<T>(Xn, L, tq, fe, A.P);
         }
         __syncthreads();
         // ---- kxs, W[i][t]
         if (t < L) {
-            double xs = 0.0;
-            for (int fe = 0; fe < d_eff; ++fe) { const double x = U[fe * lp + t]; xs = fma(x, x, xs); }
+            T xs = T(0);
+            for (int fe = 0; fe < d_eff; ++fe) { const T x = U[fe * lp + t]; xs = fma(x, x, xs); }
             for (int i = wave; i < c; i += NW) {
-                const lr_const_ptr<double> Si = lr_as_const(A.S) + size_t(i) * d_eff;
+                const lr_const_ptr<T> Si = lr_as_const(A.S) + size_t(i) * d_eff;
                 if constexpr (SPEC) {
-                    const lr_const_ptr<double> tab = lr_as_const(A.spec);
+                    const lr_const_ptr<T> tab = lr_as_const(A.spec);
                     const int Q = int(A.p0);
-                    W[i * lp + t] = spectral_pair(tab, tab + Q, tab + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff,
-                                                  [&](int f) { return U[f * lp + t]; }, [&](int f) { return Si[f]; });
+                    if constexpr (sizeof(T) == sizeof(float))
+                        W[i * lp + t] = spectral_pair_f32(tab, tab + Q, tab + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff,
+                                                          [&](int f) { return U[f * lp + t]; }, [&](int f) { return Si[f]; });
+                    else
+                        W[i * lp + t] = spectral_pair(tab, tab + Q, tab + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff,
+                                                      [&](int f) { return U[f * lp + t]; }, [&](int f) { return Si[f]; });
                     continue;
                 }
-                double ip = 0.0, ss = 0.0;
+                if constexpr (sizeof(T) == sizeof(float)) {
+                    W[i * lp + t] = lr_kappa_f32(A.kind, A.p0, A.p1, d_eff, xs, [&](int f) { return U[f * lp + t]; }, [&](int f) { return Si[f]; });
+                    continue;
+                }
+                T ip = T(0), ss = T(0);
                 for (int fe = 0; fe < d_eff; ++fe) {
-                    const double y = Si[fe];
+                    const T y = Si[fe];
                     ip = fma(U[fe * lp + t], y, ip);
                     ss = fma(y, y, ss);
                 }
-                W[i * lp + t] = base_eval<double>(A.kind, ip, xs, ss, A.p0, A.p1);
+                W[i * lp + t] = base_eval<T>(A.kind, ip, xs, ss, A.p0, A.p1);
             }
         }
         __syncthreads();
         // ---- whitening into U (the observations are no longer needed): feat[j][t] = sum_i W[i][t] * Wh[i][j]
         {
-            const lr_const_ptr<double> Wh = lr_as_const(A.Wh);
+            const lr_const_ptr<T> Wh = lr_as_const(A.Wh);
             const int tr = t < L ? t : 0;
 #pragma unroll
             for (int k = 0; k < LR_FUSED2_COLS; ++k) {
                 const int j = wave + k * NW;
                 if (j < c) {
-                    double acc = 0.0;
+                    T acc = T(0);
 #pragma unroll 4
                     for (int i = 0; i < c; ++i) acc = fma(W[i * lp + tr], Wh[size_t(i) * c + j], acc);
                     if (t < L) U[j * lp + t] = acc;
@@ -249,21 +319,21 @@ __device__ __forceinline__ void lr_seq_features_fused2_body(const LrFusedArgs& A
         for (int k = 0; k < LR_FUSED2_COLS; ++k) {
             const int j = wave + k * NW;
             if (j < c && A.difference) {
-                const double f0 = U[j * lp + tt], f1 = U[j * lp + tt + 1];
+                const T f0 = U[j * lp + tt], f1 = U[j * lp + tt + 1];
                 if (t < l) U[j * lp + t] = f1 - f0;
             }
         }
         __syncthreads();
         // ---- level 1 and the exclusive running sums for level 2 (thread = column), W = E_2
-        if (threadIdx.x == 0) phi[0] = 1.0;
+        if (threadIdx.x == 0) phi[0] = T(1);
         for (int j = threadIdx.x; j < c; j += THREADS) {
-            double run = 0.0;
-            const double* u = U + size_t(j) * lp;
-            double* e = W + size_t(j) * lp;
+            T run = T(0);
+            const T* u = U + size_t(j) * lp;
+            T* e = W + size_t(j) * lp;
             const bool more = A.M >= 2;
 #pragma unroll 8
             for (int q = 0; q < l; ++q) {
-                const double v = u[q];
+                const T v = u[q];
                 if (more) e[q] = run;
                 run += v;
             }
@@ -272,17 +342,17 @@ __device__ __forceinline__ void lr_seq_features_fused2_body(const LrFusedArgs& A
         __syncthreads();
         for (int lev = 2; lev <= A.M; ++lev) {
             const lr_const_ptr<int32_t> colptr = lr_as_const(A.sk[lev - 2].colptr);
-            const lr_const_ptr<LrEntry> ent = lr_as_const(A.sk[lev - 2].ent);
-            double out[LR_FUSED2_COLS];
+            const auto ent = lr_as_const(A.sk[lev - 2].ent);
+            T out[LR_FUSED2_COLS];
 #pragma unroll
             for (int k = 0; k < LR_FUSED2_COLS; ++k) {
                 const int j = wave + k * NW;
-                double acc = 0.0;
+                T acc = T(0);
                 if (j < r) {
                     const int e0 = colptr[j], e1 = colptr[j + 1];
 #pragma unroll UNROLL
                     for (int e = e0; e < e1; ++e) {
-                        const double val = ent[e].val;
+                        const T val = ent[e].val;
                         const int i1 = ent[e].i1, i2 = ent[e].i2;
                         acc = fma(val * U[i1 * lp + tt], W[i2 * lp + tt], acc);
                     }
@@ -299,11 +369,11 @@ __device__ __forceinline__ void lr_seq_features_fused2_body(const LrFusedArgs& A
             const int off = 1 + c + (lev - 2) * r;
             const bool more = lev < A.M;
             for (int j = threadIdx.x; j < r; j += THREADS) {
-                double run = 0.0;
-                double* e = W + size_t(j) * lp;
+                T run = T(0);
+                T* e = W + size_t(j) * lp;
 #pragma unroll 8
                 for (int q = 0; q < l; ++q) {
-                    const double v = e[q];
+                    const T v = e[q];
                     if (more) e[q] = run;                                                       // signature_algs.py:186
                     run += v;
                 }
@@ -318,6 +388,10 @@ template <int THREADS, int UNROLL>
 __global__ __launch_bounds__(THREADS) void lr_seq_features_fused2_kernel(LrFusedArgs A) { lr_seq_features_fused2_body<THREADS, UNROLL, false>(A); }
 template <int THREADS, int UNROLL>
 __global__ __launch_bounds__(THREADS) void lr_seq_features_fused2_spectral_kernel(LrFusedArgs A) { lr_seq_features_fused2_body<THREADS, UNROLL, true>(A); }
+template <int THREADS, int UNROLL>
+__global__ __launch_bounds__(THREADS) void lr_seq_features_fused2_f32_kernel(LrFusedArgsF32 A) { lr_seq_features_fused2_body<THREADS, UNROLL, false>(A); }
+template <int THREADS, int UNROLL>
+__global__ __launch_bounds__(THREADS) void lr_seq_features_fused2_spectral_f32_kernel(LrFusedArgsF32 A) { lr_seq_features_fused2_body<THREADS, UNROLL, true>(A); }
 
 // ---- inducing tensors ---------------------------------------------------------------------------------------------------
 // One workgroup per tensor t.  Rows (k, e) of the tensor's lt * E components: scaled (kernels.py:367-398), kappa against the
@@ -326,27 +400,28 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_fused2_spectral_kerne
 // column.  The sketches' entries come from L2 (they are the same for every tensor).  A few hundred multiply-adds per thread:
 // the point is one launch instead of about twenty.
 constexpr int LR_TENS_THREADS = 128;
-template <bool SPEC>
-__device__ __forceinline__ void lr_tens_features_fused_body(const LrTensFusedArgs& A) {
-    extern __shared__ double lr_lds[];
+template <bool SPEC, typename Args>
+__device__ __forceinline__ void lr_tens_features_fused_body(const Args& A) {
+    using T = typename Args::value_type;
+    T* const lr_lds = lr_dyn_lds<T>();
     const int c = A.c, r = A.r, lt = A.lt, E = A.E, d_eff = A.P.d_eff();
     const int rows = lt * E, w = c > r ? c : r;
-    double* const zs = lr_lds;                       // [rows][d_eff]
-    double* const kx = zs + rows * d_eff;            // [rows][c]
-    double* const ft = kx + rows * c;                // [rows][c]
-    double* const U = ft + rows * c;                 // [lt][c]
-    double* Ra = U + lt * c;                         // [w]
-    double* Rb = Ra + w;                             // [w]
+    T* const zs = lr_lds;                            // [rows][d_eff]
+    T* const kx = zs + rows * d_eff;                 // [rows][c]
+    T* const ft = kx + rows * c;                     // [rows][c]
+    T* const U = ft + rows * c;                      // [lt][c]
+    T* Ra = U + lt * c;                              // [w]
+    T* Rb = Ra + w;                                  // [w]
     const int64_t t = blockIdx.x;
-    double* phi = A.Phi + t * int64_t(A.F);
+    T* phi = A.Phi + t * int64_t(A.F);
     for (int q = threadIdx.x; q < rows * d_eff; q += LR_TENS_THREADS) {
         const int row = q / d_eff, fe = q - row * d_eff;
         const int k = row / E, e = row - k * E;
         const int lag = fe / A.P.d_in, f = fe - lag * A.P.d_in;
-        double x = A.Z[((int64_t(k) * A.T + t) * E + e) * d_eff + fe];
+        T x = A.Z[((int64_t(k) * A.T + t) * E + e) * d_eff + fe];
         if (A.P.has_ls) {                            // kernels.py:374-379 / :391-395
-            x = x / A.P.lsv(f);
-            if (A.P.num_lags > 0) x = x * A.P.gamma[lag];
+            x = x / T(A.P.lsv(f));
+            if (A.P.num_lags > 0) x = x * T(A.P.gamma[lag]);
         }
         zs[q] = x;
     }
@@ -355,21 +430,32 @@ __device__ __forceinline__ void lr_tens_features_fused_body(const LrTensFusedArg
         const int row = q / c, i = q - row * c;
         if constexpr (SPEC) {
             const int Q = int(A.p0);
-            kx[q] = spectral_pair(A.spec, A.spec + Q, A.spec + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff,
-                                  [&](int f) { return zs[row * d_eff + f]; }, [&](int f) { return A.S[size_t(i) * d_eff + f]; });
+            if constexpr (sizeof(T) == sizeof(float))
+                kx[q] = spectral_pair_f32(A.spec, A.spec + Q, A.spec + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff,
+                                          [&](int f) { return zs[row * d_eff + f]; }, [&](int f) { return A.S[size_t(i) * d_eff + f]; });
+            else
+                kx[q] = spectral_pair(A.spec, A.spec + Q, A.spec + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff,
+                                      [&](int f) { return zs[row * d_eff + f]; }, [&](int f) { return A.S[size_t(i) * d_eff + f]; });
             continue;
         }
-        double ip = 0.0, xs = 0.0, ss = 0.0;
+        if constexpr (sizeof(T) == sizeof(float)) {
+            if (lr_dist_kind(A.kind)) {                  // float32: the distance from the differences (lr_kappa)
+                kx[q] = lr_kappa_f32(A.kind, A.p0, A.p1, d_eff, T(0), [&](int f) { return zs[row * d_eff + f]; },
+                                    [&](int f) { return A.S[size_t(i) * d_eff + f]; });
+                continue;
+            }
+        }
+        T ip = T(0), xs = T(0), ss = T(0);
         for (int fe = 0; fe < d_eff; ++fe) {
-            const double x = zs[row * d_eff + fe], y = A.S[size_t(i) * d_eff + fe];
+            const T x = zs[row * d_eff + fe], y = A.S[size_t(i) * d_eff + fe];
             ip = fma(x, y, ip); xs = fma(x, x, xs); ss = fma(y, y, ss);
         }
-        kx[q] = base_eval<double>(A.kind, ip, xs, ss, A.p0, A.p1);
+        kx[q] = base_eval<T>(A.kind, ip, xs, ss, A.p0, A.p1);
     }
     __syncthreads();
     for (int q = threadIdx.x; q < rows * c; q += LR_TENS_THREADS) {
         const int row = q / c, j = q - row * c;
-        double acc = 0.0;
+        T acc = T(0);
         for (int i = 0; i < c; ++i) acc = fma(kx[row * c + i], A.Wh[size_t(i) * c + j], acc);
         ft[q] = acc;
     }
@@ -379,26 +465,26 @@ __device__ __forceinline__ void lr_tens_features_fused_body(const LrTensFusedArg
         U[q] = E == 2 ? ft[(k * 2 + 1) * c + j] - ft[(k * 2) * c + j] : ft[k * c + j];
     }
     __syncthreads();
-    if (threadIdx.x == 0) phi[0] = 1.0;
+    if (threadIdx.x == 0) phi[0] = T(1);
     int k = 0;
     for (int i = 1; i <= A.M; ++i) {
-        const double* R = U + k * c;
+        const T* R = U + k * c;
         int kw = c;
         ++k;
-        double* cur = Ra;
-        double* nxt = Rb;
+        T* cur = Ra;
+        T* nxt = Rb;
         for (int j = 1; j < i; ++j) {
-            const LrFusedSketch sk = A.sk[j - 1];
-            const double* Uk = U + k * c;
+            const auto sk = A.sk[j - 1];
+            const T* Uk = U + k * c;
             for (int jo = threadIdx.x; jo < r; jo += LR_TENS_THREADS) {
-                double acc = 0.0;
+                T acc = T(0);
                 for (int e = sk.colptr[jo]; e < sk.colptr[jo + 1]; ++e) acc = fma(sk.ent[e].val * Uk[sk.ent[e].i1], R[sk.ent[e].i2], acc);
                 cur[jo] = acc;
             }
             __syncthreads();
             R = cur;
             kw = r;
-            double* tmp = cur; cur = nxt; nxt = tmp;
+            T* tmp = cur; cur = nxt; nxt = tmp;
             ++k;
         }
         const int off = i == 1 ? 1 : 1 + c + (i - 2) * r;
@@ -409,5 +495,7 @@ __device__ __forceinline__ void lr_tens_features_fused_body(const LrTensFusedArg
 
 __global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_fused_kernel(LrTensFusedArgs A) { lr_tens_features_fused_body<false>(A); }
 __global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_fused_spectral_kernel(LrTensFusedArgs A) { lr_tens_features_fused_body<true>(A); }
+__global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_fused_f32_kernel(LrTensFusedArgsF32 A) { lr_tens_features_fused_body<false>(A); }
+__global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_fused_spectral_f32_kernel(LrTensFusedArgsF32 A) { lr_tens_features_fused_body<true>(A); }
 
 }  // namespace gpsig

@@ -134,6 +134,15 @@ def _launch_f64(*arrays):
     return L_
 
 
+def _launch_lr(kern, *arrays):
+    """_Launch for the low-rank entry points.  All-float32 arguments run the float32 feature and Gram kernels when the kernel object's
+    ``lr_native_f32`` is set (the state is drawn and whitened in float64 either way); otherwise they raise as _launch_f64 does, and
+    _f32_upcast computes the call in float64 and rounds it.  It does so too where the library has no float32 kernel for the call."""
+    if getattr(kern, "lr_native_f32", False):
+        return _Launch(*arrays)
+    return _launch_f64(*arrays)
+
+
 def _is_f32(a):
     return a is not None and hasattr(a, "dtype") and str(a.dtype).endswith("float32")
 
@@ -161,11 +170,17 @@ def _f32_upcast(method):
             o_, de = min(o_, M_), int(getattr(self, "num_features", 0)) * (int(getattr(self, "num_lags", 0) or 0) + 1)
             ho = (o_ == 2 and 3 <= M_ <= 5 and de <= 8) or (o_ in (3, 4) and M_ in (4, 5) and 4 < de <= 8)
         if not (all_f32 and (getattr(self, "num_features", 0) == 1 or getattr(self, "_base", None) == "cosine" or ho)):
+            # low-rank mode with lr_native_f32: a float32 attempt the library refuses is retried in float64 from the same random state,
+            # so that the retry draws what the float64 evaluation would have drawn
+            rng_state = (self.rng.bit_generator.state if all_f32 and getattr(self, "low_rank", False) and getattr(self, "lr_native_f32", False)
+                         else None)
             try:
                 return method(self, *args, **kwargs)
             except NotImplementedError:
                 if not all_f32:
                     raise
+                if rng_state is not None:
+                    self.rng.bit_generator.state = rng_state
         if getattr(self, "_graph_recording", False):
             # graphed(): the float64 copies, the float64 result and its rounding would be torch temporaries recorded inside the capture and
             # recycled after it -- a replay would write into whatever lives there then
@@ -321,6 +336,7 @@ class SignatureKernel:
         self._base_params = (0.0, 0.0)
         self.rng = np.random.default_rng()   # low-rank mode: source of landmarks and projections (the reference uses TF's global RNG)
         self.device_draw = True              # ... drawn on the device for CUDA tensors (gpsig_lr_draw), on the host for host arrays
+        self.lr_native_f32 = False           # low-rank mode, all-float32 arguments: float32 feature / Gram kernels (default: float64, rounded)
 
     # ---- validators (kernels.py:94-133) ------------------------------------------------------
     @staticmethod
@@ -483,9 +499,9 @@ class SignatureKernel:
         if not presliced:
             X, _ = self._slice(X, None)
         if self.low_rank and not self.normalization:
-            L_ = _launch_f64(X)
+            L_ = _launch_lr(self, X)
             st = lr_state or self.draw_low_rank(X=X, _implicit=True)
-            p = self._params(L_.keep)
+            p = self._params(L_.keep, L_.dtype_id)
             lr = st.as_c(L_.keep)
             Phi, pp, n = self._lr_features(L_, p, lr, X)
             out, optr = L_.out((self.num_levels + 1, n) if return_levels else (n,))
@@ -502,9 +518,9 @@ class SignatureKernel:
     def K_tens(self, Z, return_levels=False, increments=False, lr_state=None):
         """Reference: kernels.py:513-536.  (T, T) or (M+1, T, T); never normalised."""
         if self.low_rank:
-            L_ = _launch_f64(Z)
+            L_ = _launch_lr(self, Z)
             st = lr_state or self.draw_low_rank(Z=Z, increments=increments, _implicit=True)
-            p = self._params(L_.keep)
+            p = self._params(L_.keep, L_.dtype_id)
             lr = st.as_c(L_.keep)
             Phi, pp, t = self._lr_features(L_, p, lr, Z, tensors=True, increments=increments)
             out, optr = L_.out((self.num_levels + 1, t, t) if return_levels else (t, t))
@@ -523,9 +539,9 @@ class SignatureKernel:
         if not presliced:
             X, _ = self._slice(X, None)
         if self.low_rank:
-            L_ = _launch_f64(Z, X)
+            L_ = _launch_lr(self, Z, X)
             st = lr_state or self.draw_low_rank(X=X, Z=Z, increments=increments, _implicit=True)
-            p = self._params(L_.keep)
+            p = self._params(L_.keep, L_.dtype_id)
             lr = st.as_c(L_.keep)
             PZ, pz, t = self._lr_features(L_, p, lr, Z, tensors=True, increments=increments)
             PX, px, n = self._lr_features(L_, p, lr, X)
@@ -549,8 +565,8 @@ class SignatureKernel:
         if self.low_rank:
             # one shared draw of landmarks / projections for all three matrices (kernels.py:613-621)
             st = self.draw_low_rank(X=X, Z=Z, increments=increments)
-            L_ = _launch_f64(Z, X)
-            p = self._params(L_.keep)
+            L_ = _launch_lr(self, Z, X)
+            p = self._params(L_.keep, L_.dtype_id)
             lr = st.as_c(L_.keep)
             lv, nrm = int(bool(return_levels)), int(bool(self.normalization))
             m1 = (self.num_levels + 1,) if return_levels else ()
@@ -621,11 +637,11 @@ class SignatureKernel:
         per level (low_rank_calculations.py:76-193).  Returns a LowRankState that can be passed to K(..., lr_state=).
         A state returned to the caller is the caller's: later draws never write into it, for host arrays and CUDA tensors alike
         (only the per-evaluation draws of K / Kdiag / K_tens / ... with lr_state=None reuse one device block of the kernel object)."""
-        L_ = _launch_f64(X, X2, Z)
+        L_ = _launch_lr(self, X, X2, Z)
         if L_.device_mode and self.device_draw:
             return self._draw_low_rank_on_device(L_, X, X2, Z, increments, reuse=_implicit)
-        L_ = _launch_f64(X, X2)
-        p = self._params(L_.keep, _lib.F64)
+        L_ = _launch_lr(self, X, X2)
+        p = self._params(L_.keep, L_.dtype_id)          # float32 points are gathered into float64 landmarks
         total = 0
         seqs = []
         for A in (X, X2):
@@ -664,7 +680,7 @@ class SignatureKernel:
         reuse: draw into the kernel object's own state (the implicit draw of an evaluation that was given no lr_state: nobody else
         holds it, and a fresh device block per evaluation would be a hipMalloc -- a device-wide synchronisation -- each);
         otherwise a fresh state that belongs to the caller."""
-        p = self._params(L_.keep, _lib.F64)
+        p = self._params(L_.keep, L_.dtype_id)          # float32 points: the landmarks are widened, the draw is float64's
         n1, l1 = self._seq_dims(X) if X is not None else (0, 1)
         n2, l2 = self._seq_dims(X2) if X2 is not None else (0, 1)
         t = self._tens_dims(Z, increments) if Z is not None else 0
@@ -711,9 +727,9 @@ class SignatureKernel:
         return Phi, pp, n
 
     def _K_lr(self, X, X2, return_levels, lr_state):
-        L_ = _launch_f64(X, X2)
+        L_ = _launch_lr(self, X, X2)
         st = lr_state or self.draw_low_rank(X=X, X2=X2, _implicit=True)
-        p = self._params(L_.keep)
+        p = self._params(L_.keep, L_.dtype_id)
         lr = st.as_c(L_.keep)
         PA, pa, n1 = self._lr_features(L_, p, lr, X)
         if X2 is None:
@@ -728,9 +744,9 @@ class SignatureKernel:
     def _K_seq_n_seq_covs_lr(self, X, X2, full_X2_cov, return_levels, lr_state):
         """kernels.py:696-761, low-rank branch: level Grams of the factor matrices (HIP: features + fp64-MFMA GEMMs), then the
         normalisation / weighting of :706-761 as elementwise torch ops on the device."""
-        L_ = _launch_f64(X, X2)
+        L_ = _launch_lr(self, X, X2)
         st = lr_state or self.draw_low_rank(X=X, X2=X2, _implicit=True)
-        p = self._params(L_.keep)
+        p = self._params(L_.keep, L_.dtype_id)
         ones = np.ones(self.num_levels + 1)
         L_.keep.append(ones)
         p.sigma, p.variances = 1.0, ones.ctypes.data_as(C.POINTER(C.c_double))      # raw level Grams; weights are applied below
@@ -753,7 +769,7 @@ class SignatureKernel:
         dev = L_.dev if L_.device_mode else torch.device("cuda", 0)
         t = lambda a: a if _is_torch(a) else torch.as_tensor(a, device=dev)
         Kxx, Kxx2, K22 = t(Kxx), t(Kxx2), t(K22)
-        w = torch.as_tensor(float(self.sigma) * np.asarray(self.variances, dtype=np.float64), device=dev)
+        w = torch.as_tensor(float(self.sigma) * np.asarray(self.variances, dtype=np.float64), dtype=Kxx.dtype, device=dev)
         if self.normalization:
             Kxx = Kxx + JITTER * torch.eye(n1, dtype=Kxx.dtype, device=dev)[None]                   # :709
             dsq = torch.sqrt(torch.diagonal(Kxx, dim1=1, dim2=2))

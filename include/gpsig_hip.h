@@ -152,7 +152,8 @@ int gpsig_set_shard(gpsig_ctx* ctx, int index, int count);
  *   "lr_fused"    low-rank sequence features (gpsig_lr_seq_features): 1 (default) one fused kernel, a workgroup per sequence with
  *                 the (width, length) intermediates in LDS, wherever they fit -- two arrays where a wavefront can hold its output
  *                 columns in registers (at most 64 time steps, components and rank bound), three otherwise; 2 always the three-array
- *                 form; 0 one elementwise kernel per reference op
+ *                 form; 0 one elementwise kernel per reference op.  Float32 features (p->dtype = GPSIG_F32) have the two fused forms
+ *                 only: 0 answers GPSIG_ERR_UNSUPPORTED for them.  Also gpsig_lr_tens_features: 0 the multi-pass route.
  *   "wide"        (round 6) the wide-state-space route (csrc/wide_api.hip): kernel arguments by rocBLAS dgemm on augmented rows, fused
  *                 map / difference / recursion kernels, behind the levels, weighted-sum, fused-evaluation entry points and their gradients.
  *                 -1 (default) where the exact-shape kernels are not built or lose: Kzx beyond 8 columns, the sequence lattices beyond
@@ -283,7 +284,12 @@ int gpsig_kernel_K_seq_n_seq_covs(gpsig_ctx* ctx, const gpsig_params* p, const v
                                   int32_t return_levels, void* Kxx, void* Kxx2, void* Kx2x2);
 
 /* ---- low-rank mode (low_rank=True): gpsig/low_rank_calculations.py, gpsig/signature_algs.py:162-222,
- * gpsig/kernels.py:239-311, :424-426, :442-458, :499-501, :525-527, :560-574.  float64 only.
+ * gpsig/kernels.py:239-311, :424-426, :442-458, :499-501, :525-527, :560-574.
+ * Float types: the state (landmarks, whitening, projections) is float64 always.  p->dtype = GPSIG_F32 (float32 points, features and
+ * Grams) is accepted by gpsig_lr_seq_features / gpsig_lr_tens_features (the fused kernels only: option lr_fused != 0 and the float32
+ * LDS footprint within bounds, else GPSIG_ERR_UNSUPPORTED), gpsig_lr_kernel / gpsig_lr_kernel_diag (float32 factors in, float32 out),
+ * and gpsig_lr_draw / gpsig_lr_gather_points (float32 points, widened before any arithmetic: the state drawn is bitwise that of the
+ * widened points).  The spectral base kernel included.  Every other low-rank entry point is float64 only.
  *
  * The reference draws landmarks and random projections with TensorFlow's RNG inside the graph; here they are
  * drawn by the caller and passed in (all HOST pointers), which makes the device code deterministic:
@@ -328,7 +334,8 @@ void gpsig_lr_state_destroy(gpsig_lr_state* state);
 int gpsig_lr_state_sizes(gpsig_ctx* ctx, const gpsig_lr_state* state, int32_t* sizes /* 5: c, d', r, projections, Jacobi sweeps */, int32_t* nnz);
 int gpsig_lr_state_export(gpsig_ctx* ctx, const gpsig_lr_state* state, double* landmarks, double* jitter_diag, double* whitening,
                           double* eigenvalues, const gpsig_sketch* sketches);
-/* scaled / lagged observations number idx[0..R) (flat index n*L + t) of X -> out (R, d') on the HOST (landmark candidates) */
+/* scaled / lagged observations number idx[0..R) (flat index n*L + t) of X -> out (R, d') on the HOST (landmark candidates; float64 for
+ * float32 X too) */
 int gpsig_lr_gather_points(gpsig_ctx* ctx, const gpsig_params* p, const void* X, int64_t N, int32_t L, const int64_t* idx,
                            int64_t R, double* out_host);
 /* kappa(A, B) of already scaled points, all on the HOST: A (na, d'), B (nb, d') -> out (na, nb) */
@@ -369,7 +376,7 @@ int gpsig_lr_seq_features(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_low
 /* SignatureKernel._K_tens_lr_feat (kernels.py:285-311): Nystrom_map + tensor_kern_lr_feature.  Phi: (T, F). */
 int gpsig_lr_tens_features(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_lowrank* lr, const void* Z, int64_t T,
                            int32_t increments, void* Phi);
-/* Kernel matrix from factors: level Grams PhiA_m PhiB_m^T (fp64 MFMA), optional per-side level normalisation
+/* Kernel matrix from factors: level Grams PhiA_m PhiB_m^T (fp64 MFMA; float32 factors: v_mfma_f32_16x16x4_f32), optional per-side level normalisation
  * 1/sqrt(|Phi_m|^2 + jitter) (kernels.py:457-469, :574-581), sigma*variances, level sum.  PhiB == NULL: symmetric, with
  * the jitter of kernels.py:431 on the diagonal when normalising.  out: (N1, N2) or (M+1, N1, N2). */
 int gpsig_lr_kernel(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_lowrank* lr, const void* PhiA, const void* PhiB, int64_t N1,
