@@ -803,6 +803,47 @@ class _LrSeqFeatures(torch.autograd.Function):
 _SPECTRAL_FAMILY = {"rbf": 0, "exp": 1, "mixed": 2}
 
 
+class _LrSeqFeaturesSpectral(torch.autograd.Function):
+    """_LrSeqFeatures for SignatureSpectral, whose base-kernel parameters are trained: scaled sequences (N, L, d), S (c, d), Wh (c, c) and the
+    positive alpha (Q), omega (Q, d), gamma (Q, d) -> Phi, by gpsig_lr_seq_features_spectral_dev (the spectral fused feature kernels on a
+    table packed on the device); the reverse pass by gpsig_lr_seq_features_spectral_grad (csrc/lr_grad_api.hip: the spectral instance of
+    lr_seq_features_grad_kernel down to dkxs, then the spectral cross op's reverse kernels): gradients of all six tensors.  Raises
+    NotImplementedError outside the library's limits (the caller falls back to torch ops)."""
+
+    @staticmethod
+    def forward(ctx, Xs, S, Wh, alpha, omega, gamma, spec, family, sketches, r):
+        X, Sd, Whd, a, o, g = (_c(t) for t in (Xs, S, Wh, alpha, omega, gamma))
+        n, l, d = X.shape
+        cc = Sd.shape[0]
+        keep = []
+        p = spec.params(d, float(a.shape[0]), keep)
+        p.base_params[1] = float(_SPECTRAL_FAMILY[family])
+        arr = _sketch_array(sketches, keep)
+        F = 1 + cc + (spec.num_levels - 1) * int(r)
+        out = torch.empty((n, F), dtype=torch.float64, device=X.device)
+        _ctx_for(X).call("gpsig_lr_seq_features_spectral_dev", p, cc, int(r), len(sketches), arr, _ptr(X), n, l, _ptr(Sd), _ptr(Whd), _ptr(a),
+                         _ptr(o), _ptr(g), _ptr(out))
+        ctx.spec, ctx.family, ctx.sketches, ctx.r = spec, family, sketches, int(r)
+        ctx.dt = tuple(t.dtype for t in (Xs, S, Wh, alpha, omega, gamma))
+        ctx.save_for_backward(X, Sd, Whd, a, o, g)
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        X, Sd, Whd, a, o, g = ctx.saved_tensors
+        n, l, d = X.shape
+        cc = Sd.shape[0]
+        keep = []
+        p = ctx.spec.params(d, float(a.shape[0]), keep)
+        p.base_params[1] = float(_SPECTRAL_FAMILY[ctx.family])
+        arr = _sketch_array(ctx.sketches, keep)
+        G = _c(G)
+        grads = [torch.empty_like(t) for t in (X, Sd, Whd, a, o, g)]
+        _ctx_for(X).call("gpsig_lr_seq_features_spectral_grad", p, cc, ctx.r, len(ctx.sketches), arr, _ptr(X), n, l, _ptr(Sd), _ptr(Whd),
+                         _ptr(a), _ptr(o), _ptr(g), _ptr(G), *(_ptr(t) for t in grads))
+        return tuple(t.to(dt) for t, dt in zip(grads, ctx.dt)) + (None, None, None, None)
+
+
 class _SpectralCross(torch.autograd.Function):
     """SignatureSpectral's kappa(P, S) (kernels.py:921-942) for points P (n, d) and landmarks S (c, d) -> (n, c), by gpsig_spectral_cross; the
     reverse pass by gpsig_spectral_cross_grad: d points, d landmarks, d alpha, d omega, d gamma, the parameters read from device memory.
@@ -870,8 +911,8 @@ class _LowRankScope:
 
     def seq(self, Xs):
         """signature_algs.py:162-192 (with :191 summing P, as evidently intended).  (N, L, d') -> [(N, 1), (N, c), (N, r), ...].
-        Through the HIP feature kernel and its reverse pass (_LrSeqFeatures) where they are built; torch ops otherwise (long sequences
-        at large ranks, more than 64 components, module option ``lr_hip = False``)."""
+        Through the HIP feature kernel and its reverse pass (_LrSeqFeatures; SignatureSpectral: _LrSeqFeaturesSpectral) where they are
+        built; torch ops otherwise (long sequences at large ranks, more than 64 components, module option ``lr_hip = False``)."""
         key = id(Xs)
         if key not in self._seq and getattr(self.mod, "lr_hip", True) and Xs.is_cuda:
             mod, kern = self.mod, self.mod.kern
@@ -880,9 +921,13 @@ class _LowRankScope:
             L, d = int(Xs.shape[1]), int(Xs.shape[2])
             # what csrc/lr_grad_api.hip takes: four (width, L) arrays of a sequence in LDS, at most 64 components
             rows, lp = max(cc, r, d, 16), (L + 63) // 64 * 64 + 1
-            if kern._base != "spectral" and cc <= 64 and cc * d <= 4096 and 8 * lp * 4 * rows <= 156 * 1024 and M - 1 <= 7:
+            if cc <= 64 and cc * d <= 4096 and 8 * lp * 4 * rows <= 156 * 1024 and M - 1 <= 7:
                 try:
-                    Phi = _LrSeqFeatures.apply(Xs, self.S, self.Wh, mod.p0, mod._spec, self.host_sketches, r)
+                    if kern._base == "spectral":
+                        Phi = _LrSeqFeaturesSpectral.apply(Xs, self.S, self.Wh, positive(mod.raw_alpha), positive(mod.raw_omega),
+                                                           positive(mod.raw_sgamma), mod._spec, kern.family, self.host_sketches, r)
+                    else:
+                        Phi = _LrSeqFeatures.apply(Xs, self.S, self.Wh, mod.p0, mod._spec, self.host_sketches, r)
                     cuts = [1, cc] + [r] * (M - 1)
                     self._seq[key] = (Xs, list(torch.split(Phi, cuts, dim=1)))
                 except NotImplementedError:

@@ -33,6 +33,7 @@ enum BufId {
     B_GR7B, B_TW0, B_TW1, B_TW2,
     B_SF0, B_SF1, B_SF2, B_SF3, B_SF4, B_SF5,                               // explicit level features (sig_feat_kernel.hpp): both sides, partial products, level diagonals                              // weighted tensor-vs-sequence sums: partial factor gradients; level arrays of the fallback
     B_SPEC,                                                    // spectral base-kernel table
+    B_SPECD, B_LRDK,                                           // low-rank spectral training path (lr_grad_api.hip): the table packed on the device, dkxs
     B_LRF32,                                                   // low-rank mode, float32 calls: the state and the spectral table narrowed to float32
     B_TQ,                                                      // item counters of the Kzx tile kernel's persistent launch
     B_STASH,                                                   // what the fused reverse kernel needs of the forward recursion (gpsig_seq_gram_levels_stash)

@@ -127,5 +127,12 @@ int lr_seq_cross_spectral_launch(hipStream_t stream, const double* X, int64_t N,
                                  const double* spec, double* out);
 int lr_tens_cross_spectral_launch(hipStream_t stream, const double* Z, int64_t rows, ScaleParams P, const double* S, int c, int Q, int family,
                                   const double* spec, double* out);
+// ... and the reverse pass of kappa(P, S) (n points, c landmarks, the parameters alpha (Q), omega (Q, d), gamma (Q, d) on the device) given
+// G = dL/dK (n, c): dP (n, d) overwritten; dS (c, d), dalpha, domega, dgamma overwritten, or added to with `accumulate` (the chunks of one
+// call, in order); `part` holds spectral_cross_grad_part_doubles(n, c, d, Q) doubles of per-workgroup partial sums.  Returns the hipError_t.
+size_t spectral_cross_grad_part_doubles(int64_t n, int c, int d, int Q);
+int spectral_cross_grad_launch(hipStream_t stream, int Q, int family, int d, const double* P, int64_t n, const double* S, int c,
+                               const double* alpha, const double* omega, const double* gamma, const double* G, double* dP, double* part,
+                               double* dS, double* dalpha, double* domega, double* dgamma, bool accumulate);
 
 }  // namespace gpsig

@@ -6,6 +6,14 @@
 // gpsig_lr_draw state) because the evaluation path's caller owns them; the training path's two entry points take device pointers:
 //     gpsig_lr_seq_features_dev    Phi (N, F) = the fused feature kernel of lr_fused_kernel.hpp on (X, S, Wh)
 //     gpsig_lr_seq_features_grad   dPhi (N, F) -> dX, dS, dWh, d base parameter: lr_grad_kernel.hpp
+// and SignatureSpectral's pair, whose parameters (alpha, omega, gamma) are trained and so come as device pointers too:
+//     gpsig_lr_seq_features_spectral_dev    Phi by the spectral fused instances on a table packed on the device (no host round trip)
+//     gpsig_lr_seq_features_spectral_grad   lr_seq_features_grad_spectral_kernel: dPhi -> dWh and dkxs (N, L, c) in scratch; then the
+//                                           spectral cross op's reverse kernels: dkxs -> dX, dS, dalpha, domega, dgamma
+// dkxs takes N L c doubles.  Above LR_SPECTRAL_DKXS_BUDGET bytes the sequences go in chunks that fit it: each chunk's dS and parameter sums
+// are added to the outputs in chunk order, the dWh partials of all chunks are reduced once in workgroup order -- deterministic either way.
+// Scratch: B_GR0 dWh partials, B_GR1 the per-workgroup E_i and kxs, B_LRDK dkxs, B_GR2 the cross op's partials (own buffers: none of them
+// can be resized while another one's reader is queued; ensure() waits for the stream before it frees anything anyway).
 // The projections of an evaluation are value-independent random objects: they come from the host once per draw, are kept on the
 // device by content (with the two transposed copies the reverse pass gathers over) and reused by every call that passes the same ones.
 #include "ctx.hpp"
@@ -22,6 +30,8 @@ int lr_fused2_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid);
 }
 
 namespace {
+
+constexpr size_t LR_SPECTRAL_DKXS_BUDGET = size_t(256) << 20;      // bytes of dkxs per chunk of sequences (spectral reverse pass)
 
 uint64_t fnv(uint64_t h, const void* p, size_t n) {
     const unsigned char* b = static_cast<const unsigned char*>(p);
@@ -112,12 +122,25 @@ int upload_sketches(gpsig_ctx* c, int cc, int r, int nsk, const gpsig_sketch* sk
     return GPSIG_OK;
 }
 
-int check(gpsig_ctx* c, const gpsig_params* p, int cc, int r, int nsk) {
+int check(gpsig_ctx* c, const gpsig_params* p, int cc, int r, int nsk, bool spectral = false) {
     if (!c) return GPSIG_ERR_INVALID;
     if (!p) return fail(c, GPSIG_ERR_INVALID, "params is NULL");
     if (p->dtype != GPSIG_F64) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for float64 only");
-    if (p->base_kernel == GPSIG_BASE_SPECTRAL) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is not built for the spectral base kernel");
-    if (p->base_kernel < GPSIG_BASE_LINEAR || p->base_kernel > GPSIG_BASE_MATERN52) return fail(c, GPSIG_ERR_INVALID, "unknown base kernel %d", p->base_kernel);
+    if (spectral) {                  // the spectral entry points: the limits of the reverse pass and of the cross op, UNSUPPORTED beyond them
+        if (p->base_kernel != GPSIG_BASE_SPECTRAL) return fail(c, GPSIG_ERR_INVALID, "the spectral entry points take the spectral base kernel");
+        const int Q = int(p->base_params[0]), family = int(p->base_params[1]), d = p->num_features;
+        if (Q < 1 || double(Q) != p->base_params[0] || family < 0 || family > 2 || double(family) != p->base_params[1])
+            return fail(c, GPSIG_ERR_INVALID, "spectral kernel: bad number of components / family");
+        if (Q > 64) return fail(c, GPSIG_ERR_UNSUPPORTED, "the spectral training path is built for at most 64 components");
+        if (d > SPECTRAL_STRIDE) return fail(c, GPSIG_ERR_UNSUPPORTED, "the spectral base kernel is built for at most %d features", int(SPECTRAL_STRIDE));
+        if (p->num_lags != 0 || (p->order != 1 && p->num_levels > 1)) return fail(c, GPSIG_ERR_UNSUPPORTED, "the spectral training path is built for order 1 without lags");
+        if (nsk > LR_FUSED_MAX_SKETCHES) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for num_levels <= %d", LR_FUSED_MAX_SKETCHES + 1);
+        if (cc > 64 || int64_t(cc) * d > int64_t(LR_GRAD_KS) * LR_GRAD_THREADS)
+            return fail(c, GPSIG_ERR_UNSUPPORTED, "the spectral training path is built for num_components <= 64 and num_components x columns <= %d", LR_GRAD_KS * LR_GRAD_THREADS);
+    } else if (p->base_kernel == GPSIG_BASE_SPECTRAL) {
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is not built for the spectral base kernel");
+    }
+    if (!spectral && (p->base_kernel < GPSIG_BASE_LINEAR || p->base_kernel > GPSIG_BASE_MATERN52)) return fail(c, GPSIG_ERR_INVALID, "unknown base kernel %d", p->base_kernel);
     if (p->num_levels < 1) return fail(c, GPSIG_ERR_INVALID, "num_levels must be >= 1");
     if (p->order != 1 && p->num_levels > 1) return fail(c, GPSIG_ERR_UNSUPPORTED, "Low-rank mode not implemented for order higher than 1.");
     if (cc < 1 || r < 1) return fail(c, GPSIG_ERR_INVALID, "num_components and rank_bound must be positive");
@@ -126,6 +149,24 @@ int check(gpsig_ctx* c, const gpsig_params* p, int cc, int r, int nsk) {
     if (p->num_features < 1 || p->num_lags != 0) return fail(c, GPSIG_ERR_INVALID, "the level primitives take their columns as they come (num_lags = 0)");
     HIPCHK(c, hipSetDevice(c->device));
     return GPSIG_OK;
+}
+
+// alpha (Q), omega (Q, d), gamma (Q, d) -> the table layout of the spectral fused instances: alpha[Q], omega[Q][SPECTRAL_STRIDE],
+// gamma[Q][SPECTRAL_STRIDE], zero beyond the d features
+__global__ __launch_bounds__(256) void lr_spectral_pack_kernel(const double* __restrict__ alpha, const double* __restrict__ omega,
+                                                               const double* __restrict__ gamma, int Q, int d, double* __restrict__ tab) {
+    const int n = Q * (1 + 2 * SPECTRAL_STRIDE);
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < n; q += gridDim.x * blockDim.x) {
+        double v = 0.0;
+        if (q < Q) {
+            v = alpha[q];
+        } else {
+            const int k = q - Q, which = k / (Q * SPECTRAL_STRIDE), rem = k - which * Q * SPECTRAL_STRIDE;
+            const int row = rem / SPECTRAL_STRIDE, f = rem - row * SPECTRAL_STRIDE;
+            if (f < d) v = (which ? gamma : omega)[row * d + f];
+        }
+        tab[q] = v;
+    }
 }
 
 }  // namespace
@@ -208,6 +249,119 @@ int gpsig_lr_seq_features_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, 
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(lr_grad_reduce_kernel, dim3(unsigned((width + 255) / 256)), dim3(256), 0, c->stream, static_cast<const double*>(part), int(grid), width,
                        gS, int64_t(cc) * d, gWh, int64_t(cc) * cc, g_base);
+    HIPCHK(c, hipGetLastError());
+    return GPSIG_OK;
+}
+
+
+int gpsig_lr_seq_features_spectral_dev(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches,
+                                       const void* X, int64_t N, int32_t L, const double* S, const double* Wh, const double* alpha,
+                                       const double* omega, const double* gamma, void* Phi) {
+    CHK(check(c, p, cc, r, nsk, true));
+    if (N < 0 || L < 1 || (N > 0 && (!X || !S || !Wh || !alpha || !omega || !gamma || !Phi))) return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
+    const int M = p->num_levels, d = p->num_features, F = 1 + cc + (M - 1) * r, Q = int(p->base_params[0]);
+    // the evaluation path's choice of form (api.hip): the two-array kernel where it is built, else the three-array one
+    const bool two = c->lr_fused == 1 && lr_fused2_ok(cc, r, L);
+    const size_t lds = two ? lr_fused2_lds_bytes(cc, r, d, L, c->lr_fused_pad) : lr_fused_lds_bytes(cc, r, d, L, c->lr_fused_pad);
+    if (lds > LR_FUSED_MAX_LDS) return fail(c, GPSIG_ERR_UNSUPPORTED, "a sequence's low-rank arrays (%zu bytes) exceed the LDS", lds);
+    LrGradSketch gs[LR_FUSED_MAX_SKETCHES];
+    CHK(upload_sketches(c, cc, r, nsk, sketches, gs));
+    if (N == 0) return GPSIG_OK;
+    void* tab;
+    const int ntab = Q * (1 + 2 * SPECTRAL_STRIDE);
+    CHK(ensure(c, B_SPECD, sizeof(double) * size_t(ntab) + 64, &tab));
+    hipLaunchKernelGGL(lr_spectral_pack_kernel, dim3(unsigned((ntab + 255) / 256)), dim3(256), 0, c->stream, alpha, omega, gamma, Q, d,
+                       static_cast<double*>(tab));
+    HIPCHK(c, hipGetLastError());
+    LrFusedArgs A;
+    memset(&A, 0, sizeof(A));
+    A.X = static_cast<const double*>(X); A.N = N; A.L = L;
+    A.P.d_in = d;
+    A.S = S; A.Wh = Wh;
+    A.c = cc; A.r = r; A.M = M; A.difference = p->difference; A.kind = int(GPSIG_BASE_SPECTRAL);
+    A.p0 = Q; A.p1 = p->base_params[1];
+    A.spec = static_cast<const double*>(tab);
+    for (int i = 0; i < nsk; ++i) A.sk[i] = LrFusedSketch{gs[i].colptr, gs[i].ent};
+    A.Phi = static_cast<double*>(Phi); A.F = F;
+    A.lp = lr_fused_stride(L, c->lr_fused_pad);
+    A.rows_b = std::max(std::max(cc, r), d);
+    const unsigned grid = unsigned(N < (int64_t(1) << 20) ? N : (int64_t(1) << 20));
+    const int rc = two ? lr_fused2_launch(c->stream, A, grid) : lr_fused_launch(c->stream, A, grid, c->lr_fused_variant);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "fused low-rank spectral feature kernel: %s", hipGetErrorString(hipError_t(rc)));
+    return GPSIG_OK;
+}
+
+int gpsig_lr_seq_features_spectral_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches,
+                                        const void* X, int64_t N, int32_t L, const double* S, const double* Wh, const double* alpha,
+                                        const double* omega, const double* gamma, const void* dPhi, void* gX, double* gS, double* gWh,
+                                        double* dalpha, double* domega, double* dgamma) {
+    CHK(check(c, p, cc, r, nsk, true));
+    if (N < 0 || L < 1 || !gS || !gWh || !dalpha || !domega || !dgamma ||
+        (N > 0 && (!X || !S || !Wh || !alpha || !omega || !gamma || !dPhi || !gX)))
+        return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
+    const int M = p->num_levels, d = p->num_features, F = 1 + cc + (M - 1) * r, Q = int(p->base_params[0]), family = int(p->base_params[1]);
+    const size_t lds = lr_grad_lds_bytes(cc, r, d, L, c->lr_fused_pad);
+    if (lds > LR_FUSED_MAX_LDS) return fail(c, GPSIG_ERR_UNSUPPORTED, "a sequence's low-rank arrays (%zu bytes) exceed the LDS in the reverse pass", lds);
+    LrGradSketch gs[LR_FUSED_MAX_SKETCHES];
+    CHK(upload_sketches(c, cc, r, nsk, sketches, gs));
+    if (N == 0) {
+        CHK(zero_async(c, gS, sizeof(double) * size_t(cc) * d));
+        CHK(zero_async(c, gWh, sizeof(double) * size_t(cc) * cc));
+        CHK(zero_async(c, dalpha, sizeof(double) * size_t(Q)));
+        CHK(zero_async(c, domega, sizeof(double) * size_t(Q) * d));
+        CHK(zero_async(c, dgamma, sizeof(double) * size_t(Q) * d));
+        return GPSIG_OK;
+    }
+    // sequences per chunk: dkxs of a chunk within the budget
+    const int64_t per_seq = int64_t(L) * cc * int64_t(sizeof(double));
+    const int64_t nb = std::min<int64_t>(N, std::max<int64_t>(1, int64_t(LR_SPECTRAL_DKXS_BUDGET) / per_seq));
+    const int l = p->difference ? L - 1 : L;
+    const unsigned gmax = unsigned(nb < 512 ? nb : 512);              // as the other families' reverse pass
+    const int64_t kxs_off = (int64_t(cc) + int64_t(M > 2 ? M - 2 : 0) * r) * (l > 0 ? l : 1);
+    const int64_t escr_stride = kxs_off + int64_t(cc) * L + 8;
+    int64_t nparts = 0;                                                // workgroups over all chunks: one dWh partial each
+    for (int64_t n0 = 0; n0 < N; n0 += nb) nparts += std::min<int64_t>(N - n0, 512);
+    void *part, *escr, *dk, *cpart;
+    CHK(ensure(c, B_GR0, sizeof(double) * size_t(nparts) * size_t(cc) * cc + 64, &part));
+    CHK(ensure(c, B_GR1, sizeof(double) * size_t(gmax) * size_t(escr_stride) + 64, &escr));
+    CHK(ensure(c, B_LRDK, sizeof(double) * size_t(nb) * size_t(L) * cc + 64, &dk));
+    CHK(ensure(c, B_GR2, sizeof(double) * spectral_cross_grad_part_doubles(nb * L, cc, d, Q) + 64, &cpart));
+    LrGradSpectralArgs A;
+    memset(&A, 0, sizeof(A));
+    A.L = L; A.d = d;
+    A.S = S; A.Wh = Wh;
+    A.c = cc; A.r = r; A.M = M; A.difference = p->difference; A.kind = int(GPSIG_BASE_SPECTRAL);
+    A.p0 = Q; A.p1 = family;
+    for (int i = 0; i < nsk; ++i) A.sk[i] = gs[i];
+    A.F = F;
+    A.escr = static_cast<double*>(escr); A.escr_stride = escr_stride;
+    A.lp = lr_fused_stride(L, c->lr_fused_pad);
+    A.rows_b = std::max(std::max(std::max(cc, r), d), 16);
+    A.alpha = alpha; A.omega = omega; A.gamma = gamma;
+    A.dkxs = static_cast<double*>(dk); A.kxs_off = kxs_off;
+    const bool wide = c->lr_grad_threads != 512;
+    const void* kern = wide ? reinterpret_cast<const void*>(lr_seq_features_grad_spectral_kernel<1024>)
+                            : reinterpret_cast<const void*>(lr_seq_features_grad_spectral_kernel<512>);
+    if (lds > 48 * 1024) HIPCHK(c, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+    int64_t at = 0;
+    for (int64_t n0 = 0; n0 < N; n0 += nb) {
+        const int64_t nn = std::min(nb, N - n0);
+        const unsigned grid = unsigned(nn < 512 ? nn : 512);
+        const double* Xc = static_cast<const double*>(X) + n0 * int64_t(L) * d;
+        A.X = Xc; A.N = nn;
+        A.dPhi = static_cast<const double*>(dPhi) + n0 * int64_t(F);
+        A.part = static_cast<double*>(part) + at * int64_t(cc) * cc;
+        if (wide) hipLaunchKernelGGL(lr_seq_features_grad_spectral_kernel<1024>, dim3(grid), dim3(1024), lds, c->stream, A);
+        else hipLaunchKernelGGL(lr_seq_features_grad_spectral_kernel<512>, dim3(grid), dim3(512), lds, c->stream, A);
+        HIPCHK(c, hipGetLastError());
+        const int rc = spectral_cross_grad_launch(c->stream, Q, family, d, Xc, nn * L, S, cc, alpha, omega, gamma, A.dkxs,
+                                                  static_cast<double*>(gX) + n0 * int64_t(L) * d, static_cast<double*>(cpart), gS, dalpha, domega,
+                                                  dgamma, n0 > 0);
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral cross reverse pass: %s", hipGetErrorString(hipError_t(rc)));
+        at += grid;
+    }
+    hipLaunchKernelGGL(lr_grad_reduce_kernel, dim3(unsigned((int64_t(cc) * cc + 255) / 256)), dim3(256), 0, c->stream, static_cast<const double*>(part),
+                       int(nparts), int64_t(cc) * cc, gS, int64_t(0), gWh, int64_t(cc) * cc, static_cast<double*>(nullptr));
     HIPCHK(c, hipGetLastError());
     return GPSIG_OK;
 }

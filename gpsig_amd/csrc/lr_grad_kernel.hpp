@@ -18,6 +18,12 @@
 // dWh, dS and the base kernel's own parameter are summed over the sequences a workgroup processes in registers and leave as one partial
 // per workgroup (added up by lr_grad_reduce_kernel in a fixed order).  Layout and lane mappings as in lr_fused_kernel.hpp: arrays
 // [column][time] with an odd row stride, lane = time for everything elementwise in time, thread = column for the running sums.
+//
+// SignatureSpectral (lr_seq_features_grad_spectral_kernel, SPEC): kappa(x, S_i) by spectral_pair on the trainable parameters (ld = d,
+// read through the scalar unit); kxs is computed once per sequence and kept in the workgroup's scratch next to the E_i for the dWh sums.
+// The kernel stops at dkxs: it writes dkxs (N, L, c) to HBM and sums dWh only.  The spectral cross op's reverse kernels
+// (spectral_cross_api.hip) turn dkxs into dx, dS, dalpha, domega and dgamma: the parameters' sums over every (point, landmark, component)
+// are reduced there per workgroup and combined in a fixed order.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -26,6 +32,7 @@
 #include "aux_kernels.hpp"
 #include "grad_core.hpp"
 #include "lr_fused_args.hpp"
+#include "spectral_pair.hpp"
 
 namespace gpsig {
 
@@ -49,6 +56,13 @@ struct LrGradArgs {
     int lp, rows_b;
 };
 
+// the spectral instance's arguments (p0 = Q, p1 = family): the trainable parameters (Q), (Q, d), (Q, d) on the device; dkxs (N, L, c) out;
+// kxs of the current sequence at escr + kxs_off; part holds dWh alone ([grid][c c]); gX, dS and the base parameter are not written
+struct LrGradSpectralArgs : LrGradArgs {
+    const double* alpha; const double* omega; const double* gamma;
+    double* dkxs; int64_t kxs_off;
+};
+
 constexpr int LR_GRAD_THREADS = 512;                   // (the smaller of the two workgroup sizes built: what the per-thread tables are sized for)
 constexpr int LR_GRAD_KW = 8, LR_GRAD_KS = 8;          // (i, j) pairs of dWh and (i, f) pairs of dS per thread: c <= 64, c d <= 4096
 
@@ -60,8 +74,8 @@ inline size_t lr_grad_lds_bytes(int c, int r, int d, int L, int pad = 1) {
     return sizeof(double) * size_t(lp) * 4 * size_t(kb);
 }
 
-template <int THREADS>
-__global__ __launch_bounds__(THREADS) void lr_seq_features_grad_kernel(LrGradArgs A) {
+template <int THREADS, bool SPEC, typename Args>
+__device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
     constexpr int NW = THREADS / 64, UNROLL = 8;
     extern __shared__ double lrg_lds[];
     const int lp = A.lp, c = A.c, r = A.r, L = A.L, d = A.d, M = A.M;
@@ -105,6 +119,18 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_grad_kernel(LrGradArg
         }
     };
     auto cross = [&](const double* xb, double* kb) {
+        if constexpr (SPEC) {
+            const lr_const_ptr<double> al = lr_as_const(A.alpha), om = lr_as_const(A.omega), ga = lr_as_const(A.gamma);
+            const int Q = int(A.p0), family = int(A.p1);
+            for (int ch = 0; ch < nchunk; ++ch) {
+                const int t = ch * 64 + lane;
+                if (t < L)
+                    for (int i = wave; i < c; i += NW)
+                        kb[i * lp + t] = spectral_pair(al, om, ga, d, Q, family, d, [&](int f) { return xb[f * lp + t]; },
+                                                       [&](int f) { return Sg[size_t(i) * d + f]; });
+            }
+            return;
+        }
         for (int ch = 0; ch < nchunk; ++ch) {
             const int t = ch * 64 + lane;
             if (t < L) {
@@ -138,6 +164,11 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_grad_kernel(LrGradArg
         __syncthreads();
         cross(B1, BX);
         __syncthreads();
+        if constexpr (SPEC)                                     // kxs for the dWh sums below (the spectral kappa is the costly phase)
+            for (int q = threadIdx.x; q < c * L; q += THREADS) {
+                const int i = q / L, t = q - i * L;
+                escr[A.kxs_off + q] = BX[i * lp + t];
+            }
         for (int ch = 0; ch < nchunk; ++ch) {
             const int t = ch * 64 + lane;
             if (t < L) {
@@ -242,10 +273,17 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_grad_kernel(LrGradArg
                     Xb[j * lp + t] = A.difference ? (t >= 1 ? B1[j * lp + t - 1] : 0.0) - (t < l ? B1[j * lp + t] : 0.0) : B1[j * lp + t];
         }
         __syncthreads();
-        // x -> B1 and kxs -> B0 once more (U and dU are done with)
-        load_x(Xn, B1);
-        __syncthreads();
-        cross(B1, B0);
+        // x -> B1 and kxs -> B0 once more (U and dU are done with); the spectral instance reads kxs back from its scratch
+        if constexpr (SPEC) {
+            for (int q = threadIdx.x; q < c * L; q += THREADS) {
+                const int i = q / L, t = q - i * L;
+                B0[i * lp + t] = escr[A.kxs_off + q];
+            }
+        } else {
+            load_x(Xn, B1);
+            __syncthreads();
+            cross(B1, B0);
+        }
         __syncthreads();
         // dWh[i][j] += sum_t kxs[i][t] dfeat[j][t]
 #pragma unroll
@@ -271,6 +309,14 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_grad_kernel(LrGradArg
             }
         }
         __syncthreads();
+        if constexpr (SPEC) {                        // dkxs (L, c) of this sequence out; the spectral cross op's reverse kernels take it from here
+            double* dk = A.dkxs + n * int64_t(L) * c;
+            for (int q = threadIdx.x; q < L * c; q += THREADS) {
+                const int t = q / c, i = q - t * c;
+                dk[q] = Y[i * lp + t];
+            }
+            continue;                                // (the loop's first barrier orders these reads before Y is written again)
+        }
         // through the base kernel: d kappa / dx = wy S_i + wx x,  d kappa / dS_i = wy x + ws S_i  (BaseGrad of grad_core.hpp)
         //   Y[i][t] <- dkxs wy,  Xb[i][t] <- dkxs ws,  B0[wave][t] <- this wave's share of sum_i dkxs wx
         for (int ch = 0; ch < nchunk; ++ch) {
@@ -326,6 +372,15 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_grad_kernel(LrGradArg
         }
     }
     // ---- this workgroup's partial sums
+    if constexpr (SPEC) {
+        double* part = A.part + int64_t(blockIdx.x) * (int64_t(c) * c);
+#pragma unroll
+        for (int k = 0; k < LR_GRAD_KW; ++k) {
+            const int q = k * THREADS + threadIdx.x;
+            if (q < c * c) part[q] = accW[k];
+        }
+        return;
+    }
     double* part = A.part + int64_t(blockIdx.x) * (int64_t(c) * d + int64_t(c) * c + 1);
 #pragma unroll
     for (int k = 0; k < LR_GRAD_KS; ++k) {
@@ -348,6 +403,13 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_grad_kernel(LrGradArg
         part[int64_t(c) * d + int64_t(c) * c] = s;
     }
 }
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void lr_seq_features_grad_kernel(LrGradArgs A) { lr_seq_features_grad_body<THREADS, false>(A); }
+
+// SignatureSpectral: kxs by spectral_pair, dkxs out instead of the base-kernel phase (above)
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void lr_seq_features_grad_spectral_kernel(LrGradSpectralArgs A) { lr_seq_features_grad_body<THREADS, true>(A); }
 
 // out[q] = sum over the workgroups' partials, in order
 __global__ void lr_grad_reduce_kernel(const double* __restrict__ part, int nparts, int64_t width, double* __restrict__ gS, int64_t nS,

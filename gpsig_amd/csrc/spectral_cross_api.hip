@@ -7,6 +7,8 @@
 //     The reverse pass: dP by one thread per point (landmarks wave-uniform); dS and the parameters -- sums over every pair -- by
 //     workgroups of (landmark, slice of the points) that reduce in LDS into per-workgroup partial sums, combined by a second pass in a
 //     fixed order: no atomics, two runs agree bit for bit.  Per-pair arithmetic: spectral_pair.hpp.
+//   * spectral_cross_grad_launch: the same reverse pass for the low-rank training path's spectral entry points (lr_grad_api.hip), which
+//     hand over dkxs as G, partial sums in a buffer of their own and, for the second and later chunks of sequences, add to the outputs.
 #include "ctx.hpp"
 #include "lr_fused_args.hpp"
 #include "spectral_pair.hpp"
@@ -54,6 +56,7 @@ struct SpecCrossArgs {
     const double* G;                                                    // (n, c)
     double* dP;
     double* part; int nchunk, nv;                                       // partial sums: (c * nchunk, nv), nv = d + Q (1 + 2d)
+    int accumulate;                                                     // the combine pass adds dS and the parameters' sums to its outputs
 };
 
 constexpr int SC_THREADS = 256;
@@ -214,11 +217,14 @@ __global__ __launch_bounds__(SC_THREADS) void spectral_cross_grad_combine_kernel
         __syncthreads();
     }
     if (threadIdx.x != 0) return;
-    if (o < cd) { dS[o] = red[0]; return; }
-    const int v = int(o - cd), w = 1 + 2 * d, q = v / w, k = v % w;
-    if (k == 0) dalpha[q] = red[0];
-    else if (k <= d) domega[q * d + k - 1] = red[0];
-    else dgamma[q * d + k - 1 - d] = red[0];
+    double* out;
+    if (o < cd) {
+        out = dS + o;
+    } else {
+        const int v = int(o - cd), w = 1 + 2 * d, q = v / w, k = v % w;
+        out = k == 0 ? dalpha + q : (k <= d ? domega + q * d + k - 1 : dgamma + q * d + k - 1 - d);
+    }
+    *out = A.accumulate ? *out + red[0] : red[0];
 }
 
 int cross_check(gpsig_ctx* c, int Q, int family, int d, int64_t n, int cc) {
@@ -242,6 +248,46 @@ int lr_seq_cross_spectral_launch(hipStream_t stream, const double* X, int64_t N,
 int lr_tens_cross_spectral_launch(hipStream_t stream, const double* Z, int64_t rows, ScaleParams P, const double* S, int c, int Q, int family,
                                   const double* spec, double* out) {
     hipLaunchKernelGGL(lr_tens_cross_spectral_kernel, dim3(grid_for(rows * c)), dim3(256), 0, stream, Z, rows, P, S, c, Q, family, spec, out);
+    return int(hipGetLastError());
+}
+
+
+// at most 32 slices of the points per landmark: the partial sums stay small (c * 32 rows) and a workgroup a few hundred pairs deep
+static int cross_grad_slices(int64_t n) {
+    const int64_t slices = (n + SC_THREADS - 1) / SC_THREADS;
+    return int(slices < 32 ? slices : 32);
+}
+
+size_t spectral_cross_grad_part_doubles(int64_t n, int cc, int d, int Q) {
+    return size_t(cc) * size_t(cross_grad_slices(n)) * size_t(d + Q * (1 + 2 * d));
+}
+
+int spectral_cross_grad_launch(hipStream_t stream, int Q, int family, int d, const double* P, int64_t n, const double* S, int cc,
+                               const double* alpha, const double* omega, const double* gamma, const double* G, double* dP, double* part,
+                               double* dS, double* dalpha, double* domega, double* dgamma, bool accumulate) {
+    SpecCrossArgs A{};
+    A.P = P; A.n = n; A.S = S; A.c = cc; A.d = d; A.Q = Q; A.family = family; A.alpha = alpha; A.omega = omega; A.gamma = gamma;
+    A.G = G; A.dP = dP;
+    A.nchunk = cross_grad_slices(n);
+    A.nv = d + Q * (1 + 2 * d);
+    A.part = part;
+    A.accumulate = accumulate ? 1 : 0;
+    const unsigned gp = unsigned(grid_for(n, SC_THREADS));
+    const dim3 gl(unsigned(A.nchunk), unsigned(cc));
+    if (d <= 8) {
+        hipLaunchKernelGGL(spectral_cross_grad_points_kernel<8>, dim3(gp), dim3(SC_THREADS), 0, stream, A);
+        hipLaunchKernelGGL(spectral_cross_grad_landmarks_kernel<8>, gl, dim3(SC_THREADS), 0, stream, A);
+    } else if (d <= 16) {
+        hipLaunchKernelGGL(spectral_cross_grad_points_kernel<16>, dim3(gp), dim3(SC_THREADS), 0, stream, A);
+        hipLaunchKernelGGL(spectral_cross_grad_landmarks_kernel<16>, gl, dim3(SC_THREADS), 0, stream, A);
+    } else {
+        hipLaunchKernelGGL(spectral_cross_grad_points_kernel<32>, dim3(gp), dim3(SC_THREADS), 0, stream, A);
+        hipLaunchKernelGGL(spectral_cross_grad_landmarks_kernel<32>, gl, dim3(SC_THREADS), 0, stream, A);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return int(e);
+    const unsigned outs = unsigned(int64_t(cc) * d + int64_t(Q) * (1 + 2 * d));
+    hipLaunchKernelGGL(spectral_cross_grad_combine_kernel, dim3(outs), dim3(SC_THREADS), 0, stream, A, dS, dalpha, domega, dgamma);
     return int(hipGetLastError());
 }
 
@@ -274,32 +320,11 @@ int gpsig_spectral_cross_grad(gpsig_ctx* c, int32_t Q, int32_t family, int32_t d
         return GPSIG_OK;
     }
     if (!P || !S || !alpha || !omega || !gamma || !G || !dP) return fail(c, GPSIG_ERR_INVALID, "NULL pointer");
-    SpecCrossArgs A{};
-    A.P = P; A.n = n; A.S = S; A.c = cc; A.d = d; A.Q = Q; A.family = family; A.alpha = alpha; A.omega = omega; A.gamma = gamma;
-    A.G = G; A.dP = dP;
-    // at most 32 slices of the points per landmark: the partial sums stay small (c * 32 rows) and a workgroup a few hundred pairs deep
-    const int64_t slices = (n + SC_THREADS - 1) / SC_THREADS;
-    A.nchunk = int(slices < 32 ? slices : 32);
-    A.nv = d + Q * (1 + 2 * d);
     void* part;
-    CHK(ensure(c, B_GR0, sizeof(double) * size_t(cc) * A.nchunk * A.nv + 64, &part));
-    A.part = static_cast<double*>(part);
-    const unsigned gp = unsigned(grid_for(n, SC_THREADS));
-    const dim3 gl(unsigned(A.nchunk), unsigned(cc));
-    if (d <= 8) {
-        hipLaunchKernelGGL(spectral_cross_grad_points_kernel<8>, dim3(gp), dim3(SC_THREADS), 0, c->stream, A);
-        hipLaunchKernelGGL(spectral_cross_grad_landmarks_kernel<8>, gl, dim3(SC_THREADS), 0, c->stream, A);
-    } else if (d <= 16) {
-        hipLaunchKernelGGL(spectral_cross_grad_points_kernel<16>, dim3(gp), dim3(SC_THREADS), 0, c->stream, A);
-        hipLaunchKernelGGL(spectral_cross_grad_landmarks_kernel<16>, gl, dim3(SC_THREADS), 0, c->stream, A);
-    } else {
-        hipLaunchKernelGGL(spectral_cross_grad_points_kernel<32>, dim3(gp), dim3(SC_THREADS), 0, c->stream, A);
-        hipLaunchKernelGGL(spectral_cross_grad_landmarks_kernel<32>, gl, dim3(SC_THREADS), 0, c->stream, A);
-    }
-    HIPCHK(c, hipGetLastError());
-    const unsigned outs = unsigned(int64_t(cc) * d + int64_t(Q) * (1 + 2 * d));
-    hipLaunchKernelGGL(spectral_cross_grad_combine_kernel, dim3(outs), dim3(SC_THREADS), 0, c->stream, A, dS, dalpha, domega, dgamma);
-    HIPCHK(c, hipGetLastError());
+    CHK(ensure(c, B_GR0, sizeof(double) * spectral_cross_grad_part_doubles(n, cc, d, Q) + 64, &part));
+    const int rc = spectral_cross_grad_launch(c->stream, Q, family, d, P, n, S, cc, alpha, omega, gamma, G, dP, static_cast<double*>(part), dS,
+                                              dalpha, domega, dgamma, false);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral cross reverse pass: %s", hipGetErrorString(hipError_t(rc)));
     return GPSIG_OK;
 }
 

@@ -360,6 +360,19 @@ int gpsig_lr_seq_features_dev(gpsig_ctx* ctx, const gpsig_params* p, int32_t num
 int gpsig_lr_seq_features_grad(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
                                const gpsig_sketch* sketches, const void* X, int64_t N, int32_t L, const double* S, const double* Wh,
                                const void* dPhi, void* gX, double* gS, double* gWh, double* g_base);
+/* The same pair for SignatureSpectral, whose parameters are trained: p->base_kernel = GPSIG_BASE_SPECTRAL, p->base_params = {Q, family};
+ * alpha (Q), omega (Q, d), gamma (Q, d) are DEVICE pointers read on the device (p->base_table is ignored; no host round trip per step).
+ * _grad: dPhi (N, F) -> gX (N, L, d), gS (c, d), gWh (c, c), dalpha (Q), domega (Q, d), dgamma (Q, d), all overwritten; deterministic
+ * (no floating-point atomics, partial sums combined in a fixed order).  Limits: float64, device-pointer mode, num_lags = 0, order 1,
+ * num_levels <= 8, Q <= 64, d <= 32, num_components <= 64, num_components x d <= 4096, a sequence's arrays within the LDS; outside them
+ * GPSIG_ERR_UNSUPPORTED.  gpsig_lr_seq_features_dev / _grad keep refusing the spectral kernel. */
+int gpsig_lr_seq_features_spectral_dev(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
+                                       const gpsig_sketch* sketches, const void* X, int64_t N, int32_t L, const double* S, const double* Wh,
+                                       const double* alpha, const double* omega, const double* gamma, void* Phi);
+int gpsig_lr_seq_features_spectral_grad(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
+                                        const gpsig_sketch* sketches, const void* X, int64_t N, int32_t L, const double* S, const double* Wh,
+                                        const double* alpha, const double* omega, const double* gamma, const void* dPhi, void* gX,
+                                        double* gS, double* gWh, double* dalpha, double* domega, double* dgamma);
 /* SignatureSpectral's Nystrom cross matrix for the TRAINING path (kernels.py:921-942, low_rank_calculations.py:59): K (n, c) = kappa(P, S)
  * for points P (n, d) and landmarks S (c, d), the parameters alpha (Q), omega (Q, d), gamma (Q, d) read from DEVICE memory (they change at
  * every optimiser step: no trip through the host), family 0 = rbf, 1 = exp, 2 = mixed; 1 <= Q <= 64, d <= 32.  Device pointers, device-pointer
