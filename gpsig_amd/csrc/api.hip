@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gpsig_hip.h"
@@ -411,7 +412,7 @@ int32_t lr_sketch_capacity(int64_t D, int r, int sparsity) {
     return int32_t(cap);
 }
 
-int lr_state_layout(gpsig_lr_state* st, int M) {
+int lr_state_layout(gpsig_lr_state* st) {
     using gpsig::LrEntry;
     size_t o = 0;
     auto take = [&](size_t n, size_t align = 16) { o = (o + align - 1) / align * align; const size_t at = o; o += n; return at; };
@@ -435,7 +436,6 @@ int lr_state_layout(gpsig_lr_state* st, int M) {
         o_sk[i][5] = take(sizeof(LrEntry) * (size_t(s.cap) + 1));
         k2 = st->r;
     }
-    (void)M;
     if (o > st->bytes) {
         if (st->block) { (void)hipStreamSynchronize(st->ctx->stream); (void)hipFree(st->block); st->block = nullptr; st->bytes = 0; }
         if (hipMalloc(&st->block, o + 256) != hipSuccess) return GPSIG_ERR_NOMEM;
@@ -492,93 +492,71 @@ int lr_check(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr) {
     return GPSIG_OK;
 }
 
-// FNV-1a over 64-bit words (a tail shorter than a word is folded in bytewise)
-static uint64_t lr_fnv(uint64_t h, const void* p, size_t n) {
-    const unsigned char* b = static_cast<const unsigned char*>(p);
-    size_t i = 0;
-    for (; i + 8 <= n; i += 8) {
-        uint64_t w;
-        memcpy(&w, b + i, 8);
-        h = (h ^ w) * 0x100000001b3ull;
-    }
-    for (; i < n; ++i) h = (h ^ b[i]) * 0x100000001b3ull;
-    return h;
-}
-
 // upload landmarks, whitening and sketches into one scratch block -- unless the block already holds exactly these (content hash):
 // the random objects of one evaluation go through several calls, and every upload is a host synchronisation
-int lr_upload(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, int d_eff, LrDev* D) {
+int lr_upload(gpsig_ctx* c, const gpsig_lowrank* lr, int d_eff, LrDev* D) {
     if (lr->device_state) {                  // already where the kernels read it
         if (lr->device_state->d_eff != d_eff) return fail(c, GPSIG_ERR_INVALID, "the low-rank state was drawn for %d columns, the call has %d", lr->device_state->d_eff, d_eff);
         lr_state_dev(lr->device_state, D);
         return GPSIG_OK;
     }
     const int cc = lr->num_components;
-    uint64_t hsh = 0xcbf29ce484222325ull;
+    uint64_t hsh = FNV1A_BASIS;
     const int64_t dims[4] = {cc, d_eff, lr->rank_bound, lr->num_sketches};
-    hsh = lr_fnv(hsh, dims, sizeof(dims));
-    hsh = lr_fnv(hsh, lr->landmarks, sizeof(double) * size_t(cc) * d_eff);
-    hsh = lr_fnv(hsh, lr->whitening, sizeof(double) * size_t(cc) * cc);
+    hsh = fnv1a(hsh, dims, sizeof(dims));
+    hsh = fnv1a(hsh, lr->landmarks, sizeof(double) * size_t(cc) * d_eff);
+    hsh = fnv1a(hsh, lr->whitening, sizeof(double) * size_t(cc) * cc);
     for (int i = 0; i < lr->num_sketches; ++i) {
         const gpsig_sketch& sk = lr->sketches[i];
         const int64_t sd[4] = {sk.k1, sk.k2, sk.r, sk.nnz};
-        hsh = lr_fnv(hsh, sd, sizeof(sd));
-        hsh = lr_fnv(hsh, sk.colptr, sizeof(int32_t) * (size_t(sk.r) + 1));
-        hsh = lr_fnv(hsh, sk.i1, sizeof(int32_t) * size_t(sk.nnz));
-        hsh = lr_fnv(hsh, sk.i2, sizeof(int32_t) * size_t(sk.nnz));
-        hsh = lr_fnv(hsh, sk.val, sizeof(double) * size_t(sk.nnz));
+        hsh = fnv1a(hsh, sd, sizeof(sd));
+        hsh = fnv1a(hsh, sk.colptr, sizeof(int32_t) * (size_t(sk.r) + 1));
+        hsh = fnv1a(hsh, sk.i1, sizeof(int32_t) * size_t(sk.nnz));
+        hsh = fnv1a(hsh, sk.i2, sizeof(int32_t) * size_t(sk.nnz));
+        hsh = fnv1a(hsh, sk.val, sizeof(double) * size_t(sk.nnz));
     }
-    if (hsh == 0) hsh = 1;
     size_t bytes = sizeof(double) * (size_t(cc) * d_eff + size_t(cc) * cc);
     for (int i = 0; i < lr->num_sketches; ++i)
         bytes += sizeof(int32_t) * (size_t(lr->sketches[i].r) + 1 + 2 * size_t(lr->sketches[i].nnz)) + sizeof(double) * size_t(lr->sketches[i].nnz) +
                  sizeof(LrEntry) * size_t(lr->sketches[i].nnz) + 96;
-    void* dbase;
-    CHK(ensure(c, B_LR0, bytes + 64, &dbase));
-    const bool cached = c->lr_hash == hsh && c->lr_base == dbase && c->lr_offsets.size() == size_t(2 + 5 * lr->num_sketches);
-    std::vector<unsigned char> h(cached ? 0 : bytes + 64);
-    std::vector<size_t> offs;
-    size_t o = 0;
-    auto place = [&](const void* src, size_t n, size_t align = 8) -> unsigned char* {
-        size_t at;
-        if (cached) {
-            at = c->lr_offsets[offs.size()];
-        } else {
-            o = (o + align - 1) / align * align;
-            if (n) memcpy(h.data() + o, src, n);
-            at = o;
-            o += n;
-        }
-        offs.push_back(at);
-        return static_cast<unsigned char*>(dbase) + at;
-    };
+    ContentUpload up(c->lr_cache);
+    CHK(up.open(c, B_LR0, bytes + 64, hsh, size_t(2 + 5 * lr->num_sketches)));
     D->c = cc; D->r = lr->rank_bound; D->nsk = lr->num_sketches;
-    D->S = reinterpret_cast<const double*>(place(lr->landmarks, sizeof(double) * size_t(cc) * d_eff));
-    D->Wh = reinterpret_cast<const double*>(place(lr->whitening, sizeof(double) * size_t(cc) * cc));
+    D->S = up.place<double>(lr->landmarks, sizeof(double) * size_t(cc) * d_eff, 8);
+    D->Wh = up.place<double>(lr->whitening, sizeof(double) * size_t(cc) * cc, 8);
     for (int i = 0; i < lr->num_sketches; ++i) {
         const gpsig_sketch& sk = lr->sketches[i];
-        D->colptr.push_back(reinterpret_cast<const int32_t*>(place(sk.colptr, sizeof(int32_t) * (size_t(sk.r) + 1))));
-        D->i1.push_back(reinterpret_cast<const int32_t*>(place(sk.i1, sizeof(int32_t) * size_t(sk.nnz))));
-        D->i2.push_back(reinterpret_cast<const int32_t*>(place(sk.i2, sizeof(int32_t) * size_t(sk.nnz))));
-        D->val.push_back(reinterpret_cast<const double*>(place(sk.val, sizeof(double) * size_t(sk.nnz))));
+        D->colptr.push_back(up.place<int32_t>(sk.colptr, sizeof(int32_t) * (size_t(sk.r) + 1), 8));
+        D->i1.push_back(up.place<int32_t>(sk.i1, sizeof(int32_t) * size_t(sk.nnz), 8));
+        D->i2.push_back(up.place<int32_t>(sk.i2, sizeof(int32_t) * size_t(sk.nnz), 8));
+        D->val.push_back(up.place<double>(sk.val, sizeof(double) * size_t(sk.nnz), 8));
         std::vector<LrEntry> packed;
-        if (!cached) {
+        if (!up.cached) {
             packed.resize(size_t(sk.nnz) + 1);
             for (int64_t e = 0; e < sk.nnz; ++e) packed[size_t(e)] = LrEntry{sk.val[e], sk.i1[e], sk.i2[e]};
         }
-        D->ent.push_back(reinterpret_cast<const LrEntry*>(place(packed.data(), sizeof(LrEntry) * size_t(sk.nnz), 16)));
+        D->ent.push_back(up.place<LrEntry>(packed.data(), sizeof(LrEntry) * size_t(sk.nnz), 16));
         D->nent.push_back(sk.nnz);
         D->k1.push_back(sk.k1); D->k2.push_back(sk.k2);
     }
-    if (!cached) {
-        CHK(no_capture(c, "the low-rank objects changed and have to be uploaded"));
-        ++c->alloc_gen;                  // a recorded graph read the old contents of this buffer: its replays are refused from here on
-        c->lr_hash = 0;
-        HIPCHK(c, hipMemcpyAsync(dbase, h.data(), o, hipMemcpyHostToDevice, c->stream));
-        CHK(host_sync(c));                       // h goes out of scope
-        c->lr_hash = hsh; c->lr_base = dbase; c->lr_offsets = offs;
+    return up.commit(c, "the low-rank objects changed and have to be uploaded");
+}
+
+// the whitening transposed, as the multi-pass routes' GEMM reads it (feat = kxs Wh = kxs (Wh^T)^T): a device-drawn state keeps one,
+// a host state's is made here into B_LR7
+int lr_whitening_t(gpsig_ctx* c, const gpsig_lowrank* lr, int cc, const double** wht) {
+    void* d;
+    CHK(ensure(c, B_LR7, sizeof(double) * size_t(cc) * cc + 8, &d));
+    if (lr->device_state) {
+        *wht = lr->device_state->WhT;
+        return GPSIG_OK;
     }
-    (void)p;
+    std::vector<double> t(size_t(cc) * cc);
+    for (int a = 0; a < cc; ++a)
+        for (int b = 0; b < cc; ++b) t[size_t(b) * cc + a] = lr->whitening[size_t(a) * cc + b];
+    HIPCHK(c, hipMemcpyAsync(d, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, c->stream));
+    CHK(host_sync(c));
+    *wht = static_cast<const double*>(d);
     return GPSIG_OK;
 }
 
@@ -597,11 +575,18 @@ int lr_gemm(gpsig_ctx* c, const double* A, const double* B, int64_t N1, int64_t 
     return GPSIG_OK;
 }
 
-int lr_level_offsets(gpsig_ctx* c, int M, int cc, int r, const int32_t** dev_off, int* F) {
+// where level m's features start in a row of Phi: off[m] .. off[m + 1], F = off[M + 1]
+std::vector<int32_t> lr_level_offsets_host(int M, int cc, int r) {
     std::vector<int32_t> off(M + 2);
     off[0] = 0; off[1] = 1;
     if (M >= 1) off[2] = 1 + cc;
     for (int m = 2; m <= M; ++m) off[m + 1] = off[m] + r;
+    return off;
+}
+
+// ... and their device copy in B_LR1
+int lr_level_offsets(gpsig_ctx* c, int M, int cc, int r, const int32_t** dev_off, int* F) {
+    const std::vector<int32_t> off = lr_level_offsets_host(M, cc, r);
     *F = off[M + 1];
     void* d;
     CHK(ensure(c, B_LR1, sizeof(int32_t) * off.size(), &d));
@@ -627,112 +612,38 @@ int lr_gemm(gpsig_ctx* c, const float* A, const float* B, int64_t N1, int64_t N2
     return GPSIG_OK;
 }
 
-struct LrDevF32 { const float* S; const float* Wh; const float* spec; const LrEntryF32* ent[LR_FUSED_MAX_SKETCHES]; };
-
-int lr_narrow(gpsig_ctx* c, const gpsig_params* p, const LrDev& D, int d_eff, const double* spec, LrDevF32* F) {
-    const int64_t nS = int64_t(D.c) * d_eff, nW = int64_t(D.c) * D.c;
-    const int64_t nspec = spec ? int64_t(p->base_params[0]) * (1 + 2 * SPECTRAL_STRIDE) : 0;
-    auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
-    size_t bytes = up16(sizeof(float) * nS) + up16(sizeof(float) * nW) + up16(sizeof(float) * nspec);
-    for (int i = 0; i < D.nsk; ++i) bytes += sizeof(LrEntryF32) * size_t(D.nent[i]) + 16;
-    void* base;
-    CHK(ensure(c, B_LRF32, bytes + 16, &base));
-    char* b = static_cast<char*>(base);
-    float* S = reinterpret_cast<float*>(b); b += up16(sizeof(float) * nS);
-    float* Wh = reinterpret_cast<float*>(b); b += up16(sizeof(float) * nW);
-    float* sp = reinterpret_cast<float*>(b); b += up16(sizeof(float) * nspec);
-    int rc = lr_narrow_launch(c->stream, D.S, nS, S);
-    if (rc == 0) rc = lr_narrow_launch(c->stream, D.Wh, nW, Wh);
-    if (rc == 0 && spec) rc = lr_narrow_launch(c->stream, spec, nspec, sp);
-    for (int i = 0; i < D.nsk && rc == 0; ++i) {
-        LrEntryF32* e = reinterpret_cast<LrEntryF32*>(b);
-        rc = lr_narrow_entries_launch(c->stream, D.ent[i], D.nent[i], e);
-        F->ent[i] = e;
-        b += sizeof(LrEntryF32) * size_t(D.nent[i]) + 16;
+// what the fused kernels read of the state: float64 where lr_upload put it, float32 narrowed on the device once per call into B_LRF32
+template <typename Args>
+int lr_state_args(gpsig_ctx* c, const gpsig_params* p, const LrDev& D, int d_eff, const double* spec, Args* A) {
+    if constexpr (std::is_same<typename Args::value_type, double>::value) {
+        A->S = D.S; A->Wh = D.Wh; A->spec = spec;
+        for (int i = 0; i < D.nsk; ++i) A->sk[i] = LrFusedSketch{D.colptr[i], D.ent[i]};
+        return GPSIG_OK;
+    } else {
+        const int64_t nS = int64_t(D.c) * d_eff, nW = int64_t(D.c) * D.c;
+        const int64_t nspec = spec ? int64_t(p->base_params[0]) * (1 + 2 * SPECTRAL_STRIDE) : 0;
+        auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
+        size_t bytes = up16(sizeof(float) * nS) + up16(sizeof(float) * nW) + up16(sizeof(float) * nspec);
+        for (int i = 0; i < D.nsk; ++i) bytes += sizeof(LrEntryF32) * size_t(D.nent[i]) + 16;
+        void* base;
+        CHK(ensure(c, B_LRF32, bytes + 16, &base));
+        char* b = static_cast<char*>(base);
+        float* S = reinterpret_cast<float*>(b); b += up16(sizeof(float) * nS);
+        float* Wh = reinterpret_cast<float*>(b); b += up16(sizeof(float) * nW);
+        float* sp = reinterpret_cast<float*>(b); b += up16(sizeof(float) * nspec);
+        int rc = lr_narrow_launch(c->stream, D.S, nS, S);
+        if (rc == 0) rc = lr_narrow_launch(c->stream, D.Wh, nW, Wh);
+        if (rc == 0 && spec) rc = lr_narrow_launch(c->stream, spec, nspec, sp);
+        for (int i = 0; i < D.nsk && rc == 0; ++i) {
+            LrEntryF32* e = reinterpret_cast<LrEntryF32*>(b);
+            rc = lr_narrow_entries_launch(c->stream, D.ent[i], D.nent[i], e);
+            A->sk[i] = LrFusedSketchF32{D.colptr[i], e};
+            b += sizeof(LrEntryF32) * size_t(D.nent[i]) + 16;
+        }
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "narrowing the low-rank state to float32: %s", hipGetErrorString(hipError_t(rc)));
+        A->S = S; A->Wh = Wh; A->spec = spec ? sp : nullptr;
+        return GPSIG_OK;
     }
-    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "narrowing the low-rank state to float32: %s", hipGetErrorString(hipError_t(rc)));
-    F->S = S; F->Wh = Wh; F->spec = spec ? sp : nullptr;
-    return GPSIG_OK;
-}
-
-// gpsig_lr_seq_features for float32 sequences: the fused kernels only (lr_fused != 0 and the float32 footprint within LDS); elsewhere
-// UNSUPPORTED, and the Python layer computes the call in float64 and rounds it
-int lr_seq_features_f32(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L, void* Phi) {
-    const int M = p->num_levels;
-    ScaleParams s;
-    CHK(scale_params(c, p, true, &s));
-    const int d_eff = s.d_eff();
-    const int cc = lr->num_components, r = lr->rank_bound;
-    const bool two = c->lr_fused == 1 && lr_fused2_ok(cc, r, L);
-    const size_t lds = two ? lr_fused2_lds_bytes_f32(cc, r, d_eff, L, c->lr_fused_pad) : lr_fused_lds_bytes_f32(cc, r, d_eff, L, c->lr_fused_pad);
-    if (c->lr_fused == 0 || lds > LR_FUSED_MAX_LDS || M - 1 > LR_FUSED_MAX_SKETCHES)
-        return fail(c, GPSIG_ERR_UNSUPPORTED, "float32 low-rank features are built for the fused kernels only (lr_fused != 0, %zu bytes of LDS)", lds);
-    LrDev D;
-    CHK(lr_upload(c, p, lr, d_eff, &D));
-    const int F = 1 + cc + (M - 1) * r;
-    const void* dX;
-    CHK(in_dev(c, B_IN0, X, sizeof(float) * size_t(N) * L * p->num_features, &dX));
-    void* dPhi;
-    CHK(out_dev(c, B_OUT0, Phi, sizeof(float) * size_t(N) * F, &dPhi));
-    if (N <= 0) return finish(c);
-    double p0, p1;
-    base_p(p, &p0, &p1);
-    const double* spec;
-    CHK(spectral_table(c, p, &spec));
-    LrDevF32 G;
-    CHK(lr_narrow(c, p, D, d_eff, spec, &G));
-    LrFusedArgsF32 A;
-    A.X = static_cast<const float*>(dX); A.N = N; A.L = L; A.P = s; A.S = G.S; A.Wh = G.Wh;
-    A.c = cc; A.r = r; A.M = M; A.difference = p->difference; A.kind = int(p->base_kernel); A.p0 = float(p0); A.p1 = float(p1);
-    for (int i = 0; i < LR_FUSED_MAX_SKETCHES; ++i) A.sk[i] = LrFusedSketchF32{nullptr, nullptr};
-    for (int i = 0; i < D.nsk; ++i) A.sk[i] = LrFusedSketchF32{D.colptr[i], G.ent[i]};
-    A.Phi = static_cast<float*>(dPhi); A.F = F;
-    A.lp = lr_fused_stride(L, c->lr_fused_pad);
-    A.spec = G.spec;
-    A.rows_b = cc > r ? cc : r;
-    if (d_eff > A.rows_b) A.rows_b = d_eff;
-    const unsigned grid = unsigned(N < (int64_t(1) << 20) ? N : (int64_t(1) << 20));
-    const int rc = lr_fused_f32_launch(c->stream, A, grid, two);
-    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "fused float32 low-rank feature kernel: %s", hipGetErrorString(hipError_t(rc)));
-    CHK(out_done(c, Phi, dPhi, sizeof(float) * size_t(N) * F));
-    return finish(c);
-}
-
-// gpsig_lr_tens_features for float32 tensors: the fused kernel only, as above
-int lr_tens_features_f32(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* Z, int64_t T, int32_t increments, void* Phi) {
-    const int M = p->num_levels, lt = M * (M + 1) / 2, E = increments ? 2 : 1;
-    ScaleParams s;
-    CHK(scale_params(c, p, true, &s));
-    const int d_eff = s.d_eff();
-    const int cc = lr->num_components, r = lr->rank_bound;
-    const size_t lds = lr_tens_fused_lds_bytes_f32(cc, r, d_eff, lt, E);
-    if (c->lr_fused == 0 || lds > 64 * 1024 || M - 1 > LR_FUSED_MAX_SKETCHES || T > 0x7fffffff)
-        return fail(c, GPSIG_ERR_UNSUPPORTED, "float32 low-rank tensor features are built for the fused kernel only (lr_fused != 0, %zu bytes of LDS)", lds);
-    LrDev D;
-    CHK(lr_upload(c, p, lr, d_eff, &D));
-    const int F = 1 + cc + (M - 1) * r;
-    const void* dZ;
-    CHK(in_dev(c, B_IN0, Z, sizeof(float) * size_t(lt) * T * E * d_eff, &dZ));
-    void* dPhi;
-    CHK(out_dev(c, B_OUT0, Phi, sizeof(float) * size_t(T) * F, &dPhi));
-    if (T <= 0) return finish(c);
-    double p0, p1;
-    base_p(p, &p0, &p1);
-    const double* spec;
-    CHK(spectral_table(c, p, &spec));
-    LrDevF32 G;
-    CHK(lr_narrow(c, p, D, d_eff, spec, &G));
-    LrTensFusedArgsF32 A;
-    A.Z = static_cast<const float*>(dZ); A.T = T; A.lt = lt; A.E = E; A.P = s; A.S = G.S; A.Wh = G.Wh;
-    A.c = cc; A.r = r; A.M = M; A.kind = int(p->base_kernel); A.p0 = float(p0); A.p1 = float(p1);
-    for (int i = 0; i < LR_FUSED_MAX_SKETCHES; ++i) A.sk[i] = LrFusedSketchF32{nullptr, nullptr};
-    for (int i = 0; i < D.nsk; ++i) A.sk[i] = LrFusedSketchF32{D.colptr[i], G.ent[i]};
-    A.Phi = static_cast<float*>(dPhi); A.F = F;
-    A.spec = G.spec;
-    const int rc = lr_tens_fused_f32_launch(c->stream, A);
-    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "fused float32 low-rank tensor feature kernel: %s", hipGetErrorString(hipError_t(rc)));
-    CHK(out_done(c, Phi, dPhi, sizeof(float) * size_t(T) * F));
-    return finish(c);
 }
 
 // low-rank Gram products (gpsig_lr_kernel / gpsig_lr_kernel_diag) in the features' float type: factors, scaling and the GEMM in T, level
@@ -783,10 +694,7 @@ int lr_kernel_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, co
             HIPCHK(c, hipGetLastError());
         }
     } else {
-        std::vector<int32_t> hoff(M1 + 1);
-        hoff[0] = 0; hoff[1] = 1;
-        if (M >= 1) hoff[2] = 1 + cc;
-        for (int m = 2; m <= M; ++m) hoff[m + 1] = hoff[m] + r;
+        const std::vector<int32_t> hoff = lr_level_offsets_host(M, cc, r);
         for (int m = 0; m <= M; ++m) {
             const int wdt = hoff[m + 1] - hoff[m];
             hipLaunchKernelGGL(lr_scale_factors_kernel<T>, dim3(grid_for(N1 * wdt)), dim3(256), 0, c->stream, static_cast<const T*>(dA),
@@ -828,6 +736,213 @@ int lr_kernel_diag_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* l
         HIPCHK(c, hipGetLastError());
     }
     CHK(out_done(c, out, dout, ob));
+    return finish(c);
+}
+
+// The multi-pass routes (float64): one kernel per reference op, the only route for shapes beyond the LDS (lr_fused = 0, or a sequence's
+// or tensor's arrays too large).  Scaled points, state and spectral table as the fused routes'.
+int lr_seq_features_passes(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const ScaleParams& s, const LrDev& D, const double* dX,
+                           int64_t N, int32_t L, const double* spec, void* Phi, void* dPhi) {
+    const int M = p->num_levels, cc = D.c, r = D.r, F = 1 + cc + (M - 1) * r;
+    const int l = p->difference ? L - 1 : L;
+    double* phi = static_cast<double*>(dPhi);
+    double p0, p1;
+    base_p(p, &p0, &p1);
+    void *kxs, *feat, *U, *Pa, *Pb;
+    const int wmax = cc > r ? cc : r;
+    CHK(ensure(c, B_LR2, sizeof(double) * size_t(N) * L * cc + 8, &kxs));
+    CHK(ensure(c, B_LR3, sizeof(double) * size_t(N) * L * cc + 8, &feat));
+    CHK(ensure(c, B_LR4, sizeof(double) * size_t(N) * (l > 0 ? l : 1) * cc + 8, &U));
+    CHK(ensure(c, B_LR5, sizeof(double) * size_t(N) * (l > 0 ? l : 1) * wmax + 8, &Pa));
+    CHK(ensure(c, B_LR6, sizeof(double) * size_t(N) * (l > 0 ? l : 1) * wmax + 8, &Pb));
+    if (N <= 0) return finish(c);
+    // Nystrom features (low_rank_calculations.py:59-60): kappa(X, S) then the whitening GEMM on the matrix cores
+    if (p->base_kernel == GPSIG_BASE_SPECTRAL) {
+        const int rc = lr_seq_cross_spectral_launch(c->stream, dX, N, int(L), s, D.S, cc, int(p0), int(p1), spec,
+                                                    static_cast<double*>(kxs));
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral Nystrom cross kernel: %s", hipGetErrorString(hipError_t(rc)));
+    } else {
+        hipLaunchKernelGGL(lr_seq_cross_kernel<double>, dim3(grid_for(N * L * cc)), dim3(256), 0, c->stream, dX, N, int(L), s, D.S, cc,
+                           int(p->base_kernel), p0, p1, static_cast<double*>(kxs));
+        HIPCHK(c, hipGetLastError());
+    }
+    // feat = kxs (NL, c) * Wh (c, c) on the transposed whitening
+    const double* wht;
+    CHK(lr_whitening_t(c, lr, cc, &wht));
+    CHK(lr_gemm(c, static_cast<const double*>(kxs), wht, N * L, cc, cc, cc, cc, static_cast<double*>(feat), cc));
+    // level 0 and level 1 (signature_algs.py:177-182)
+    hipLaunchKernelGGL(fill_kernel<double>, dim3(grid_for(N * F)), dim3(256), 0, c->stream, phi, N * F, 0.0);
+    HIPCHK(c, hipGetLastError());
+    if (l > 0) {
+        hipLaunchKernelGGL(lr_time_diff_kernel<double>, dim3(grid_for(N * l * cc)), dim3(256), 0, c->stream,
+                           static_cast<const double*>(feat), N, int(L), cc, int(p->difference), static_cast<double*>(U));
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(lr_timesum_kernel<double>, dim3(grid_for(N * cc)), dim3(256), 0, c->stream, static_cast<const double*>(U), N, l,
+                           cc, phi, int64_t(F), 1);
+        HIPCHK(c, hipGetLastError());
+        // P = U; for level i: P = excumsum_t(P); P = sketch(U, P); Phi_i = sum_t P     (signature_algs.py:184-191)
+        HIPCHK(c, hipMemcpyAsync(Pa, U, sizeof(double) * size_t(N) * l * cc, hipMemcpyDeviceToDevice, c->stream));
+        double *cur = static_cast<double*>(Pa), *nxt = static_cast<double*>(Pb);
+        int kw = cc;
+        for (int i = 2; i <= M; ++i) {
+            hipLaunchKernelGGL(lr_excumsum_kernel<double>, dim3(grid_for(N * kw)), dim3(256), 0, c->stream, cur, N, l, kw, phi, int64_t(F), 0, 0);
+            HIPCHK(c, hipGetLastError());
+            hipLaunchKernelGGL(lr_sketch_kernel<double>, dim3(grid_for(N * l * r)), dim3(256), 0, c->stream, static_cast<const double*>(U),
+                               int64_t(cc), static_cast<const double*>(cur), int64_t(kw), N * l, r, D.colptr[i - 2], D.i1[i - 2], D.i2[i - 2],
+                               D.val[i - 2], nxt, int64_t(r));
+            HIPCHK(c, hipGetLastError());
+            hipLaunchKernelGGL(lr_timesum_kernel<double>, dim3(grid_for(N * r)), dim3(256), 0, c->stream, static_cast<const double*>(nxt), N, l,
+                               r, phi, int64_t(F), 1 + cc + (i - 2) * r);
+            HIPCHK(c, hipGetLastError());
+            double* t = cur; cur = nxt; nxt = t;
+            kw = r;
+        }
+    }
+    hipLaunchKernelGGL(fill_strided_kernel<double>, dim3(grid_for(N)), dim3(256), 0, c->stream, phi, N, int64_t(F), 1.0);
+    HIPCHK(c, hipGetLastError());
+    CHK(out_done(c, Phi, dPhi, sizeof(double) * size_t(N) * F));
+    return finish(c);
+}
+
+int lr_tens_features_passes(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const ScaleParams& s, const LrDev& D, const double* dZ,
+                            int64_t T, int E, const double* spec, void* Phi, void* dPhi) {
+    const int M = p->num_levels, lt = M * (M + 1) / 2, cc = D.c, r = D.r, F = 1 + cc + (M - 1) * r;
+    const int increments = E == 2;
+    double* phi = static_cast<double*>(dPhi);
+    double p0, p1;
+    base_p(p, &p0, &p1);
+    const int64_t rows = int64_t(lt) * T * E;
+    void *kxs, *feat, *U, *Ra, *Rb;
+    const int wmax = cc > r ? cc : r;
+    CHK(ensure(c, B_LR2, sizeof(double) * size_t(rows) * cc + 8, &kxs));
+    CHK(ensure(c, B_LR3, sizeof(double) * size_t(rows) * cc + 8, &feat));
+    CHK(ensure(c, B_LR4, sizeof(double) * size_t(lt) * T * cc + 8, &U));
+    CHK(ensure(c, B_LR5, sizeof(double) * size_t(T) * wmax + 8, &Ra));
+    CHK(ensure(c, B_LR6, sizeof(double) * size_t(T) * wmax + 8, &Rb));
+    const double* wht;
+    CHK(lr_whitening_t(c, lr, cc, &wht));
+    if (p->base_kernel == GPSIG_BASE_SPECTRAL) {
+        const int rc = lr_tens_cross_spectral_launch(c->stream, dZ, rows, s, D.S, cc, int(p0), int(p1), spec,
+                                                     static_cast<double*>(kxs));
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral Nystrom cross kernel: %s", hipGetErrorString(hipError_t(rc)));
+    } else {
+        hipLaunchKernelGGL(lr_tens_cross_kernel<double>, dim3(grid_for(rows * cc)), dim3(256), 0, c->stream, dZ, rows, s, D.S, cc,
+                           int(p->base_kernel), p0, p1, static_cast<double*>(kxs));
+        HIPCHK(c, hipGetLastError());
+    }
+    CHK(lr_gemm(c, static_cast<const double*>(kxs), wht, rows, cc, cc, cc, cc, static_cast<double*>(feat), cc));
+    // increments: F(z[.,1]) - F(z[.,0]) (kernels.py:304); rows are ((k*T + t)*E + e): a "time difference" over e with L = E
+    if (increments) {
+        hipLaunchKernelGGL(lr_time_diff_kernel<double>, dim3(grid_for(int64_t(lt) * T * cc)), dim3(256), 0, c->stream,
+                           static_cast<const double*>(feat), int64_t(lt) * T, 2, cc, 1, static_cast<double*>(U));
+        HIPCHK(c, hipGetLastError());
+    } else {
+        HIPCHK(c, hipMemcpyAsync(U, feat, sizeof(double) * size_t(lt) * T * cc, hipMemcpyDeviceToDevice, c->stream));
+    }
+    hipLaunchKernelGGL(fill_kernel<double>, dim3(grid_for(T * F)), dim3(256), 0, c->stream, phi, T * F, 0.0);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(fill_strided_kernel<double>, dim3(grid_for(T)), dim3(256), 0, c->stream, phi, T, int64_t(F), 1.0);
+    HIPCHK(c, hipGetLastError());
+    // tensor_kern_lr_feature (signature_algs.py:211-221): R = U[k]; R = sketch_{j-1}(U[k'], R)
+    const double* Ud = static_cast<const double*>(U);
+    int k = 0;
+    for (int i = 1; i <= M; ++i) {
+        const double* R = Ud + size_t(k) * T * cc;
+        int kw = cc;
+        ++k;
+        double *cur = static_cast<double*>(Ra), *nxt = static_cast<double*>(Rb);
+        for (int j = 1; j < i; ++j) {
+            hipLaunchKernelGGL(lr_sketch_kernel<double>, dim3(grid_for(T * r)), dim3(256), 0, c->stream, Ud + size_t(k) * T * cc, int64_t(cc), R,
+                               int64_t(kw), T, r, D.colptr[j - 1], D.i1[j - 1], D.i2[j - 1], D.val[j - 1], cur, int64_t(r));
+            HIPCHK(c, hipGetLastError());
+            R = cur;
+            kw = r;
+            double* t = cur; cur = nxt; nxt = t;
+            ++k;
+        }
+        const int off = i == 1 ? 1 : 1 + cc + (i - 2) * r;
+        hipLaunchKernelGGL(copy_block_kernel<double>, dim3(grid_for(T * kw)), dim3(256), 0, c->stream, R, T, kw, int64_t(kw), phi, int64_t(F), off);
+        HIPCHK(c, hipGetLastError());
+    }
+    CHK(out_done(c, Phi, dPhi, sizeof(double) * size_t(T) * F));
+    return finish(c);
+}
+
+// gpsig_lr_seq_features in T: the fused kernels (lr_fused_kernel.hpp: one workgroup per sequence, intermediates in LDS) where a sequence's
+// arrays fit, else the multi-pass route -- float64 only: for float32 that is UNSUPPORTED, and the Python layer computes the call in float64
+// and rounds it.  float64 tests the three-array footprint before it may pick either form, float32 the footprint of the form it picks.
+template <typename T>
+int lr_seq_features_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L, void* Phi) {
+    constexpr bool f32 = std::is_same<T, float>::value;
+    const int M = p->num_levels, cc = lr->num_components, r = lr->rank_bound;
+    ScaleParams s;
+    CHK(scale_params(c, p, true, &s));
+    const int d_eff = s.d_eff();
+    // two arrays in LDS instead of three where a wavefront can hold its output columns in registers (lr_fused2): a third workgroup per CU
+    const bool two = c->lr_fused == 1 && lr_fused2_ok(cc, r, L);
+    const size_t lds = !f32 ? lr_fused_lds_bytes(cc, r, d_eff, L, c->lr_fused_pad)
+                       : two ? lr_fused2_lds_bytes_f32(cc, r, d_eff, L, c->lr_fused_pad) : lr_fused_lds_bytes_f32(cc, r, d_eff, L, c->lr_fused_pad);
+    const bool fused = c->lr_fused != 0 && lds <= LR_FUSED_MAX_LDS && M - 1 <= LR_FUSED_MAX_SKETCHES;
+    if (f32 && !fused)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "float32 low-rank features are built for the fused kernels only (lr_fused != 0, %zu bytes of LDS)", lds);
+    LrDev D;
+    CHK(lr_upload(c, lr, d_eff, &D));
+    const int F = 1 + cc + (M - 1) * r;
+    const void* dX;
+    CHK(in_dev(c, B_IN0, X, sizeof(T) * size_t(N) * L * p->num_features, &dX));
+    void* dPhi;
+    CHK(out_dev(c, B_OUT0, Phi, sizeof(T) * size_t(N) * F, &dPhi));
+    double p0, p1;
+    base_p(p, &p0, &p1);
+    const double* spec = nullptr;        // BASE_SPECTRAL: its parameter table (p0 = Q, p1 = family), read by the spectral instances
+    if (!f32 || N > 0) CHK(spectral_table(c, p, &spec));                     // (float32 uploads nothing for an empty call)
+    if (!fused) return lr_seq_features_passes(c, p, lr, s, D, static_cast<const double*>(dX), N, L, spec, Phi, dPhi);
+    if (N <= 0) return finish(c);
+    std::conditional_t<f32, LrFusedArgsF32, LrFusedArgs> A{};
+    A.X = static_cast<const T*>(dX); A.N = N; A.L = L; A.P = s;
+    A.c = cc; A.r = r; A.M = M; A.difference = p->difference; A.kind = int(p->base_kernel); A.p0 = T(p0); A.p1 = T(p1);
+    A.Phi = static_cast<T*>(dPhi);
+    CHK(lr_state_args(c, p, D, d_eff, spec, &A));
+    const int rc = lr_fused_launch(c->stream, A, c->lr_fused_pad, two, c->lr_fused_variant);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, f32 ? "fused float32 low-rank feature kernel: %s" : "fused low-rank feature kernel: %s", hipGetErrorString(hipError_t(rc)));
+    CHK(out_done(c, Phi, dPhi, sizeof(T) * size_t(N) * F));
+    return finish(c);
+}
+
+// gpsig_lr_tens_features in T: the fused kernel where a tensor's arrays fit 64 KB of LDS, else the multi-pass route (float64 only, as above)
+template <typename T>
+int lr_tens_features_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* Z, int64_t T_, int32_t increments, void* Phi) {
+    constexpr bool f32 = std::is_same<T, float>::value;
+    const int M = p->num_levels, lt = M * (M + 1) / 2, E = increments ? 2 : 1, cc = lr->num_components, r = lr->rank_bound;
+    ScaleParams s;
+    CHK(scale_params(c, p, true, &s));
+    const int d_eff = s.d_eff();
+    const size_t lds = f32 ? lr_tens_fused_lds_bytes_f32(cc, r, d_eff, lt, E) : lr_tens_fused_lds_bytes(cc, r, d_eff, lt, E);
+    const bool fused = c->lr_fused != 0 && lds <= 64 * 1024 && M - 1 <= LR_FUSED_MAX_SKETCHES && T_ <= 0x7fffffff;
+    if (f32 && !fused)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "float32 low-rank tensor features are built for the fused kernel only (lr_fused != 0, %zu bytes of LDS)", lds);
+    LrDev D;
+    CHK(lr_upload(c, lr, d_eff, &D));
+    const int F = 1 + cc + (M - 1) * r;
+    const void* dZ;
+    CHK(in_dev(c, B_IN0, Z, sizeof(T) * size_t(lt) * T_ * E * d_eff, &dZ));
+    void* dPhi;
+    CHK(out_dev(c, B_OUT0, Phi, sizeof(T) * size_t(T_) * F, &dPhi));
+    if (T_ <= 0) return finish(c);
+    double p0, p1;
+    base_p(p, &p0, &p1);
+    const double* spec;
+    CHK(spectral_table(c, p, &spec));
+    if (!fused) return lr_tens_features_passes(c, p, lr, s, D, static_cast<const double*>(dZ), T_, E, spec, Phi, dPhi);
+    std::conditional_t<f32, LrTensFusedArgsF32, LrTensFusedArgs> A{};
+    A.Z = static_cast<const T*>(dZ); A.T = T_; A.lt = lt; A.E = E; A.P = s;
+    A.c = cc; A.r = r; A.M = M; A.kind = int(p->base_kernel); A.p0 = T(p0); A.p1 = T(p1);
+    A.Phi = static_cast<T*>(dPhi);
+    CHK(lr_state_args(c, p, D, d_eff, spec, &A));
+    const int rc = lr_tens_fused_launch(c->stream, A);
+    if (rc != 0)
+        return fail(c, GPSIG_ERR_HIP, f32 ? "fused float32 low-rank tensor feature kernel: %s" : "fused low-rank tensor feature kernel: %s", hipGetErrorString(hipError_t(rc)));
+    CHK(out_done(c, Phi, dPhi, sizeof(T) * size_t(T_) * F));
     return finish(c);
 }
 
@@ -2897,217 +3012,16 @@ int gpsig_lr_whitening(gpsig_ctx* c, const gpsig_params* p, const double* S_host
 int gpsig_lr_seq_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L, void* Phi) {
     ENTER_LR(c, p);
     CHK(lr_check(c, p, lr));
-    if (p->dtype == GPSIG_F32) return lr_seq_features_f32(c, p, lr, X, N, L, Phi);
-    const int M = p->num_levels;
-    ScaleParams s;
-    CHK(scale_params(c, p, true, &s));
-    const int d_eff = s.d_eff();
-    LrDev D;
-    CHK(lr_upload(c, p, lr, d_eff, &D));
-    const int cc = D.c, r = D.r;
-    const int F = 1 + cc + (M - 1) * r;
-    const int l = p->difference ? L - 1 : L;
-    const void* dX;
-    CHK(in_dev(c, B_IN0, X, sizeof(double) * size_t(N) * L * p->num_features, &dX));
-    void* dPhi;
-    CHK(out_dev(c, B_OUT0, Phi, sizeof(double) * size_t(N) * F, &dPhi));
-    double* phi = static_cast<double*>(dPhi);
-    double p0, p1;
-    base_p(p, &p0, &p1);
-    const double* spec;                  // BASE_SPECTRAL: its parameter table (p0 = Q, p1 = family), read by the spectral instances
-    CHK(spectral_table(c, p, &spec));
-    // One kernel, one workgroup per sequence, intermediates in LDS (lr_fused_kernel.hpp) when a sequence's three arrays fit
-    const size_t fused_lds = lr_fused_lds_bytes(cc, r, d_eff, L, c->lr_fused_pad);
-    if (c->lr_fused != 0 && fused_lds <= LR_FUSED_MAX_LDS && M - 1 <= LR_FUSED_MAX_SKETCHES) {
-        if (N <= 0) return finish(c);
-        LrFusedArgs A;
-        A.X = static_cast<const double*>(dX); A.N = N; A.L = L; A.P = s; A.S = D.S; A.Wh = D.Wh;
-        A.c = cc; A.r = r; A.M = M; A.difference = p->difference; A.kind = int(p->base_kernel); A.p0 = p0; A.p1 = p1;
-        for (int i = 0; i < LR_FUSED_MAX_SKETCHES; ++i) A.sk[i] = LrFusedSketch{nullptr, nullptr};
-        for (int i = 0; i < D.nsk; ++i) A.sk[i] = LrFusedSketch{D.colptr[i], D.ent[i]};
-        A.Phi = phi; A.F = F;
-        A.lp = lr_fused_stride(L, c->lr_fused_pad);
-        A.spec = spec;
-        A.rows_b = cc > r ? cc : r;
-        if (d_eff > A.rows_b) A.rows_b = d_eff;
-        const unsigned grid = unsigned(N < (int64_t(1) << 20) ? N : (int64_t(1) << 20));
-        // two arrays in LDS instead of three where a wavefront can hold its output columns in registers (lr_fused2): a third workgroup per CU
-        const int rc = (c->lr_fused == 1 && lr_fused2_ok(cc, r, L)) ? lr_fused2_launch(c->stream, A, grid)
-                                                                    : lr_fused_launch(c->stream, A, grid, c->lr_fused_variant);
-        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "fused low-rank feature kernel: %s", hipGetErrorString(hipError_t(rc)));
-        CHK(out_done(c, Phi, dPhi, sizeof(double) * size_t(N) * F));
-        return finish(c);
-    }
-    void *kxs, *feat, *U, *Pa, *Pb;
-    const int wmax = cc > r ? cc : r;
-    CHK(ensure(c, B_LR2, sizeof(double) * size_t(N) * L * cc + 8, &kxs));
-    CHK(ensure(c, B_LR3, sizeof(double) * size_t(N) * L * cc + 8, &feat));
-    CHK(ensure(c, B_LR4, sizeof(double) * size_t(N) * (l > 0 ? l : 1) * cc + 8, &U));
-    CHK(ensure(c, B_LR5, sizeof(double) * size_t(N) * (l > 0 ? l : 1) * wmax + 8, &Pa));
-    CHK(ensure(c, B_LR6, sizeof(double) * size_t(N) * (l > 0 ? l : 1) * wmax + 8, &Pb));
-    if (N <= 0) return finish(c);
-    // Nystrom features (low_rank_calculations.py:59-60): kappa(X, S) then the whitening GEMM on the matrix cores
-    if (p->base_kernel == GPSIG_BASE_SPECTRAL) {
-        const int rc = lr_seq_cross_spectral_launch(c->stream, static_cast<const double*>(dX), N, int(L), s, D.S, cc, int(p0), int(p1), spec,
-                                                    static_cast<double*>(kxs));
-        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral Nystrom cross kernel: %s", hipGetErrorString(hipError_t(rc)));
-    } else {
-        hipLaunchKernelGGL(lr_seq_cross_kernel<double>, dim3(grid_for(N * L * cc)), dim3(256), 0, c->stream, static_cast<const double*>(dX),
-                           N, int(L), s, D.S, cc, int(p->base_kernel), p0, p1, static_cast<double*>(kxs));
-        HIPCHK(c, hipGetLastError());
-    }
-    // feat = kxs (NL, c) * Wh (c, c) = kxs * (Wh^T)^T : pass B = Wh^T, i.e. read Wh column-wise -> upload is row-major Wh, so
-    // B[j][k] must be Wh[k][j]: use the transposed copy made below
-    void* wht;
-    CHK(ensure(c, B_LR7, sizeof(double) * size_t(cc) * cc + 8, &wht));
-    if (lr->device_state) {
-        wht = lr->device_state->WhT;
-    } else {
-        std::vector<double> t(size_t(cc) * cc);
-        for (int a = 0; a < cc; ++a)
-            for (int b = 0; b < cc; ++b) t[size_t(b) * cc + a] = lr->whitening[size_t(a) * cc + b];
-        HIPCHK(c, hipMemcpyAsync(wht, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, c->stream));
-        CHK(host_sync(c));
-    }
-    CHK(lr_gemm(c, static_cast<const double*>(kxs), static_cast<const double*>(wht), N * L, cc, cc, cc, cc, static_cast<double*>(feat), cc));
-    // level 0 and level 1 (signature_algs.py:177-182)
-    hipLaunchKernelGGL(fill_kernel<double>, dim3(grid_for(N * F)), dim3(256), 0, c->stream, phi, N * F, 0.0);
-    HIPCHK(c, hipGetLastError());
-    {
-        // Phi[:, 0] = 1
-        std::vector<double> ones(1, 1.0);
-        (void)ones;
-    }
-    if (l > 0) {
-        hipLaunchKernelGGL(lr_time_diff_kernel<double>, dim3(grid_for(N * l * cc)), dim3(256), 0, c->stream,
-                           static_cast<const double*>(feat), N, int(L), cc, int(p->difference), static_cast<double*>(U));
-        HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(lr_timesum_kernel<double>, dim3(grid_for(N * cc)), dim3(256), 0, c->stream, static_cast<const double*>(U), N, l,
-                           cc, phi, int64_t(F), 1);
-        HIPCHK(c, hipGetLastError());
-        // P = U; for level i: P = excumsum_t(P); P = sketch(U, P); Phi_i = sum_t P     (signature_algs.py:184-191)
-        HIPCHK(c, hipMemcpyAsync(Pa, U, sizeof(double) * size_t(N) * l * cc, hipMemcpyDeviceToDevice, c->stream));
-        double *cur = static_cast<double*>(Pa), *nxt = static_cast<double*>(Pb);
-        int kw = cc;
-        for (int i = 2; i <= M; ++i) {
-            hipLaunchKernelGGL(lr_excumsum_kernel<double>, dim3(grid_for(N * kw)), dim3(256), 0, c->stream, cur, N, l, kw, phi, int64_t(F), 0, 0);
-            HIPCHK(c, hipGetLastError());
-            hipLaunchKernelGGL(lr_sketch_kernel<double>, dim3(grid_for(N * l * r)), dim3(256), 0, c->stream, static_cast<const double*>(U),
-                               int64_t(cc), static_cast<const double*>(cur), int64_t(kw), N * l, r, D.colptr[i - 2], D.i1[i - 2], D.i2[i - 2],
-                               D.val[i - 2], nxt, int64_t(r));
-            HIPCHK(c, hipGetLastError());
-            hipLaunchKernelGGL(lr_timesum_kernel<double>, dim3(grid_for(N * r)), dim3(256), 0, c->stream, static_cast<const double*>(nxt), N, l,
-                               r, phi, int64_t(F), 1 + cc + (i - 2) * r);
-            HIPCHK(c, hipGetLastError());
-            double* t = cur; cur = nxt; nxt = t;
-            kw = r;
-        }
-    }
-    hipLaunchKernelGGL(fill_strided_kernel<double>, dim3(grid_for(N)), dim3(256), 0, c->stream, phi, N, int64_t(F), 1.0);
-    HIPCHK(c, hipGetLastError());
-    CHK(out_done(c, Phi, dPhi, sizeof(double) * size_t(N) * F));
-    return finish(c);
+    if (p->dtype == GPSIG_F32) return lr_seq_features_t<float>(c, p, lr, X, N, L, Phi);
+    return lr_seq_features_t<double>(c, p, lr, X, N, L, Phi);
 }
 
 int gpsig_lr_tens_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* Z, int64_t T, int32_t increments,
                            void* Phi) {
     ENTER_LR(c, p);
     CHK(lr_check(c, p, lr));
-    if (p->dtype == GPSIG_F32) return lr_tens_features_f32(c, p, lr, Z, T, increments, Phi);
-    const int M = p->num_levels, lt = M * (M + 1) / 2, E = increments ? 2 : 1;
-    ScaleParams s;
-    CHK(scale_params(c, p, true, &s));
-    const int d_eff = s.d_eff();
-    LrDev D;
-    CHK(lr_upload(c, p, lr, d_eff, &D));
-    const int cc = D.c, r = D.r;
-    const int F = 1 + cc + (M - 1) * r;
-    const void* dZ;
-    CHK(in_dev(c, B_IN0, Z, sizeof(double) * size_t(lt) * T * E * d_eff, &dZ));
-    void* dPhi;
-    CHK(out_dev(c, B_OUT0, Phi, sizeof(double) * size_t(T) * F, &dPhi));
-    double* phi = static_cast<double*>(dPhi);
-    if (T <= 0) return finish(c);
-    double p0, p1;
-    base_p(p, &p0, &p1);
-    const double* spec;
-    CHK(spectral_table(c, p, &spec));
-    if (c->lr_fused != 0 && lr_tens_fused_lds_bytes(cc, r, d_eff, lt, E) <= 64 * 1024 && M - 1 <= LR_FUSED_MAX_SKETCHES && T <= 0x7fffffff) {
-        LrTensFusedArgs A;
-        A.Z = static_cast<const double*>(dZ); A.T = T; A.lt = lt; A.E = E; A.P = s; A.S = D.S; A.Wh = D.Wh;
-        A.c = cc; A.r = r; A.M = M; A.kind = int(p->base_kernel); A.p0 = p0; A.p1 = p1;
-        for (int i = 0; i < LR_FUSED_MAX_SKETCHES; ++i) A.sk[i] = LrFusedSketch{nullptr, nullptr};
-        for (int i = 0; i < D.nsk; ++i) A.sk[i] = LrFusedSketch{D.colptr[i], D.ent[i]};
-        A.Phi = phi; A.F = F;
-        A.spec = spec;
-        const int rc = lr_tens_fused_launch(c->stream, A);
-        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "fused low-rank tensor feature kernel: %s", hipGetErrorString(hipError_t(rc)));
-        CHK(out_done(c, Phi, dPhi, sizeof(double) * size_t(T) * F));
-        return finish(c);
-    }
-    const int64_t rows = int64_t(lt) * T * E;
-    void *kxs, *feat, *U, *Ra, *Rb, *wht;
-    const int wmax = cc > r ? cc : r;
-    CHK(ensure(c, B_LR2, sizeof(double) * size_t(rows) * cc + 8, &kxs));
-    CHK(ensure(c, B_LR3, sizeof(double) * size_t(rows) * cc + 8, &feat));
-    CHK(ensure(c, B_LR4, sizeof(double) * size_t(lt) * T * cc + 8, &U));
-    CHK(ensure(c, B_LR5, sizeof(double) * size_t(T) * wmax + 8, &Ra));
-    CHK(ensure(c, B_LR6, sizeof(double) * size_t(T) * wmax + 8, &Rb));
-    CHK(ensure(c, B_LR7, sizeof(double) * size_t(cc) * cc + 8, &wht));
-    if (lr->device_state) {
-        wht = lr->device_state->WhT;
-    } else {
-        std::vector<double> t(size_t(cc) * cc);
-        for (int a = 0; a < cc; ++a)
-            for (int b = 0; b < cc; ++b) t[size_t(b) * cc + a] = lr->whitening[size_t(a) * cc + b];
-        HIPCHK(c, hipMemcpyAsync(wht, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, c->stream));
-        CHK(host_sync(c));
-    }
-    if (p->base_kernel == GPSIG_BASE_SPECTRAL) {
-        const int rc = lr_tens_cross_spectral_launch(c->stream, static_cast<const double*>(dZ), rows, s, D.S, cc, int(p0), int(p1), spec,
-                                                     static_cast<double*>(kxs));
-        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral Nystrom cross kernel: %s", hipGetErrorString(hipError_t(rc)));
-    } else {
-        hipLaunchKernelGGL(lr_tens_cross_kernel<double>, dim3(grid_for(rows * cc)), dim3(256), 0, c->stream, static_cast<const double*>(dZ), rows,
-                           s, D.S, cc, int(p->base_kernel), p0, p1, static_cast<double*>(kxs));
-        HIPCHK(c, hipGetLastError());
-    }
-    CHK(lr_gemm(c, static_cast<const double*>(kxs), static_cast<const double*>(wht), rows, cc, cc, cc, cc, static_cast<double*>(feat), cc));
-    // increments: F(z[.,1]) - F(z[.,0]) (kernels.py:304); rows are ((k*T + t)*E + e): a "time difference" over e with L = E
-    if (increments) {
-        hipLaunchKernelGGL(lr_time_diff_kernel<double>, dim3(grid_for(int64_t(lt) * T * cc)), dim3(256), 0, c->stream,
-                           static_cast<const double*>(feat), int64_t(lt) * T, 2, cc, 1, static_cast<double*>(U));
-        HIPCHK(c, hipGetLastError());
-    } else {
-        HIPCHK(c, hipMemcpyAsync(U, feat, sizeof(double) * size_t(lt) * T * cc, hipMemcpyDeviceToDevice, c->stream));
-    }
-    hipLaunchKernelGGL(fill_kernel<double>, dim3(grid_for(T * F)), dim3(256), 0, c->stream, phi, T * F, 0.0);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(fill_strided_kernel<double>, dim3(grid_for(T)), dim3(256), 0, c->stream, phi, T, int64_t(F), 1.0);
-    HIPCHK(c, hipGetLastError());
-    // tensor_kern_lr_feature (signature_algs.py:211-221): R = U[k]; R = sketch_{j-1}(U[k'], R)
-    const double* Ud = static_cast<const double*>(U);
-    int k = 0;
-    for (int i = 1; i <= M; ++i) {
-        const double* R = Ud + size_t(k) * T * cc;
-        int kw = cc;
-        ++k;
-        double *cur = static_cast<double*>(Ra), *nxt = static_cast<double*>(Rb);
-        for (int j = 1; j < i; ++j) {
-            hipLaunchKernelGGL(lr_sketch_kernel<double>, dim3(grid_for(T * r)), dim3(256), 0, c->stream, Ud + size_t(k) * T * cc, int64_t(cc), R,
-                               int64_t(kw), T, r, D.colptr[j - 1], D.i1[j - 1], D.i2[j - 1], D.val[j - 1], cur, int64_t(r));
-            HIPCHK(c, hipGetLastError());
-            R = cur;
-            kw = r;
-            double* t = cur; cur = nxt; nxt = t;
-            ++k;
-        }
-        const int off = i == 1 ? 1 : 1 + cc + (i - 2) * r;
-        hipLaunchKernelGGL(copy_block_kernel<double>, dim3(grid_for(T * kw)), dim3(256), 0, c->stream, R, T, kw, int64_t(kw), phi, int64_t(F), off);
-        HIPCHK(c, hipGetLastError());
-    }
-    CHK(out_done(c, Phi, dPhi, sizeof(double) * size_t(T) * F));
-    return finish(c);
+    if (p->dtype == GPSIG_F32) return lr_tens_features_t<float>(c, p, lr, Z, T, increments, Phi);
+    return lr_tens_features_t<double>(c, p, lr, Z, T, increments, Phi);
 }
 
 int gpsig_lr_kernel(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* PhiA, const void* PhiB, int64_t N1, int64_t N2,
@@ -3159,7 +3073,7 @@ int gpsig_lr_draw(gpsig_ctx* c, const gpsig_params* p, int32_t num_components, i
     if (!st->ctx) return fail(c, GPSIG_ERR_INVALID, "the state's context has been destroyed");
     st->c = num_components; st->d_eff = d_eff; st->r = rank_bound; st->nsk = nsk; st->sparsity = sparsity;
     CHK(no_capture(c, "a low-rank draw may have to allocate"));
-    if (lr_state_layout(st, M) != GPSIG_OK) { if (!*inout) delete st; return fail(c, GPSIG_ERR_NOMEM, "hipMalloc failed for the low-rank state"); }
+    if (lr_state_layout(st) != GPSIG_OK) { if (!*inout) delete st; return fail(c, GPSIG_ERR_NOMEM, "hipMalloc failed for the low-rank state"); }
     if (!*inout) c->lr_states.push_back(st);
     *inout = st;
     const PhiloxKey key{uint32_t(seed), uint32_t(seed >> 32)};

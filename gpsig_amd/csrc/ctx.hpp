@@ -21,6 +21,13 @@ struct DevBuf {
     size_t cap = 0;
 };
 
+// what a scratch buffer filled from the host holds, keyed by content (ContentUpload)
+struct UploadCache {
+    uint64_t hash = 0;                     // 0: nothing uploaded
+    void* base = nullptr;                  // the block the offsets below refer to
+    std::vector<size_t> offsets;           // byte offsets of the uploaded arrays inside it, in the order they were placed
+};
+
 enum BufId {
     B_IN0, B_IN1, B_IN2,          // host-mode input staging
     B_OUT0, B_OUT1, B_OUT2,       // host-mode output staging
@@ -134,15 +141,10 @@ struct gpsig_ctx {
     void* spec_base = nullptr;
     // low-rank mode: what B_LR0 / B_LR1 currently hold (keyed by content: the random objects of an evaluation are handed to several
     // calls -- tensor features, sequence features, products -- and every upload was a host synchronisation)
-    uint64_t lr_hash = 0;                  // 0: nothing uploaded
-    void* lr_base = nullptr;               // the B_LR0 block the offsets below refer to
-    std::vector<size_t> lr_offsets;        // byte offsets of the uploaded arrays inside it, in lr_upload's order
+    UploadCache lr_cache;                  // B_LR0: landmarks, whitening and projections (lr_upload, api.hip)
     int64_t lr_off_key[3] = {-1, -1, -1};  // (M, c, r) of the level offsets in B_LR1
     void* lr_off_base = nullptr;
-    // the projections of the training path's low-rank entry points (lr_grad_api.hip), kept in B_LR8 by content
-    uint64_t lrg_hash = 0;
-    void* lrg_base = nullptr;
-    std::vector<size_t> lrg_offsets;
+    UploadCache lr_sketch_cache;           // B_LR8: the projections of the training path's entry points (upload_sketches, lr_grad_api.hip)
     // timing of the pair-recursion launches
     std::vector<hipEvent_t> ev;     // pairs (start, stop)
     size_t ev_used = 0;
@@ -267,6 +269,68 @@ inline int ensure(gpsig_ctx* c, int id, size_t bytes, void** out) {
     *out = b.p;
     return GPSIG_OK;
 }
+
+// FNV-1a over 64-bit words (a tail shorter than a word is folded in bytewise), from FNV1A_BASIS
+constexpr uint64_t FNV1A_BASIS = 0xcbf29ce484222325ull;
+inline uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
+    const unsigned char* b = static_cast<const unsigned char*>(p);
+    size_t i = 0;
+    for (; i + 8 <= n; i += 8) {
+        uint64_t w;
+        memcpy(&w, b + i, 8);
+        h = (h ^ w) * 0x100000001b3ull;
+    }
+    for (; i < n; ++i) h = (h ^ b[i]) * 0x100000001b3ull;
+    return h;
+}
+
+// One upload of host arrays into a scratch buffer kept by content: open() takes the buffer and tells (`cached`) whether it already
+// holds what was hashed to `hash`; place() returns each array's device address, in a fixed order, and copies the array into the
+// host image only when it does not; commit() uploads the image and waits for it before the image goes out of scope.
+class ContentUpload {
+public:
+    explicit ContentUpload(UploadCache& cache) : cache_(cache) {}
+    bool cached = false;
+    int open(gpsig_ctx* c, int id, size_t bytes, uint64_t hash, size_t narrays) {
+        hash_ = hash ? hash : 1;
+        CHK(ensure(c, id, bytes, &base_));
+        cached = cache_.hash == hash_ && cache_.base == base_ && cache_.offsets.size() == narrays;
+        if (!cached) host_.resize(bytes);
+        return GPSIG_OK;
+    }
+    template <typename T>
+    const T* place(const void* src, size_t n, size_t align) {
+        size_t at;
+        if (cached) {
+            at = cache_.offsets[offs_.size()];
+        } else {
+            o_ = (o_ + align - 1) / align * align;
+            if (n) memcpy(host_.data() + o_, src, n);
+            at = o_;
+            o_ += n;
+        }
+        offs_.push_back(at);
+        return reinterpret_cast<const T*>(static_cast<const unsigned char*>(base_) + at);
+    }
+    int commit(gpsig_ctx* c, const char* what) {
+        if (cached) return GPSIG_OK;
+        CHK(no_capture(c, what));
+        ++c->alloc_gen;                  // a recorded graph read the old contents of this buffer: its replays are refused from here on
+        cache_.hash = 0;
+        HIPCHK(c, hipMemcpyAsync(base_, host_.data(), o_, hipMemcpyHostToDevice, c->stream));
+        CHK(host_sync(c));               // the host image goes out of scope
+        cache_.hash = hash_; cache_.base = base_; cache_.offsets = offs_;
+        return GPSIG_OK;
+    }
+
+private:
+    UploadCache& cache_;
+    uint64_t hash_ = 0;
+    void* base_ = nullptr;
+    std::vector<unsigned char> host_;
+    std::vector<size_t> offs_;
+    size_t o_ = 0;
+};
 
 // Device copy of the task list identified by `key` (its defining integers, key[9] = which builder).  On a miss `build` fills
 // c->host_tasks (returning a number kept with the list) and the list is uploaded into the least recently used slot.  *tasks is null for an empty list.

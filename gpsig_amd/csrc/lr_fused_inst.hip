@@ -1,92 +1,74 @@
-// lr_fused_inst.hip -- the fused low-rank feature kernel and its launcher (own translation unit: api.hip only sees the arguments).
+// lr_fused_inst.hip -- the fused low-rank feature kernels, float64 and float32, plain and spectral, and their launchers (own translation
+// unit: api.hip and lr_grad_api.hip only see the arguments, lr_fused_args.hpp).
 #include "lr_fused_kernel.hpp"
 
 namespace gpsig {
 
 namespace {
-template <int THREADS, int UNROLL>
-int launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, size_t lds) {
-    if (lds > 48 * 1024) {                           // dynamic LDS beyond the default has to be requested: per launch (no process-wide cache of what
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lr_seq_features_fused_kernel<THREADS, UNROLL>),   // one device was granted)
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) return int(e);
-    }
-    hipLaunchKernelGGL((lr_seq_features_fused_kernel<THREADS, UNROLL>), dim3(grid), dim3(THREADS), lds, stream, A);
-    return int(hipGetLastError());
+// what every caller of the sequence route would derive the same way: F, the LDS row stride, the work arrays' rows, the grid
+template <typename Args>
+void seq_fields(Args& A, int pad, unsigned* grid) {
+    A.F = 1 + A.c + (A.M - 1) * A.r;
+    A.lp = lr_fused_stride(A.L, pad);
+    A.rows_b = A.c > A.r ? A.c : A.r;
+    if (A.P.d_eff() > A.rows_b) A.rows_b = A.P.d_eff();
+    *grid = unsigned(A.N < (int64_t(1) << 20) ? A.N : (int64_t(1) << 20));
 }
 }  // namespace
 
-int lr_fused_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, int variant) {
-    const size_t lds = sizeof(double) * size_t(A.lp) * (size_t(A.c) + 2 * size_t(A.rows_b));
-    if (A.kind == BASE_SPECTRAL) return lr_fused_spectral_launch(stream, A, grid, lds);
+// SignatureSpectral's instances (its kappa in phase 1), the two-array form and float32: one instance each, 512 threads and 8 entries per
+// scalar-load batch (the family's phase 1 -- Q components of 3d multiply-adds, an exp and a cos per pair -- is not worth a variant search)
+int lr_fused_launch(hipStream_t stream, LrFusedArgs A, int pad, bool two_arrays, int variant) {
+    unsigned grid;
+    seq_fields(A, pad, &grid);
+    const bool spec = A.kind == BASE_SPECTRAL;
+    if (two_arrays) {
+        const size_t lds = lr_fused2_lds_bytes(A.c, A.r, A.P.d_eff(), A.L, pad);
+        return spec ? lr_launch(lr_seq_features_fused2_spectral_kernel<512, 8>, grid, 512, lds, stream, A)
+                    : lr_launch(lr_seq_features_fused2_kernel<512, 8>, grid, 512, lds, stream, A);
+    }
+    const size_t lds = lr_fused_lds_bytes(A.c, A.r, A.P.d_eff(), A.L, pad);
+    if (spec) return lr_launch(lr_seq_features_fused_spectral_kernel<512, 8>, grid, 512, lds, stream, A);
     // BASELINE configs[2]'s sequences (L=50, c=r=50, 'sqrt'), same box: 256 threads / 4 entries per batch 4.32 ms, 256 / 8 3.84,
     // 512 / 4 2.71, 512 / 8 2.57, 1024 / 4 3.09, 1024 / 8 4.01 (profiles/r02_lowrank.txt)
     switch (variant) {
-        case 1: return launch<256, 4>(stream, A, grid, lds);
-        case 2: return launch<256, 8>(stream, A, grid, lds);
-        case 3: return launch<512, 4>(stream, A, grid, lds);
-        default: return launch<512, 8>(stream, A, grid, lds);
+        case 1: return lr_launch(lr_seq_features_fused_kernel<256, 4>, grid, 256, lds, stream, A);
+        case 2: return lr_launch(lr_seq_features_fused_kernel<256, 8>, grid, 256, lds, stream, A);
+        case 3: return lr_launch(lr_seq_features_fused_kernel<512, 4>, grid, 512, lds, stream, A);
+        default: return lr_launch(lr_seq_features_fused_kernel<512, 8>, grid, 512, lds, stream, A);
     }
 }
 
-int lr_fused2_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid) {
-    const size_t lds = sizeof(double) * size_t(A.lp) * 2 * size_t(A.rows_b);
-    if (A.kind == BASE_SPECTRAL) return lr_fused2_spectral_launch(stream, A, grid, lds);
-    auto kern = lr_seq_features_fused2_kernel<512, 8>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) return int(e);
+int lr_fused_launch(hipStream_t stream, LrFusedArgsF32 A, int pad, bool two_arrays, int /*variant: the float64 instances'*/) {
+    unsigned grid;
+    seq_fields(A, pad, &grid);
+    const bool spec = A.kind == BASE_SPECTRAL;
+    if (two_arrays) {
+        const size_t lds = lr_fused2_lds_bytes_f32(A.c, A.r, A.P.d_eff(), A.L, pad);
+        return spec ? lr_launch(lr_seq_features_fused2_spectral_f32_kernel<512, 8>, grid, 512, lds, stream, A)
+                    : lr_launch(lr_seq_features_fused2_f32_kernel<512, 8>, grid, 512, lds, stream, A);
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, A);
-    return int(hipGetLastError());
+    const size_t lds = lr_fused_lds_bytes_f32(A.c, A.r, A.P.d_eff(), A.L, pad);
+    return spec ? lr_launch(lr_seq_features_fused_spectral_f32_kernel<512, 8>, grid, 512, lds, stream, A)
+                : lr_launch(lr_seq_features_fused_f32_kernel<512, 8>, grid, 512, lds, stream, A);
 }
 
-int lr_tens_fused_launch(hipStream_t stream, const LrTensFusedArgs& A) {
+int lr_tens_fused_launch(hipStream_t stream, LrTensFusedArgs A) {
+    A.F = 1 + A.c + (A.M - 1) * A.r;
     const size_t lds = lr_tens_fused_lds_bytes(A.c, A.r, A.P.d_eff(), A.lt, A.E);
-    if (A.kind == BASE_SPECTRAL) return lr_tens_fused_spectral_launch(stream, A, lds);
-    hipLaunchKernelGGL(lr_tens_features_fused_kernel, dim3(unsigned(A.T)), dim3(LR_TENS_THREADS), lds, stream, A);
-    return int(hipGetLastError());
+    return A.kind == BASE_SPECTRAL ? lr_launch(lr_tens_features_fused_spectral_kernel, unsigned(A.T), LR_TENS_THREADS, lds, stream, A)
+                                   : lr_launch(lr_tens_features_fused_kernel, unsigned(A.T), LR_TENS_THREADS, lds, stream, A);
 }
 
-// ---- SignatureSpectral: the same kernels with its kappa in phase 1, one instance each (the family's phase 1 -- Q components of 3d
-// multiply-adds, an exp and a cos per pair -- is not worth a variant search of its own)
-int lr_fused_spectral_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, size_t lds) {
-    auto kern = lr_seq_features_fused_spectral_kernel<512, 8>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) return int(e);
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, A);
-    return int(hipGetLastError());
+int lr_tens_fused_launch(hipStream_t stream, LrTensFusedArgsF32 A) {
+    A.F = 1 + A.c + (A.M - 1) * A.r;
+    const size_t lds = lr_tens_fused_lds_bytes_f32(A.c, A.r, A.P.d_eff(), A.lt, A.E);
+    return A.kind == BASE_SPECTRAL ? lr_launch(lr_tens_features_fused_spectral_f32_kernel, unsigned(A.T), LR_TENS_THREADS, lds, stream, A)
+                                   : lr_launch(lr_tens_features_fused_f32_kernel, unsigned(A.T), LR_TENS_THREADS, lds, stream, A);
 }
 
-int lr_fused2_spectral_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, size_t lds) {
-    auto kern = lr_seq_features_fused2_spectral_kernel<512, 8>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) return int(e);
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, A);
-    return int(hipGetLastError());
-}
-
-int lr_tens_fused_spectral_launch(hipStream_t stream, const LrTensFusedArgs& A, size_t lds) {
-    hipLaunchKernelGGL(lr_tens_features_fused_spectral_kernel, dim3(unsigned(A.T)), dim3(LR_TENS_THREADS), lds, stream, A);
-    return int(hipGetLastError());
-}
-
-// ---- float32 forms: one instance each (512 threads, 8 entries per scalar-load batch: the float64 default)
+// ---- float32: what the kernels read of the float64 state, narrowed on the device
 namespace {
-template <typename K, typename Args>
-int launch_f32(K kern, hipStream_t stream, const Args& A, unsigned grid, unsigned threads, size_t lds) {
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) return int(e);
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, stream, A);
-    return int(hipGetLastError());
-}
-
 __global__ __launch_bounds__(256) void lr_narrow_kernel(const double* __restrict__ in, int64_t n, float* __restrict__ out) {
     for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) out[i] = float(in[i]);
 }
@@ -101,23 +83,6 @@ unsigned narrow_grid(int64_t n) {
     return unsigned(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 }  // namespace
-
-int lr_fused_f32_launch(hipStream_t stream, const LrFusedArgsF32& A, unsigned grid, bool two_arrays) {
-    if (two_arrays) {
-        const size_t lds = sizeof(float) * size_t(A.lp) * 2 * size_t(A.rows_b);
-        return A.kind == BASE_SPECTRAL ? launch_f32(lr_seq_features_fused2_spectral_f32_kernel<512, 8>, stream, A, grid, 512, lds)
-                                       : launch_f32(lr_seq_features_fused2_f32_kernel<512, 8>, stream, A, grid, 512, lds);
-    }
-    const size_t lds = sizeof(float) * size_t(A.lp) * (size_t(A.c) + 2 * size_t(A.rows_b));
-    return A.kind == BASE_SPECTRAL ? launch_f32(lr_seq_features_fused_spectral_f32_kernel<512, 8>, stream, A, grid, 512, lds)
-                                   : launch_f32(lr_seq_features_fused_f32_kernel<512, 8>, stream, A, grid, 512, lds);
-}
-
-int lr_tens_fused_f32_launch(hipStream_t stream, const LrTensFusedArgsF32& A) {
-    const size_t lds = lr_tens_fused_lds_bytes_f32(A.c, A.r, A.P.d_eff(), A.lt, A.E);
-    return A.kind == BASE_SPECTRAL ? launch_f32(lr_tens_features_fused_spectral_f32_kernel, stream, A, unsigned(A.T), LR_TENS_THREADS, lds)
-                                   : launch_f32(lr_tens_features_fused_f32_kernel, stream, A, unsigned(A.T), LR_TENS_THREADS, lds);
-}
 
 int lr_narrow_launch(hipStream_t stream, const double* in, int64_t n, float* out) {
     if (n <= 0) return 0;

@@ -4,7 +4,8 @@
 // inside the differentiated graph (gpsig/low_rank_calculations.py:47-60): landmarks and whitening are functions of the trainable
 // parameters, new at every step, and live where the step runs.  gpsig_lr_seq_features (api.hip) takes them from the host (or from a
 // gpsig_lr_draw state) because the evaluation path's caller owns them; the training path's two entry points take device pointers:
-//     gpsig_lr_seq_features_dev    Phi (N, F) = the fused feature kernel of lr_fused_kernel.hpp on (X, S, Wh)
+//     gpsig_lr_seq_features_dev    Phi (N, F) = the fused feature kernel of lr_fused_kernel.hpp on (X, S, Wh), launched by
+//                                  lr_fused_inst.hip (fused_features below: the evaluation path's arguments on device pointers)
 //     gpsig_lr_seq_features_grad   dPhi (N, F) -> dX, dS, dWh, d base parameter: lr_grad_kernel.hpp
 // and SignatureSpectral's pair, whose parameters (alpha, omega, gamma) are trained and so come as device pointers too:
 //     gpsig_lr_seq_features_spectral_dev    Phi by the spectral fused instances on a table packed on the device (no host round trip)
@@ -15,37 +16,26 @@
 // Scratch: B_GR0 dWh partials, B_GR1 the per-workgroup E_i and kxs, B_LRDK dkxs, B_GR2 the cross op's partials (own buffers: none of them
 // can be resized while another one's reader is queued; ensure() waits for the stream before it frees anything anyway).
 // The projections of an evaluation are value-independent random objects: they come from the host once per draw, are kept on the
-// device by content (with the two transposed copies the reverse pass gathers over) and reused by every call that passes the same ones.
+// device by content (with the two transposed copies the reverse pass gathers over: ContentUpload, ctx.hpp, as api.hip's lr_upload)
+// and reused by every call that passes the same ones.
 #include "ctx.hpp"
 #include "lr_grad_kernel.hpp"
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 using namespace gpsig;
-
-namespace gpsig {
-int lr_fused_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid, int variant);
-int lr_fused2_launch(hipStream_t stream, const LrFusedArgs& A, unsigned grid);
-}
 
 namespace {
 
 constexpr size_t LR_SPECTRAL_DKXS_BUDGET = size_t(256) << 20;      // bytes of dkxs per chunk of sequences (spectral reverse pass)
 
-uint64_t fnv(uint64_t h, const void* p, size_t n) {
-    const unsigned char* b = static_cast<const unsigned char*>(p);
-    size_t i = 0;
-    for (; i + 8 <= n; i += 8) { uint64_t w; memcpy(&w, b + i, 8); h = (h ^ w) * 0x100000001b3ull; }
-    for (; i < n; ++i) h = (h ^ b[i]) * 0x100000001b3ull;
-    return h;
-}
-
 // the projections of levels 2 .. M on the device: by output column, by first operand index, by second operand index
 int upload_sketches(gpsig_ctx* c, int cc, int r, int nsk, const gpsig_sketch* sk, LrGradSketch* out) {
     if (nsk < 0 || nsk > LR_FUSED_MAX_SKETCHES) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for num_levels <= %d", LR_FUSED_MAX_SKETCHES + 1);
     if (nsk > 0 && !sk) return fail(c, GPSIG_ERR_INVALID, "NULL sketch array");
-    uint64_t h = 0xcbf29ce484222325ull;
+    uint64_t h = FNV1A_BASIS;
     int k2 = cc;
     size_t bytes = 64;
     for (int i = 0; i < nsk; ++i) {
@@ -53,39 +43,21 @@ int upload_sketches(gpsig_ctx* c, int cc, int r, int nsk, const gpsig_sketch* sk
         if (s.k1 != cc || s.k2 != k2 || s.r != r || s.nnz < 0 || !s.colptr || (s.nnz > 0 && (!s.i1 || !s.i2 || !s.val)))
             return fail(c, GPSIG_ERR_INVALID, "sketch %d has shape (%d, %d) -> %d, expected (%d, %d) -> %d", i, s.k1, s.k2, s.r, cc, k2, r);
         const int64_t sd[4] = {s.k1, s.k2, s.r, s.nnz};
-        h = fnv(h, sd, sizeof(sd));
-        h = fnv(h, s.colptr, sizeof(int32_t) * (size_t(s.r) + 1));
-        h = fnv(h, s.i1, sizeof(int32_t) * size_t(s.nnz));
-        h = fnv(h, s.i2, sizeof(int32_t) * size_t(s.nnz));
-        h = fnv(h, s.val, sizeof(double) * size_t(s.nnz));
+        h = fnv1a(h, sd, sizeof(sd));
+        h = fnv1a(h, s.colptr, sizeof(int32_t) * (size_t(s.r) + 1));
+        h = fnv1a(h, s.i1, sizeof(int32_t) * size_t(s.nnz));
+        h = fnv1a(h, s.i2, sizeof(int32_t) * size_t(s.nnz));
+        h = fnv1a(h, s.val, sizeof(double) * size_t(s.nnz));
         bytes += 3 * (sizeof(LrEntry) * (size_t(s.nnz) + 1) + 16) + sizeof(int32_t) * (size_t(s.r) + size_t(s.k1) + size_t(s.k2) + 3) + 48;
         k2 = r;
     }
-    if (h == 0) h = 1;
-    void* base;
-    CHK(ensure(c, B_LR8, bytes, &base));
-    const bool cached = c->lrg_hash == h && c->lrg_base == base && c->lrg_offsets.size() == size_t(6 * nsk);
-    std::vector<unsigned char> host(cached ? 0 : bytes);
-    std::vector<size_t> offs;
-    size_t o = 0;
-    auto place = [&](const void* src, size_t n) -> const unsigned char* {
-        size_t at;
-        if (cached) {
-            at = c->lrg_offsets[offs.size()];
-        } else {
-            o = (o + 15) / 16 * 16;
-            if (n) memcpy(host.data() + o, src, n);
-            at = o;
-            o += n;
-        }
-        offs.push_back(at);
-        return static_cast<const unsigned char*>(base) + at;
-    };
+    ContentUpload up(c->lr_sketch_cache);
+    CHK(up.open(c, B_LR8, bytes, h, size_t(6 * nsk)));
     for (int i = 0; i < nsk; ++i) {
         const gpsig_sketch& s = sk[i];
         std::vector<LrEntry> e0, e1, e2;
         std::vector<int32_t> p1, p2;
-        if (!cached) {
+        if (!up.cached) {
             const size_t nnz = size_t(s.nnz);
             e0.resize(nnz + 1); e1.resize(nnz + 1); e2.resize(nnz + 1);
             p1.assign(size_t(s.k1) + 1, 0); p2.assign(size_t(s.k2) + 1, 0);
@@ -104,22 +76,14 @@ int upload_sketches(gpsig_ctx* c, int cc, int r, int nsk, const gpsig_sketch* sk
                 }
         }
         LrGradSketch& g = out[i];
-        g.colptr = reinterpret_cast<const int32_t*>(place(s.colptr, sizeof(int32_t) * (size_t(s.r) + 1)));
-        g.ent = reinterpret_cast<const LrEntry*>(place(e0.data(), sizeof(LrEntry) * size_t(s.nnz)));
-        g.ptr1 = reinterpret_cast<const int32_t*>(place(p1.data(), sizeof(int32_t) * (size_t(s.k1) + 1)));
-        g.ent1 = reinterpret_cast<const LrEntry*>(place(e1.data(), sizeof(LrEntry) * size_t(s.nnz)));
-        g.ptr2 = reinterpret_cast<const int32_t*>(place(p2.data(), sizeof(int32_t) * (size_t(s.k2) + 1)));
-        g.ent2 = reinterpret_cast<const LrEntry*>(place(e2.data(), sizeof(LrEntry) * size_t(s.nnz)));
+        g.colptr = up.place<int32_t>(s.colptr, sizeof(int32_t) * (size_t(s.r) + 1), 16);
+        g.ent = up.place<LrEntry>(e0.data(), sizeof(LrEntry) * size_t(s.nnz), 16);
+        g.ptr1 = up.place<int32_t>(p1.data(), sizeof(int32_t) * (size_t(s.k1) + 1), 16);
+        g.ent1 = up.place<LrEntry>(e1.data(), sizeof(LrEntry) * size_t(s.nnz), 16);
+        g.ptr2 = up.place<int32_t>(p2.data(), sizeof(int32_t) * (size_t(s.k2) + 1), 16);
+        g.ent2 = up.place<LrEntry>(e2.data(), sizeof(LrEntry) * size_t(s.nnz), 16);
     }
-    if (!cached) {
-        CHK(no_capture(c, "the projections of a low-rank evaluation have to be uploaded"));
-        ++c->alloc_gen;                  // a recorded graph read the old contents of this buffer
-        c->lrg_hash = 0;
-        HIPCHK(c, hipMemcpyAsync(base, host.data(), o, hipMemcpyHostToDevice, c->stream));
-        CHK(host_sync(c));               // `host` goes out of scope
-        c->lrg_hash = h; c->lrg_base = base; c->lrg_offsets = offs;
-    }
-    return GPSIG_OK;
+    return up.commit(c, "the projections of a low-rank evaluation have to be uploaded");
 }
 
 int check(gpsig_ctx* c, const gpsig_params* p, int cc, int r, int nsk, bool spectral = false) {
@@ -169,6 +133,54 @@ __global__ __launch_bounds__(256) void lr_spectral_pack_kernel(const double* __r
     }
 }
 
+// the fused feature kernels (lr_fused_inst.hip) on device-resident landmarks and whitening: the caller scaled the inputs (no lengthscales,
+// no lags); `two` picks the two-array form, else the three-array instance of lr_fused_variant
+int fused_features(gpsig_ctx* c, const gpsig_params* p, int cc, int r, int nsk, const LrGradSketch* gs, const void* X, int64_t N, int L,
+                   const double* S, const double* Wh, const double* spec, bool two, void* Phi, const char* what) {
+    LrFusedArgs A{};
+    A.X = static_cast<const double*>(X); A.N = N; A.L = L;
+    A.P.d_in = p->num_features;
+    A.S = S; A.Wh = Wh;
+    A.c = cc; A.r = r; A.M = p->num_levels; A.difference = p->difference; A.kind = int(p->base_kernel);
+    A.p0 = p->base_params[0]; A.p1 = p->base_params[1];
+    A.spec = spec;
+    for (int i = 0; i < nsk; ++i) A.sk[i] = LrFusedSketch{gs[i].colptr, gs[i].ent};
+    A.Phi = static_cast<double*>(Phi);
+    const int rc = lr_fused_launch(c->stream, A, c->lr_fused_pad, two, c->lr_fused_variant);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "%s: %s", what, hipGetErrorString(hipError_t(rc)));
+    return GPSIG_OK;
+}
+
+// the LrGradArgs fields both reverse passes fill the same way; the caller sets the sequences, dPhi, part and what is its own
+void grad_args(const gpsig_ctx* c, const gpsig_params* p, int cc, int r, int nsk, const LrGradSketch* gs, int L, const double* S, const double* Wh,
+               void* escr, int64_t escr_stride, LrGradArgs* A) {
+    const int M = p->num_levels, d = p->num_features;
+    A->L = L; A->d = d;
+    A->S = S; A->Wh = Wh;
+    A->c = cc; A->r = r; A->M = M; A->difference = p->difference; A->kind = int(p->base_kernel);
+    A->p0 = p->base_params[0]; A->p1 = p->base_params[1];
+    for (int i = 0; i < nsk; ++i) A->sk[i] = gs[i];
+    A->F = 1 + cc + (M - 1) * r;
+    A->escr = static_cast<double*>(escr); A->escr_stride = escr_stride;
+    A->lp = lr_fused_stride(L, c->lr_fused_pad);
+    A->rows_b = std::max(std::max(std::max(cc, r), d), 16);
+}
+
+// the reverse kernel in the workgroup size lr_grad_threads picks: one workgroup per CU at these LDS sizes, 1024 threads give the scalar
+// loads of the projections' entries twice the wavefronts to hide behind
+template <typename Args>
+int grad_launch(gpsig_ctx* c, const Args& A, unsigned grid, size_t lds) {
+    const bool wide = c->lr_grad_threads != 512;
+    void (*kern)(Args);
+    if constexpr (std::is_same<Args, LrGradSpectralArgs>::value)
+        kern = wide ? lr_seq_features_grad_spectral_kernel<1024> : lr_seq_features_grad_spectral_kernel<512>;
+    else
+        kern = wide ? lr_seq_features_grad_kernel<1024> : lr_seq_features_grad_kernel<512>;
+    const int rc = lr_launch(kern, grid, wide ? 1024 : 512, lds, c->stream, A);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "low-rank reverse kernel: %s", hipGetErrorString(hipError_t(rc)));
+    return GPSIG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -177,27 +189,13 @@ int gpsig_lr_seq_features_dev(gpsig_ctx* c, const gpsig_params* p, int32_t cc, i
                               int64_t N, int32_t L, const double* S, const double* Wh, void* Phi) {
     CHK(check(c, p, cc, r, nsk));
     if (N < 0 || L < 1 || (N > 0 && (!X || !S || !Wh || !Phi))) return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
-    const int M = p->num_levels, d = p->num_features, F = 1 + cc + (M - 1) * r;
-    const size_t lds = lr_fused_lds_bytes(cc, r, d, L, c->lr_fused_pad);
+    // always the three-array form (the instance of lr_fused_variant): lr_fused does not apply here
+    const size_t lds = lr_fused_lds_bytes(cc, r, p->num_features, L, c->lr_fused_pad);
     if (lds > LR_FUSED_MAX_LDS) return fail(c, GPSIG_ERR_UNSUPPORTED, "a sequence's low-rank arrays (%zu bytes) exceed the LDS", lds);
     LrGradSketch gs[LR_FUSED_MAX_SKETCHES];
     CHK(upload_sketches(c, cc, r, nsk, sketches, gs));
     if (N == 0) return GPSIG_OK;
-    LrFusedArgs A;
-    memset(&A, 0, sizeof(A));
-    A.X = static_cast<const double*>(X); A.N = N; A.L = L;
-    A.P.d_in = d;                          // no lengthscales, no lags: the caller scaled the inputs
-    A.S = S; A.Wh = Wh;
-    A.c = cc; A.r = r; A.M = M; A.difference = p->difference; A.kind = int(p->base_kernel);
-    A.p0 = p->base_params[0]; A.p1 = p->base_params[1];
-    for (int i = 0; i < nsk; ++i) A.sk[i] = LrFusedSketch{gs[i].colptr, gs[i].ent};
-    A.Phi = static_cast<double*>(Phi); A.F = F;
-    A.lp = lr_fused_stride(L, c->lr_fused_pad);
-    A.rows_b = std::max(std::max(cc, r), d);
-    const unsigned grid = unsigned(N < (int64_t(1) << 20) ? N : (int64_t(1) << 20));
-    const int rc = lr_fused_launch(c->stream, A, grid, c->lr_fused_variant);
-    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "fused low-rank feature kernel: %s", hipGetErrorString(hipError_t(rc)));
-    return GPSIG_OK;
+    return fused_features(c, p, cc, r, nsk, gs, X, N, L, S, Wh, nullptr, false, Phi, "fused low-rank feature kernel");
 }
 
 int gpsig_lr_seq_features_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches, const void* X,
@@ -205,7 +203,7 @@ int gpsig_lr_seq_features_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, 
                                double* g_base) {
     CHK(check(c, p, cc, r, nsk));
     if (N < 0 || L < 1 || !gS || !gWh || (N > 0 && (!X || !S || !Wh || !dPhi || !gX))) return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
-    const int M = p->num_levels, d = p->num_features, F = 1 + cc + (M - 1) * r;
+    const int M = p->num_levels, d = p->num_features;
     if (cc > 64 || int64_t(cc) * d > int64_t(LR_GRAD_KS) * LR_GRAD_THREADS)
         return fail(c, GPSIG_ERR_UNSUPPORTED, "the low-rank reverse pass is built for num_components <= 64 and num_components x columns <= %d", LR_GRAD_KS * LR_GRAD_THREADS);
     const size_t lds = lr_grad_lds_bytes(cc, r, d, L, c->lr_fused_pad);
@@ -225,28 +223,13 @@ int gpsig_lr_seq_features_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, 
     void *part, *escr;
     CHK(ensure(c, B_GR0, sizeof(double) * size_t(grid) * size_t(width) + 64, &part));
     CHK(ensure(c, B_GR1, sizeof(double) * size_t(grid) * size_t(escr_stride) + 64, &escr));
-    LrGradArgs A;
-    memset(&A, 0, sizeof(A));
-    A.X = static_cast<const double*>(X); A.N = N; A.L = L; A.d = d;
-    A.S = S; A.Wh = Wh;
-    A.c = cc; A.r = r; A.M = M; A.difference = p->difference; A.kind = int(p->base_kernel);
-    A.p0 = p->base_params[0]; A.p1 = p->base_params[1];
-    for (int i = 0; i < nsk; ++i) A.sk[i] = gs[i];
-    A.dPhi = static_cast<const double*>(dPhi); A.F = F;
+    LrGradArgs A{};
+    grad_args(c, p, cc, r, nsk, gs, L, S, Wh, escr, escr_stride, &A);
+    A.X = static_cast<const double*>(X); A.N = N;
+    A.dPhi = static_cast<const double*>(dPhi);
     A.gX = static_cast<double*>(gX);
     A.part = static_cast<double*>(part);
-    A.escr = static_cast<double*>(escr); A.escr_stride = escr_stride;
-    A.lp = lr_fused_stride(L, c->lr_fused_pad);
-    A.rows_b = std::max(std::max(std::max(cc, r), d), 16);
-    // one workgroup per CU at these LDS sizes: 1024 threads give the scalar loads of the projections' entries twice the wavefronts to hide behind
-    const bool wide = c->lr_grad_threads != 512;
-    // (set on every launch that needs it, like sig_feat_grad_launch: a process-wide cache of the granted size would be wrong on a second device
-    // and racy between contexts)
-    const void* kern = wide ? reinterpret_cast<const void*>(lr_seq_features_grad_kernel<1024>) : reinterpret_cast<const void*>(lr_seq_features_grad_kernel<512>);
-    if (lds > 48 * 1024) HIPCHK(c, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    if (wide) hipLaunchKernelGGL(lr_seq_features_grad_kernel<1024>, dim3(grid), dim3(1024), lds, c->stream, A);
-    else hipLaunchKernelGGL(lr_seq_features_grad_kernel<512>, dim3(grid), dim3(512), lds, c->stream, A);
-    HIPCHK(c, hipGetLastError());
+    CHK(grad_launch(c, A, grid, lds));
     hipLaunchKernelGGL(lr_grad_reduce_kernel, dim3(unsigned((width + 255) / 256)), dim3(256), 0, c->stream, static_cast<const double*>(part), int(grid), width,
                        gS, int64_t(cc) * d, gWh, int64_t(cc) * cc, g_base);
     HIPCHK(c, hipGetLastError());
@@ -259,8 +242,8 @@ int gpsig_lr_seq_features_spectral_dev(gpsig_ctx* c, const gpsig_params* p, int3
                                        const double* omega, const double* gamma, void* Phi) {
     CHK(check(c, p, cc, r, nsk, true));
     if (N < 0 || L < 1 || (N > 0 && (!X || !S || !Wh || !alpha || !omega || !gamma || !Phi))) return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
-    const int M = p->num_levels, d = p->num_features, F = 1 + cc + (M - 1) * r, Q = int(p->base_params[0]);
-    // the evaluation path's choice of form (api.hip): the two-array kernel where it is built, else the three-array one
+    const int d = p->num_features, Q = int(p->base_params[0]);
+    // the two-array kernel where lr_fused == 1 and it is built, else the three-array one (also for lr_fused == 0); the footprint of that form
     const bool two = c->lr_fused == 1 && lr_fused2_ok(cc, r, L);
     const size_t lds = two ? lr_fused2_lds_bytes(cc, r, d, L, c->lr_fused_pad) : lr_fused_lds_bytes(cc, r, d, L, c->lr_fused_pad);
     if (lds > LR_FUSED_MAX_LDS) return fail(c, GPSIG_ERR_UNSUPPORTED, "a sequence's low-rank arrays (%zu bytes) exceed the LDS", lds);
@@ -273,22 +256,7 @@ int gpsig_lr_seq_features_spectral_dev(gpsig_ctx* c, const gpsig_params* p, int3
     hipLaunchKernelGGL(lr_spectral_pack_kernel, dim3(unsigned((ntab + 255) / 256)), dim3(256), 0, c->stream, alpha, omega, gamma, Q, d,
                        static_cast<double*>(tab));
     HIPCHK(c, hipGetLastError());
-    LrFusedArgs A;
-    memset(&A, 0, sizeof(A));
-    A.X = static_cast<const double*>(X); A.N = N; A.L = L;
-    A.P.d_in = d;
-    A.S = S; A.Wh = Wh;
-    A.c = cc; A.r = r; A.M = M; A.difference = p->difference; A.kind = int(GPSIG_BASE_SPECTRAL);
-    A.p0 = Q; A.p1 = p->base_params[1];
-    A.spec = static_cast<const double*>(tab);
-    for (int i = 0; i < nsk; ++i) A.sk[i] = LrFusedSketch{gs[i].colptr, gs[i].ent};
-    A.Phi = static_cast<double*>(Phi); A.F = F;
-    A.lp = lr_fused_stride(L, c->lr_fused_pad);
-    A.rows_b = std::max(std::max(cc, r), d);
-    const unsigned grid = unsigned(N < (int64_t(1) << 20) ? N : (int64_t(1) << 20));
-    const int rc = two ? lr_fused2_launch(c->stream, A, grid) : lr_fused_launch(c->stream, A, grid, c->lr_fused_variant);
-    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "fused low-rank spectral feature kernel: %s", hipGetErrorString(hipError_t(rc)));
-    return GPSIG_OK;
+    return fused_features(c, p, cc, r, nsk, gs, X, N, L, S, Wh, static_cast<const double*>(tab), two, Phi, "fused low-rank spectral feature kernel");
 }
 
 int gpsig_lr_seq_features_spectral_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches,
@@ -326,23 +294,10 @@ int gpsig_lr_seq_features_spectral_grad(gpsig_ctx* c, const gpsig_params* p, int
     CHK(ensure(c, B_GR1, sizeof(double) * size_t(gmax) * size_t(escr_stride) + 64, &escr));
     CHK(ensure(c, B_LRDK, sizeof(double) * size_t(nb) * size_t(L) * cc + 64, &dk));
     CHK(ensure(c, B_GR2, sizeof(double) * spectral_cross_grad_part_doubles(nb * L, cc, d, Q) + 64, &cpart));
-    LrGradSpectralArgs A;
-    memset(&A, 0, sizeof(A));
-    A.L = L; A.d = d;
-    A.S = S; A.Wh = Wh;
-    A.c = cc; A.r = r; A.M = M; A.difference = p->difference; A.kind = int(GPSIG_BASE_SPECTRAL);
-    A.p0 = Q; A.p1 = family;
-    for (int i = 0; i < nsk; ++i) A.sk[i] = gs[i];
-    A.F = F;
-    A.escr = static_cast<double*>(escr); A.escr_stride = escr_stride;
-    A.lp = lr_fused_stride(L, c->lr_fused_pad);
-    A.rows_b = std::max(std::max(std::max(cc, r), d), 16);
+    LrGradSpectralArgs A{};
+    grad_args(c, p, cc, r, nsk, gs, L, S, Wh, escr, escr_stride, &A);
     A.alpha = alpha; A.omega = omega; A.gamma = gamma;
     A.dkxs = static_cast<double*>(dk); A.kxs_off = kxs_off;
-    const bool wide = c->lr_grad_threads != 512;
-    const void* kern = wide ? reinterpret_cast<const void*>(lr_seq_features_grad_spectral_kernel<1024>)
-                            : reinterpret_cast<const void*>(lr_seq_features_grad_spectral_kernel<512>);
-    if (lds > 48 * 1024) HIPCHK(c, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
     int64_t at = 0;
     for (int64_t n0 = 0; n0 < N; n0 += nb) {
         const int64_t nn = std::min(nb, N - n0);
@@ -351,9 +306,7 @@ int gpsig_lr_seq_features_spectral_grad(gpsig_ctx* c, const gpsig_params* p, int
         A.X = Xc; A.N = nn;
         A.dPhi = static_cast<const double*>(dPhi) + n0 * int64_t(F);
         A.part = static_cast<double*>(part) + at * int64_t(cc) * cc;
-        if (wide) hipLaunchKernelGGL(lr_seq_features_grad_spectral_kernel<1024>, dim3(grid), dim3(1024), lds, c->stream, A);
-        else hipLaunchKernelGGL(lr_seq_features_grad_spectral_kernel<512>, dim3(grid), dim3(512), lds, c->stream, A);
-        HIPCHK(c, hipGetLastError());
+        CHK(grad_launch(c, A, grid, lds));
         const int rc = spectral_cross_grad_launch(c->stream, Q, family, d, Xc, nn * L, S, cc, alpha, omega, gamma, A.dkxs,
                                                   static_cast<double*>(gX) + n0 * int64_t(L) * d, static_cast<double*>(cpart), gS, dalpha, domega,
                                                   dgamma, n0 > 0);
