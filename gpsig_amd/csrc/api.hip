@@ -1,9 +1,13 @@
 // api.hip -- implementation of the C ABI declared in include/gpsig_hip.h.
 //
 // Host-side orchestration only: input preparation, kernel-shape selection, task lists, scratch
-// memory, HIP-event timing.  All arithmetic happens in the kernels of seq_gram_kernel.hpp and
-// aux_kernels.hpp.  There is deliberately no CPU fallback: without a HIP device every entry point
-// fails with GPSIG_ERR_HIP.
+// memory, HIP-event timing.  All arithmetic happens in kernels: the pair recursions of seq_gram_kernel.hpp
+// and seq_pk2_kernel.hpp, the tensor kernels and elementwise passes of aux_kernels.hpp and tvs_tile_kernel.hpp,
+// the level features and their contraction of sig_feat_kernel.hpp, low-rank mode's lowrank_kernels.hpp,
+// lr_fused_kernel.hpp and lr_draw_kernels.hpp, and the wide route's wide_kernels.hpp (wide_api.hip).  The kernels
+// are instantiated in the instance units; launchers.hpp declares their lookups, and the sequence-Gram units are
+// found through the table of descriptors below.  There is deliberately no CPU fallback: without a HIP device
+// every entry point fails with GPSIG_ERR_HIP.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -15,6 +19,7 @@
 #include <vector>
 
 #include "../../include/gpsig_hip.h"
+#include "launchers.hpp"
 #include "aux_kernels.hpp"
 #include "lowrank_kernels.hpp"
 #include "lr_fused_args.hpp"
@@ -24,130 +29,6 @@
 #include "tvs_tile_kernel.hpp"
 #include "seq_pk2_kernel.hpp"
 #include "sig_feat_kernel.hpp"
-
-namespace gpsig {
-typedef hipError_t (*TvsTileLaunchFn)(TvsTileArgs&, size_t, hipStream_t, int);
-TvsTileLaunchFn tvs_tile_lookup(int M, int NW, int D, bool incr, int kind);
-TvsTileLaunchFn tvs_tile_lookup_ho(int M, int NW, int D, bool incr);
-int tvs_tile_width(int d);
-bool seq_pk2_select(int rows, int d, int M, int* G, int* C, int* D);
-typedef hipError_t (*SigFeatLaunchFn)(const SigFeatArgs&, unsigned, size_t, hipStream_t);
-SigFeatLaunchFn sig_feat_lookup(int d, int M);
-hipError_t sig_gram_launch(const SigGramArgs& G, int ntiles, hipStream_t stream, int dma, int* used_dma);
-hipError_t sig_reduce_launch(const SigReduceArgs& R, hipStream_t stream);
-hipError_t sig_convert_launch(const void* in, void* out, int64_t n, bool widen, hipStream_t stream);
-bool solver_dsyevd(void** handle_slot, hipStream_t stream, int n, double* A, double* ev, double* work, int* info, std::string* err);
-void solver_release(void* handle);
-bool solver_dgemm(void** handle_slot, hipStream_t stream, bool transA, bool transB, int m, int n, int k, double alpha, const double* A, int lda,
-                  const double* B, int ldb, double beta, double* C, int ldc, std::string* err);      // lowrank_solver.hip
-int tvs_tile_waves(int M, int D, int E, int kind);
-typedef hipError_t (*SeqLaunchFn)(const SeqGramArgs&, int, size_t, hipStream_t);
-SeqLaunchFn seq_pk2_lookup(int G, int C, int D, int M, int mode, int pack, int waves);
-SeqLaunchFn seq_lookup_inc_exact(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_inc_ex_g16_d4(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_inc_ex_g16_d8(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_inc_ex_g16_d16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_inc_ex_g64_d4(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_inc_ex_g64_d8(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_inc_ex_g64_d16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptd_ex_g16_d4(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptd_ex_g16_d8(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptd_ex_g16_d16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptd_ex_g64_d4(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptd_ex_g64_d8(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptd_ex_g64_d16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_inc_g16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_inc_g64(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptd_exact(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptdrbf_exact(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptdrbf_stash(int, int, int, int);
-SeqLaunchFn seq_lookup_ptdmatern_stash(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ptdm12_exact(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptdm32_exact(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptdm52_exact(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptdrbf_ex_g16_d4(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptdrbf_ex_g16_d8(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptdrbf_ex_g16_d16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptdrbf_ex_g64_d4(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptdrbf_ex_g64_d8(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptdrbf_ex_g64_d16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptd_g16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptd_spectral_g16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptd_spectral_g64(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptd_g64(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptn_g16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ptn_g64(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ho_inc_d4(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_inc_d8(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_inc_d16(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_ptd_d4(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_ptd_d8(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_ptd_d16(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_f32_inc_d4(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_f32_inc_d8(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_f32_inc_d16(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_f32_ptd_d4(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_f32_ptd_d8(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_f32_ptd_d16(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_ptn_d4(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_ptn_d8(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_ptn_d16(int, int, int, int, int);
-typedef hipError_t (*TvsLaunchFn)(const TvsArgs&, hipStream_t);
-TvsLaunchFn tvs_lookup(int M, int TT, bool incr, bool f32);
-SeqLaunchFn seq_lookup_f32_inc_exact(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_inc_ex_g16_d4(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_inc_ex_g16_d8(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_inc_ex_g16_d16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_inc_ex_g64_d4(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_inc_ex_g64_d8(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_inc_ex_g64_d16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptd_ex_g16_d4(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptd_ex_g16_d8(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptd_ex_g16_d16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptd_ex_g64_d4(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptd_ex_g64_d8(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptd_ex_g64_d16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_inc_g16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_inc_g64(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptd_exact(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptdrbf_exact(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptdrbf_ex_g16_d4(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptdrbf_ex_g16_d8(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptdrbf_ex_g16_d16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptdrbf_ex_g64_d4(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptdrbf_ex_g64_d8(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptdrbf_ex_g64_d16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptd_g16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptd_g64(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptn_g16(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_f32_ptn_g64(int, int, int, int, bool);
-SeqLaunchFn seq_lookup_ho_f32_ptn_d4(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_f32_ptn_d8(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_f32_ptn_d16(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_inc_d32(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_ptd_d32(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_ptn_d32(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_f32_inc_d32(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_f32_ptd_d32(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_f32_ptn_d32(int, int, int, int, int);
-SeqLaunchFn seq_lookup_ho_ptdrbf_exact(int G, int C, int D, int M, int order);
-SeqLaunchFn seq_lookup_ho_ptdrbf_exact_o4(int G, int C, int D, int M, int order);
-SeqLaunchFn seq_lookup_ho_ptdm12_exact(int kind, int G, int C, int D, int M, int order);     // the Matern families' exact higher-order instances
-SeqLaunchFn seq_lookup_ho_ptdm32_exact(int kind, int G, int C, int D, int M, int order);
-SeqLaunchFn seq_lookup_ho_ptdm52_exact(int kind, int G, int C, int D, int M, int order);
-typedef hipError_t (*TvsLaneTLaunchFn)(const TvsLaneTArgs&, hipStream_t);
-bool tvs_lanet_plan(int M, int d, bool incr, TvsLaneTLaunchFn* fns, int* ngroups);
-// wide_api.hip: state spaces beyond the exact-shape kernels' columns (kernel arguments by dgemm, fused map / difference / recursion kernels)
-bool wide_tvs_available(const gpsig_ctx* c, const gpsig_params* p, int d, int64_t Tn, int64_t N, int L);
-int wide_tvs_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz, int d, const double* Z, const double* Xs, int64_t Tn, int64_t N, int L,
-                     int increments, const double* fx, const double* w, int sum_levels, double* out, double* aux);
-bool wide_tens_available(const gpsig_ctx* c, const gpsig_params* p, int64_t Tn);
-int wide_tens_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz, int d, const double* Z, int64_t Tn, int increments, const double* w,
-                      int sum_levels, double* out);
-bool wide_lat_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L2);
-int wide_lat_forward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Xs, const double* Ys, int64_t N1, int64_t N2, int L1, int L2, bool diag,
-                     double* out);
-}  // namespace gpsig
 
 using namespace gpsig;
 
@@ -170,98 +51,42 @@ constexpr int N_SEQ_TABLE = int(sizeof(SEQ_TABLE) / sizeof(SEQ_TABLE[0]));
 constexpr int N_SEQ_TABLE_GENERIC = int(sizeof(SEQ_TABLE_GENERIC) / sizeof(SEQ_TABLE_GENERIC[0]));
 constexpr int N_SEQ_TABLE_SPECTRAL = int(sizeof(SEQ_TABLE_SPECTRAL) / sizeof(SEQ_TABLE_SPECTRAL[0]));
 
-// float64, differences, the RBF kernel at compile time.  These instances use the table-driven exp on prescaled records
-// (SEQ_FAST_RBF in seq_gram_kernel.hpp): whoever launches one prepares the records with the prescale and the norm column.
-SeqLaunchFn seq_launcher_rbf(const SeqConfig& c) {
-    SeqLaunchFn f = nullptr;
-    if ((f = seq_lookup_ptdrbf_exact(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-    if ((f = seq_lookup_ptdrbf_ex_g16_d4(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-    if ((f = seq_lookup_ptdrbf_ex_g16_d8(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-    if ((f = seq_lookup_ptdrbf_ex_g16_d16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-    if ((f = seq_lookup_ptdrbf_ex_g64_d4(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-    if ((f = seq_lookup_ptdrbf_ex_g64_d8(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-    return seq_lookup_ptdrbf_ex_g64_d16(c.G, c.C, c.D, c.MMAX, c.exact);
+// the instance units, in the order of launchers.hpp's lists: constant data, nothing is registered at load time
+#define X_UNIT(n) &seq_lookup_##n##_unit,
+const SeqUnit* const SEQ_UNITS[] = {GPSIG_SEQ_UNITS(X_UNIT)};
+const SeqHoUnit* const SEQ_HO_UNITS[] = {GPSIG_SEQ_HO_UNITS(X_UNIT)};
+#undef X_UNIT
+
+// the first unit of this element type, mode and compile-time base kernel (-1: none) that holds the configuration.  A unit with a base kernel at
+// compile time is asked only by name of that kernel, never as part of the generic lookup: the float64 RBF and Matern instances use the
+// table-driven exp on prescaled records (SEQ_FAST_RBF in seq_gram_kernel.hpp; whoever launches one prepares the records with the prescale and
+// the norm column), and the spectral ones take points where the others take inner products.
+SeqLaunchFn seq_unit_lookup(bool f32, int mode, int kind, const SeqConfig& c) {
+    for (const SeqUnit* u : SEQ_UNITS)
+        if (u->f32 == f32 && u->mode == mode && u->kind == kind)
+            if (SeqLaunchFn f = u->lookup(c.G, c.C, c.D, c.MMAX, c.exact)) return f;
+    return nullptr;
 }
 
+// float32 with differences: the RBF kernel at compile time where the configuration is exact, else (and everywhere else) the generic units.
+// MODE_PT_NODIFF has no exact units: an exact configuration there yields null.
 SeqLaunchFn seq_launcher(int mode, const SeqConfig& c, bool f32, int kind) {
-    SeqLaunchFn f = nullptr;
-    if (f32) {
-        if (mode == MODE_INC) {
-            if ((f = seq_lookup_f32_inc_exact(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (c.exact && (f = seq_lookup_f32_inc_ex_g16_d4(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (c.exact && (f = seq_lookup_f32_inc_ex_g16_d8(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (c.exact && (f = seq_lookup_f32_inc_ex_g16_d16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (c.exact && (f = seq_lookup_f32_inc_ex_g64_d4(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (c.exact && (f = seq_lookup_f32_inc_ex_g64_d8(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (c.exact && (f = seq_lookup_f32_inc_ex_g64_d16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if ((f = seq_lookup_f32_inc_g16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            return seq_lookup_f32_inc_g64(c.G, c.C, c.D, c.MMAX, c.exact);
-        }
-        if (mode == MODE_PT_DIFF) {
-            if (kind == BASE_RBF && c.exact && (f = seq_lookup_f32_ptdrbf_exact(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (kind == BASE_RBF && c.exact && (f = seq_lookup_f32_ptdrbf_ex_g16_d4(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (kind == BASE_RBF && c.exact && (f = seq_lookup_f32_ptdrbf_ex_g16_d8(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (kind == BASE_RBF && c.exact && (f = seq_lookup_f32_ptdrbf_ex_g16_d16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (kind == BASE_RBF && c.exact && (f = seq_lookup_f32_ptdrbf_ex_g64_d4(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (kind == BASE_RBF && c.exact && (f = seq_lookup_f32_ptdrbf_ex_g64_d8(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (kind == BASE_RBF && c.exact && (f = seq_lookup_f32_ptdrbf_ex_g64_d16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if ((f = seq_lookup_f32_ptd_exact(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (c.exact && (f = seq_lookup_f32_ptd_ex_g16_d4(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (c.exact && (f = seq_lookup_f32_ptd_ex_g16_d8(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (c.exact && (f = seq_lookup_f32_ptd_ex_g16_d16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (c.exact && (f = seq_lookup_f32_ptd_ex_g64_d4(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (c.exact && (f = seq_lookup_f32_ptd_ex_g64_d8(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if (c.exact && (f = seq_lookup_f32_ptd_ex_g64_d16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            if ((f = seq_lookup_f32_ptd_g16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-            return seq_lookup_f32_ptd_g64(c.G, c.C, c.D, c.MMAX, c.exact);
-        }
-        if (c.exact) return nullptr;
-        if ((f = seq_lookup_f32_ptn_g16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        return seq_lookup_f32_ptn_g64(c.G, c.C, c.D, c.MMAX, c.exact);
-    }
-    if (mode == MODE_INC) {
-        if ((f = seq_lookup_inc_exact(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        if (c.exact && (f = seq_lookup_inc_ex_g16_d4(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        if (c.exact && (f = seq_lookup_inc_ex_g16_d8(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        if (c.exact && (f = seq_lookup_inc_ex_g16_d16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        if (c.exact && (f = seq_lookup_inc_ex_g64_d4(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        if (c.exact && (f = seq_lookup_inc_ex_g64_d8(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        if (c.exact && (f = seq_lookup_inc_ex_g64_d16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        if ((f = seq_lookup_inc_g16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        return seq_lookup_inc_g64(c.G, c.C, c.D, c.MMAX, c.exact);
-    }
-    if (mode == MODE_PT_DIFF) {
-        if ((f = seq_lookup_ptd_exact(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        if (c.exact && (f = seq_lookup_ptd_ex_g16_d4(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        if (c.exact && (f = seq_lookup_ptd_ex_g16_d8(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        if (c.exact && (f = seq_lookup_ptd_ex_g16_d16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        if (c.exact && (f = seq_lookup_ptd_ex_g64_d4(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        if (c.exact && (f = seq_lookup_ptd_ex_g64_d8(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        if (c.exact && (f = seq_lookup_ptd_ex_g64_d16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        if ((f = seq_lookup_ptd_g16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-        return seq_lookup_ptd_g64(c.G, c.C, c.D, c.MMAX, c.exact);
-    }
-    if ((f = seq_lookup_ptn_g16(c.G, c.C, c.D, c.MMAX, c.exact))) return f;
-    return seq_lookup_ptn_g64(c.G, c.C, c.D, c.MMAX, c.exact);
+    if (f32 && mode == MODE_PT_DIFF && kind == BASE_RBF && c.exact)
+        if (SeqLaunchFn f = seq_unit_lookup(true, mode, BASE_RBF, c)) return f;
+    return seq_unit_lookup(f32, mode, -1, c);
 }
 
 SeqLaunchFn seq_launcher_ho(int mode, const SeqHOConfig& c, bool f32) {
-#define HO_PICK(V)                                                                \
-    do {                                                                          \
-        if (c.D == 4) return seq_lookup_ho_##V##_d4(c.G, c.C, c.D, c.MMAX, c.OMAX);   \
-        if (c.D == 8) return seq_lookup_ho_##V##_d8(c.G, c.C, c.D, c.MMAX, c.OMAX);   \
-        if (c.D == 16) return seq_lookup_ho_##V##_d16(c.G, c.C, c.D, c.MMAX, c.OMAX); \
-        return seq_lookup_ho_##V##_d32(c.G, c.C, c.D, c.MMAX, c.OMAX);            \
-    } while (0)
-    if (f32) {
-        if (mode == MODE_INC) HO_PICK(f32_inc);
-        if (mode == MODE_PT_DIFF) HO_PICK(f32_ptd);
-        HO_PICK(f32_ptn);
-    }
-    if (mode == MODE_INC) HO_PICK(inc);
-    if (mode == MODE_PT_DIFF) HO_PICK(ptd);
-    HO_PICK(ptn);
-#undef HO_PICK
+    for (const SeqHoUnit* u : SEQ_HO_UNITS)
+        if (u->f32 == f32 && u->mode == mode && u->D == c.D) return u->lookup(c.G, c.C, c.D, c.MMAX, c.OMAX);
+    return nullptr;
+}
+
+// the Matern families' exact higher-order instances: each unit answers for its own family only
+SeqLaunchFn seq_lookup_ho_matern_exact(int kind, int G, int C, int D, int M, int order) {
+    for (auto lookup : {seq_lookup_ho_ptdm12_exact, seq_lookup_ho_ptdm32_exact, seq_lookup_ho_ptdm52_exact})
+        if (SeqLaunchFn f = lookup(kind, G, C, D, M, order)) return f;
+    return nullptr;
 }
 
 }  // namespace
@@ -1263,8 +1088,7 @@ static int plan_seq(gpsig_ctx* c, const gpsig_params* p, int d_eff, int Ly, SeqP
         out->cfg = SEQ_TABLE_SPECTRAL[k];
         out->mode = g0.mode;
         out->d_eff = d_eff;
-        out->fn = out->cfg.G == 16 ? seq_lookup_ptd_spectral_g16(out->cfg.G, out->cfg.C, out->cfg.D, out->cfg.MMAX, false)
-                                   : seq_lookup_ptd_spectral_g64(out->cfg.G, out->cfg.C, out->cfg.D, out->cfg.MMAX, false);
+        out->fn = seq_unit_lookup(false, g0.mode, BASE_SPECTRAL, out->cfg);
         if (!out->fn) return fail(c, GPSIG_ERR_UNSUPPORTED, "spectral seq-gram kernel shape missing from this build");
         return GPSIG_OK;
     }
@@ -1292,9 +1116,7 @@ static int plan_seq(gpsig_ctx* c, const gpsig_params* p, int d_eff, int Ly, SeqP
             }
         }
         if (sizeof(TT) == 8 && c->allow_exact && g0.mode == MODE_PT_DIFF && seq_is_matern(p->base_kernel) && c->matern_fast != 0) {
-            SeqLaunchFn ex = p->base_kernel == GPSIG_BASE_MATERN12 ? seq_lookup_ho_ptdm12_exact(BASE_MATERN12, h.G, h.C, h.D, p->num_levels, p->order)
-                             : (p->base_kernel == GPSIG_BASE_MATERN32 ? seq_lookup_ho_ptdm32_exact(BASE_MATERN32, h.G, h.C, h.D, p->num_levels, p->order)
-                                                                      : seq_lookup_ho_ptdm52_exact(BASE_MATERN52, h.G, h.C, h.D, p->num_levels, p->order));
+            SeqLaunchFn ex = seq_lookup_ho_matern_exact(p->base_kernel, h.G, h.C, h.D, p->num_levels, p->order);
             if (ex) {
                 out->fn = ex;
                 out->cfg = SeqConfig{h.G, h.C, h.D, p->num_levels, true};
@@ -1342,17 +1164,14 @@ static int plan_seq(gpsig_ctx* c, const gpsig_params* p, int d_eff, int Ly, SeqP
     out->d_eff = d_eff;
     out->fn = nullptr;
     if (!f32 && g0.mode == MODE_PT_DIFF && p->base_kernel == GPSIG_BASE_RBF && tab[k].exact) {
-        out->fn = seq_launcher_rbf(tab[k]);
+        out->fn = seq_unit_lookup(false, MODE_PT_DIFF, BASE_RBF, tab[k]);
         out->rbf_prescaled = out->fn != nullptr;
         out->prescale = SEQ_RBF_PRESCALE;
         if (out->fn) out->fast_kind = BASE_RBF;
     }
     // the Matern families at compile time on prescaled records (round 5: seq_step_matern_prescaled), the shapes of GPSIG_SEQ_CONFIGS_EXACT
     if (!f32 && g0.mode == MODE_PT_DIFF && seq_is_matern(p->base_kernel) && tab[k].exact && c->matern_fast != 0) {
-        const SeqConfig& t = tab[k];
-        out->fn = p->base_kernel == GPSIG_BASE_MATERN12 ? seq_lookup_ptdm12_exact(t.G, t.C, t.D, t.MMAX, t.exact)
-                  : (p->base_kernel == GPSIG_BASE_MATERN32 ? seq_lookup_ptdm32_exact(t.G, t.C, t.D, t.MMAX, t.exact)
-                                                           : seq_lookup_ptdm52_exact(t.G, t.C, t.D, t.MMAX, t.exact));
+        out->fn = seq_unit_lookup(false, MODE_PT_DIFF, p->base_kernel, tab[k]);
         out->rbf_prescaled = out->fn != nullptr;            // (the records' spare column is written and ignored)
         out->prescale = seq_matern_prescale(p->base_kernel);
         if (out->fn) out->fast_kind = p->base_kernel;

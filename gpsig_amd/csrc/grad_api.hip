@@ -5,6 +5,7 @@
 // reference differentiates these through TensorFlow (training.py:149-164); there is no reference gradient code
 // to cite, the formulas are in grad_core.hpp.  Host side only: staging, chunking by the scratch budget, launches.
 #include "ctx.hpp"
+#include "launchers.hpp"
 #include "grad_kernels.hpp"
 #include "grad_ho_kernels.hpp"
 #include "grad_wave_ho_kernel.hpp"
@@ -12,34 +13,6 @@
 #include "grad_fused_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*WaveLaunchFn)(const WaveGradArgs&, int, hipStream_t);
-typedef hipError_t (*WaveHoLaunchFn)(const WaveHoArgs&, int, size_t, hipStream_t);
-WaveHoLaunchFn wave_ho_lookup(int G, int C, int order, int M);      // grad_wave_ho_inst.hip: prefixes through an HBM slot
-WaveHoLaunchFn wave_ho_undo_lookup_g16(int C, int order, int M);    // grad_wave_ho_inst_u16.hip / _u64.hip: scratch-free
-WaveHoLaunchFn wave_ho_undo_lookup_g64(int C, int order, int M);
-WaveHoLaunchFn wave_ho_undo_lookup_g32(int C, int order, int M);
-WaveHoLaunchFn wave_o1_lookup(int G, int C, int M);                    // first order from a dM lattice: seq_grad_wave_o1_kernel
-WaveHoLaunchFn wave_ho_levels_lookup_g16(int C, int order, int M);   // the forward pass: seq_levels_wave_ho_kernel
-WaveHoLaunchFn wave_ho_levels_lookup_g32(int C, int order, int M);
-WaveHoLaunchFn wave_ho_levels_lookup_g64(int C, int order, int M);
-struct HoSweeps { WaveHoLaunchFn fn; int G, C; size_t lds, slot; };
-WaveLaunchFn wave_lookup_inc(int G, int C, int DP, int LQ);
-WaveLaunchFn wave_lookup_ptd(int G, int C, int DP, int LQ);
-WaveLaunchFn wave_lookup_ptn(int G, int C, int DP, int LQ);
-typedef hipError_t (*Wave2LaunchFn)(const Wave2Args&, int, size_t, hipStream_t);
-Wave2LaunchFn wave2_lookup_inc(int G, int C, int DP, int LQ);
-Wave2LaunchFn lam_undo_lookup_ptd_rbf(int G, int C, int DP, int LQ);
-Wave2LaunchFn lam_undo_lookup_ptd_gen(int G, int C, int DP, int LQ);
-Wave2LaunchFn lam_undo_lookup_ptn_rbf(int G, int C, int DP, int LQ);
-Wave2LaunchFn lam_undo_lookup_ptn_gen(int G, int C, int DP, int LQ);
-typedef hipError_t (*FusedGradLaunchFn)(const FusedGradArgs&, int, size_t, hipStream_t);
-FusedGradLaunchFn fused_grad_stash_lookup(int kind, int DP, int LQ);
-FusedGradLaunchFn fused_grad_lookup_diff_g16(int kind, int DP, int LQ);
-FusedGradLaunchFn fused_grad_lookup_diff_g32(int kind, int DP, int LQ);
-FusedGradLaunchFn fused_grad_lookup_diff_g64(int kind, int DP, int LQ);
-FusedGradLaunchFn fused_grad_lookup_nodiff_g16(int kind, int DP, int LQ);
-FusedGradLaunchFn fused_grad_lookup_nodiff_g32(int kind, int DP, int LQ);
-FusedGradLaunchFn fused_grad_lookup_nodiff_g64(int kind, int DP, int LQ);
 // G: lanes per pair group -- 16 (four pairs per wavefront), 32 (two) or 64 (one); diff: the lattice of double increments (difference=True, the
 // reference's default) or the kernel matrix of the points itself
 static FusedGradLaunchFn fused_grad_lookup(int kind, int DP, int LQ, int G, bool diff) {
@@ -48,23 +21,6 @@ static FusedGradLaunchFn fused_grad_lookup(int kind, int DP, int LQ, int G, bool
     if (G == 64) return diff ? fused_grad_lookup_diff_g64(kind, DP, LQ) : fused_grad_lookup_nodiff_g64(kind, DP, LQ);
     return nullptr;
 }
-// sig_feat_grad_api.hip: SignatureLinear's levels differentiated through the feature contraction
-int sig_features_grad(gpsig_ctx* c, const gpsig_params* p, int d, const double* X, const double* Y, int64_t N1, int64_t N2, int L1, int L2, bool diag,
-                      bool sym, const double* G, double* gX, double* gY, bool* done);
-// tvs_grad_api.hip: the tile kernel of the tensor-vs-sequence reverse pass (tvs_grad_tile_kernel.hpp)
-bool tvs_grad_tile_ho_available(const gpsig_ctx* c, const gpsig_params* p, int d, int L, int increments);
-int tvs_grad_tile_device(gpsig_ctx* c, const gpsig_params* p, int d, const double* Z, const double* X, const double* G, int64_t Tn, int64_t N,
-                         int L, int increments, const double* fac, const double* aux, double* gZ, double* gX, double* gfac, double* gb, size_t budget, bool* done);
-// wide_api.hip: state spaces beyond the exact-shape kernels' columns
-bool wide_tvs_available(const gpsig_ctx* c, const gpsig_params* p, int d, int64_t Tn, int64_t N, int L);
-int wide_tvs_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Z, const double* X, const double* G, int64_t Tn, int64_t N, int L,
-                      int increments, const double* fac, const double* aux, double* gZ, double* gX, double* gfac);
-bool wide_tens_available(const gpsig_ctx* c, const gpsig_params* p, int64_t Tn);
-int wide_tens_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Z, int64_t Tn, int increments, const double* G, double* gZ);
-bool wide_lat_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L2);
-bool wide_lat_ho_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L2);
-int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Xs, const double* Ys, int64_t N1, int64_t N2, int L1, int L2, bool diag,
-                      const double* G, double* gX, double* gY);
 }  // namespace gpsig
 
 using namespace gpsig;

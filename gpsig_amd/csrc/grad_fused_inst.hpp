@@ -2,11 +2,10 @@
 // 4 / 8 (four columns per lane) and 16 (two; with differences only), num_levels 2 .. 6 at compile time.  Included by grad_fused_inst_*.hip, one unit
 // per (lanes per pair, difference) so that the build runs them side by side.
 #pragma once
+#include "launchers.hpp"
 #include "grad_fused_kernel.hpp"
 
 namespace gpsig {
-
-typedef hipError_t (*FusedGradLaunchFn)(const FusedGradArgs&, int, size_t, hipStream_t);
 
 template <int DP, int LQ, int KIND, int G, bool DIFF>
 static hipError_t fused_grad_launch(const FusedGradArgs& a, int ntasks, size_t lds, hipStream_t s) {

@@ -1,9 +1,9 @@
 // seq_grad_fused_kernel instances that run the backward sweep only, from the stash the evaluation kernel wrote (seq_inst_ptdrbf_stash.hip: RBF and the Matern
 // families with differences, 16 lanes per pair, four columns per lane, 4 / 8 padded features, num_levels 4 / 5)
+#include "launchers.hpp"
 #include "grad_fused_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*FusedGradLaunchFn)(const FusedGradArgs&, int, size_t, hipStream_t);
 
 template <int DP, int LQ, int KIND>
 static hipError_t fused_grad_stash_launch(const FusedGradArgs& a, int ntasks, size_t lds, hipStream_t s) {

@@ -1,9 +1,9 @@
 // instances of the higher-order reverse sweeps (grad_wave_ho_kernel.hpp): lanes per pair x columns per lane x order (2, 3, 4); the scratch-free
 // kernel with num_levels 2-5 at compile time, the slot kernel (prefixes through HBM) with num_levels <= 5 at run time
+#include "launchers.hpp"
 #include "grad_wave_ho_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*WaveHoLaunchFn)(const WaveHoArgs&, int, size_t, hipStream_t);
 
 #ifndef GPSIG_HO_UNDO_ONLY
 template <int G, int C, int O>

@@ -1,9 +1,9 @@
 // grad_wave_inst.hpp -- instantiation list of seq_grad_wave_kernel for one lattice mode (included by grad_wave_inst_*.hip)
 #pragma once
+#include "launchers.hpp"
 #include "grad_wave_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*WaveLaunchFn)(const WaveGradArgs&, int, hipStream_t);
 
 template <int G, int C, int DP, int LQ, int MODE>
 hipError_t wave_launch(const WaveGradArgs& a, int nblocks, hipStream_t s) {
@@ -16,7 +16,6 @@ hipError_t wave_launch(const WaveGradArgs& a, int nblocks, hipStream_t s) {
     X(16, 2, 4) X(16, 2, 8) X(16, 2, 16) X(16, 4, 4) X(16, 4, 8) X(16, 4, 16) \
     X(64, 2, 4) X(64, 2, 8) X(64, 2, 16) X(64, 4, 4) X(64, 4, 8) X(64, 4, 16) X(64, 8, 4) X(64, 8, 8)
 
-typedef hipError_t (*Wave2LaunchFn)(const Wave2Args&, int, size_t, hipStream_t);
 // Level variants of the scratch-free kernels: num_levels 4 and 5 at compile time (LQ = 3, 4), otherwise LQ = 4 or 7 at run time.
 #define GPSIG_W2_PICK(LAUNCH, G_, C_, D_)                                           \
     if (G == G_ && C == C_ && DP == D_)                                             \

@@ -12,6 +12,8 @@
 
 #include <string>
 
+#include "launchers.hpp"
+
 namespace {
 
 struct SolverApi {

@@ -1,10 +1,10 @@
 // Exact higher-order seq-gram instances, orders 3 and 4 (round 6): as seq_inst_ho_ptdrbf_exact.hip on the shape the planner takes for up to 128 record
 // rows at these orders (64 lanes per pair, 2 columns per lane), 8 feature columns, num_levels 4 / 5.
+#include "launchers.hpp"
 #include "seq_configs.hpp"
 #include "seq_gram_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*SeqLaunchFn)(const SeqGramArgs&, int, size_t, hipStream_t);
 
 SeqLaunchFn seq_lookup_ho_ptdrbf_exact_o4(int G, int C, int D, int M, int order) {
 #define GPSIG_HO_EXACT(D_, M_, O_) \

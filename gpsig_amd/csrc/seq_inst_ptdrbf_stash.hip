@@ -1,10 +1,10 @@
 // seq-gram kernel instantiations: the float64 RBF instances of the fused reverse kernel's headline shapes (16 lanes per pair, 4 columns per lane,
 // 4 / 8 padded features, num_levels 4 / 5 at compile time) that also write the reverse pass's stash (seq_gram_kernel.hpp: STASH)
+#include "launchers.hpp"
 #include "seq_configs.hpp"
 #include "seq_gram_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*SeqLaunchFn)(const SeqGramArgs&, int, size_t, hipStream_t);
 
 SeqLaunchFn seq_lookup_ptdrbf_stash(int G, int C, int D, int MMAX) {
     if (G != 16 || C != 4) return nullptr;

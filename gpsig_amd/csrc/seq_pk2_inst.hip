@@ -1,8 +1,8 @@
 // seq_pk2_kernel instantiations (float32, two y sequences packed per pair group) and their lookup.
+#include "launchers.hpp"
 #include "seq_pk2_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*SeqLaunchFn)(const SeqGramArgs&, int, size_t, hipStream_t);
 
 // (G, C, D, num_levels): a pair group of G lanes x C columns holds y records of up to G * C rows
 #define GPSIG_PK2_SHAPES(X) X(16, 4, 8, 4) X(16, 4, 8, 5) X(64, 2, 16, 5) X(64, 2, 16, 6) X(64, 2, 8, 5)

@@ -11,21 +11,10 @@
 // pair on the matrix cores plus a sweep per SEQUENCE.  Reference: TensorFlow's autodiff of signature_algs.py:8-35 behind
 // kernels.py:208-237 (no gradient code of its own to cite).
 #include "ctx.hpp"
+#include "launchers.hpp"
 #include "sig_feat_grad_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*SigFeatLaunchFn)(const SigFeatArgs&, unsigned, size_t, hipStream_t);
-SigFeatLaunchFn sig_feat_lookup(int d, int M);                       // sig_feat_inst.hip
-typedef hipError_t (*SigFeatGradLaunchFn)(const SigFeatGradArgs&, unsigned, size_t, hipStream_t);
-SigFeatGradLaunchFn sig_feat_grad_pick_a(int d, int M);              // d = 1 .. 4     (sig_feat_grad_inst_a.hip)
-SigFeatGradLaunchFn sig_feat_grad_pick_b(int d, int M);              // d = 5 .. 8
-SigFeatGradLaunchFn sig_feat_grad_pick_c(int d, int M);              // d = 9 .. 12
-SigFeatGradLaunchFn sig_feat_grad_pick_d(int d, int M);              // d = 13 .. 16
-SigFeatGradLaunchFn sig_feat_grad_pick_e(int d, int M);              // d = 17 .. 24
-SigFeatGradLaunchFn sig_feat_grad_pick_f(int d, int M);              // d = 25 .. 32
-bool solver_dgemm(void** handle_slot, hipStream_t stream, bool transA, bool transB, int m, int n, int k, double alpha, const double* A, int lda,
-                  const double* B, int ldb, double beta, double* C, int ldc, std::string* err);      // lowrank_solver.hip
-
 static SigFeatGradLaunchFn sig_feat_grad_lookup(int d, int M) {
     if (d < 1 || d > 32) return nullptr;
     return d <= 4 ? sig_feat_grad_pick_a(d, M) : d <= 8 ? sig_feat_grad_pick_b(d, M) : d <= 12 ? sig_feat_grad_pick_c(d, M)

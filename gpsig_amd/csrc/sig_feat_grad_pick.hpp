@@ -2,10 +2,10 @@
 // the sig_feat_grad_inst_*.hip translation units, which are compiled in parallel (the same shapes as sig_feat_pick.hpp).
 #pragma once
 
+#include "launchers.hpp"
 #include "sig_feat_grad_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*SigFeatGradLaunchFn)(const SigFeatGradArgs&, unsigned, size_t, hipStream_t);
 
 template <int D, int M>
 static hipError_t sig_feat_grad_launch(const SigFeatGradArgs& A, unsigned grid, size_t lds, hipStream_t stream) {

@@ -1,16 +1,9 @@
 // Lookup of the feature kernels (instantiated in sig_feat_inst_{a..f}.hip: D <= 32 columns, M levels with D^M <= SIG_MAX_TOP) and the
 // launchers of the contraction and its reduce.
+#include "launchers.hpp"
 #include "sig_feat_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*SigFeatLaunchFn)(const SigFeatArgs&, unsigned, size_t, hipStream_t);
-SigFeatLaunchFn sig_feat_pick_a(int d, int M);       // d = 1 .. 4     (sig_feat_inst_a.hip)
-SigFeatLaunchFn sig_feat_pick_b(int d, int M);       // d = 5 .. 8
-SigFeatLaunchFn sig_feat_pick_c(int d, int M);       // d = 9 .. 12
-SigFeatLaunchFn sig_feat_pick_d(int d, int M);       // d = 13 .. 16
-SigFeatLaunchFn sig_feat_pick_e(int d, int M);       // d = 17 .. 24
-SigFeatLaunchFn sig_feat_pick_f(int d, int M);       // d = 25 .. 32
-
 SigFeatLaunchFn sig_feat_lookup(int d, int M) {
     if (d < 1 || d > 32) return nullptr;
     return d <= 4 ? sig_feat_pick_a(d, M) : d <= 8 ? sig_feat_pick_b(d, M) : d <= 12 ? sig_feat_pick_c(d, M) : d <= 16 ? sig_feat_pick_d(d, M)

@@ -2,10 +2,10 @@
 // sig_feat_inst_*.hip translation units, which are compiled in parallel.
 #pragma once
 
+#include "launchers.hpp"
 #include "sig_feat_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*SigFeatLaunchFn)(const SigFeatArgs&, unsigned, size_t, hipStream_t);
 
 template <int D, int M>
 static hipError_t sig_feat_launch(const SigFeatArgs& A, unsigned grid, size_t lds, hipStream_t stream) {

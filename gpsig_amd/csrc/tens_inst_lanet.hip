@@ -1,9 +1,9 @@
 // tensor-vs-sequence kernel instantiations, tensor-lane variant (one lane per inducing tensor): see tens_inst.hip
+#include "launchers.hpp"
 #include "aux_kernels.hpp"
 
 namespace gpsig {
 // ---- tensor-lane variant: levels are swept in groups [LO, HI] whose components fit the register file
-typedef hipError_t (*TvsLaneTLaunchFn)(const TvsLaneTArgs&, hipStream_t);
 
 template <int LO, int HI, int D, bool INCR>
 static hipError_t tvs_lanet_launch(const TvsLaneTArgs& A, hipStream_t stream) {

@@ -1,10 +1,10 @@
 // tens_inst_seq.hpp -- one translation unit of tens_vs_seq_kernel instantiations (one lane per sequence; 1 or 2 tensors per wave, with / without
 // increments): #define TENS_T (element type), TENS_NAME (the unit's lookup function) and TENS_MS(X) (its num_levels values) before including.
 // (Round 5: all of num_levels 1..8 in both precisions used to be ONE unit, which took seven minutes by itself -- the longest pole of the build.)
+#include "launchers.hpp"
 #include "aux_kernels.hpp"
 
 namespace gpsig {
-typedef hipError_t (*TvsLaunchFn)(const TvsArgs&, hipStream_t);
 
 template <typename T, int M, int TT, bool INCR>
 static hipError_t tvs_launch(const TvsArgs& A, hipStream_t stream) {

@@ -2,20 +2,11 @@
 // preparation of the operands in the forward tile kernel's layouts, launch, reduction of the partial sums.  Called by
 // gpsig_tens_vs_seq_levels_grad (grad_api.hip) with device pointers; *done = false leaves the call to the older kernels.
 #include "ctx.hpp"
+#include "launchers.hpp"
 #include "tvs_tile_kernel.hpp"
 #include "tvs_grad_tile_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*TvsGradTileLaunchFn)(const TvsGradTileArgs&, dim3, size_t, hipStream_t);
-TvsGradTileLaunchFn tvs_grad_tile_lookup_m1(int, int, bool);
-TvsGradTileLaunchFn tvs_grad_tile_lookup_m2(int, int, bool);
-TvsGradTileLaunchFn tvs_grad_tile_lookup_m3(int, int, bool);
-TvsGradTileLaunchFn tvs_grad_tile_lookup_m4(int, int, bool);
-TvsGradTileLaunchFn tvs_grad_tile_lookup_m5(int, int, bool);
-TvsGradTileLaunchFn tvs_grad_tile_lookup_m6(int, int, bool);
-TvsGradTileLaunchFn tvs_grad_tile_lookup_ho(int M, int D, bool paired, int kind);      // tvs_grad_tile_inst_ho.hip: SignatureRBF and the Matern families, order > 1
-int tvs_tile_width(int d);
-
 static TvsGradTileLaunchFn tvs_grad_tile_lookup(int M, int D, int kind, bool paired) {
     switch (M) {
         case 1: return tvs_grad_tile_lookup_m1(D, kind, paired);

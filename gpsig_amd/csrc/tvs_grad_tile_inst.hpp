@@ -1,9 +1,9 @@
 // One translation unit of tvs_grad_tile_kernel instantiations: #define TVSG_M before including.  Feature widths 4, 6, 8; the
 // base kernel linear / RBF / run-time family; incremental tensors of the non-linear families as lane pairs.
+#include "launchers.hpp"
 #include "tvs_grad_tile_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*TvsGradTileLaunchFn)(const TvsGradTileArgs&, dim3, size_t, hipStream_t);
 
 template <int M, int D, int KIND, bool PAIRED>
 static hipError_t tvs_grad_tile_launch(const TvsGradTileArgs& A, dim3 grid, size_t lds, hipStream_t stream) {

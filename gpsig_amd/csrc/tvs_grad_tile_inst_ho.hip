@@ -1,9 +1,9 @@
 // reverse pass of the tensor-vs-sequence chains, tile kernel: the HIGHER-ORDER chains (signature_algs.py:129-160) of SignatureRBF at a run-time order,
 // num_levels 3, 4, 5, feature widths 4, 6, 8 (the forward instances of tvs_tile_inst_ho.hip leave the chain totals these continue from)
+#include "launchers.hpp"
 #include "tvs_grad_tile_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*TvsGradTileLaunchFn)(const TvsGradTileArgs&, dim3, size_t, hipStream_t);
 
 template <int M, int D, bool PAIRED, int KIND = BASE_RBF>
 static hipError_t tvs_grad_tile_launch_ho(const TvsGradTileArgs& A, dim3 grid, size_t lds, hipStream_t stream) {

@@ -1,14 +1,8 @@
 // Dispatch over the tvs_tile_kernel translation units (tvs_tile_inst_m*.hip) and the planner's shape rules.
+#include "launchers.hpp"
 #include "tvs_tile_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*TvsTileLaunchFn)(TvsTileArgs&, size_t, hipStream_t, int);
-TvsTileLaunchFn tvs_tile_lookup_m2(int, int, bool, int);
-TvsTileLaunchFn tvs_tile_lookup_m3(int, int, bool, int);
-TvsTileLaunchFn tvs_tile_lookup_m4(int, int, bool, int);
-TvsTileLaunchFn tvs_tile_lookup_m5(int, int, bool, int);
-TvsTileLaunchFn tvs_tile_lookup_m6(int, int, bool, int);
-
 // feature width the kernel is built for (0: none)
 int tvs_tile_width(int d) { return d <= 4 ? 4 : (d <= 6 ? 6 : (d <= 8 ? 8 : 0)); }
 

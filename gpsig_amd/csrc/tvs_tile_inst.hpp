@@ -1,9 +1,9 @@
 // One translation unit of tvs_tile_kernel instantiations: #define TVS_TILE_M and TVS_TILE_NWS(X) (the waves-per-workgroup
 // values built for that num_levels) before including.  Feature widths: 4, 6, 8.
+#include "launchers.hpp"
 #include "tvs_tile_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*TvsTileLaunchFn)(TvsTileArgs&, size_t, hipStream_t, int);
 
 // Persistent launch: as many workgroups as the chip holds at once (the occupancy the runtime reports for this instance and its LDS), each of
 // their four wavefronts drawing (tensor block, run of sequences) items from the per-block counters A.queue -- long runs first, short ones last

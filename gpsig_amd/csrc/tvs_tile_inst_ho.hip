@@ -1,10 +1,10 @@
 // Higher-order instances of the Kzx tile kernel (round 6): the chains of signature_algs.py:129-160 for the RBF kernel, num_levels 3 / 4 / 5, feature widths
 // 4 / 6 / 8, with and without increments; the order is a run-time argument (>= 2).  Level sets as the first-order instances' (the state between time steps is
 // the same: the running totals).
+#include "launchers.hpp"
 #include "tvs_tile_kernel.hpp"
 
 namespace gpsig {
-typedef hipError_t (*TvsTileLaunchFn)(TvsTileArgs&, size_t, hipStream_t, int);
 
 template <int M, int NW, int D, bool INCR>
 static hipError_t tvs_tile_launch_ho(TvsTileArgs& A, size_t lds, hipStream_t stream, int num_cus) {

@@ -3,32 +3,13 @@
 // Called from api.hip (evaluations, level primitives) and grad_api.hip (their gradients) with device pointers; *done = false leaves the call to the
 // exact-shape kernels.  float64, order 1, RBF and the Matern families (the distance kernels: kappa is a function of the ONE number the dgemm yields).
 #include "ctx.hpp"
+#include "launchers.hpp"
 #include "aux_kernels.hpp"
 #include "wide_kernels.hpp"
 
 #include <string>
 
-
 namespace gpsig {
-
-bool solver_dgemm(void** handle_slot, hipStream_t stream, bool transA, bool transB, int m, int n, int k, double alpha, const double* A, int lda,
-                  const double* B, int ldb, double beta, double* C, int ldc, std::string* err);          // lowrank_solver.hip
-
-bool solver_dgemm_batched(void** handle_slot, hipStream_t stream, bool transA, bool transB, int m, int n, int k, double alpha, const double* A, int lda,
-                          int64_t sa, const double* B, int ldb, int64_t sb, double beta, double* C, int ldc, int64_t sc, int batch, std::string* err);
-
-// grad_api.hip: the sweeps of the higher-order reverse pass (grad_wave_ho_kernel.hpp)
-struct WaveHoArgs;
-typedef hipError_t (*WaveHoLaunchFn)(const WaveHoArgs&, int, size_t, hipStream_t);
-struct HoSweeps { WaveHoLaunchFn fn; int G, C; size_t lds, slot; };
-bool ho_sweeps_plan(const gpsig_ctx* c, const gpsig_params* p, int R1, int R2, HoSweeps* hs);
-int ho_sweeps_launch(gpsig_ctx* c, const HoSweeps& hs, int M, int R1, int R2, const double* dM, double* lam, const double* G, int64_t gm, int64_t gi,
-                     int64_t gj, int64_t N2, bool diag, int64_t pair0, int64_t npairs);
-bool ho_levels_plan(const gpsig_ctx* c, const gpsig_params* p, int R1, int R2, HoSweeps* hs);
-bool o1_sweeps_plan(const gpsig_ctx* c, const gpsig_params* p, int R1, int R2, HoSweeps* hs);
-int ho_levels_launch(gpsig_ctx* c, const HoSweeps& hs, int M, int R1, int R2, const double* dM, double* out, int64_t gm, int64_t gi, int64_t gj, int64_t N2,
-                     bool diag, int64_t pair0, int64_t npairs);
-
 namespace {
 
 bool wide_kind(int base_kernel) {
