@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the signature-kernel evaluation path on MI355X: sequence-pairs/s of SignatureKernel.K (and Kzx).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5] [--base linear|rbf]
+    python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5] [--base linear|rbf] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workloads (BASELINE.json configs; the names C1..C5 are SURVEY.md section 8's):
@@ -20,7 +20,14 @@ Workloads (BASELINE.json configs; the names C1..C5 are SURVEY.md section 8's):
   c5  configs[4]: N=2048, L=128, d=16, num_levels=6, fp32, SignatureRBF, full Gram.
 One step = one complete evaluation with the inputs already resident in HBM and the result left in HBM; --steps is the number
 of timed steps and `ms_per_step` the wall time of one.  Rank 0 prints ONE strict-JSON line under 2 KB, the headline of the
-full record, so that a reader keeping only the end of the output can parse it.  --record FILE writes the full record: the
+full record, so that a reader keeping only the end of the output can parse it.
+A plain run does what the headline needs and nothing more: it sets up, warms up, times the steps, writes --dump-outputs and prints
+the line (contract fields, `clock_ghz` -- sampled on the device during the timed region --, and the `roofline` fields that come from
+the timed region itself: the dominant kernel's HIP-event time, `bound`, `frac`, `alu_frac`, `stream_frac`).  Everything that takes time
+of its own is behind --full: `cpu_baseline`, `rel_err` and the other checks of the timed output, `end_to_end_ms_host_pointers`, the
+rocprofv3 --pmc passes behind `roofline.traffic` and `issue_frac`, and `secondary`.  --no-cpu-baseline, --no-traffic and
+--no-secondary leave single legs out of a --full run.
+--record FILE writes the full record (with --full: all of the following): the
 driver's contract fields + `roofline` (what binds the dominant kernel -- `bound`, `issue_frac`, `alu_frac` --, the
 pair-stream fraction of SURVEY 8(d) as `stream_frac`, the kernel's HIP-event time on the library's stream, the HBM traffic
 measured by two rocprofv3 --pmc passes of this very command), `clock_ghz` (the shader clock during the timed region, sampled
@@ -28,7 +35,7 @@ on the device), `cpu_baseline` (the oracle's op-for-op restatement of the refere
 sample), `rel_err` (a sub-sample of the timed output against the oracle, outside the timed region),
 `end_to_end_ms_host_pointers` (the same evaluation from and to host memory: H2D + compute + D2H) and, on the default
 single-GPU line, `secondary`: the other single-GPU configurations (c2 through the pair recursion, c2 at order 5, c2 RBF, c3, c3 with increments, c3 with SignatureLinear, c5), 3 warm-up + 10 steps each
-(measured only when --record asks for the record).
+(measured only when --full --record asks for the record).
 --dump-outputs DIR writes what the last timed step computed (K; or Kzz, Kzx, Kxx_diag for c3) as DIR/<name>.npy in the
 workload's float type, below 64 MB in all: an array above its share is a seeded sample of its rows, <name>_rows.npy the
 row indices.  The inputs are seeded, so two builds run with the same arguments can be compared array for array.
@@ -1014,10 +1021,14 @@ def main(argv=None):
     ap.add_argument("--weak", action="store_true", help="--gpus N > 1: N_total = 4096 * sqrt(N) instead of configs[3]")
     ap.add_argument("--chunks", type=int, default=4, help="pieces a rank's row block is computed / gathered in")
     ap.add_argument("--lattice", action="store_true", help="SignatureLinear through the pair recursion instead of the feature contraction")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="default line only: leave out the other single-GPU configurations")
-    ap.add_argument("--no-traffic", action="store_true", help="do not run the two rocprofv3 --pmc passes (roofline.traffic falls back to profiles/hbm_traffic.json)")
-    ap.add_argument("--timed-loop-only", action="store_true", help="warm-up + timed steps and nothing else (what the --pmc passes run)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baseline, rel_err and the other checks of the timed output against the oracle, the evaluation "
+                         "from host pointers, the rocprofv3 --pmc passes (traffic, issue_frac) and, with --record, the secondary configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full --record without the other single-GPU configurations")
+    ap.add_argument("--no-traffic", action="store_true",
+                    help="--full without the rocprofv3 --pmc passes (roofline.traffic falls back to profiles/hbm_traffic.json)")
+    ap.add_argument("--timed-loop-only", action="store_true", help="a plain run even where --full is given (what the --pmc passes run)")
     ap.add_argument("--rendezvous-check", action="store_true", help="start the ranks, gather ranks_seen, print it; no evaluation (CPU-testable)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed as DIR/<name>.npy (a seeded sample of rows where it exceeds the size cap)")
@@ -1052,8 +1063,9 @@ def main(argv=None):
                          "c5 is a single-GPU workload")
     base = args.base or WORKLOADS[cfg]["base"]
 
+    lean = args.timed_loop_only or not args.full      # the plain run: set up, warm up, time the steps, dump, print
     cpu = None
-    if rank == 0 and not (args.no_cpu_baseline or args.timed_loop_only or args.rendezvous_check):
+    if rank == 0 and not (lean or args.no_cpu_baseline or args.rendezvous_check):
         # before CUDA is initialised in this process; the N > 1 lines carry the C restatement only (the other ranks wait in the rendezvous)
         cpu = cpu_baseline(cfg, base, args.increments, numpy_leg=(n_gpus == 1))
 
@@ -1097,7 +1109,6 @@ def main(argv=None):
             dist.destroy_process_group()
         return
 
-    lean = args.timed_loop_only
     res = run_workload(cfg, base, args.increments, args.steps, args.warmup, dev, rank, world, chunks=args.chunks, weak=args.weak,
                        checks=not lean, host_e2e=not lean, lattice=args.lattice,
                        traffic="off" if lean else ("static" if (args.no_traffic or args.lattice) else "measure"),

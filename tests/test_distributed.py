@@ -384,6 +384,17 @@ def test_bench_refuses_a_world_size_that_differs_from_gpus():
     assert rc != 0 and line is None and "WORLD_SIZE=2" in err
 
 
+def test_bench_accepts_full():
+    """--full is accepted and handed on to the ranks bench.py starts (the run is refused later, for its WORLD_SIZE)."""
+    rc, line, err = _run_bench(["--gpus", "1", "--steps", "1", "--full", "--no-cpu-baseline"], {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
+    assert rc != 0 and line is None and "WORLD_SIZE=2" in err and "unrecognized" not in err
+    mod = _bench_module()
+    assert mod.rank_launch_command(2, ["--gpus", "2", "--full"])[-3:] == ["--gpus", "2", "--full"]
+    with pytest.raises(SystemExit) as e:
+        mod.main(["--steps", "0", "--full"])               # parsed; refused for --steps
+    assert e.value.code == 2
+
+
 def test_bench_rank_launch_command():
     import importlib.util
     import sys

@@ -1,5 +1,5 @@
-"""bench.py on the GPU box: the N > 1 line is produced by N ranks bench.py starts itself, and the default line carries the
-measurement (clock, what binds, measured traffic)."""
+"""bench.py on the GPU: a plain run does what its headline needs and nothing else; with --full the N > 1 line is produced by N ranks
+bench.py starts itself, and the default line carries the measurement (clock, what binds, measured traffic)."""
 import json
 import os
 import subprocess
@@ -13,14 +13,14 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(args, env_extra=None, timeout=1500):
-    """The full record bench.py writes with --record, after checking the one line it prints: the last line of stdout, strict JSON,
-    under 2 KB, the record's headline."""
+def _bench(args, env_extra=None, timeout=1500, full=True):
+    """The full record bench.py --full writes with --record (full=False: a plain run's), after checking the one line it prints: the
+    last line of stdout, strict JSON, under 2 KB, the record's headline."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(env_extra or {})
     with tempfile.TemporaryDirectory() as tmp:
         rec = os.path.join(tmp, "record.json")
-        pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--record", rec], env=env, capture_output=True, text=True,
+        pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + (["--full"] if full else []) + ["--record", rec], env=env, capture_output=True, text=True,
                             timeout=timeout)
         assert pr.returncode == 0, pr.stderr[-3000:]
         with open(rec) as f:
@@ -28,7 +28,7 @@ def _bench(args, env_extra=None, timeout=1500):
     out = pr.stdout.splitlines()
     assert [ln for ln in out if ln.startswith("{")] == out[-1:] and len(out[-1]) < 2048, pr.stdout[-3000:]
     line = json.loads(out[-1], parse_constant=_no_constant)
-    for k in ("value", "ms_per_step", "steps", "warmup", "n_gpus", "rel_err"):
+    for k in ("value", "ms_per_step", "steps", "warmup", "n_gpus") + (("rel_err",) if full else ()):
         assert line[k] == record[k], k
     assert line["roofline"]["bound"] == record["roofline"]["bound"]
     return record
@@ -85,6 +85,41 @@ def test_dump_outputs_is_the_timed_result(cfg):
             a = a[got[k + "_rows"].astype(np.int64)]
         assert got[k].dtype == np.float64 and got[k].shape == a.shape
         assert np.abs(got[k] - a).max() <= 1e-12 * np.abs(a).max(), k
+
+
+def test_plain_run_is_the_headline_and_nothing_else(tmp_path):
+    """Without --full: the line's contract fields and the timed region's own figures, the dump of the last timed step (equal to the
+    library's evaluation of the same seeded inputs), and none of what takes time of its own -- no CPU baseline, no comparison with the
+    oracle, no host-pointer evaluation, no rocprofv3 pass, no secondary configurations.  --full --timed-loop-only is the same run."""
+    import importlib.util
+    import numpy as np
+    import torch
+    from gpsig_amd import kernels
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    t0 = time.perf_counter()
+    rec = _bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path)], full=False)
+    wall = time.perf_counter() - t0
+    assert rec["metric"] == bench.METRIC and rec["unit"] == "sequence-pairs/s" and rec["higher_is_better"] is True and rec["dtype"] == "f64"
+    assert rec["n_gpus"] == 1 and rec["steps"] == 5 and rec["warmup"] == 2 and rec["config"]["name"] == "c2"
+    assert rec["ms_per_step"] > 0 and abs(rec["value"] - 4096.0 * 4096.0 / (rec["ms_per_step"] * 1e-3)) <= 1e-9 * rec["value"]
+    rf = rec["roofline"]
+    assert rf["bound"] == "mfma" and 0.5 < rf["frac"] < 1.0 and rf["kernel_ms_per_launch"] > 0 and 1.0 < rec["clock_ghz"] < 2.6
+    for k in ("cpu_baseline", "rel_err", "end_to_end_ms_host_pointers", "secondary"):
+        assert k not in rec, k
+    assert rf["traffic"] is None and rf["traffic_source"] is None and rf["issue_frac"] is None
+    # 30 s outside the steps is the budget of such a run; the steps themselves are 7 x ~10 ms here
+    assert wall - 7 * rec["ms_per_step"] * 1e-3 < 30.0, wall
+    w = bench.WORKLOADS["c2"]
+    kern = kernels.SignatureLinear(w["L"] * w["d"], w["d"], w["M"], lengthscales=bench.lengthscales(w))
+    want = kern.K(torch.as_tensor(bench.make_inputs(w), device="cuda:0")).cpu().numpy()
+    got = {f[:-4]: np.load(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))}
+    assert sorted(got) == ["K", "K_rows"]
+    a = want[got["K_rows"].astype(np.int64)]
+    assert got["K"].dtype == np.float64 and got["K"].shape == a.shape and np.abs(got["K"] - a).max() <= 1e-12 * np.abs(a).max()
+    same = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--timed-loop-only"], full=False)
+    assert "rel_err" not in same and "cpu_baseline" not in same and same["roofline"]["traffic"] is None
 
 
 def test_clock_probe_reads_a_plausible_shader_clock():

@@ -6,7 +6,7 @@ for rnd in 1 2 3; do
   for cfg in "c3" "c3 --increments"; do
     for lib in default libgpsig_hip_e1024.so libgpsig_hip_e2048.so; do
       if [ $lib = default ]; then unset GPSIG_LIB; else export GPSIG_LIB=$PWD/gpsig_amd/lib/$lib; fi
-      python bench.py --config $cfg --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+      python bench.py --full --config $cfg --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('round $rnd  $cfg  lib=$lib  Kzx kernel ms %.3f  ms/step %.3f  rel_err %.2e' % (d['roofline']['kernel_ms_per_launch'], d['ms_per_step'], d['rel_err']))"

@@ -7,7 +7,7 @@ timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo 
 tail -4 $O/pytest_gpu.log
 for cfg in "$@"; do
   tag=$(echo $cfg | tr -d ' -')
-  timeout 600 python bench.py --config $cfg --no-cpu-baseline > $O/q_bench_$tag.json 2> $O/q_bench_$tag.err
+  timeout 600 python bench.py --full --config $cfg --no-cpu-baseline > $O/q_bench_$tag.json 2> $O/q_bench_$tag.err
   python - <<PY
 import json
 try:

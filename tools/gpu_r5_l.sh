@@ -3,4 +3,4 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/r05l; mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -q -x > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log
-timeout 1500 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.json
+timeout 1500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.json

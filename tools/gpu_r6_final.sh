@@ -3,7 +3,7 @@
 # the order benches, the reference-shapes visit (tools/gpu_r6_h.sh), and the GPU suite
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
 O=gpurun_out/r06f; mkdir -p $O
-( time python bench.py ) > $O/bench_default.json 2> $O/bench_default.err
+( time python bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err
 tail -c 600 $O/bench_default.json
 bash tools/gpu_pmc.sh c2 > $O/pmc.log 2>&1
 cp gpurun_out/r02/pmc_c2.txt gpurun_out/r02/kernel_stats_c2.txt $O/ 2>/dev/null

@@ -8,9 +8,9 @@ timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo 
 tail -3 $O/pytest_gpu.log
 for cfg in "c2" "c2 --base rbf" "c3" "c3 --increments" "c3 --base linear" "c5" "c5 --base linear"; do
   tag=$(echo $cfg | tr -d ' -')
-  timeout 600 python bench.py --config $cfg > $O/bench_$tag.json 2> $O/bench_$tag.err; tail -1 $O/bench_$tag.json
+  timeout 600 python bench.py --full --config $cfg > $O/bench_$tag.json 2> $O/bench_$tag.err; tail -1 $O/bench_$tag.json
 done
-timeout 900 python bench.py --config c4 --steps 2 --warmup 1 > $O/bench_c4_1gpu.json 2> $O/bench_c4_1gpu.err; tail -1 $O/bench_c4_1gpu.json
+timeout 900 python bench.py --full --config c4 --steps 2 --warmup 1 > $O/bench_c4_1gpu.json 2> $O/bench_c4_1gpu.err; tail -1 $O/bench_c4_1gpu.json
 for cfg in "c2" "c3" "c3 --increments" "c5"; do
   tag=$(echo $cfg | tr -d ' -')
   timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_$tag -o p -- python bench.py --config $cfg --steps 5 --warmup 2 --no-cpu-baseline > $O/prof_$tag.log 2>&1

@@ -9,12 +9,12 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout 1800 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log
   tail -3 $O/pytest_gpu.log
 fi
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.json
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.json
 for cfg in "c2 --lattice" "c2 --base rbf" "c3" "c3 --increments" "c3 --base linear" "c5" "c5 --base linear"; do
   tag=$(echo $cfg | tr -d ' -')
-  timeout 600 python bench.py --config $cfg --no-cpu-baseline > $O/bench_$tag.json 2> $O/bench_$tag.err
+  timeout 600 python bench.py --full --config $cfg --no-cpu-baseline > $O/bench_$tag.json 2> $O/bench_$tag.err
 done
-timeout 900 python bench.py --config c4 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_c4_1gpu.json 2> $O/bench_c4_1gpu.err
+timeout 900 python bench.py --full --config c4 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_c4_1gpu.json 2> $O/bench_c4_1gpu.err
 for cfg in "c2" "c2 --lattice" "c2 --base rbf" "c3" "c3 --increments" "c3 --base linear" "c5"; do
   tag=$(echo $cfg | tr -d ' -')
   : > $O/pmc_$tag.txt

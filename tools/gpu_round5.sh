@@ -10,12 +10,12 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout 1800 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log
   tail -3 $O/pytest_gpu.log
 fi
-timeout 1500 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.json
+timeout 1500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.json
 : > $O/bench_lines.jsonl
 for cfg in "c2" "c2 --lattice" "c2 --base rbf" "c3" "c3 --increments" "c3 --base linear" "c5" "c5 --base linear"; do
-  timeout 900 python bench.py --config $cfg --no-cpu-baseline 2>/dev/null | tail -1 >> $O/bench_lines.jsonl
+  timeout 900 python bench.py --full --config $cfg --no-cpu-baseline 2>/dev/null | tail -1 >> $O/bench_lines.jsonl
 done
-timeout 900 python bench.py --config c4 --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 >> $O/bench_lines.jsonl
+timeout 900 python bench.py --full --config c4 --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 >> $O/bench_lines.jsonl
 for cfg in "c2" "c2 --lattice" "c2 --base rbf" "c3" "c3 --increments" "c5"; do
   tag=$(echo $cfg | tr -d ' -')
   : > $O/pmc_$tag.txt
@@ -53,6 +53,6 @@ rm -rf /tmp/pmc_run
 for cfg in "c3 --verify" "c2 --verify"; do timeout 600 python tools/bench_lr.py --config $cfg 2>/dev/null >> $O/bench_lowrank.jsonl; done
 timeout 300 python tools/bench_host_e2e.py > $O/bench_host_e2e.txt 2>&1
 timeout 600 python tools/bench_rank_share.py > $O/bench_rank_share.txt 2>&1
-GPSIG_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 2 --steps 1 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_c4_2ranks_gloo_one_gpu.json
+GPSIG_BENCH_BACKEND=gloo timeout 900 python bench.py --full --gpus 2 --steps 1 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_c4_2ranks_gloo_one_gpu.json
 timeout 300 tools/microbench4 20000 > $O/microbench4.txt 2>&1
 ls $O
