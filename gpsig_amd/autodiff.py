@@ -682,6 +682,34 @@ def _add_lags(X, lags):
     return torch.cat((X[:, :, None, :], _lin_interp(time, X, time_lags)), dim=2)                    # :59-61
 
 
+class _DenseSelection:
+    """One projection as a dense (entries, r) matrix holding each entry's value in its output column: summing an entry's product into its
+    column is then a GEMM (index_add does it with atomics on r addresses per row: 6-14 ms for the inducing tensors' six chained
+    projections at the reference's default ranks; this: well under a millisecond) ... and the two operand selections a[:, i1], b[:, i2]
+    as products with 0 / 1 matrices (k1, entries), (k2, entries): the reverse pass of a gather is a scatter-add with atomics as well, that
+    of a product another product.  Up to 2^24 doubles each, so built at first use (``get``): None beyond that size."""
+
+    def __init__(self, i1, i2, val, colt, k1, k2, r):
+        self._args, self._built, self._mats = (i1, i2, val, colt, k1, k2, r), False, None
+
+    def get(self):
+        if not self._built:
+            i1, i2, val, colt, k1, k2, r = self._args
+            nnz, device = int(val.shape[0]), val.device
+            if nnz * max(r, k1, k2) <= (1 << 24):
+                ar = torch.arange(nnz, device=device)
+                out_m = torch.zeros((nnz, r), dtype=torch.float64, device=device)
+                sel1 = torch.zeros((k1, nnz), dtype=torch.float64, device=device)
+                sel2 = torch.zeros((k2, nnz), dtype=torch.float64, device=device)
+                if nnz:
+                    out_m[ar, colt] = val
+                    sel1[i1, ar] = 1.0
+                    sel2[i2, ar] = 1.0
+                self._mats = (sel1, sel2, out_m)
+            self._built, self._args = True, None
+        return self._mats
+
+
 class LowRankDraw:
     """The random objects of ONE low-rank evaluation that do not depend on values (the reference draws them inside the graph per
     evaluation: kernels.py:443-446, low_rank_calculations.py:12-20, :52, :92-101): which ``num_components`` of the evaluation's points are
@@ -703,24 +731,9 @@ class LowRankDraw:
             for s_ in self.sketches:
                 col = np.repeat(np.arange(s_.r), np.diff(s_.colptr))
                 i1, i2, val, colt = t(s_.i1, torch.int64), t(s_.i2, torch.int64), t(s_.val, torch.float64), t(col, torch.int64)
-                # the projection as a dense (entries, r) matrix holding each entry's value in its output column: summing an entry's product
-                # into its column is then a GEMM (index_add does it with atomics on r addresses per row: 6-14 ms for the inducing
-                # tensors' six chained projections at the reference's default ranks; this: well under a millisecond)
-                # ... and the two operand selections a[:, i1], b[:, i2] as products with 0 / 1 matrices (k1, entries), (k2, entries): the
-                # reverse pass of a gather is a scatter-add with atomics as well, that of a product another product
-                dense = None
-                nnz = int(val.shape[0])
-                if nnz * max(int(s_.r), int(s_.k1), int(s_.k2)) <= (1 << 24):
-                    ar = torch.arange(nnz, device=device)
-                    out_m = torch.zeros((nnz, int(s_.r)), dtype=torch.float64, device=device)
-                    sel1 = torch.zeros((int(s_.k1), nnz), dtype=torch.float64, device=device)
-                    sel2 = torch.zeros((int(s_.k2), nnz), dtype=torch.float64, device=device)
-                    if nnz:
-                        out_m[ar, colt] = val
-                        sel1[i1, ar] = 1.0
-                        sel2[i2, ar] = 1.0
-                    dense = (sel1, sel2, out_m)
-                sk.append((i1, i2, val, colt, int(s_.r), dense))
+                # the projection as dense matrices for the torch routes (_DenseSelection), built when one of them first applies it: the HIP
+                # ops (_LrSeqFeatures, _LrTensFeatures and their spectral twins) read the host-side sketches and never ask
+                sk.append((i1, i2, val, colt, int(s_.r), _DenseSelection(i1, i2, val, colt, int(s_.k1), int(s_.k2), int(s_.r))))
             self._dev[key] = (t(self.idx, torch.int64), t(self.jitter_diag, torch.float64), sk)
         return self._dev[key]
 
@@ -729,6 +742,7 @@ def _apply_sketch(sk, A, B):
     """lr_hadamard_prod_rand (low_rank_calculations.py:76-193) given its random matrix: out[..., j] = sum over the entries e of
     column j of val[e] A[..., i1[e]] B[..., i2[e]].  (..., k1), (..., k2) -> (..., r); rows in chunks of at most 2^27 products."""
     i1, i2, val, col, r, dense = sk
+    dense = dense.get()
     lead = A.shape[:-1]
     A2, B2 = A.reshape(-1, A.shape[-1]), B.reshape(-1, B.shape[-1])
     rows, nnz = A2.shape[0], max(int(i1.shape[0]), 1)
@@ -844,6 +858,86 @@ class _LrSeqFeaturesSpectral(torch.autograd.Function):
         return tuple(t.to(dt) for t, dt in zip(grads, ctx.dt)) + (None, None, None, None)
 
 
+class _LrTensFeatures(torch.autograd.Function):
+    """_K_tens_lr_feat (kernels.py:285-311) given the landmarks and the whitening: scaled inducing tensors (lt, T[, 2], d), S (c, d), Wh (c, c)
+    -> Phi (T, 1 + c + (M-1) r), by the fused HIP tensor kernel (gpsig_lr_tens_features_dev); the reverse pass by
+    lr_tens_features_grad_kernel (csrc/lr_tens_grad_kernel.hpp): dPhi -> dZ, dS, dWh, d base parameter.  The twin of _LrSeqFeatures; the torch
+    route of the same map is _LowRankScope._tens_torch.  Raises NotImplementedError outside the library's limits."""
+
+    @staticmethod
+    def forward(ctx, Zs, S, Wh, p0, spec, sketches, r, increments):
+        Z, Sd, Whd = _c(Zs), _c(S), _c(Wh)
+        T, d = Z.shape[1], Z.shape[-1]
+        cc = Sd.shape[0]
+        keep = []
+        p = spec.params(d, _p0_value(p0), keep)
+        arr = _sketch_array(sketches, keep)
+        F = 1 + cc + (spec.num_levels - 1) * int(r)
+        out = torch.empty((T, F), dtype=torch.float64, device=Z.device)
+        _ctx_for(Z).call("gpsig_lr_tens_features_dev", p, cc, int(r), len(sketches), arr, _ptr(Z), T, int(bool(increments)), _ptr(Sd), _ptr(Whd),
+                         _ptr(out))
+        ctx.spec, ctx.sketches, ctx.r, ctx.has_p0, ctx.increments = spec, sketches, int(r), p0 is not None, bool(increments)
+        ctx.dt = (Zs.dtype, S.dtype, Wh.dtype)
+        ctx.save_for_backward(Z, Sd, Whd, p0 if p0 is not None else Z.new_empty(0))
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        Z, Sd, Whd, p0 = ctx.saved_tensors
+        T, d = Z.shape[1], Z.shape[-1]
+        cc = Sd.shape[0]
+        keep = []
+        p = ctx.spec.params(d, _p0_value(p0) if ctx.has_p0 else 0.0, keep)
+        arr = _sketch_array(ctx.sketches, keep)
+        G = _c(G)
+        gZ, gS, gWh = torch.empty_like(Z), torch.empty_like(Sd), torch.empty_like(Whd)
+        gb = torch.zeros(2, dtype=torch.float64, device=Z.device)
+        _ctx_for(Z).call("gpsig_lr_tens_features_grad", p, cc, ctx.r, len(ctx.sketches), arr, _ptr(Z), T, int(ctx.increments), _ptr(Sd), _ptr(Whd),
+                         _ptr(G), _ptr(gZ), _ptr(gS), _ptr(gWh), C.cast(gb.data_ptr(), C.POINTER(C.c_double)))
+        gp0 = gb[0].to(p0.device).reshape(p0.shape).to(p0.dtype) if ctx.has_p0 else None
+        return gZ.to(ctx.dt[0]), gS.to(ctx.dt[1]), gWh.to(ctx.dt[2]), gp0, None, None, None, None
+
+
+class _LrTensFeaturesSpectral(torch.autograd.Function):
+    """_LrTensFeatures for SignatureSpectral: also the positive alpha (Q), omega (Q, d), gamma (Q, d), by gpsig_lr_tens_features_spectral_dev;
+    the reverse pass by gpsig_lr_tens_features_spectral_grad (the spectral instance of lr_tens_features_grad_kernel down to dkx, then the spectral
+    cross op's reverse kernels on the tensors' points as they lie in memory): gradients of all six tensors.  Raises NotImplementedError
+    outside the library's limits (the caller falls back to torch ops)."""
+
+    @staticmethod
+    def forward(ctx, Zs, S, Wh, alpha, omega, gamma, spec, family, sketches, r, increments):
+        Z, Sd, Whd, a, o, g = (_c(t) for t in (Zs, S, Wh, alpha, omega, gamma))
+        T, d = Z.shape[1], Z.shape[-1]
+        cc = Sd.shape[0]
+        keep = []
+        p = spec.params(d, float(a.shape[0]), keep)
+        p.base_params[1] = float(_SPECTRAL_FAMILY[family])
+        arr = _sketch_array(sketches, keep)
+        F = 1 + cc + (spec.num_levels - 1) * int(r)
+        out = torch.empty((T, F), dtype=torch.float64, device=Z.device)
+        _ctx_for(Z).call("gpsig_lr_tens_features_spectral_dev", p, cc, int(r), len(sketches), arr, _ptr(Z), T, int(bool(increments)), _ptr(Sd),
+                         _ptr(Whd), _ptr(a), _ptr(o), _ptr(g), _ptr(out))
+        ctx.spec, ctx.family, ctx.sketches, ctx.r, ctx.increments = spec, family, sketches, int(r), bool(increments)
+        ctx.dt = tuple(t.dtype for t in (Zs, S, Wh, alpha, omega, gamma))
+        ctx.save_for_backward(Z, Sd, Whd, a, o, g)
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        Z, Sd, Whd, a, o, g = ctx.saved_tensors
+        T, d = Z.shape[1], Z.shape[-1]
+        cc = Sd.shape[0]
+        keep = []
+        p = ctx.spec.params(d, float(a.shape[0]), keep)
+        p.base_params[1] = float(_SPECTRAL_FAMILY[ctx.family])
+        arr = _sketch_array(ctx.sketches, keep)
+        G = _c(G)
+        grads = [torch.empty_like(t) for t in (Z, Sd, Whd, a, o, g)]
+        _ctx_for(Z).call("gpsig_lr_tens_features_spectral_grad", p, cc, ctx.r, len(ctx.sketches), arr, _ptr(Z), T, int(ctx.increments), _ptr(Sd),
+                         _ptr(Whd), _ptr(a), _ptr(o), _ptr(g), _ptr(G), *(_ptr(t) for t in grads))
+        return tuple(t.to(dt) for t, dt in zip(grads, ctx.dt)) + (None, None, None, None, None)
+
+
 class _SpectralCross(torch.autograd.Function):
     """SignatureSpectral's kappa(P, S) (kernels.py:921-942) for points P (n, d) and landmarks S (c, d) -> (n, c), by gpsig_spectral_cross; the
     reverse pass by gpsig_spectral_cross_grad: d points, d landmarks, d alpha, d omega, d gamma, the parameters read from device memory.
@@ -953,23 +1047,48 @@ class _LowRankScope:
             return Phi
 
     def tens(self, Zs, increments):
-        """signature_algs.py:194-222, kernels.py:285-311.  (lt, T[, 2], d') -> [(T, 1), (T, c), (T, r), ...]."""
+        """signature_algs.py:194-222, kernels.py:285-311.  (lt, T[, 2], d') -> [(T, 1), (T, c), (T, r), ...].
+        Through the fused HIP tensor kernel and its reverse pass (_LrTensFeatures; SignatureSpectral: _LrTensFeaturesSpectral) where they are
+        built; torch ops otherwise (more than 64 components, a tensor's arrays beyond the LDS, module option ``lr_hip = False`` or, for the
+        tensors alone, ``lr_tens_hip = False``: A/B runs, tools/bench_lr_tens_train.py)."""
         key = id(Zs)
+        if key not in self._tens and getattr(self.mod, "lr_hip", True) and getattr(self.mod, "lr_tens_hip", True) and Zs.is_cuda:
+            mod, kern = self.mod, self.mod.kern
+            M, cc = kern.num_levels, int(self.S.shape[0])
+            r = int(self.host_sketches[0].r) if self.host_sketches else int(kern.rank_bound)
+            lt, d, E = int(Zs.shape[0]), int(Zs.shape[-1]), 2 if increments else 1
+            # what csrc/lr_grad_api.hip takes (lr_tens_grad_lds_bytes): a tensor's arrays in LDS, at most 64 components
+            lds = 8 * (lt * E * (d + 2 * cc) + 2 * lt * cc + M * (M - 1) // 2 * r + 2 * max(cc, r) + 16)
+            if cc <= 64 and cc * d <= 4096 and lds <= 156 * 1024 and M - 1 <= 7 and lt == M * (M + 1) // 2:
+                try:
+                    if kern._base == "spectral":
+                        Phi = _LrTensFeaturesSpectral.apply(Zs, self.S, self.Wh, positive(mod.raw_alpha), positive(mod.raw_omega),
+                                                            positive(mod.raw_sgamma), mod._spec, kern.family, self.host_sketches, r, increments)
+                    else:
+                        Phi = _LrTensFeatures.apply(Zs, self.S, self.Wh, mod.p0, mod._spec, self.host_sketches, r, increments)
+                    cuts = [1, cc] + [r] * (M - 1)
+                    self._tens[key] = (Zs, list(torch.split(Phi, cuts, dim=1)))
+                except NotImplementedError:
+                    pass
         if key not in self._tens:
-            lt, T, d = Zs.shape[0], Zs.shape[1], Zs.shape[-1]
-            if increments:
-                F = self._nys(Zs.reshape(lt * T * 2, d)).reshape(lt, T, 2, -1)
-                F = F[:, :, 1] - F[:, :, 0]                                                         # kernels.py:300-304
-            else:
-                F = self._nys(Zs.reshape(lt * T, d)).reshape(lt, T, -1)
-            Phi, k = [torch.ones((T, 1), dtype=F.dtype, device=F.device)], 0
-            for i in range(1, self.mod.kern.num_levels + 1):
-                R = F[k]; k += 1
-                for j in range(1, i):
-                    R = _apply_sketch(self.sk[j - 1], F[k], R); k += 1                              # signature_algs.py:217 / :219
-                Phi.append(R)
-            self._tens[key] = (Zs, Phi)
+            self._tens[key] = (Zs, self._tens_torch(Zs, increments))
         return self._tens[key][1]
+
+    def _tens_torch(self, Zs, increments):
+        """The same feature map as torch ops (kept as the checker of the HIP reverse pass and for shapes it is not built for)."""
+        lt, T, d = Zs.shape[0], Zs.shape[1], Zs.shape[-1]
+        if increments:
+            F = self._nys(Zs.reshape(lt * T * 2, d)).reshape(lt, T, 2, -1)
+            F = F[:, :, 1] - F[:, :, 0]                                                             # kernels.py:300-304
+        else:
+            F = self._nys(Zs.reshape(lt * T, d)).reshape(lt, T, -1)
+        Phi, k = [torch.ones((T, 1), dtype=F.dtype, device=F.device)], 0
+        for i in range(1, self.mod.kern.num_levels + 1):
+            R = F[k]; k += 1
+            for j in range(1, i):
+                R = _apply_sketch(self.sk[j - 1], F[k], R); k += 1                                  # signature_algs.py:217 / :219
+            Phi.append(R)
+        return Phi
 
 
 def _low_rank_scoped(fn):

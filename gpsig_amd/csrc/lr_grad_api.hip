@@ -15,11 +15,17 @@
 // are added to the outputs in chunk order, the dWh partials of all chunks are reduced once in workgroup order -- deterministic either way.
 // Scratch: B_GR0 dWh partials, B_GR1 the per-workgroup E_i and kxs, B_LRDK dkxs, B_GR2 the cross op's partials (own buffers: none of them
 // can be resized while another one's reader is queued; ensure() waits for the stream before it frees anything anyway).
+// The inducing tensors' feature map (_K_tens_lr_feat, kernels.py:285-311) has the same two pairs:
+//     gpsig_lr_tens_features_dev / _spectral_dev     Phi (T, F) by the fused tensor kernels of lr_fused_kernel.hpp (lr_tens_fused_launch)
+//     gpsig_lr_tens_features_grad / _spectral_grad   lr_tens_grad_kernel.hpp: dPhi -> dZ, dS, dWh, d base parameter; the spectral instance stops
+//                                                    at dkx (lt T E, c), which the cross op's reverse kernels take with Z viewed (lt T E, d)
+// Above the dkx budget the tensors go in chunks: a chunk's points are lt runs of Z, one per component, each handed to the cross op in turn.
 // The projections of an evaluation are value-independent random objects: they come from the host once per draw, are kept on the
 // device by content (with the two transposed copies the reverse pass gathers over: ContentUpload, ctx.hpp, as api.hip's lr_upload)
 // and reused by every call that passes the same ones.
 #include "ctx.hpp"
 #include "lr_grad_kernel.hpp"
+#include "lr_tens_grad_kernel.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -181,6 +187,56 @@ int grad_launch(gpsig_ctx* c, const Args& A, unsigned grid, size_t lds) {
     return GPSIG_OK;
 }
 
+// what the tensor entry points take beyond check(): the reverse kernel's per-thread tables and the LDS footprints of both directions
+int tens_check(gpsig_ctx* c, const gpsig_params* p, int cc, int r, int64_t T, int E) {
+    const int M = p->num_levels, d = p->num_features, lt = M * (M + 1) / 2;
+    if (T < 0 || T > 0x7fffffff) return fail(c, GPSIG_ERR_INVALID, "bad number of tensors");
+    if (M - 1 > LR_FUSED_MAX_SKETCHES) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for num_levels <= %d", LR_FUSED_MAX_SKETCHES + 1);
+    if (cc > 64 || int64_t(cc) * d > int64_t(LR_GRAD_KS) * LR_GRAD_THREADS)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "the low-rank reverse pass is built for num_components <= 64 and num_components x columns <= %d", LR_GRAD_KS * LR_GRAD_THREADS);
+    const size_t lds = std::max(lr_tens_grad_lds_bytes(cc, r, d, lt, E, M), lr_tens_fused_lds_bytes(cc, r, d, lt, E));
+    if (lds > LR_FUSED_MAX_LDS) return fail(c, GPSIG_ERR_UNSUPPORTED, "a tensor's low-rank arrays (%zu bytes) exceed the LDS", lds);
+    return GPSIG_OK;
+}
+
+// the fused tensor kernels (lr_fused_inst.hip) on device-resident landmarks and whitening: already-scaled tensors, no lengthscales, no lags
+int tens_features(gpsig_ctx* c, const gpsig_params* p, int cc, int r, int nsk, const LrGradSketch* gs, const void* Z, int64_t T, int E, const double* S,
+                  const double* Wh, const double* spec, void* Phi, const char* what) {
+    LrTensFusedArgs A{};
+    A.Z = static_cast<const double*>(Z); A.T = T; A.lt = p->num_levels * (p->num_levels + 1) / 2; A.E = E;
+    A.P.d_in = p->num_features;
+    A.S = S; A.Wh = Wh;
+    A.c = cc; A.r = r; A.M = p->num_levels; A.kind = int(p->base_kernel);
+    A.p0 = p->base_params[0]; A.p1 = p->base_params[1];
+    A.spec = spec;
+    for (int i = 0; i < nsk; ++i) A.sk[i] = LrFusedSketch{gs[i].colptr, gs[i].ent};
+    A.Phi = static_cast<double*>(Phi);
+    const int rc = lr_tens_fused_launch(c->stream, A);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "%s: %s", what, hipGetErrorString(hipError_t(rc)));
+    return GPSIG_OK;
+}
+
+void tens_grad_args(const gpsig_params* p, int cc, int r, int nsk, const LrGradSketch* gs, const void* Z, int64_t T, int E, const double* S,
+                    const double* Wh, const void* dPhi, LrTensGradArgs* A) {
+    const int M = p->num_levels;
+    A->Z = static_cast<const double*>(Z); A->T = T; A->lt = M * (M + 1) / 2; A->E = E; A->d = p->num_features;
+    A->S = S; A->Wh = Wh;
+    A->c = cc; A->r = r; A->M = M; A->kind = int(p->base_kernel);
+    A->p0 = p->base_params[0]; A->p1 = p->base_params[1];
+    for (int i = 0; i < nsk; ++i) A->sk[i] = gs[i];
+    A->dPhi = static_cast<const double*>(dPhi); A->F = 1 + cc + (M - 1) * r;
+}
+
+template <typename Args>
+int tens_grad_launch(gpsig_ctx* c, const Args& A, unsigned grid) {
+    void (*kern)(Args);
+    if constexpr (std::is_same<Args, LrTensGradSpectralArgs>::value) kern = lr_tens_features_grad_spectral_kernel;
+    else kern = lr_tens_features_grad_kernel;
+    const int rc = lr_launch(kern, grid, LR_TENS_GRAD_THREADS, lr_tens_grad_lds_bytes(A.c, A.r, A.d, A.lt, A.E, A.M), c->stream, A);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "low-rank tensor reverse kernel: %s", hipGetErrorString(hipError_t(rc)));
+    return GPSIG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -311,6 +367,126 @@ int gpsig_lr_seq_features_spectral_grad(gpsig_ctx* c, const gpsig_params* p, int
                                                   static_cast<double*>(gX) + n0 * int64_t(L) * d, static_cast<double*>(cpart), gS, dalpha, domega,
                                                   dgamma, n0 > 0);
         if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral cross reverse pass: %s", hipGetErrorString(hipError_t(rc)));
+        at += grid;
+    }
+    hipLaunchKernelGGL(lr_grad_reduce_kernel, dim3(unsigned((int64_t(cc) * cc + 255) / 256)), dim3(256), 0, c->stream, static_cast<const double*>(part),
+                       int(nparts), int64_t(cc) * cc, gS, int64_t(0), gWh, int64_t(cc) * cc, static_cast<double*>(nullptr));
+    HIPCHK(c, hipGetLastError());
+    return GPSIG_OK;
+}
+
+int gpsig_lr_tens_features_dev(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches, const void* Z,
+                               int64_t T, int32_t increments, const double* S, const double* Wh, void* Phi) {
+    CHK(check(c, p, cc, r, nsk));
+    const int E = increments ? 2 : 1;
+    CHK(tens_check(c, p, cc, r, T, E));
+    if (T > 0 && (!Z || !S || !Wh || !Phi)) return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
+    LrGradSketch gs[LR_FUSED_MAX_SKETCHES];
+    CHK(upload_sketches(c, cc, r, nsk, sketches, gs));
+    if (T == 0) return GPSIG_OK;
+    return tens_features(c, p, cc, r, nsk, gs, Z, T, E, S, Wh, nullptr, Phi, "fused low-rank tensor feature kernel");
+}
+
+int gpsig_lr_tens_features_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches, const void* Z,
+                                int64_t T, int32_t increments, const double* S, const double* Wh, const void* dPhi, void* gZ, double* gS, double* gWh,
+                                double* g_base) {
+    CHK(check(c, p, cc, r, nsk));
+    const int E = increments ? 2 : 1, d = p->num_features;
+    CHK(tens_check(c, p, cc, r, T, E));
+    if (!gS || !gWh || (T > 0 && (!Z || !S || !Wh || !dPhi || !gZ))) return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
+    LrGradSketch gs[LR_FUSED_MAX_SKETCHES];
+    CHK(upload_sketches(c, cc, r, nsk, sketches, gs));
+    if (T == 0) {
+        CHK(zero_async(c, gS, sizeof(double) * size_t(cc) * d));
+        CHK(zero_async(c, gWh, sizeof(double) * size_t(cc) * cc));
+        if (g_base) CHK(zero_async(c, g_base, sizeof(double)));
+        return GPSIG_OK;
+    }
+    const int64_t width = int64_t(cc) * d + int64_t(cc) * cc + 1;
+    const unsigned grid = unsigned(T < 512 ? T : 512);                 // as the sequences' reverse pass: the partial sums stay bounded
+    void* part;
+    CHK(ensure(c, B_GR0, sizeof(double) * size_t(grid) * size_t(width) + 64, &part));
+    LrTensGradArgs A{};
+    tens_grad_args(p, cc, r, nsk, gs, Z, T, E, S, Wh, dPhi, &A);
+    A.t0 = 0; A.nt = T;
+    A.gZ = static_cast<double*>(gZ);
+    A.part = static_cast<double*>(part);
+    CHK(tens_grad_launch(c, A, grid));
+    hipLaunchKernelGGL(lr_grad_reduce_kernel, dim3(unsigned((width + 255) / 256)), dim3(256), 0, c->stream, static_cast<const double*>(part), int(grid), width,
+                       gS, int64_t(cc) * d, gWh, int64_t(cc) * cc, g_base);
+    HIPCHK(c, hipGetLastError());
+    return GPSIG_OK;
+}
+
+int gpsig_lr_tens_features_spectral_dev(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches,
+                                        const void* Z, int64_t T, int32_t increments, const double* S, const double* Wh, const double* alpha,
+                                        const double* omega, const double* gamma, void* Phi) {
+    CHK(check(c, p, cc, r, nsk, true));
+    const int E = increments ? 2 : 1, d = p->num_features, Q = int(p->base_params[0]);
+    CHK(tens_check(c, p, cc, r, T, E));
+    if (T > 0 && (!Z || !S || !Wh || !alpha || !omega || !gamma || !Phi)) return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
+    LrGradSketch gs[LR_FUSED_MAX_SKETCHES];
+    CHK(upload_sketches(c, cc, r, nsk, sketches, gs));
+    if (T == 0) return GPSIG_OK;
+    void* tab;
+    const int ntab = Q * (1 + 2 * SPECTRAL_STRIDE);
+    CHK(ensure(c, B_SPECD, sizeof(double) * size_t(ntab) + 64, &tab));
+    hipLaunchKernelGGL(lr_spectral_pack_kernel, dim3(unsigned((ntab + 255) / 256)), dim3(256), 0, c->stream, alpha, omega, gamma, Q, d,
+                       static_cast<double*>(tab));
+    HIPCHK(c, hipGetLastError());
+    return tens_features(c, p, cc, r, nsk, gs, Z, T, E, S, Wh, static_cast<const double*>(tab), Phi, "fused low-rank spectral tensor feature kernel");
+}
+
+int gpsig_lr_tens_features_spectral_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches,
+                                         const void* Z, int64_t T, int32_t increments, const double* S, const double* Wh, const double* alpha,
+                                         const double* omega, const double* gamma, const void* dPhi, void* gZ, double* gS, double* gWh,
+                                         double* dalpha, double* domega, double* dgamma) {
+    CHK(check(c, p, cc, r, nsk, true));
+    const int E = increments ? 2 : 1, M = p->num_levels, lt = M * (M + 1) / 2, d = p->num_features, Q = int(p->base_params[0]),
+              family = int(p->base_params[1]);
+    CHK(tens_check(c, p, cc, r, T, E));
+    if (!gS || !gWh || !dalpha || !domega || !dgamma || (T > 0 && (!Z || !S || !Wh || !alpha || !omega || !gamma || !dPhi || !gZ)))
+        return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
+    LrGradSketch gs[LR_FUSED_MAX_SKETCHES];
+    CHK(upload_sketches(c, cc, r, nsk, sketches, gs));
+    if (T == 0) {
+        CHK(zero_async(c, gS, sizeof(double) * size_t(cc) * d));
+        CHK(zero_async(c, gWh, sizeof(double) * size_t(cc) * cc));
+        CHK(zero_async(c, dalpha, sizeof(double) * size_t(Q)));
+        CHK(zero_async(c, domega, sizeof(double) * size_t(Q) * d));
+        CHK(zero_async(c, dgamma, sizeof(double) * size_t(Q) * d));
+        return GPSIG_OK;
+    }
+    // tensors per chunk: dkx of a chunk within the budget
+    const int64_t per_tens = int64_t(lt) * E * cc * int64_t(sizeof(double));
+    const int64_t nb = std::min<int64_t>(T, std::max<int64_t>(1, int64_t(LR_SPECTRAL_DKXS_BUDGET) / per_tens));
+    const bool whole = nb == T;                                        // one launch: dkx is in the flat point order of Z
+    int64_t nparts = 0;                                                // workgroups over all chunks: one dWh partial each
+    for (int64_t n0 = 0; n0 < T; n0 += nb) nparts += std::min<int64_t>(std::min(nb, T - n0), 512);
+    void *part, *dk, *cpart;
+    CHK(ensure(c, B_GR0, sizeof(double) * size_t(nparts) * size_t(cc) * cc + 64, &part));
+    CHK(ensure(c, B_LRDK, sizeof(double) * size_t(nb) * size_t(lt) * E * cc + 64, &dk));
+    CHK(ensure(c, B_GR2, sizeof(double) * spectral_cross_grad_part_doubles(whole ? int64_t(lt) * T * E : nb * E, cc, d, Q) + 64, &cpart));
+    LrTensGradSpectralArgs A{};
+    tens_grad_args(p, cc, r, nsk, gs, Z, T, E, S, Wh, dPhi, &A);
+    A.alpha = alpha; A.omega = omega; A.gamma = gamma;
+    A.dkx = static_cast<double*>(dk);
+    const double* Zd = static_cast<const double*>(Z);
+    int64_t at = 0;
+    for (int64_t n0 = 0; n0 < T; n0 += nb) {
+        const int64_t nn = std::min(nb, T - n0);
+        const unsigned grid = unsigned(nn < 512 ? nn : 512);
+        A.t0 = n0; A.nt = nn;
+        A.part = static_cast<double*>(part) + at * int64_t(cc) * cc;
+        CHK(tens_grad_launch(c, A, grid));
+        // the chunk's points: component k's are the run (k T + n0) E .. of Z's flat rows, nn E of them; their dkx rows k nn E ..
+        for (int k = 0; k < (whole ? 1 : lt); ++k) {
+            const int64_t row0 = (int64_t(k) * T + n0) * E, n = whole ? int64_t(lt) * T * E : nn * E;
+            const int rc = spectral_cross_grad_launch(c->stream, Q, family, d, Zd + row0 * d, n, S, cc, alpha, omega, gamma,
+                                                      A.dkx + int64_t(k) * nn * E * cc, static_cast<double*>(gZ) + row0 * d,
+                                                      static_cast<double*>(cpart), gS, dalpha, domega, dgamma, n0 > 0 || k > 0);
+            if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral cross reverse pass: %s", hipGetErrorString(hipError_t(rc)));
+        }
         at += grid;
     }
     hipLaunchKernelGGL(lr_grad_reduce_kernel, dim3(unsigned((int64_t(cc) * cc + 255) / 256)), dim3(256), 0, c->stream, static_cast<const double*>(part),

@@ -373,6 +373,30 @@ int gpsig_lr_seq_features_spectral_grad(gpsig_ctx* ctx, const gpsig_params* p, i
                                         const gpsig_sketch* sketches, const void* X, int64_t N, int32_t L, const double* S, const double* Wh,
                                         const double* alpha, const double* omega, const double* gamma, const void* dPhi, void* gX,
                                         double* gS, double* gWh, double* dalpha, double* domega, double* dgamma);
+/* The inducing tensors' feature map for the TRAINING path: _K_tens_lr_feat (kernels.py:285-311: Nystrom_map + tensor_kern_lr_feature) given
+ * landmarks S (c, d) and whitening Wh (c, c) on the device, like the four sequence entry points above.  Z: T inducing tensors of
+ * lt = M (M + 1) / 2 components, (lt, T, d) or, with `increments`, (lt, T, 2, d) -- already scaled (no lengthscales inside, p->num_lags = 0),
+ * DEVICE pointer; Phi (T, F = 1 + c + (M-1) r) by the fused tensor kernels (one workgroup per tensor).
+ * _grad: dPhi (T, F) -> gZ (Z's layout), gS (c, d), gWh (c, c), g_base[0] (the base kernel's own parameter, or NULL), all overwritten: one
+ * kernel that repeats the forward pass in LDS and walks every level's chain of projections backwards, per-workgroup partial sums combined
+ * in a fixed order (no floating-point atomics: bit-for-bit repeatable).  The Matern families take no gradient through a zero distance, as
+ * the sequence pair.  The spectral pair takes alpha (Q), omega (Q, d), gamma (Q, d) as DEVICE pointers (p->base_params = {Q, family}) and also
+ * returns dalpha, domega, dgamma.  T = 0: the summed outputs are zeroed.  Limits: float64, device-pointer mode (GPSIG_ERR_INVALID otherwise),
+ * order 1, num_levels <= 8, num_components <= 64, num_components x d <= 4096, a tensor's arrays within the LDS (spectral: Q <= 64, d <= 32);
+ * outside them GPSIG_ERR_UNSUPPORTED. */
+int gpsig_lr_tens_features_dev(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
+                               const gpsig_sketch* sketches, const void* Z, int64_t T, int32_t increments, const double* S, const double* Wh,
+                               void* Phi);
+int gpsig_lr_tens_features_grad(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
+                                const gpsig_sketch* sketches, const void* Z, int64_t T, int32_t increments, const double* S, const double* Wh,
+                                const void* dPhi, void* gZ, double* gS, double* gWh, double* g_base);
+int gpsig_lr_tens_features_spectral_dev(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
+                                        const gpsig_sketch* sketches, const void* Z, int64_t T, int32_t increments, const double* S,
+                                        const double* Wh, const double* alpha, const double* omega, const double* gamma, void* Phi);
+int gpsig_lr_tens_features_spectral_grad(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
+                                         const gpsig_sketch* sketches, const void* Z, int64_t T, int32_t increments, const double* S,
+                                         const double* Wh, const double* alpha, const double* omega, const double* gamma, const void* dPhi,
+                                         void* gZ, double* gS, double* gWh, double* dalpha, double* domega, double* dgamma);
 /* SignatureSpectral's Nystrom cross matrix for the TRAINING path (kernels.py:921-942, low_rank_calculations.py:59): K (n, c) = kappa(P, S)
  * for points P (n, d) and landmarks S (c, d), the parameters alpha (Q), omega (Q, d), gamma (Q, d) read from DEVICE memory (they change at
  * every optimiser step: no trip through the host), family 0 = rbf, 1 = exp, 2 = mixed; 1 <= Q <= 64, d <= 32.  Device pointers, device-pointer
