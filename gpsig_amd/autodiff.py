@@ -1006,16 +1006,23 @@ class _LowRankScope:
     def seq(self, Xs):
         """signature_algs.py:162-192 (with :191 summing P, as evidently intended).  (N, L, d') -> [(N, 1), (N, c), (N, r), ...].
         Through the HIP feature kernel and its reverse pass (_LrSeqFeatures; SignatureSpectral: _LrSeqFeaturesSpectral) where they are
-        built; torch ops otherwise (long sequences at large ranks, more than 64 components, module option ``lr_hip = False``)."""
+        built (sequences beyond the LDS in time tiles; SignatureSpectral: whole sequences only); torch ops otherwise (more than 64
+        components, ranks beyond a 64-step tile, module option ``lr_hip = False``)."""
         key = id(Xs)
         if key not in self._seq and getattr(self.mod, "lr_hip", True) and Xs.is_cuda:
             mod, kern = self.mod, self.mod.kern
             M, cc = kern.num_levels, int(self.S.shape[0])
             r = int(self.host_sketches[0].r) if self.host_sketches else int(kern.rank_bound)
             L, d = int(Xs.shape[1]), int(Xs.shape[2])
-            # what csrc/lr_grad_api.hip takes: four (width, L) arrays of a sequence in LDS, at most 64 components
+            # what csrc/lr_grad_api.hip takes: at most 64 components, and in LDS (csrc/lr_tile_plan.hpp) one 64-step tile of a sequence's
+            # arrays with its carry rows, three in the forward direction and four in the reverse pass -- longer sequences go in tiles;
+            # SignatureSpectral: the four (width, L) arrays of a whole sequence
             rows, lp = max(cc, r, d, 16), (L + 63) // 64 * 64 + 1
-            if cc <= 64 and cc * d <= 4096 and 8 * lp * 4 * rows <= 156 * 1024 and M - 1 <= 7:
+            if kern._base == "spectral":
+                fits = 8 * lp * 4 * rows <= 156 * 1024
+            else:
+                fits = max(8 * (65 * 4 * rows + 17 * rows), 8 * (65 * (cc + 2 * max(cc, r, d)) + 8 * max(cc, r, d))) <= 156 * 1024
+            if cc <= 64 and cc * d <= 4096 and fits and M - 1 <= 7:
                 try:
                     if kern._base == "spectral":
                         Phi = _LrSeqFeaturesSpectral.apply(Xs, self.S, self.Wh, positive(mod.raw_alpha), positive(mod.raw_omega),

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "aux_kernels.hpp"
+#include "lr_tile_plan.hpp"       // LR_FUSED_MAX_LDS, lr_fused_stride, lr_fused_lds_bytes (HIP-free: the tile plan needs them too)
 
 namespace gpsig {
 
@@ -27,7 +28,6 @@ using LrFusedSketch = LrSketch<LrEntry>;
 using LrFusedSketchF32 = LrSketch<LrEntryF32>;
 
 constexpr int LR_FUSED_MAX_SKETCHES = 7;            // levels 2 .. 8
-constexpr size_t LR_FUSED_MAX_LDS = 156 * 1024;     // of the 160 KB a CU has (one workgroup per CU at that size)
 
 // The float32 forms run the same bodies on float: points, landmarks, whitening, sketch values, spectral table and features in float32,
 // phase 1 on the hardware transcendentals.  The state stays float64 (drawn and whitened in float64); lr_narrow_launch converts what the
@@ -49,14 +49,6 @@ struct LrFusedFields {
 };
 struct LrFusedArgs : LrFusedFields<double, LrEntry> {};
 struct LrFusedArgsF32 : LrFusedFields<float, LrEntryF32> {};
-
-inline int lr_fused_stride(int L, int pad) { return (L + 63) / 64 * 64 + pad; }
-inline size_t lr_fused_lds_bytes(int c, int r, int d_eff, int L, int pad = 1) {
-    const int lp = lr_fused_stride(L, pad);
-    int kb = c > r ? c : r;
-    if (d_eff > kb) kb = d_eff;
-    return sizeof(double) * size_t(lp) * (size_t(c) + 2 * size_t(kb));
-}
 
 // two-array form (lr_seq_features_fused2_kernel): usable for L <= 64 and at most 8 output columns per wavefront of the 512-thread workgroup
 inline bool lr_fused2_ok(int c, int r, int L) { return L <= 64 && c <= 64 && r <= 64; }

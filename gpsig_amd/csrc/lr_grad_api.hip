@@ -7,6 +7,9 @@
 //     gpsig_lr_seq_features_dev    Phi (N, F) = the fused feature kernel of lr_fused_kernel.hpp on (X, S, Wh), launched by
 //                                  lr_fused_inst.hip (fused_features below: the evaluation path's arguments on device pointers)
 //     gpsig_lr_seq_features_grad   dPhi (N, F) -> dX, dS, dWh, d base parameter: lr_grad_kernel.hpp
+// Where a sequence's arrays exceed the LDS (lr_fused_lds_bytes / lr_grad_lds_bytes, lr_tile_plan.hpp), the same two entry points launch the
+// time-tiled kernels of lr_tiled_kernel.hpp, each direction on its own: shapes that fit keep the whole-sequence kernels.  The tiled reverse
+// pass keeps the E_i of a whole sequence per workgroup in B_GR1; the plan shrinks the grid to hold that within LR_TILE_SCRATCH_BUDGET.
 // and SignatureSpectral's pair, whose parameters (alpha, omega, gamma) are trained and so come as device pointers too:
 //     gpsig_lr_seq_features_spectral_dev    Phi by the spectral fused instances on a table packed on the device (no host round trip)
 //     gpsig_lr_seq_features_spectral_grad   lr_seq_features_grad_spectral_kernel: dPhi -> dWh and dkxs (N, L, c) in scratch; then the
@@ -26,6 +29,7 @@
 #include "ctx.hpp"
 #include "lr_grad_kernel.hpp"
 #include "lr_tens_grad_kernel.hpp"
+#include "lr_tiled_kernel.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -169,17 +173,28 @@ void grad_args(const gpsig_ctx* c, const gpsig_params* p, int cc, int r, int nsk
     A->F = 1 + cc + (M - 1) * r;
     A->escr = static_cast<double*>(escr); A->escr_stride = escr_stride;
     A->lp = lr_fused_stride(L, c->lr_fused_pad);
-    A->rows_b = std::max(std::max(std::max(cc, r), d), 16);
+    A->rows_b = lr_grad_rows(cc, r, d);
+}
+
+// the tiled kernels' arguments (lr_tiled_kernel.hpp) from the plan of one direction
+void tiled_args(const gpsig_ctx* c, const gpsig_params* p, int cc, int r, int nsk, const LrGradSketch* gs, int L, const double* S, const double* Wh,
+                const LrTileDir& D, bool reverse, LrTiledArgs* A) {
+    grad_args(c, p, cc, r, nsk, gs, L, S, Wh, nullptr, 0, A);
+    A->lp = D.lp; A->TL = D.TL; A->ntiles = D.ntiles;
+    A->rows_b = reverse ? lr_grad_rows(cc, r, A->d) : lr_fused_rows(cc, r, A->d);
 }
 
 // the reverse kernel in the workgroup size lr_grad_threads picks: one workgroup per CU at these LDS sizes, 1024 threads give the scalar
 // loads of the projections' entries twice the wavefronts to hide behind
 template <typename Args>
 int grad_launch(gpsig_ctx* c, const Args& A, unsigned grid, size_t lds) {
-    const bool wide = c->lr_grad_threads != 512;
+    // (the tiled form is built at 512 threads alone: at 1024, 128 registers a thread, it would keep scratch memory)
+    const bool wide = c->lr_grad_threads != 512 && !std::is_same<Args, LrTiledArgs>::value;
     void (*kern)(Args);
     if constexpr (std::is_same<Args, LrGradSpectralArgs>::value)
         kern = wide ? lr_seq_features_grad_spectral_kernel<1024> : lr_seq_features_grad_spectral_kernel<512>;
+    else if constexpr (std::is_same<Args, LrTiledArgs>::value)
+        kern = lr_seq_features_grad_tiled_kernel<512>;
     else
         kern = wide ? lr_seq_features_grad_kernel<1024> : lr_seq_features_grad_kernel<512>;
     const int rc = lr_launch(kern, grid, wide ? 1024 : 512, lds, c->stream, A);
@@ -245,13 +260,22 @@ int gpsig_lr_seq_features_dev(gpsig_ctx* c, const gpsig_params* p, int32_t cc, i
                               int64_t N, int32_t L, const double* S, const double* Wh, void* Phi) {
     CHK(check(c, p, cc, r, nsk));
     if (N < 0 || L < 1 || (N > 0 && (!X || !S || !Wh || !Phi))) return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
-    // always the three-array form (the instance of lr_fused_variant): lr_fused does not apply here
-    const size_t lds = lr_fused_lds_bytes(cc, r, p->num_features, L, c->lr_fused_pad);
-    if (lds > LR_FUSED_MAX_LDS) return fail(c, GPSIG_ERR_UNSUPPORTED, "a sequence's low-rank arrays (%zu bytes) exceed the LDS", lds);
+    // always the three-array form (the instance of lr_fused_variant): lr_fused does not apply here; beyond the LDS its time-tiled form
+    const LrTileDir D = lr_tile_dir(false, cc, r, p->num_features, L, p->difference ? L - 1 : L, c->lr_fused_pad);
+    if (!D.untiled && D.TL == 0)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "a %d-step tile of a sequence's low-rank arrays (%zu bytes) exceeds the LDS", LR_TILE_STEP,
+                    lr_tiled_fused_lds_bytes(cc, r, p->num_features, LR_TILE_STEP, c->lr_fused_pad));
     LrGradSketch gs[LR_FUSED_MAX_SKETCHES];
     CHK(upload_sketches(c, cc, r, nsk, sketches, gs));
     if (N == 0) return GPSIG_OK;
-    return fused_features(c, p, cc, r, nsk, gs, X, N, L, S, Wh, nullptr, false, Phi, "fused low-rank feature kernel");
+    if (D.untiled) return fused_features(c, p, cc, r, nsk, gs, X, N, L, S, Wh, nullptr, false, Phi, "fused low-rank feature kernel");
+    LrTiledArgs A{};
+    tiled_args(c, p, cc, r, nsk, gs, L, S, Wh, D, false, &A);
+    A.X = static_cast<const double*>(X); A.N = N;
+    A.Phi = static_cast<double*>(Phi);
+    const int rc = lr_launch(lr_seq_features_tiled_kernel<1024>, unsigned(N < (1 << 20) ? N : (1 << 20)), 1024, D.lds, c->stream, A);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "tiled low-rank feature kernel: %s", hipGetErrorString(hipError_t(rc)));
+    return GPSIG_OK;
 }
 
 int gpsig_lr_seq_features_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches, const void* X,
@@ -262,8 +286,14 @@ int gpsig_lr_seq_features_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, 
     const int M = p->num_levels, d = p->num_features;
     if (cc > 64 || int64_t(cc) * d > int64_t(LR_GRAD_KS) * LR_GRAD_THREADS)
         return fail(c, GPSIG_ERR_UNSUPPORTED, "the low-rank reverse pass is built for num_components <= 64 and num_components x columns <= %d", LR_GRAD_KS * LR_GRAD_THREADS);
-    const size_t lds = lr_grad_lds_bytes(cc, r, d, L, c->lr_fused_pad);
-    if (lds > LR_FUSED_MAX_LDS) return fail(c, GPSIG_ERR_UNSUPPORTED, "a sequence's low-rank arrays (%zu bytes) exceed the LDS in the reverse pass", lds);
+    const LrTilePlan plan = lr_tile_plan(cc, r, d, L, M, p->difference, c->lr_fused_pad, N);
+    const size_t lds = plan.rev.lds;
+    if (!plan.rev.untiled && plan.rev.TL == 0)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "a %d-step tile of a sequence's low-rank arrays (%zu bytes) exceeds the LDS in the reverse pass", LR_TILE_STEP,
+                    lr_tiled_grad_lds_bytes(cc, r, d, LR_TILE_STEP, c->lr_fused_pad));
+    if (N > 0 && plan.grid == 0)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "one workgroup's scratch for a sequence of %d steps (%lld bytes) exceeds the reverse pass's budget", plan.l,
+                    (long long)(plan.escr_stride * int64_t(sizeof(double))));
     LrGradSketch gs[LR_FUSED_MAX_SKETCHES];
     CHK(upload_sketches(c, cc, r, nsk, sketches, gs));
     const int64_t width = int64_t(cc) * d + int64_t(cc) * cc + 1;
@@ -273,19 +303,30 @@ int gpsig_lr_seq_features_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, 
         if (g_base) CHK(zero_async(c, g_base, sizeof(double)));
         return GPSIG_OK;
     }
-    const int l = p->difference ? L - 1 : L;
-    const unsigned grid = unsigned(N < 512 ? N : 512);                 // one workgroup per CU at these LDS sizes, two rounds' worth of them
-    const int64_t escr_stride = (int64_t(cc) + int64_t(M > 2 ? M - 2 : 0) * r) * (l > 0 ? l : 1) + 8;
+    // one workgroup per CU at these LDS sizes, two rounds' worth of them (512); fewer where the tiled form's scratch would exceed its budget
+    const unsigned grid = unsigned(plan.grid);
+    const int64_t escr_stride = plan.escr_stride;
     void *part, *escr;
     CHK(ensure(c, B_GR0, sizeof(double) * size_t(grid) * size_t(width) + 64, &part));
     CHK(ensure(c, B_GR1, sizeof(double) * size_t(grid) * size_t(escr_stride) + 64, &escr));
-    LrGradArgs A{};
-    grad_args(c, p, cc, r, nsk, gs, L, S, Wh, escr, escr_stride, &A);
-    A.X = static_cast<const double*>(X); A.N = N;
-    A.dPhi = static_cast<const double*>(dPhi);
-    A.gX = static_cast<double*>(gX);
-    A.part = static_cast<double*>(part);
-    CHK(grad_launch(c, A, grid, lds));
+    if (plan.rev.untiled) {
+        LrGradArgs A{};
+        grad_args(c, p, cc, r, nsk, gs, L, S, Wh, escr, escr_stride, &A);
+        A.X = static_cast<const double*>(X); A.N = N;
+        A.dPhi = static_cast<const double*>(dPhi);
+        A.gX = static_cast<double*>(gX);
+        A.part = static_cast<double*>(part);
+        CHK(grad_launch(c, A, grid, lds));
+    } else {
+        LrTiledArgs A{};
+        tiled_args(c, p, cc, r, nsk, gs, L, S, Wh, plan.rev, true, &A);
+        A.escr = static_cast<double*>(escr); A.escr_stride = escr_stride;
+        A.X = static_cast<const double*>(X); A.N = N;
+        A.dPhi = static_cast<const double*>(dPhi);
+        A.gX = static_cast<double*>(gX);
+        A.part = static_cast<double*>(part);
+        CHK(grad_launch(c, A, grid, lds));
+    }
     hipLaunchKernelGGL(lr_grad_reduce_kernel, dim3(unsigned((width + 255) / 256)), dim3(256), 0, c->stream, static_cast<const double*>(part), int(grid), width,
                        gS, int64_t(cc) * d, gWh, int64_t(cc) * cc, g_base);
     HIPCHK(c, hipGetLastError());

@@ -66,12 +66,180 @@ struct LrGradSpectralArgs : LrGradArgs {
 constexpr int LR_GRAD_THREADS = 512;                   // (the smaller of the two workgroup sizes built: what the per-thread tables are sized for)
 constexpr int LR_GRAD_KW = 8, LR_GRAD_KS = 8;          // (i, j) pairs of dWh and (i, f) pairs of dS per thread: c <= 64, c d <= 4096
 
-inline size_t lr_grad_lds_bytes(int c, int r, int d, int L, int pad = 1) {
-    const int lp = lr_fused_stride(L, pad);
-    int kb = c > r ? c : r;
-    if (d > kb) kb = d;
-    if (kb < 16) kb = 16;                              // (a row per wavefront for the per-wave partial sums: up to 1024 threads)
-    return sizeof(double) * size_t(lp) * 4 * size_t(kb);
+// (the LDS footprint, lr_grad_lds_bytes: lr_tile_plan.hpp)
+
+// ---- loops shared with the tiled kernels (lr_tiled_kernel.hpp): `n` time steps / points of arrays with row stride lp, nchunk chunks of 64 lanes
+// out[row][t] (+)= sum_e val * a[ia][t] * b[ib][t] over the entries of `row`, t < n: the forward sketch's loop (also the two gathers of the
+// reverse pass, over the by-i1 / by-i2 copies of a sketch)
+template <int NW, int UNROLL>
+__device__ __forceinline__ void lr_sketch_apply(const int32_t* ptr_, const LrEntry* ent_, int nrows, const double* a, const double* b, double* out,
+                                                bool accumulate, int lp, int n, int nchunk, int lane, int wave) {
+    const lr_const_ptr<int32_t> ptr = lr_as_const(ptr_);
+    const lr_const_ptr<LrEntry> ent = lr_as_const(ent_);
+    for (int row = wave; row < nrows; row += NW) {
+        const int e0 = ptr[row], e1 = ptr[row + 1];
+        for (int ch = 0; ch < nchunk; ++ch) {
+            const int t = ch * 64 + lane;
+            const int tt = t < n ? t : 0;                   // idle lanes read a valid address
+            double acc = 0.0;
+#pragma unroll UNROLL
+            for (int e = e0; e < e1; ++e) {
+                const double val = ent[e].val;
+                const int ia = ent[e].i1, ib = ent[e].i2;
+                acc = fma(val * a[ia * lp + tt], b[ib * lp + tt], acc);
+            }
+            if (t < n) out[row * lp + t] = accumulate ? out[row * lp + t] + acc : acc;
+        }
+    }
+}
+// xb[f][t] = the n points (n, d) at Xn
+template <int THREADS>
+__device__ __forceinline__ void lr_load_points(const double* Xn, int n, int d, int lp, double* xb) {
+    for (int q = threadIdx.x; q < n * d; q += THREADS) {
+        const int t = q / d, f = q - t * d;
+        xb[f * lp + t] = Xn[q];
+    }
+}
+// kb[i][t] = kappa(x_t, S_i) for the families of base_eval
+template <int NW>
+__device__ __forceinline__ void lr_cross_base(int kind, double p0, double p1, lr_const_ptr<double> Sg, int c, int d, const double* xb, double* kb,
+                                              int lp, int n, int nchunk, int lane, int wave) {
+    for (int ch = 0; ch < nchunk; ++ch) {
+        const int t = ch * 64 + lane;
+        if (t < n) {
+            double xs = 0.0;
+            for (int f = 0; f < d; ++f) { const double x = xb[f * lp + t]; xs = fma(x, x, xs); }
+            for (int i = wave; i < c; i += NW) {
+                double ip = 0.0, ss = 0.0;
+                for (int f = 0; f < d; ++f) {
+                    const double y = Sg[size_t(i) * d + f];
+                    ip = fma(xb[f * lp + t], y, ip);
+                    ss = fma(y, y, ss);
+                }
+                kb[i * lp + t] = base_eval<double>(kind, ip, xs, ss, p0, p1);
+            }
+        }
+    }
+}
+
+// The tail of a sequence's (a tile's) reverse pass, on the points [q0, np) of the arrays (row stride lp); kxs in B0, dfeat in Xb:
+//   dWh[i][j] += sum_t kxs[i][t] dfeat[j][t]  (accW, KW pairs per thread: KW THREADS >= c c);  dkxs[i][t] = sum_j dfeat[j][t] Wh[i][j] -> Y
+template <int THREADS, int KW>
+__device__ __forceinline__ void lr_grad_whiten_adjoint(int c, int lp, int q0, int np, const double* B0, const double* Xb, lr_const_ptr<double> Whg,
+                                                       double* Y, double (&accW)[KW], int lane, int wave) {
+    constexpr int NW = THREADS / 64;
+    const int nchunk = (np + 63) / 64;
+#pragma unroll
+    for (int k = 0; k < KW; ++k) {
+        const int q = k * THREADS + threadIdx.x;
+        if (q < c * c) {
+            const int i = q / c, j = q - i * c;
+            double acc = 0.0;
+            for (int t = q0; t < np; ++t) acc = fma(B0[i * lp + t], Xb[j * lp + t], acc);
+            accW[k] += acc;
+        }
+    }
+    for (int ch = 0; ch < nchunk; ++ch) {
+        const int t = ch * 64 + lane;
+        if (t >= q0 && t < np) {
+            for (int i = wave; i < c; i += NW) {
+                double acc = 0.0;
+#pragma unroll 4
+                for (int j = 0; j < c; ++j) acc = fma(Xb[j * lp + t], Whg[size_t(i) * c + j], acc);
+                Y[i * lp + t] = acc;
+            }
+        }
+    }
+}
+// ... and through the base kernel: d kappa / dx = wy S_i + wx x,  d kappa / dS_i = wy x + ws S_i  (BaseGrad of grad_core.hpp); x in B1, dkxs in Y.
+//   Y[i][t] <- dkxs wy,  Xb[i][t] <- dkxs ws,  B0[wave][t] <- this wave's share of sum_i dkxs wx;  the points' gX rows (point t is the
+//   sequence's point t0 + t) are written, dS and the base parameter's sums go to accS (KS pairs per thread: KS THREADS >= c d) and accP
+template <int THREADS, typename Args, int KS>
+__device__ __forceinline__ void lr_grad_base_phase(const Args& A, lr_const_ptr<double> Sg, int64_t n, int t0, int q0, int np, double* B0, const double* B1,
+                                                   double* Xb, double* Y, double (&accS)[KS], double& accP, int lane, int wave) {
+    constexpr int NW = THREADS / 64;
+    const int lp = A.lp, c = A.c, d = A.d, L = A.L;
+    const int nchunk = (np + 63) / 64;
+    for (int ch = 0; ch < nchunk; ++ch) {
+        const int t = ch * 64 + lane;
+        const bool mine = t >= q0 && t < np;
+        double ax = 0.0;
+        if (mine) {
+            double xs = 0.0;
+            for (int f = 0; f < d; ++f) { const double x = B1[f * lp + t]; xs = fma(x, x, xs); }
+            for (int i = wave; i < c; i += NW) {
+                double ip = 0.0, ss = 0.0;
+                for (int f = 0; f < d; ++f) {
+                    const double y = Sg[size_t(i) * d + f];
+                    ip = fma(B1[f * lp + t], y, ip);
+                    ss = fma(y, y, ss);
+                }
+                const BaseGrad bg = base_eval_grad(A.kind, ip, xs, ss, A.p0, A.p1);
+                const double dk = Y[i * lp + t];
+                Y[i * lp + t] = dk * (bg.cy - bg.cd);
+                Xb[i * lp + t] = dk * (bg.cx2 + bg.cd);
+                ax = fma(dk, bg.cx + bg.cd, ax);
+                accP = fma(dk, bg.dp0, accP);
+            }
+        }
+        __syncthreads();                         // (kxs in B0 was last read by the dWh sums, before the caller's barrier)
+        if (mine) B0[wave * lp + t] = ax;
+        __syncthreads();
+        // dx[t][f] = sum_i Y[i][t] S_i[f] + x[f][t] sum_w B0[w][t]
+        if (mine) {
+            double axs = 0.0;
+#pragma unroll
+            for (int w2 = 0; w2 < NW; ++w2) axs += B0[w2 * lp + t];
+            for (int f = wave; f < d; f += NW) {
+                double acc = axs * B1[f * lp + t];
+                for (int i = 0; i < c; ++i) acc = fma(Y[i * lp + t], Sg[size_t(i) * d + f], acc);
+                A.gX[(n * int64_t(L) + t0 + t) * d + f] = acc;
+            }
+        }
+        __syncthreads();
+    }
+    // dS[i][f] += sum_t Y[i][t] x[f][t] + S_i[f] sum_t Xb[i][t]
+#pragma unroll
+    for (int k = 0; k < KS; ++k) {
+        const int q = k * THREADS + threadIdx.x;
+        if (q < c * d) {
+            const int i = q / d, f = q - i * d;
+            double a1 = 0.0, a2 = 0.0;
+            for (int t = q0; t < np; ++t) {
+                a1 = fma(Y[i * lp + t], B1[f * lp + t], a1);
+                a2 += Xb[i * lp + t];
+            }
+            accS[k] += fma(a2, Sg[size_t(i) * d + f], a1);
+        }
+    }
+}
+// this workgroup's partial sums [c d + c c + 1]: dS, dWh, d base parameter (`red`: NW doubles of LDS)
+template <int THREADS, typename Args, int KW, int KS>
+__device__ __forceinline__ void lr_grad_write_partials(const Args& A, const double (&accW)[KW], const double (&accS)[KS], double accP,
+                                                       double* red, int lane, int wave) {
+    constexpr int NW = THREADS / 64;
+    const int c = A.c, d = A.d;
+    double* part = A.part + int64_t(blockIdx.x) * (int64_t(c) * d + int64_t(c) * c + 1);
+#pragma unroll
+    for (int k = 0; k < KS; ++k) {
+        const int q = k * THREADS + threadIdx.x;
+        if (q < c * d) part[q] = accS[k];
+    }
+#pragma unroll
+    for (int k = 0; k < KW; ++k) {
+        const int q = k * THREADS + threadIdx.x;
+        if (q < c * c) part[int64_t(c) * d + q] = accW[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) accP += __shfl_xor(accP, o, 64);
+    if (lane == 0) red[wave] = accP;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int w2 = 0; w2 < NW; ++w2) s += red[w2];
+        part[int64_t(c) * d + int64_t(c) * c] = s;
+    }
 }
 
 template <int THREADS, bool SPEC, typename Args>
@@ -91,33 +259,11 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
     const lr_const_ptr<double> Sg = lr_as_const(A.S);
     const lr_const_ptr<double> Whg = lr_as_const(A.Wh);
 
-    // out[row][t] (+)= sum_e val * a[ia][t] * b[ib][t] over the entries of `row`: the forward sketch's loop
     auto apply = [&](const int32_t* ptr_, const LrEntry* ent_, int nrows, const double* a, const double* b, double* out, bool accumulate) {
-        const lr_const_ptr<int32_t> ptr = lr_as_const(ptr_);
-        const lr_const_ptr<LrEntry> ent = lr_as_const(ent_);
-        for (int row = wave; row < nrows; row += NW) {
-            const int e0 = ptr[row], e1 = ptr[row + 1];
-            for (int ch = 0; ch < nchunk; ++ch) {
-                const int t = ch * 64 + lane;
-                const int tt = t < l ? t : 0;                   // idle lanes read a valid address
-                double acc = 0.0;
-#pragma unroll UNROLL
-                for (int e = e0; e < e1; ++e) {
-                    const double val = ent[e].val;
-                    const int ia = ent[e].i1, ib = ent[e].i2;
-                    acc = fma(val * a[ia * lp + tt], b[ib * lp + tt], acc);
-                }
-                if (t < l) out[row * lp + t] = accumulate ? out[row * lp + t] + acc : acc;
-            }
-        }
+        lr_sketch_apply<NW, UNROLL>(ptr_, ent_, nrows, a, b, out, accumulate, lp, l, nchunk, lane, wave);
     };
     // x[f][t] and kxs[i][t] = kappa(x_t, S_i) of the current sequence
-    auto load_x = [&](const double* Xn, double* xb) {
-        for (int q = threadIdx.x; q < L * d; q += THREADS) {
-            const int t = q / d, f = q - t * d;
-            xb[f * lp + t] = Xn[q];
-        }
-    };
+    auto load_x = [&](const double* Xn, double* xb) { lr_load_points<THREADS>(Xn, L, d, lp, xb); };
     auto cross = [&](const double* xb, double* kb) {
         if constexpr (SPEC) {
             const lr_const_ptr<double> al = lr_as_const(A.alpha), om = lr_as_const(A.omega), ga = lr_as_const(A.gamma);
@@ -131,22 +277,7 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
             }
             return;
         }
-        for (int ch = 0; ch < nchunk; ++ch) {
-            const int t = ch * 64 + lane;
-            if (t < L) {
-                double xs = 0.0;
-                for (int f = 0; f < d; ++f) { const double x = xb[f * lp + t]; xs = fma(x, x, xs); }
-                for (int i = wave; i < c; i += NW) {
-                    double ip = 0.0, ss = 0.0;
-                    for (int f = 0; f < d; ++f) {
-                        const double y = Sg[size_t(i) * d + f];
-                        ip = fma(xb[f * lp + t], y, ip);
-                        ss = fma(y, y, ss);
-                    }
-                    kb[i * lp + t] = base_eval<double>(A.kind, ip, xs, ss, A.p0, A.p1);
-                }
-            }
-        }
+        lr_cross_base<NW>(A.kind, A.p0, A.p1, Sg, c, d, xb, kb, lp, L, nchunk, lane, wave);
     };
 
     double accW[LR_GRAD_KW], accS[LR_GRAD_KS], accP = 0.0;      // this workgroup's sums over its sequences: dWh, dS, d base parameter
@@ -285,29 +416,7 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
             cross(B1, B0);
         }
         __syncthreads();
-        // dWh[i][j] += sum_t kxs[i][t] dfeat[j][t]
-#pragma unroll
-        for (int k = 0; k < LR_GRAD_KW; ++k) {
-            const int q = k * THREADS + threadIdx.x;
-            if (q < c * c) {
-                const int i = q / c, j = q - i * c;
-                double acc = 0.0;
-                for (int t = 0; t < L; ++t) acc = fma(B0[i * lp + t], Xb[j * lp + t], acc);
-                accW[k] += acc;
-            }
-        }
-        // dkxs[i][t] = sum_j dfeat[j][t] Wh[i][j] -> Y
-        for (int ch = 0; ch < nchunk; ++ch) {
-            const int t = ch * 64 + lane;
-            if (t < L) {
-                for (int i = wave; i < c; i += NW) {
-                    double acc = 0.0;
-#pragma unroll 4
-                    for (int j = 0; j < c; ++j) acc = fma(Xb[j * lp + t], Whg[size_t(i) * c + j], acc);
-                    Y[i * lp + t] = acc;
-                }
-            }
-        }
+        lr_grad_whiten_adjoint<THREADS>(c, lp, 0, L, B0, Xb, Whg, Y, accW, lane, wave);
         __syncthreads();
         if constexpr (SPEC) {                        // dkxs (L, c) of this sequence out; the spectral cross op's reverse kernels take it from here
             double* dk = A.dkxs + n * int64_t(L) * c;
@@ -317,59 +426,7 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
             }
             continue;                                // (the loop's first barrier orders these reads before Y is written again)
         }
-        // through the base kernel: d kappa / dx = wy S_i + wx x,  d kappa / dS_i = wy x + ws S_i  (BaseGrad of grad_core.hpp)
-        //   Y[i][t] <- dkxs wy,  Xb[i][t] <- dkxs ws,  B0[wave][t] <- this wave's share of sum_i dkxs wx
-        for (int ch = 0; ch < nchunk; ++ch) {
-            const int t = ch * 64 + lane;
-            double ax = 0.0;
-            if (t < L) {
-                double xs = 0.0;
-                for (int f = 0; f < d; ++f) { const double x = B1[f * lp + t]; xs = fma(x, x, xs); }
-                for (int i = wave; i < c; i += NW) {
-                    double ip = 0.0, ss = 0.0;
-                    for (int f = 0; f < d; ++f) {
-                        const double y = Sg[size_t(i) * d + f];
-                        ip = fma(B1[f * lp + t], y, ip);
-                        ss = fma(y, y, ss);
-                    }
-                    const BaseGrad bg = base_eval_grad(A.kind, ip, xs, ss, A.p0, A.p1);
-                    const double dk = Y[i * lp + t];
-                    Y[i * lp + t] = dk * (bg.cy - bg.cd);
-                    Xb[i * lp + t] = dk * (bg.cx2 + bg.cd);
-                    ax = fma(dk, bg.cx + bg.cd, ax);
-                    accP = fma(dk, bg.dp0, accP);
-                }
-            }
-            __syncthreads();                         // (kxs in B0 was last read by the dWh sums above, before the previous barrier)
-            if (t < L) B0[wave * lp + t] = ax;
-            __syncthreads();
-            // dx[t][f] = sum_i Y[i][t] S_i[f] + x[f][t] sum_w B0[w][t]
-            if (t < L) {
-                double axs = 0.0;
-#pragma unroll
-                for (int w2 = 0; w2 < NW; ++w2) axs += B0[w2 * lp + t];
-                for (int f = wave; f < d; f += NW) {
-                    double acc = axs * B1[f * lp + t];
-                    for (int i = 0; i < c; ++i) acc = fma(Y[i * lp + t], Sg[size_t(i) * d + f], acc);
-                    A.gX[(n * int64_t(L) + t) * d + f] = acc;
-                }
-            }
-            __syncthreads();
-        }
-        // dS[i][f] += sum_t Y[i][t] x[f][t] + S_i[f] sum_t Xb[i][t]
-#pragma unroll
-        for (int k = 0; k < LR_GRAD_KS; ++k) {
-            const int q = k * THREADS + threadIdx.x;
-            if (q < c * d) {
-                const int i = q / d, f = q - i * d;
-                double a1 = 0.0, a2 = 0.0;
-                for (int t = 0; t < L; ++t) {
-                    a1 = fma(Y[i * lp + t], B1[f * lp + t], a1);
-                    a2 += Xb[i * lp + t];
-                }
-                accS[k] += fma(a2, Sg[size_t(i) * d + f], a1);
-            }
-        }
+        lr_grad_base_phase<THREADS>(A, Sg, n, 0, 0, L, B0, B1, Xb, Y, accS, accP, lane, wave);
     }
     // ---- this workgroup's partial sums
     if constexpr (SPEC) {
@@ -381,27 +438,7 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
         }
         return;
     }
-    double* part = A.part + int64_t(blockIdx.x) * (int64_t(c) * d + int64_t(c) * c + 1);
-#pragma unroll
-    for (int k = 0; k < LR_GRAD_KS; ++k) {
-        const int q = k * THREADS + threadIdx.x;
-        if (q < c * d) part[q] = accS[k];
-    }
-#pragma unroll
-    for (int k = 0; k < LR_GRAD_KW; ++k) {
-        const int q = k * THREADS + threadIdx.x;
-        if (q < c * c) part[int64_t(c) * d + q] = accW[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) accP += __shfl_xor(accP, o, 64);
-    if (lane == 0) lrg_lds[wave] = accP;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w2 = 0; w2 < NW; ++w2) s += lrg_lds[w2];
-        part[int64_t(c) * d + int64_t(c) * c] = s;
-    }
+    lr_grad_write_partials<THREADS>(A, accW, accS, accP, lrg_lds, lane, wave);
 }
 
 template <int THREADS>

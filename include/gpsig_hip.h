@@ -354,7 +354,12 @@ int gpsig_lr_whitening(gpsig_ctx* ctx, const gpsig_params* p, const double* land
  * levels 2..M are value-independent random objects: HOST arrays, kept on the device by content across calls.
  * _grad: dPhi (N, F) -> gX (N, L, d), gS (c, d), gWh (c, c), g_base[0] (the base kernel's own parameter, or NULL) -- what tf.gradients
  * returns for _K_seq_lr_feat (kernels.py:239-261) given the landmarks and the whitening; the caller chains gS and gWh through the
- * gather and the eigendecomposition (gpsig_amd/autodiff.py).  num_components <= 64. */
+ * gather and the eigendecomposition (gpsig_amd/autodiff.py).  num_components <= 64 and num_components x d <= 4096 in _grad.
+ * Sequence length: where a sequence's arrays fit the LDS the whole sequence is kept on chip (three arrays of max(c, r, d) rows forward,
+ * four in _grad: at c = r = 50 up to L = 128 and L = 64); longer sequences are walked in time tiles of a multiple of 64 steps (64 at 64
+ * rows, 256 at 16 rows), each direction on its own, with the same results up to rounding in _grad.  GPSIG_ERR_UNSUPPORTED only where a
+ * single 64-step tile does not fit (more than about 75 rows in _grad), or where one workgroup's scratch of (c + (M-2) r) L doubles
+ * exceeds 256 MB. */
 int gpsig_lr_seq_features_dev(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
                               const gpsig_sketch* sketches, const void* X, int64_t N, int32_t L, const double* S, const double* Wh, void* Phi);
 int gpsig_lr_seq_features_grad(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
