@@ -748,7 +748,7 @@ def _apply_sketch(sk, A, B):
     rows, nnz = A2.shape[0], max(int(i1.shape[0]), 1)
     step = max(1, (1 << 27) // nnz)
     outs = []
-    for r0 in range(0, rows, step):
+    for r0 in range(0, max(rows, 1), step):                  # (no rows -- a one-point sequence with the time difference: one empty chunk)
         a, b = A2[r0:r0 + step], B2[r0:r0 + step]
         if dense is not None and dense[0].dtype == a.dtype:
             outs.append(((a @ dense[0]) * (b @ dense[1])) @ dense[2])
@@ -812,6 +812,49 @@ class _LrSeqFeatures(torch.autograd.Function):
                          _ptr(gX), _ptr(gS), _ptr(gWh), C.cast(gb.data_ptr(), C.POINTER(C.c_double)))
         gp0 = gb[0].to(p0.device).reshape(p0.shape).to(p0.dtype) if ctx.has_p0 else None
         return gX.to(ctx.dt[0]), gS.to(ctx.dt[1]), gWh.to(ctx.dt[2]), gp0, None, None, None
+
+
+class _LrSeqFeaturesRagged(torch.autograd.Function):
+    """_LrSeqFeatures for a ragged batch: ``lengths`` (N,) int32 on the sequences' device, 1 <= lengths[n] <= L.  Phi[n] is the features of
+    Xs[n, :lengths[n]] evaluated alone; the rows beyond a sequence's length are never read (they may hold NaN) and their gradient rows are exact
+    zeros.  By gpsig_lr_seq_features_ragged_dev / _ragged_grad (csrc/lr_ragged_inst.hip: the ragged instances of the whole-sequence and the
+    time-tiled kernels).  Raises NotImplementedError outside the library's limits (the caller falls back to torch ops)."""
+
+    @staticmethod
+    def forward(ctx, Xs, lengths, S, Wh, p0, spec, sketches, r):
+        X, Sd, Whd = _c(Xs), _c(S), _c(Wh)
+        n, l, d = X.shape
+        if lengths.dtype != torch.int32 or lengths.device != X.device or tuple(lengths.shape) != (n,):
+            raise ValueError("lengths: an int32 tensor of shape (N,) on the sequences' device")
+        lens = lengths.contiguous()
+        cc = Sd.shape[0]
+        keep = []
+        p = spec.params(d, _p0_value(p0), keep)
+        arr = _sketch_array(sketches, keep)
+        F = 1 + cc + (spec.num_levels - 1) * int(r)
+        out = torch.empty((n, F), dtype=torch.float64, device=X.device)
+        _ctx_for(X).call("gpsig_lr_seq_features_ragged_dev", p, cc, int(r), len(sketches), arr, _ptr(X), n, l, _ptr(lens), _ptr(Sd), _ptr(Whd),
+                         _ptr(out))
+        ctx.spec, ctx.sketches, ctx.r, ctx.has_p0 = spec, sketches, int(r), p0 is not None
+        ctx.dt = (Xs.dtype, S.dtype, Wh.dtype)
+        ctx.save_for_backward(X, lens, Sd, Whd, p0 if p0 is not None else X.new_empty(0))
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        X, lens, Sd, Whd, p0 = ctx.saved_tensors
+        n, l, d = X.shape
+        cc = Sd.shape[0]
+        keep = []
+        p = ctx.spec.params(d, _p0_value(p0) if ctx.has_p0 else 0.0, keep)
+        arr = _sketch_array(ctx.sketches, keep)
+        G = _c(G)
+        gX, gS, gWh = torch.empty_like(X), torch.empty_like(Sd), torch.empty_like(Whd)
+        gb = torch.zeros(2, dtype=torch.float64, device=X.device)
+        _ctx_for(X).call("gpsig_lr_seq_features_ragged_grad", p, cc, ctx.r, len(ctx.sketches), arr, _ptr(X), n, l, _ptr(lens), _ptr(Sd), _ptr(Whd),
+                         _ptr(G), _ptr(gX), _ptr(gS), _ptr(gWh), C.cast(gb.data_ptr(), C.POINTER(C.c_double)))
+        gp0 = gb[0].to(p0.device).reshape(p0.shape).to(p0.dtype) if ctx.has_p0 else None
+        return gX.to(ctx.dt[0]), None, gS.to(ctx.dt[1]), gWh.to(ctx.dt[2]), gp0, None, None, None
 
 
 _SPECTRAL_FAMILY = {"rbf": 0, "exp": 1, "mixed": 2}
@@ -1003,11 +1046,15 @@ class _LowRankScope:
     def _nys(self, pts):
         return self._cross(pts) @ self.Wh                                                           # :59-61
 
-    def seq(self, Xs):
+    def seq(self, Xs, lengths=None):
         """signature_algs.py:162-192 (with :191 summing P, as evidently intended).  (N, L, d') -> [(N, 1), (N, c), (N, r), ...].
         Through the HIP feature kernel and its reverse pass (_LrSeqFeatures; SignatureSpectral: _LrSeqFeaturesSpectral) where they are
         built (sequences beyond the LDS in time tiles; SignatureSpectral: whole sequences only); torch ops otherwise (more than 64
-        components, ranks beyond a 64-step tile, module option ``lr_hip = False``)."""
+        components, ranks beyond a 64-step tile, module option ``lr_hip = False``).
+        lengths: (N,) int32 on the sequences' device for a ragged batch (sequence n is Xs[n, :lengths[n]]; the rows beyond are not read):
+        _LrSeqFeaturesRagged within the same limits for the families other than SignatureSpectral, _seq_torch_ragged otherwise."""
+        if lengths is not None:
+            return self._seq_ragged(Xs, lengths)
         key = id(Xs)
         if key not in self._seq and getattr(self.mod, "lr_hip", True) and Xs.is_cuda:
             mod, kern = self.mod, self.mod.kern
@@ -1036,6 +1083,52 @@ class _LowRankScope:
         if key not in self._seq:
             self._seq[key] = (Xs, self._seq_torch(Xs))
         return self._seq[key][1]
+
+    def _seq_ragged(self, Xs, lengths):
+        key = (id(Xs), id(lengths))
+        if key not in self._seq and getattr(self.mod, "lr_hip", True) and Xs.is_cuda and self.mod.kern._base != "spectral":
+            mod, kern = self.mod, self.mod.kern
+            M, cc = kern.num_levels, int(self.S.shape[0])
+            r = int(self.host_sketches[0].r) if self.host_sketches else int(kern.rank_bound)
+            d = int(Xs.shape[2])
+            # the limits of seq() above: they follow from the table's L, not from the lengths
+            fits = max(8 * (65 * 4 * max(cc, r, d, 16) + 17 * max(cc, r, d, 16)), 8 * (65 * (cc + 2 * max(cc, r, d)) + 8 * max(cc, r, d))) <= 156 * 1024
+            if cc <= 64 and cc * d <= 4096 and fits and M - 1 <= 7:
+                try:
+                    Phi = _LrSeqFeaturesRagged.apply(Xs, lengths, self.S, self.Wh, mod.p0, mod._spec, self.host_sketches, r)
+                    self._seq[key] = (Xs, lengths, list(torch.split(Phi, [1, cc] + [r] * (M - 1), dim=1)))
+                except NotImplementedError:
+                    pass
+        if key not in self._seq:
+            self._seq[key] = (Xs, lengths, self._seq_torch_ragged(Xs, lengths))
+        return self._seq[key][2]
+
+    def _seq_torch_ragged(self, Xs, lengths):
+        """_seq_torch for a ragged batch (lengths (N,) integers on Xs's device, 1 <= lengths[n] <= L): the features of Xs[n, :lengths[n]]
+        evaluated alone.  The rows beyond a sequence's length may hold anything: they are replaced on the INPUT by the sequence's last valid
+        row (torch.where: no product with them, so neither the values nor autograd see a 0 * NaN; their gradient rows are exact zeros), and
+        the steps beyond its length are set to zero after the time difference, so they add nothing to any level.  The fallback of the HIP
+        route (SignatureSpectral, more than 64 components, ``lr_hip = False``, CPU tensors) and its checker."""
+        N, L, d = Xs.shape
+        lens = lengths.to(device=Xs.device, dtype=torch.long)
+        t = torch.arange(L, device=Xs.device)
+        valid = t[None, :] < lens[:, None]
+        last = Xs[torch.arange(N, device=Xs.device), lens - 1]                                      # (N, d): rows inside every sequence
+        Xc = torch.where(valid[:, :, None], Xs, last[:, None, :])
+        U = self._nys(Xc.reshape(N * L, d)).reshape(N, L, -1)                                       # kernels.py:252-254
+        if self.mod.kern.difference:
+            U = U[:, 1:] - U[:, :-1]                                                                # :180
+            steps = t[None, :-1] < (lens - 1)[:, None]
+        else:
+            steps = valid
+        U = torch.where(steps[:, :, None], U, torch.zeros((), dtype=U.dtype, device=U.device))
+        Phi = [torch.ones((N, 1), dtype=U.dtype, device=U.device), U.sum(dim=1)]                    # :177, :182
+        P = U
+        for i in range(2, self.mod.kern.num_levels + 1):
+            P = torch.cumsum(P, dim=1) - P                                                          # :186 exclusive
+            P = _apply_sketch(self.sk[i - 2], U, P)                                                 # :188 / :190
+            Phi.append(P.sum(dim=1))
+        return Phi
 
     def _seq_torch(self, Xs):
         """The same feature map as torch ops (round 3's route; kept as the checker of the HIP reverse pass and for shapes it is not
@@ -1109,6 +1202,7 @@ def _low_rank_scoped(fn):
         finally:
             self._lr = None
             self._phi_memo = None
+            self._ragged = None
     return wrapped
 
 
@@ -1127,6 +1221,7 @@ class SignatureKernelModule(torch.nn.Module):
         self.kern = kern
         self._lr = None
         self._phi_memo = None
+        self._ragged = None            # ragged evaluations: ((scaled sequences, their lengths on the device), ...) of the evaluation under way
         # linear / cosine kernel: Kzx and the level diagonals from explicit level features (one feature sweep per sequence + plain products).  True:
         # where the recursion kernels' work (tensors x sequences x steps x components x columns) exceeds feature_route_min_work -- a minibatch of 50
         # against 200 tensors is a dozen small launches slower this way (1.2 -> 1.9 ms), BASELINE configs[2] 2.6 times faster; "always"; False
@@ -1194,6 +1289,46 @@ class SignatureKernelModule(torch.nn.Module):
             X, _ = self.kern._slice(X, None)                                                        # GPflow Kernel._slice (kernels.py:411-415)
         return X.reshape(X.shape[0], -1, self.kern.num_features)                                    # kernels.py:417-418
 
+    # ---- ragged batches ------------------------------------------------------------------------------------------
+    def _ragged_lengths(self, lengths, X3):
+        """``lengths=`` of a public evaluation -> (N,) int32 on X3's device, checked on the host: a sequence of ints, a NumPy array or a torch
+        tensor on any device; integers, shape (N,), 1 <= l <= L (ValueError otherwise)."""
+        if not self.kern.low_rank:
+            raise NotImplementedError("lengths= is built for low-rank mode only: in exact mode pad each sequence by repeating its last "
+                                      "observation, which is exact there with difference=True (zero increments add nothing)")
+        if self.kern.num_lags > 0:
+            raise NotImplementedError("lengths= is not built for num_lags > 0: the lag interpolation runs on the table's own time axis")
+        N, L = int(X3.shape[0]), int(X3.shape[1])
+        host = lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else np.asarray(lengths)
+        if host.dtype.kind not in "iu":
+            raise ValueError("lengths must be integers, got %s" % host.dtype)
+        if host.shape != (N,):
+            raise ValueError("lengths must have shape (%d,), got %s" % (N, tuple(host.shape)))
+        if N and (int(host.min()) < 1 or int(host.max()) > L):
+            raise ValueError("lengths must lie in [1, %d], got [%d, %d]" % (L, int(host.min()), int(host.max())))
+        return torch.as_tensor(host.astype(np.int32), device=X3.device)
+
+    def _scaled(self, X, presliced=False, lengths=None):
+        """The scaled sequences of a public evaluation.  With ``lengths`` the table is cleaned first -- the rows beyond a sequence's length are
+        replaced by its last valid row (a gather of valid rows: nothing, NaN included, flows from or to the padded rows) -- so that the pool the
+        landmarks are gathered from holds real points only, and the lengths are kept for the evaluation's feature maps."""
+        X3 = self._seq3(X, presliced)
+        if lengths is None:
+            return self.scale_sequences(X3)
+        lens = self._ragged_lengths(lengths, X3)
+        N, L = X3.shape[0], X3.shape[1]
+        idx = torch.minimum(torch.arange(L, device=X3.device)[None, :], (lens.long() - 1)[:, None])
+        Xs = self.scale_sequences(X3[torch.arange(N, device=X3.device)[:, None], idx])
+        self._ragged = (self._ragged or ()) + ((Xs, lens),)
+        return Xs
+
+    def _lr_seq(self, Xs):
+        """The low-rank scope's features of scaled sequences, with their lengths where the evaluation gave some."""
+        for held, lens in (self._ragged or ()):
+            if held is Xs:
+                return self._lr.seq(Xs, lens)
+        return self._lr.seq(Xs)
+
     def scale_sequences(self, X):
         """kernels.py:343-364.  (N, L, d) -> (N, L, d * (num_lags + 1))."""
         k = self.kern
@@ -1236,8 +1371,8 @@ class SignatureKernelModule(torch.nn.Module):
 
     def _seq_levels(self, Xs, X2s=None):
         if self._lr is not None:                                                                    # kernels.py:426 / :451
-            P1 = self._lr.seq(Xs)
-            P2 = P1 if X2s is None else self._lr.seq(X2s)
+            P1 = self._lr_seq(Xs)
+            P2 = P1 if X2s is None else self._lr_seq(X2s)
             return torch.stack([a @ b.T for a, b in zip(P1, P2)], dim=0)
         return self._mx_seq_levels(Xs, X2s) if self._mx("seq", (Xs if X2s is None else X2s).shape[1]) else _SeqGramLevels.apply(Xs, X2s, self.p0, self._spec)
 
@@ -1279,7 +1414,7 @@ class SignatureKernelModule(torch.nn.Module):
 
     def _diag_levels(self, Xs):
         if self._lr is not None:                                                                    # kernels.py:457, :501
-            return torch.stack([torch.square(P).sum(dim=-1) for P in self._lr.seq(Xs)], dim=0)
+            return torch.stack([torch.square(P).sum(dim=-1) for P in self._lr_seq(Xs)], dim=0)
         Phi = self._phi(Xs)
         if Phi is not None:                                                                         # K_m(x, x) = |Phi_m(x)|^2
             return _LevelNorms.apply(Phi, Xs.shape[2], self._spec.num_levels)
@@ -1292,7 +1427,7 @@ class SignatureKernelModule(torch.nn.Module):
 
     def _tvs_levels(self, Zs, Xs, increments):
         if self._lr is not None:                                                                    # kernels.py:568
-            return torch.stack([a @ b.T for a, b in zip(self._lr.tens(Zs, increments), self._lr.seq(Xs))], dim=0)
+            return torch.stack([a @ b.T for a, b in zip(self._lr.tens(Zs, increments), self._lr_seq(Xs))], dim=0)
         Phi = self._phi(Xs, self._tvs_work(Zs, Xs))
         if Phi is not None:                                                                         # K_m(z, x) = <z_1 (x) .. (x) z_m, Phi_m(x)>
             lev = _split_levels(Phi, Xs.shape[2], self._spec.num_levels)
@@ -1439,11 +1574,13 @@ class SignatureKernelModule(torch.nn.Module):
 
     # ---- kernel evaluations ----------------------------------------------------------------------------------------
     @_low_rank_scoped
-    def K(self, X, X2=None, presliced=False, return_levels=False, presliced_X=False, presliced_X2=False, lr=None):
-        """kernels.py:401-476.  lr: a LowRankDraw (low-rank mode; drawn per evaluation when None)."""
-        Xs = self.scale_sequences(self._seq3(X, presliced or presliced_X))
+    def K(self, X, X2=None, presliced=False, return_levels=False, presliced_X=False, presliced_X2=False, lr=None, lengths=None, lengths2=None):
+        """kernels.py:401-476.  lr: a LowRankDraw (low-rank mode; drawn per evaluation when None).
+        lengths / lengths2 (low-rank mode): per-sequence lengths of a ragged X / X2 -- ints, a NumPy array or a torch tensor, 1 <= l <= L.
+        Sequence n is X[n, :lengths[n]]; what the rows beyond hold does not matter (NaN included), and their gradient is zero."""
+        Xs = self._scaled(X, presliced or presliced_X, lengths)
         N = Xs.shape[0]
-        X2s = None if X2 is None else self.scale_sequences(self._seq3(X2, presliced or presliced_X2))
+        X2s = None if X2 is None else self._scaled(X2, presliced or presliced_X2, lengths2)
         if (self.sum_route and not return_levels and not self.kern.low_rank and not self.matrix_route and self._d_cols <= 64 and lr is None
                 and self._spec.base in ("linear", "cosine") and Xs.is_cuda and not torch.cuda.is_current_stream_capturing()):
             # the linear / cosine kernel's level sum and its gradient as one op through the feature space (no level arrays)
@@ -1468,13 +1605,15 @@ class SignatureKernelModule(torch.nn.Module):
         return K if return_levels else K.sum(dim=0)
 
     @_low_rank_scoped
-    def Kdiag(self, X, presliced=False, return_levels=False, lr=None):
-        """kernels.py:479-510."""
+    def Kdiag(self, X, presliced=False, return_levels=False, lr=None, lengths=None):
+        """kernels.py:479-510.  lengths: as in K."""
         N = X.shape[0]
         if self.kern.normalization:
+            if lengths is not None:
+                self._ragged_lengths(lengths, self._seq3(X, presliced))                             # (checked all the same)
             Kd = self._w()[:, None].expand(-1, N)                                                   # :486-490
         else:
-            Xs = self.scale_sequences(self._seq3(X, presliced))
+            Xs = self._scaled(X, presliced, lengths)
             self._lr_open(lr, Xs)
             Kd = self._diag_levels(Xs) * self._w()[:, None]
         return Kd if return_levels else Kd.sum(dim=0)
@@ -1488,9 +1627,9 @@ class SignatureKernelModule(torch.nn.Module):
         return K if return_levels else K.sum(dim=0)
 
     @_low_rank_scoped
-    def K_tens_vs_seq(self, Z, X, return_levels=False, increments=False, presliced=False, lr=None):
-        """kernels.py:539-588."""
-        Xs = self.scale_sequences(self._seq3(X, presliced))
+    def K_tens_vs_seq(self, Z, X, return_levels=False, increments=False, presliced=False, lr=None, lengths=None):
+        """kernels.py:539-588.  lengths: as in K."""
+        Xs = self._scaled(X, presliced, lengths)
         Zs0 = self.scale_tensors(Z)
         self._lr_open(lr, Zs0, Xs)
         self._phi(Xs, self._tvs_work(Zs0, Xs))                                                      # (so that the level diagonals share the feature sweep)
@@ -1506,9 +1645,9 @@ class SignatureKernelModule(torch.nn.Module):
         return K * self._w()[:, None, None]
 
     @_low_rank_scoped
-    def K_tens_n_seq_covs(self, Z, X, full_X_cov=False, return_levels=False, increments=False, presliced=False, lr=None):
-        """kernels.py:591-671: Kzz, Kzx and Kxx (full or diagonal) from one scaling of the inputs."""
-        Xs = self.scale_sequences(self._seq3(X, presliced))
+    def K_tens_n_seq_covs(self, Z, X, full_X_cov=False, return_levels=False, increments=False, presliced=False, lr=None, lengths=None):
+        """kernels.py:591-671: Kzz, Kzx and Kxx (full or diagonal) from one scaling of the inputs.  lengths: as in K."""
+        Xs = self._scaled(X, presliced, lengths)
         N = Xs.shape[0]
         Zs = self.scale_tensors(Z)
         self._lr_open(lr, Zs, Xs)
@@ -1555,11 +1694,11 @@ class SignatureKernelModule(torch.nn.Module):
         return Kzz * w[:, None, None], Kzx * w[:, None, None], Kxx
 
     @_low_rank_scoped
-    def K_seq_n_seq_covs(self, X, X2, full_X2_cov=False, return_levels=False, presliced=False, lr=None):
+    def K_seq_n_seq_covs(self, X, X2, full_X2_cov=False, return_levels=False, presliced=False, lr=None, lengths=None, lengths2=None):
         """kernels.py:674-761 (``X`` = inducing sequences, never sliced: :679-680; ``X2`` = data), including the double division
-        of :713 + :750."""
-        Xs = self.scale_sequences(self._seq3(X, True))
-        X2s = self.scale_sequences(self._seq3(X2, presliced))
+        of :713 + :750.  lengths / lengths2: as in K, for X / X2."""
+        Xs = self._scaled(X, True, lengths)
+        X2s = self._scaled(X2, presliced, lengths2)
         self._lr_open(lr, Xs, X2s)
         N, N2 = Xs.shape[0], X2s.shape[0]
         w = self._w()

@@ -50,6 +50,25 @@ struct LrFusedFields {
 struct LrFusedArgs : LrFusedFields<double, LrEntry> {};
 struct LrFusedArgsF32 : LrFusedFields<float, LrEntryF32> {};
 
+// Ragged batches: sequence n has lengths[n] points of the L its rows have room for (N int32 on the device).  The ragged instances of the
+// sequence kernels (lr_ragged_inst.hip) are the same bodies on an argument block that carries the pointer: lr_ragged<Args> marks the block,
+// lr_seq_points gives a sequence's extent -- L for every other block, so that their instances stay the code they were.  Strides, tile
+// lengths and LDS sizes are those of L for both.
+struct LrFusedRaggedArgs : LrFusedArgs { const int32_t* lengths; };
+template <typename Args> struct lr_ragged { static constexpr bool value = false; };
+template <> struct lr_ragged<LrFusedRaggedArgs> { static constexpr bool value = true; };
+// lengths[n] through the scalar unit (n is the same for the whole workgroup), clamped to [1, L]: whatever the memory holds, a sequence's
+// indices stay inside its own L x d block
+__device__ __forceinline__ int lr_ragged_length(const int32_t* lengths, int64_t n, int L) {
+    const int v = __builtin_amdgcn_readfirstlane(lr_as_const(lengths)[n]);
+    return v < 1 ? 1 : (v > L ? L : v);
+}
+template <typename Args>
+__device__ __forceinline__ int lr_seq_points(const Args& A, int64_t n, int L) {
+    if constexpr (lr_ragged<Args>::value) return lr_ragged_length(A.lengths, n, L);
+    else return L;
+}
+
 // two-array form (lr_seq_features_fused2_kernel): usable for L <= 64 and at most 8 output columns per wavefront of the 512-thread workgroup
 inline bool lr_fused2_ok(int c, int r, int L) { return L <= 64 && c <= 64 && r <= 64; }
 inline size_t lr_fused2_lds_bytes(int c, int r, int d_eff, int L, int pad = 1) {
@@ -90,6 +109,8 @@ inline size_t lr_tens_fused_lds_bytes_f32(int c, int r, int d_eff, int lt, int E
 // launches the spectral instances.  Return the hipError_t of the launch.
 int lr_fused_launch(hipStream_t stream, LrFusedArgs A, int pad, bool two_arrays, int variant);
 int lr_fused_launch(hipStream_t stream, LrFusedArgsF32 A, int pad, bool two_arrays, int variant);
+// lr_ragged_inst.hip: the three-array float64 form with per-sequence lengths (one instance: 512 threads, 8 entries per scalar-load batch)
+int lr_ragged_fused_launch(hipStream_t stream, LrFusedRaggedArgs A, int pad);
 // ... and the tensor route's: F derived, one workgroup per tensor
 int lr_tens_fused_launch(hipStream_t stream, LrTensFusedArgs A);
 int lr_tens_fused_launch(hipStream_t stream, LrTensFusedArgsF32 A);

@@ -88,6 +88,7 @@ __device__ __forceinline__ float lr_kappa_f32(int kind, float p0, float p1, int 
 template <int THREADS, int UNROLL, bool SPEC, typename Args>
 __device__ __forceinline__ void lr_seq_features_fused_body(const Args& A) {
     using T = typename Args::value_type;
+    constexpr bool RAGGED = lr_ragged<Args>::value;
     T* const lr_lds = lr_dyn_lds<T>();
     const int lp = A.lp, c = A.c, r = A.r, L = A.L;
     T* const U = lr_lds;                                    // [c][lp]
@@ -101,18 +102,22 @@ __device__ __forceinline__ void lr_seq_features_fused_body(const Args& A) {
     const int nchunk = (L + 63) / 64;
 
     for (int64_t n = blockIdx.x; n < A.N; n += gridDim.x) {
+        // the sequence's own extent (ragged instances: lengths[n] clamped to [1, L], wave-uniform; the arrays' strides stay those of L)
+        const int Ln = lr_seq_points(A, n, L);
+        const int ln = RAGGED ? (A.difference ? Ln - 1 : Ln) : l;
+        const int nch = RAGGED ? (Ln + 63) / 64 : nchunk;
         const T* Xn = A.X + n * int64_t(L) * A.P.d_in;
         T* phi = A.Phi + n * int64_t(A.F);
         // ---- phase 0: scaled observations, bufB[fe][t]
-        for (int q = threadIdx.x; q < L * d_eff; q += THREADS) {
+        for (int q = threadIdx.x; q < Ln * d_eff; q += THREADS) {
             const int t = q / d_eff, fe = q - t * d_eff;
             bufB[fe * lp + t] = scaled_point<T>(Xn, L, t, fe, A.P);
         }
         __syncthreads();
         // ---- phase 1: kxs, bufA[i][t]
-        for (int ch = 0; ch < nchunk; ++ch) {
+        for (int ch = 0; ch < nch; ++ch) {
             const int t = ch * 64 + lane;
-            if (t < L) {
+            if (t < Ln) {
                 T xs = T(0);
                 for (int fe = 0; fe < d_eff; ++fe) { const T x = bufB[fe * lp + t]; xs = fma(x, x, xs); }
                 for (int i = wave; i < c; i += NW) {
@@ -145,9 +150,9 @@ __device__ __forceinline__ void lr_seq_features_fused_body(const Args& A) {
         }
         __syncthreads();
         // ---- phase 2: whitening, bufB[j][t] = sum_i bufA[i][t] * Wh[i][j]
-        for (int ch = 0; ch < nchunk; ++ch) {
+        for (int ch = 0; ch < nch; ++ch) {
             const int t = ch * 64 + lane;
-            if (t < L) {
+            if (t < Ln) {
                 const lr_const_ptr<T> Wh = lr_as_const(A.Wh);
                 for (int j = wave; j < c; j += NW) {
                     T acc = T(0);
@@ -159,9 +164,9 @@ __device__ __forceinline__ void lr_seq_features_fused_body(const Args& A) {
         }
         __syncthreads();
         // time difference (signature_algs.py:180) or a copy
-        for (int ch = 0; ch < nchunk; ++ch) {
+        for (int ch = 0; ch < nch; ++ch) {
             const int t = ch * 64 + lane;
-            if (t < l) {
+            if (t < ln) {
                 for (int j = wave; j < c; j += NW) {
                     const T f0 = bufB[j * lp + t];
                     U[j * lp + t] = A.difference ? bufB[j * lp + t + 1] - f0 : f0;
@@ -177,7 +182,7 @@ __device__ __forceinline__ void lr_seq_features_fused_body(const Args& A) {
             T* e = bufA + size_t(j) * lp;
             const bool more = A.M >= 2;
 #pragma unroll 8
-            for (int t = 0; t < l; ++t) {
+            for (int t = 0; t < ln; ++t) {
                 const T v = u[t];
                 if (more) e[t] = run;
                 run += v;
@@ -193,9 +198,9 @@ __device__ __forceinline__ void lr_seq_features_fused_body(const Args& A) {
             // P_lev[t][j] = sum_e val * U[t][i1] * E[t][i2]                                   low_rank_calculations.py:64-193
             for (int j = wave; j < r; j += NW) {
                 const int e0 = colptr[j], e1 = colptr[j + 1];
-                for (int ch = 0; ch < nchunk; ++ch) {
+                for (int ch = 0; ch < nch; ++ch) {
                     const int t = ch * 64 + lane;
-                    const int tt = t < l ? t : 0;                 // idle lanes read a valid address
+                    const int tt = t < ln ? t : 0;                 // idle lanes read a valid address
                     T acc = T(0);
 #pragma unroll UNROLL
                     for (int e = e0; e < e1; ++e) {
@@ -203,7 +208,7 @@ __device__ __forceinline__ void lr_seq_features_fused_body(const Args& A) {
                         const int i1 = ent[e].i1, i2 = ent[e].i2;
                         acc = fma(val * U[i1 * lp + tt], cur[i2 * lp + tt], acc);
                     }
-                    if (t < l) nxt[j * lp + t] = acc;
+                    if (t < ln) nxt[j * lp + t] = acc;
                 }
             }
             __syncthreads();
@@ -213,7 +218,7 @@ __device__ __forceinline__ void lr_seq_features_fused_body(const Args& A) {
                 T run = T(0);
                 T* e = nxt + size_t(j) * lp;
 #pragma unroll 8
-                for (int t = 0; t < l; ++t) {
+                for (int t = 0; t < ln; ++t) {
                     const T v = e[t];
                     if (more) e[t] = run;                                                       // signature_algs.py:186
                     run += v;
@@ -493,9 +498,12 @@ __device__ __forceinline__ void lr_tens_features_fused_body(const Args& A) {
     }
 }
 
+// (the kernels that are no templates are defined once: lr_ragged_inst.hip takes the bodies alone)
+#ifndef GPSIG_LR_BODIES_ONLY
 __global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_fused_kernel(LrTensFusedArgs A) { lr_tens_features_fused_body<false>(A); }
 __global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_fused_spectral_kernel(LrTensFusedArgs A) { lr_tens_features_fused_body<true>(A); }
 __global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_fused_f32_kernel(LrTensFusedArgsF32 A) { lr_tens_features_fused_body<false>(A); }
 __global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_fused_spectral_f32_kernel(LrTensFusedArgsF32 A) { lr_tens_features_fused_body<true>(A); }
+#endif
 
 }  // namespace gpsig

@@ -10,6 +10,9 @@
 // Where a sequence's arrays exceed the LDS (lr_fused_lds_bytes / lr_grad_lds_bytes, lr_tile_plan.hpp), the same two entry points launch the
 // time-tiled kernels of lr_tiled_kernel.hpp, each direction on its own: shapes that fit keep the whole-sequence kernels.  The tiled reverse
 // pass keeps the E_i of a whole sequence per workgroup in B_GR1; the plan shrinks the grid to hold that within LR_TILE_SCRATCH_BUDGET.
+// Ragged batches: gpsig_lr_seq_features_ragged_dev / _ragged_grad take N per-sequence lengths on the device and share the host paths of the pair
+// above (seq_features_dev / seq_features_grad below, one optional pointer): same checks and plan, which follow from L alone, then the ragged
+// instances of the same four kernels (lr_ragged_inst.hip).
 // and SignatureSpectral's pair, whose parameters (alpha, omega, gamma) are trained and so come as device pointers too:
 //     gpsig_lr_seq_features_spectral_dev    Phi by the spectral fused instances on a table packed on the device (no host round trip)
 //     gpsig_lr_seq_features_spectral_grad   lr_seq_features_grad_spectral_kernel: dPhi -> dWh and dkxs (N, L, c) in scratch; then the
@@ -146,8 +149,9 @@ __global__ __launch_bounds__(256) void lr_spectral_pack_kernel(const double* __r
 // the fused feature kernels (lr_fused_inst.hip) on device-resident landmarks and whitening: the caller scaled the inputs (no lengthscales,
 // no lags); `two` picks the two-array form, else the three-array instance of lr_fused_variant
 int fused_features(gpsig_ctx* c, const gpsig_params* p, int cc, int r, int nsk, const LrGradSketch* gs, const void* X, int64_t N, int L,
-                   const double* S, const double* Wh, const double* spec, bool two, void* Phi, const char* what) {
-    LrFusedArgs A{};
+                   const double* S, const double* Wh, const double* spec, bool two, void* Phi, const char* what, const int32_t* lengths = nullptr) {
+    LrFusedRaggedArgs A{};                       // (with `lengths` the ragged instance of the three-array form, lr_ragged_inst.hip)
+    A.lengths = lengths;
     A.X = static_cast<const double*>(X); A.N = N; A.L = L;
     A.P.d_in = p->num_features;
     A.S = S; A.Wh = Wh;
@@ -156,7 +160,8 @@ int fused_features(gpsig_ctx* c, const gpsig_params* p, int cc, int r, int nsk, 
     A.spec = spec;
     for (int i = 0; i < nsk; ++i) A.sk[i] = LrFusedSketch{gs[i].colptr, gs[i].ent};
     A.Phi = static_cast<double*>(Phi);
-    const int rc = lr_fused_launch(c->stream, A, c->lr_fused_pad, two, c->lr_fused_variant);
+    const int rc = lengths ? lr_ragged_fused_launch(c->stream, A, c->lr_fused_pad)
+                           : lr_fused_launch(c->stream, static_cast<const LrFusedArgs&>(A), c->lr_fused_pad, two, c->lr_fused_variant);
     if (rc != 0) return fail(c, GPSIG_ERR_HIP, "%s: %s", what, hipGetErrorString(hipError_t(rc)));
     return GPSIG_OK;
 }
@@ -252,12 +257,16 @@ int tens_grad_launch(gpsig_ctx* c, const Args& A, unsigned grid) {
     return GPSIG_OK;
 }
 
-}  // namespace
+// the launch result of a ragged reverse instance (lr_ragged_inst.hip), as grad_launch reports its own
+int ragged_rc(gpsig_ctx* c, int rc) {
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "low-rank reverse kernel (ragged): %s", hipGetErrorString(hipError_t(rc)));
+    return GPSIG_OK;
+}
 
-extern "C" {
-
-int gpsig_lr_seq_features_dev(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches, const void* X,
-                              int64_t N, int32_t L, const double* S, const double* Wh, void* Phi) {
+// the host path of gpsig_lr_seq_features_dev and of its ragged twin (`lengths`: NULL, or N per-sequence lengths on the device): checks and plan
+// are those of L either way -- the plan does not depend on the lengths, so the host never reads them
+int seq_features_dev(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches, const void* X,
+                     int64_t N, int32_t L, const int32_t* lengths, const double* S, const double* Wh, void* Phi) {
     CHK(check(c, p, cc, r, nsk));
     if (N < 0 || L < 1 || (N > 0 && (!X || !S || !Wh || !Phi))) return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
     // always the three-array form (the instance of lr_fused_variant): lr_fused does not apply here; beyond the LDS its time-tiled form
@@ -268,19 +277,23 @@ int gpsig_lr_seq_features_dev(gpsig_ctx* c, const gpsig_params* p, int32_t cc, i
     LrGradSketch gs[LR_FUSED_MAX_SKETCHES];
     CHK(upload_sketches(c, cc, r, nsk, sketches, gs));
     if (N == 0) return GPSIG_OK;
-    if (D.untiled) return fused_features(c, p, cc, r, nsk, gs, X, N, L, S, Wh, nullptr, false, Phi, "fused low-rank feature kernel");
-    LrTiledArgs A{};
+    if (D.untiled) return fused_features(c, p, cc, r, nsk, gs, X, N, L, S, Wh, nullptr, false, Phi, "fused low-rank feature kernel", lengths);
+    LrTiledRaggedArgs A{};
     tiled_args(c, p, cc, r, nsk, gs, L, S, Wh, D, false, &A);
     A.X = static_cast<const double*>(X); A.N = N;
     A.Phi = static_cast<double*>(Phi);
-    const int rc = lr_launch(lr_seq_features_tiled_kernel<1024>, unsigned(N < (1 << 20) ? N : (1 << 20)), 1024, D.lds, c->stream, A);
+    A.lengths = lengths;
+    const unsigned grid = unsigned(N < (1 << 20) ? N : (1 << 20));
+    const int rc = lengths ? lr_ragged_tiled_launch(c->stream, A, grid, D.lds)
+                           : lr_launch(lr_seq_features_tiled_kernel<1024>, grid, 1024, D.lds, c->stream, static_cast<const LrTiledArgs&>(A));
     if (rc != 0) return fail(c, GPSIG_ERR_HIP, "tiled low-rank feature kernel: %s", hipGetErrorString(hipError_t(rc)));
     return GPSIG_OK;
 }
 
-int gpsig_lr_seq_features_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches, const void* X,
-                               int64_t N, int32_t L, const double* S, const double* Wh, const void* dPhi, void* gX, double* gS, double* gWh,
-                               double* g_base) {
+// ... and of gpsig_lr_seq_features_grad and its ragged twin
+int seq_features_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches, const void* X,
+                      int64_t N, int32_t L, const int32_t* lengths, const double* S, const double* Wh, const void* dPhi, void* gX, double* gS,
+                      double* gWh, double* g_base) {
     CHK(check(c, p, cc, r, nsk));
     if (N < 0 || L < 1 || !gS || !gWh || (N > 0 && (!X || !S || !Wh || !dPhi || !gX))) return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
     const int M = p->num_levels, d = p->num_features;
@@ -310,22 +323,26 @@ int gpsig_lr_seq_features_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, 
     CHK(ensure(c, B_GR0, sizeof(double) * size_t(grid) * size_t(width) + 64, &part));
     CHK(ensure(c, B_GR1, sizeof(double) * size_t(grid) * size_t(escr_stride) + 64, &escr));
     if (plan.rev.untiled) {
-        LrGradArgs A{};
+        LrGradRaggedArgs A{};
         grad_args(c, p, cc, r, nsk, gs, L, S, Wh, escr, escr_stride, &A);
         A.X = static_cast<const double*>(X); A.N = N;
         A.dPhi = static_cast<const double*>(dPhi);
         A.gX = static_cast<double*>(gX);
         A.part = static_cast<double*>(part);
-        CHK(grad_launch(c, A, grid, lds));
+        A.lengths = lengths;
+        if (lengths) CHK(ragged_rc(c, lr_ragged_grad_launch(c->stream, A, grid, lds)));
+        else CHK(grad_launch(c, static_cast<const LrGradArgs&>(A), grid, lds));
     } else {
-        LrTiledArgs A{};
+        LrTiledRaggedArgs A{};
         tiled_args(c, p, cc, r, nsk, gs, L, S, Wh, plan.rev, true, &A);
         A.escr = static_cast<double*>(escr); A.escr_stride = escr_stride;
         A.X = static_cast<const double*>(X); A.N = N;
         A.dPhi = static_cast<const double*>(dPhi);
         A.gX = static_cast<double*>(gX);
         A.part = static_cast<double*>(part);
-        CHK(grad_launch(c, A, grid, lds));
+        A.lengths = lengths;
+        if (lengths) CHK(ragged_rc(c, lr_ragged_grad_tiled_launch(c->stream, A, grid, lds)));
+        else CHK(grad_launch(c, static_cast<const LrTiledArgs&>(A), grid, lds));
     }
     hipLaunchKernelGGL(lr_grad_reduce_kernel, dim3(unsigned((width + 255) / 256)), dim3(256), 0, c->stream, static_cast<const double*>(part), int(grid), width,
                        gS, int64_t(cc) * d, gWh, int64_t(cc) * cc, g_base);
@@ -333,6 +350,34 @@ int gpsig_lr_seq_features_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, 
     return GPSIG_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int gpsig_lr_seq_features_dev(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches, const void* X,
+                              int64_t N, int32_t L, const double* S, const double* Wh, void* Phi) {
+    return seq_features_dev(c, p, cc, r, nsk, sketches, X, N, L, nullptr, S, Wh, Phi);
+}
+
+int gpsig_lr_seq_features_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches, const void* X,
+                               int64_t N, int32_t L, const double* S, const double* Wh, const void* dPhi, void* gX, double* gS, double* gWh,
+                               double* g_base) {
+    return seq_features_grad(c, p, cc, r, nsk, sketches, X, N, L, nullptr, S, Wh, dPhi, gX, gS, gWh, g_base);
+}
+
+// ... of a ragged batch: sequence n has lengths[n] points (N int32 on the device, 1 <= lengths[n] <= L; the kernels clamp)
+int gpsig_lr_seq_features_ragged_dev(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches,
+                                     const void* X, int64_t N, int32_t L, const int32_t* lengths, const double* S, const double* Wh, void* Phi) {
+    if (c && N > 0 && !lengths) return fail(c, GPSIG_ERR_INVALID, "lengths is NULL");
+    return seq_features_dev(c, p, cc, r, nsk, sketches, X, N, L, lengths, S, Wh, Phi);
+}
+
+int gpsig_lr_seq_features_ragged_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches,
+                                      const void* X, int64_t N, int32_t L, const int32_t* lengths, const double* S, const double* Wh,
+                                      const void* dPhi, void* gX, double* gS, double* gWh, double* g_base) {
+    if (c && N > 0 && !lengths) return fail(c, GPSIG_ERR_INVALID, "lengths is NULL");
+    return seq_features_grad(c, p, cc, r, nsk, sketches, X, N, L, lengths, S, Wh, dPhi, gX, gS, gWh, g_base);
+}
 
 int gpsig_lr_seq_features_spectral_dev(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches,
                                        const void* X, int64_t N, int32_t L, const double* S, const double* Wh, const double* alpha,

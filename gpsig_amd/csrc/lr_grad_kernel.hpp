@@ -63,6 +63,10 @@ struct LrGradSpectralArgs : LrGradArgs {
     double* dkxs; int64_t kxs_off;
 };
 
+// the ragged instance's arguments (lr_fused_args.hpp: lr_ragged): sequence n has lengths[n] of its L points; gX rows beyond them are zeros
+struct LrGradRaggedArgs : LrGradArgs { const int32_t* lengths; };
+template <> struct lr_ragged<LrGradRaggedArgs> { static constexpr bool value = true; };
+
 constexpr int LR_GRAD_THREADS = 512;                   // (the smaller of the two workgroup sizes built: what the per-thread tables are sized for)
 constexpr int LR_GRAD_KW = 8, LR_GRAD_KS = 8;          // (i, j) pairs of dWh and (i, f) pairs of dS per thread: c <= 64, c d <= 4096
 
@@ -213,6 +217,11 @@ __device__ __forceinline__ void lr_grad_base_phase(const Args& A, lr_const_ptr<d
         }
     }
 }
+// the gX rows [Ln, L) of a sequence (gXn: its (L, d) block): plain stores, every row written once
+template <int THREADS>
+__device__ __forceinline__ void lr_zero_padded_rows(double* gXn, int Ln, int L, int d) {
+    for (int q = Ln * d + threadIdx.x; q < L * d; q += THREADS) gXn[q] = 0.0;
+}
 // this workgroup's partial sums [c d + c c + 1]: dS, dWh, d base parameter (`red`: NW doubles of LDS)
 template <int THREADS, typename Args, int KW, int KS>
 __device__ __forceinline__ void lr_grad_write_partials(const Args& A, const double (&accW)[KW], const double (&accS)[KS], double accP,
@@ -245,6 +254,7 @@ __device__ __forceinline__ void lr_grad_write_partials(const Args& A, const doub
 template <int THREADS, bool SPEC, typename Args>
 __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
     constexpr int NW = THREADS / 64, UNROLL = 8;
+    constexpr bool RAGGED = lr_ragged<Args>::value;
     extern __shared__ double lrg_lds[];
     const int lp = A.lp, c = A.c, r = A.r, L = A.L, d = A.d, M = A.M;
     double* const B0 = lrg_lds;                                 // U; later kxs; later per-wave partial sums
@@ -255,29 +265,30 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l = A.difference ? L - 1 : L;                     // time steps of U
     const int nchunk = (L + 63) / 64;
+    int Ln = L, ln = l, nch = nchunk;                           // the current sequence's points, steps and chunks: the ragged instances set them per sequence
     double* const escr = A.escr + int64_t(blockIdx.x) * A.escr_stride;
     const lr_const_ptr<double> Sg = lr_as_const(A.S);
     const lr_const_ptr<double> Whg = lr_as_const(A.Wh);
 
     auto apply = [&](const int32_t* ptr_, const LrEntry* ent_, int nrows, const double* a, const double* b, double* out, bool accumulate) {
-        lr_sketch_apply<NW, UNROLL>(ptr_, ent_, nrows, a, b, out, accumulate, lp, l, nchunk, lane, wave);
+        lr_sketch_apply<NW, UNROLL>(ptr_, ent_, nrows, a, b, out, accumulate, lp, ln, nch, lane, wave);
     };
     // x[f][t] and kxs[i][t] = kappa(x_t, S_i) of the current sequence
-    auto load_x = [&](const double* Xn, double* xb) { lr_load_points<THREADS>(Xn, L, d, lp, xb); };
+    auto load_x = [&](const double* Xn, double* xb) { lr_load_points<THREADS>(Xn, Ln, d, lp, xb); };
     auto cross = [&](const double* xb, double* kb) {
         if constexpr (SPEC) {
             const lr_const_ptr<double> al = lr_as_const(A.alpha), om = lr_as_const(A.omega), ga = lr_as_const(A.gamma);
             const int Q = int(A.p0), family = int(A.p1);
-            for (int ch = 0; ch < nchunk; ++ch) {
+            for (int ch = 0; ch < nch; ++ch) {
                 const int t = ch * 64 + lane;
-                if (t < L)
+                if (t < Ln)
                     for (int i = wave; i < c; i += NW)
                         kb[i * lp + t] = spectral_pair(al, om, ga, d, Q, family, d, [&](int f) { return xb[f * lp + t]; },
                                                        [&](int f) { return Sg[size_t(i) * d + f]; });
             }
             return;
         }
-        lr_cross_base<NW>(A.kind, A.p0, A.p1, Sg, c, d, xb, kb, lp, L, nchunk, lane, wave);
+        lr_cross_base<NW>(A.kind, A.p0, A.p1, Sg, c, d, xb, kb, lp, Ln, nch, lane, wave);
     };
 
     double accW[LR_GRAD_KW], accS[LR_GRAD_KS], accP = 0.0;      // this workgroup's sums over its sequences: dWh, dS, d base parameter
@@ -289,6 +300,12 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
     for (int64_t n = blockIdx.x; n < A.N; n += gridDim.x) {
         const double* Xn = A.X + n * int64_t(L) * d;
         const double* g = A.dPhi + n * int64_t(A.F);
+        if constexpr (RAGGED) {                                 // the sequence's own extent; the gX rows of its padded points are zeros
+            Ln = lr_seq_points(A, n, L);
+            ln = A.difference ? Ln - 1 : Ln;
+            nch = (Ln + 63) / 64;
+            lr_zero_padded_rows<THREADS>(A.gX + n * int64_t(L) * d, Ln, L, d);
+        }
         __syncthreads();
         // ---- forward again: x -> B1, kxs -> BX, feat -> BY, U -> B0
         load_x(Xn, B1);
@@ -296,13 +313,13 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
         cross(B1, BX);
         __syncthreads();
         if constexpr (SPEC)                                     // kxs for the dWh sums below (the spectral kappa is the costly phase)
-            for (int q = threadIdx.x; q < c * L; q += THREADS) {
-                const int i = q / L, t = q - i * L;
+            for (int q = threadIdx.x; q < c * Ln; q += THREADS) {
+                const int i = q / Ln, t = q - i * Ln;
                 escr[A.kxs_off + q] = BX[i * lp + t];
             }
-        for (int ch = 0; ch < nchunk; ++ch) {
+        for (int ch = 0; ch < nch; ++ch) {
             const int t = ch * 64 + lane;
-            if (t < L) {
+            if (t < Ln) {
                 for (int j = wave; j < c; j += NW) {
                     double acc = 0.0;
 #pragma unroll 4
@@ -312,9 +329,9 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
             }
         }
         __syncthreads();
-        for (int ch = 0; ch < nchunk; ++ch) {
+        for (int ch = 0; ch < nch; ++ch) {
             const int t = ch * 64 + lane;
-            if (t < l) {
+            if (t < ln) {
                 for (int j = wave; j < c; j += NW) {
                     const double f0 = BY[j * lp + t];
                     B0[j * lp + t] = A.difference ? BY[j * lp + t + 1] - f0 : f0;
@@ -330,22 +347,22 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
                 double run = 0.0;
                 const double* u = B0 + size_t(j) * lp;
                 double* e = cur + size_t(j) * lp;
-                double* es = escr + size_t(j) * l;
-                for (int t = 0; t < l; ++t) { const double v = u[t]; e[t] = run; es[t] = run; run += v; }
+                double* es = escr + size_t(j) * ln;
+                for (int t = 0; t < ln; ++t) { const double v = u[t]; e[t] = run; es[t] = run; run += v; }
             }
             __syncthreads();
-            int64_t eo = int64_t(c) * l;
+            int64_t eo = int64_t(c) * ln;
             for (int lev = 2; lev < M; ++lev) {
                 apply(A.sk[lev - 2].colptr, A.sk[lev - 2].ent, r, B0, cur, nxt, false);
                 __syncthreads();
                 for (int j = threadIdx.x; j < r; j += THREADS) {
                     double run = 0.0;
                     double* e = nxt + size_t(j) * lp;
-                    double* es = escr + eo + size_t(j) * l;
-                    for (int t = 0; t < l; ++t) { const double v = e[t]; e[t] = run; es[t] = run; run += v; }
+                    double* es = escr + eo + size_t(j) * ln;
+                    for (int t = 0; t < ln; ++t) { const double v = e[t]; e[t] = run; es[t] = run; run += v; }
                 }
                 __syncthreads();
-                eo += int64_t(r) * l;
+                eo += int64_t(r) * ln;
                 double* tmp = cur; cur = nxt; nxt = tmp;
             }
         }
@@ -355,9 +372,9 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
         double* Xb = cur;                           // E of that level, then dE
         if (M >= 2) {
             const double* gM = g + 1 + c + (M - 2) * r;
-            for (int ch = 0; ch < nchunk; ++ch) {
+            for (int ch = 0; ch < nch; ++ch) {
                 const int t = ch * 64 + lane;
-                if (t < l)
+                if (t < ln)
                     for (int j = wave; j < r; j += NW) Y[j * lp + t] = gM[j];
             }
         }
@@ -366,10 +383,10 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
             const int w = lev == 2 ? c : r;         // width of E_lev
             // E_lev from the scratch (the forward pass left E_{M} in `cur` already)
             int64_t eo = 0;
-            for (int k = 2; k < lev; ++k) eo += int64_t(k == 2 ? c : r) * l;
+            for (int k = 2; k < lev; ++k) eo += int64_t(k == 2 ? c : r) * ln;
             if (lev != M || true) {
-                for (int q = threadIdx.x; q < w * l; q += THREADS) {
-                    const int j = q / l, t = q - j * l;
+                for (int q = threadIdx.x; q < w * ln; q += THREADS) {
+                    const int j = q / ln, t = q - j * ln;
                     Xb[j * lp + t] = escr[eo + q];
                 }
             }
@@ -384,30 +401,30 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
             for (int j = threadIdx.x; j < w; j += THREADS) {
                 double run = gl[j];
                 double* e = Xb + size_t(j) * lp;
-                for (int t = l - 1; t >= 0; --t) { const double v = e[t]; e[t] = run; run += v; }
+                for (int t = ln - 1; t >= 0; --t) { const double v = e[t]; e[t] = run; run += v; }
             }
             __syncthreads();
             double* tmp = Xb; Xb = Y; Y = tmp;      // Y: dP_{lev-1}
         }
         // level 1: Phi_1 = sum_t U (M == 1: that is all there is)
-        for (int ch = 0; ch < nchunk; ++ch) {
+        for (int ch = 0; ch < nch; ++ch) {
             const int t = ch * 64 + lane;
-            if (t < l)
+            if (t < ln)
                 for (int j = wave; j < c; j += NW) B1[j * lp + t] += M >= 2 ? Y[j * lp + t] : g[1 + j];
         }
         __syncthreads();
         // dfeat[j][t] -> Xb: the adjoint of the time difference (signature_algs.py:180)
-        for (int ch = 0; ch < nchunk; ++ch) {
+        for (int ch = 0; ch < nch; ++ch) {
             const int t = ch * 64 + lane;
-            if (t < L)
+            if (t < Ln)
                 for (int j = wave; j < c; j += NW)
-                    Xb[j * lp + t] = A.difference ? (t >= 1 ? B1[j * lp + t - 1] : 0.0) - (t < l ? B1[j * lp + t] : 0.0) : B1[j * lp + t];
+                    Xb[j * lp + t] = A.difference ? (t >= 1 ? B1[j * lp + t - 1] : 0.0) - (t < ln ? B1[j * lp + t] : 0.0) : B1[j * lp + t];
         }
         __syncthreads();
         // x -> B1 and kxs -> B0 once more (U and dU are done with); the spectral instance reads kxs back from its scratch
         if constexpr (SPEC) {
-            for (int q = threadIdx.x; q < c * L; q += THREADS) {
-                const int i = q / L, t = q - i * L;
+            for (int q = threadIdx.x; q < c * Ln; q += THREADS) {
+                const int i = q / Ln, t = q - i * Ln;
                 B0[i * lp + t] = escr[A.kxs_off + q];
             }
         } else {
@@ -416,17 +433,17 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
             cross(B1, B0);
         }
         __syncthreads();
-        lr_grad_whiten_adjoint<THREADS>(c, lp, 0, L, B0, Xb, Whg, Y, accW, lane, wave);
+        lr_grad_whiten_adjoint<THREADS>(c, lp, 0, Ln, B0, Xb, Whg, Y, accW, lane, wave);
         __syncthreads();
         if constexpr (SPEC) {                        // dkxs (L, c) of this sequence out; the spectral cross op's reverse kernels take it from here
             double* dk = A.dkxs + n * int64_t(L) * c;
-            for (int q = threadIdx.x; q < L * c; q += THREADS) {
+            for (int q = threadIdx.x; q < Ln * c; q += THREADS) {
                 const int t = q / c, i = q - t * c;
                 dk[q] = Y[i * lp + t];
             }
             continue;                                // (the loop's first barrier orders these reads before Y is written again)
         }
-        lr_grad_base_phase<THREADS>(A, Sg, n, 0, 0, L, B0, B1, Xb, Y, accS, accP, lane, wave);
+        lr_grad_base_phase<THREADS>(A, Sg, n, 0, 0, Ln, B0, B1, Xb, Y, accS, accP, lane, wave);
     }
     // ---- this workgroup's partial sums
     if constexpr (SPEC) {
@@ -448,7 +465,8 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_grad_kernel(LrGradArg
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void lr_seq_features_grad_spectral_kernel(LrGradSpectralArgs A) { lr_seq_features_grad_body<THREADS, true>(A); }
 
-// out[q] = sum over the workgroups' partials, in order
+// out[q] = sum over the workgroups' partials, in order  (no template: defined once, lr_ragged_inst.hip takes the bodies alone)
+#ifndef GPSIG_LR_BODIES_ONLY
 __global__ void lr_grad_reduce_kernel(const double* __restrict__ part, int nparts, int64_t width, double* __restrict__ gS, int64_t nS,
                                       double* __restrict__ gWh, int64_t nW, double* __restrict__ gp) {
     const int64_t q = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -459,5 +477,6 @@ __global__ void lr_grad_reduce_kernel(const double* __restrict__ part, int npart
     else if (q < nS + nW) gWh[q - nS] = s;
     else if (gp) gp[0] = s;
 }
+#endif
 
 }  // namespace gpsig

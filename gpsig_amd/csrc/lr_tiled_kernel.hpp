@@ -28,6 +28,10 @@ struct LrTiledArgs : LrGradArgs {
     double* Phi;            // forward: (N, F)
     int TL, ntiles;
 };
+// the ragged instances' (lr_fused_args.hpp: lr_ragged): sequence n has lengths[n] of its L points -- its own number of tiles, the last one
+// short as any last tile; TL, lp and the LDS size are those of L; the reverse pass stores zeros in the gX rows beyond its points
+struct LrTiledRaggedArgs : LrTiledArgs { const int32_t* lengths; };
+template <> struct lr_ragged<LrTiledRaggedArgs> { static constexpr bool value = true; };
 
 // a tile's x -> xb, kxs -> kx, feat -> ft (may be xb), U -> u: `np` points at Xt, `tl` steps.  Ends with a barrier.
 template <int THREADS>
@@ -86,179 +90,23 @@ __device__ __forceinline__ void lr_tile_excumsum(const double* src, double* dst,
     }
 }
 
+// (the bodies of the two kernels are texts of their own, lr_tiled_fwd_body.inc and lr_tiled_rev_body.inc: lr_ragged_inst.hip includes them
+// again between the braces of its instances, whose argument block carries the per-sequence lengths)
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void lr_seq_features_tiled_kernel(LrTiledArgs A) {
-    constexpr int NW = THREADS / 64, UNROLL = 8;
-    extern __shared__ double lrt_lds[];
-    const int lp = A.lp, c = A.c, r = A.r, L = A.L, d = A.d, M = A.M, rows = A.rows_b, TL = A.TL;
-    double* const U = lrt_lds;                                  // [c][lp]
-    double* const bufA = U + size_t(c) * lp;                    // [rows][lp]
-    double* const bufB = bufA + size_t(rows) * lp;              // [rows][lp]
-    double* const cf = bufB + size_t(rows) * lp;                // [LR_TILE_LEVELS][rows]: level i at (i - 1) rows
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int halo = A.difference ? 1 : 0;
-    const int l = L - halo;
-
-    for (int64_t n = blockIdx.x; n < A.N; n += gridDim.x) {
-        const double* Xn = A.X + n * int64_t(L) * d;
-        double* phi = A.Phi + n * int64_t(A.F);
-        __syncthreads();                                         // (the previous sequence's features were read from the carries)
-        for (int q = threadIdx.x; q < M * rows; q += THREADS) cf[q] = 0.0;
-        for (int k = 0; k < A.ntiles; ++k) {
-            const int t0 = lr_tile_first(k, TL), tl = lr_tile_steps(l, k, TL), np = tl + halo;
-            const int nchunk = (tl + 63) / 64;
-            lr_tile_u<THREADS>(A, Xn + int64_t(t0) * d, tl, np, bufB, bufA, bufB, U, lane, wave);
-            lr_tile_excumsum<THREADS>(U, bufA, c, lp, tl, cf, M >= 2, nullptr, 0);                    // level 1; E_2 of the tile
-            __syncthreads();
-            double* cur = bufA;
-            double* nxt = bufB;
-            for (int lev = 2; lev <= M; ++lev) {
-                lr_sketch_apply<NW, UNROLL>(A.sk[lev - 2].colptr, A.sk[lev - 2].ent, r, U, cur, nxt, false, lp, tl, nchunk, lane, wave);
-                __syncthreads();
-                lr_tile_excumsum<THREADS>(nxt, nxt, r, lp, tl, cf + size_t(lev - 1) * rows, lev < M, nullptr, 0);
-                __syncthreads();
-                double* tmp = cur; cur = nxt; nxt = tmp;
-            }
-        }
-        if (threadIdx.x == 0) phi[0] = 1.0;
-        for (int j = threadIdx.x; j < c; j += THREADS) phi[1 + j] = cf[j];
-        for (int lev = 2; lev <= M; ++lev)
-            for (int j = threadIdx.x; j < r; j += THREADS) phi[1 + c + (lev - 2) * r + j] = cf[size_t(lev - 1) * rows + j];
-    }
+#include "lr_tiled_fwd_body.inc"
 }
 
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void lr_seq_features_grad_tiled_kernel(LrTiledArgs A) {
-    constexpr int NW = THREADS / 64, UNROLL = 8;
-    extern __shared__ double lrt_lds[];
-    const int lp = A.lp, c = A.c, r = A.r, L = A.L, d = A.d, M = A.M, rows = A.rows_b, TL = A.TL;
-    double* const B0 = lrt_lds;                                 // U; later kxs; later per-wave partial sums
-    double* const B1 = B0 + size_t(rows) * lp;                  // x; dU; x again
-    double* const BX = B1 + size_t(rows) * lp;
-    double* const BY = BX + size_t(rows) * lp;
-    double* const cf = BY + size_t(rows) * lp;                  // [LR_TILE_LEVELS][rows]: forward carries, level i at (i - 1) rows
-    double* const cb = cf + size_t(LR_TILE_LEVELS) * rows;      // [LR_TILE_LEVELS][rows]: reverse carries of dE_i at (i - 1) rows
-    double* const dun = cb + size_t(LR_TILE_LEVELS) * rows;     // [rows]: the later tile's first dU
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int halo = A.difference ? 1 : 0;
-    const int l = L - halo;
-    double* const escr = A.escr + int64_t(blockIdx.x) * A.escr_stride;
-    const lr_const_ptr<double> Sg = lr_as_const(A.S);
-    const lr_const_ptr<double> Whg = lr_as_const(A.Wh);
-
-    // this workgroup's sums over its tiles and sequences: the pairs per thread that c <= 64, c d <= 4096 need at this workgroup size
-    constexpr int KW = LR_GRAD_KW * LR_GRAD_THREADS / THREADS, KS = LR_GRAD_KS * LR_GRAD_THREADS / THREADS;
-    double accW[KW], accS[KS], accP = 0.0;
-#pragma unroll
-    for (int k = 0; k < KW; ++k) accW[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < KS; ++k) accS[k] = 0.0;
-
-    for (int64_t n = blockIdx.x; n < A.N; n += gridDim.x) {
-        const double* Xn = A.X + n * int64_t(L) * d;
-        const double* g = A.dPhi + n * int64_t(A.F);
-        __syncthreads();
-        // ---- the carries of this sequence: cf = 0;  cb_i = g_{i-1} (what the suffix sum of the last tile starts from);  dun = 0
-        for (int q = threadIdx.x; q < LR_TILE_LEVELS * rows; q += THREADS) cf[q] = 0.0;
-        for (int lev = 2; lev <= M; ++lev) {
-            const double* gl = lev == 2 ? g + 1 : g + 1 + c + (lev - 3) * r;
-            for (int j = threadIdx.x; j < (lev == 2 ? c : r); j += THREADS) cb[size_t(lev - 1) * rows + j] = gl[j];
-        }
-        for (int j = threadIdx.x; j < rows; j += THREADS) dun[j] = 0.0;
-        // ---- pass A: E_2 = excumsum_t(U), E_{i+1} = excumsum_t(sketch_i(U, E_i)) of the whole sequence -> scratch, [column][l] per level
-        for (int k = 0; M >= 2 && k < A.ntiles; ++k) {
-            const int t0 = lr_tile_first(k, TL), tl = lr_tile_steps(l, k, TL), np = tl + halo;
-            const int nchunk = (tl + 63) / 64;
-            lr_tile_u<THREADS>(A, Xn + int64_t(t0) * d, tl, np, B1, BX, BY, B0, lane, wave);
-            lr_tile_excumsum<THREADS>(B0, BX, c, lp, tl, cf, true, escr + t0, l);
-            __syncthreads();
-            int64_t eo = int64_t(c) * l;
-            double* cur = BX;
-            double* nxt = BY;
-            for (int lev = 2; lev < M; ++lev) {
-                lr_sketch_apply<NW, UNROLL>(A.sk[lev - 2].colptr, A.sk[lev - 2].ent, r, B0, cur, nxt, false, lp, tl, nchunk, lane, wave);
-                __syncthreads();
-                lr_tile_excumsum<THREADS>(nxt, nxt, r, lp, tl, cf + size_t(lev - 1) * rows, true, escr + eo + t0, l);
-                __syncthreads();
-                eo += int64_t(r) * l;
-                double* tmp = cur; cur = nxt; nxt = tmp;
-            }
-        }
-        // ---- pass B: tiles in decreasing time
-        for (int k = A.ntiles - 1; k >= 0; --k) {
-            const int t0 = lr_tile_first(k, TL), tl = lr_tile_steps(l, k, TL), np = tl + halo;
-            const int nchunk = (tl + 63) / 64, pchunk = (np + 63) / 64;
-            const int q0 = halo && k > 0 ? 1 : 0;               // the tile's first point belongs to the tile before it
-            __syncthreads();                                     // (the previous tile's dS sums read B1, BX and BY)
-            lr_tile_u<THREADS>(A, Xn + int64_t(t0) * d, tl, np, B1, BX, BY, B0, lane, wave);
-            for (int q = threadIdx.x; q < c * lp; q += THREADS) B1[q] = 0.0;                          // dU
-            double* Y = BY;                                     // dP of the level being processed
-            double* Xb = BX;                                    // E of that level, then dE
-            if (M >= 2) {
-                const double* gM = g + 1 + c + (M - 2) * r;
-                for (int ch = 0; ch < nchunk; ++ch) {
-                    const int t = ch * 64 + lane;
-                    if (t < tl)
-                        for (int j = wave; j < r; j += NW) Y[j * lp + t] = gM[j];
-                }
-            }
-            __syncthreads();
-            for (int lev = M; lev >= 2; --lev) {
-                const int w = lev == 2 ? c : r;                 // width of E_lev
-                int64_t eo = 0;
-                for (int i = 2; i < lev; ++i) eo += int64_t(i == 2 ? c : r) * l;
-                for (int q = threadIdx.x; q < w * tl; q += THREADS) {
-                    const int j = q / tl, t = q - j * tl;
-                    Xb[j * lp + t] = escr[eo + int64_t(j) * l + t0 + t];
-                }
-                __syncthreads();
-                const LrGradSketch sk = A.sk[lev - 2];
-                lr_sketch_apply<NW, UNROLL>(sk.ptr1, sk.ent1, c, Xb, Y, B1, true, lp, tl, nchunk, lane, wave);     // dU[i1] += val E[i2] dP[j]
-                __syncthreads();
-                lr_sketch_apply<NW, UNROLL>(sk.ptr2, sk.ent2, w, B0, Y, Xb, false, lp, tl, nchunk, lane, wave);    // dE[i2]  = val U[i1] dP[j]
-                __syncthreads();
-                // dP_{lev-1}[t] = g_{lev-1} + sum_{t' > t} dE[t'], in place: the later tiles' share comes in, this tile's goes out through cb
-                double* const cbl = cb + size_t(lev - 1) * rows;
-                for (int j = threadIdx.x; j < w; j += THREADS) {
-                    double run = cbl[j];
-                    double* e = Xb + size_t(j) * lp;
-                    for (int t = tl - 1; t >= 0; --t) { const double v = e[t]; e[t] = run; run += v; }
-                    cbl[j] = run;
-                }
-                __syncthreads();
-                double* tmp = Xb; Xb = Y; Y = tmp;              // Y: dP_{lev-1}
-            }
-            // level 1: Phi_1 = sum_t U (M == 1: that is all there is)
-            for (int ch = 0; ch < nchunk; ++ch) {
-                const int t = ch * 64 + lane;
-                if (t < tl)
-                    for (int j = wave; j < c; j += NW) B1[j * lp + t] += M >= 2 ? Y[j * lp + t] : g[1 + j];
-            }
-            __syncthreads();
-            // dfeat[j][q] -> Xb for the tile's own points q0 <= q < np: the adjoint of the time difference; dU beyond the tile from dun
-            for (int ch = 0; ch < pchunk; ++ch) {
-                const int t = ch * 64 + lane;
-                if (t >= q0 && t < np)
-                    for (int j = wave; j < c; j += NW)
-                        Xb[j * lp + t] = halo ? (t >= 1 ? B1[j * lp + t - 1] : 0.0) - (t < tl ? B1[j * lp + t] : dun[j]) : B1[j * lp + t];
-            }
-            __syncthreads();
-            if (tl > 0)
-                for (int j = threadIdx.x; j < c; j += THREADS) dun[j] = B1[j * lp];
-            __syncthreads();
-            // x -> B1 and kxs -> B0 once more (U and dU are done with)
-            lr_load_points<THREADS>(Xn + int64_t(t0) * d, np, d, lp, B1);
-            __syncthreads();
-            lr_cross_base<NW>(A.kind, A.p0, A.p1, Sg, c, d, B1, B0, lp, np, pchunk, lane, wave);
-            __syncthreads();
-            lr_grad_whiten_adjoint<THREADS>(c, lp, q0, np, B0, Xb, Whg, Y, accW, lane, wave);
-            __syncthreads();
-            lr_grad_base_phase<THREADS>(A, Sg, n, t0, q0, np, B0, B1, Xb, Y, accS, accP, lane, wave);
-        }
-    }
-    lr_grad_write_partials<THREADS>(A, accW, accS, accP, lrt_lds, lane, wave);
+#include "lr_tiled_rev_body.inc"
 }
+
+// ---- lr_ragged_inst.hip: the ragged instances of the three reverse / tiled kernels and their launchers (declared here, once, for lr_grad_api.hip;
+// the whole-sequence forward form's: lr_fused_args.hpp).  The whole-sequence reverse pass at 512 threads (at 1024 the ragged instance would keep
+// scratch memory); the tiled forms at the workgroup sizes of the existing instances (forward 1024, reverse 512).  Return the hipError_t of the launch.
+int lr_ragged_grad_launch(hipStream_t stream, const LrGradRaggedArgs& A, unsigned grid, size_t lds);
+int lr_ragged_tiled_launch(hipStream_t stream, const LrTiledRaggedArgs& A, unsigned grid, size_t lds);
+int lr_ragged_grad_tiled_launch(hipStream_t stream, const LrTiledRaggedArgs& A, unsigned grid, size_t lds);
 
 }  // namespace gpsig

@@ -117,23 +117,26 @@ def Kuf(feat, kern, X_new):
     raise NotImplementedError("Kuf for %s" % type(feat).__name__)
 
 
-def Kuu_Kuf_Kff(feat, kern, X_new, *, jitter=0.0, full_f_cov=False):
+def Kuu_Kuf_Kff(feat, kern, X_new, *, jitter=0.0, full_f_cov=False, lengths=None):
     """Reference: inducing_variables.py:51-66 (tensors), :122-137 (sequences): the three matrices SVGP needs in
-    one call.  (``tf.shape(X)`` at :63/:134 is an undefined name in the reference; X_new is what is meant.)"""
+    one call.  (``tf.shape(X)`` at :63/:134 is an undefined name in the reference; X_new is what is meant.)
+    lengths: per-sequence lengths of a ragged X_new (autodiff.SignatureKernelModule in low-rank mode)."""
     assert _is_kernel(kern)
+    rag_t = {} if lengths is None else {"lengths": lengths}
+    rag_s = {} if lengths is None else {"lengths2": lengths}
     if isinstance(feat, InducingTensors):
         if feat.learn_weights:
             Kzz, Kzx, Kxx = kern.K_tens_n_seq_covs(feat.Z, X_new, full_X_cov=full_f_cov, return_levels=True,
-                                                   increments=feat.increments)
+                                                   increments=feat.increments, **rag_t)
             Kzz, Kzx, Kxx = _mix_square(feat.W, Kzz), _mix_left(feat.W, Kzx), Kxx.sum(0)
         else:
-            Kzz, Kzx, Kxx = kern.K_tens_n_seq_covs(feat.Z, X_new, full_X_cov=full_f_cov, increments=feat.increments)
+            Kzz, Kzx, Kxx = kern.K_tens_n_seq_covs(feat.Z, X_new, full_X_cov=full_f_cov, increments=feat.increments, **rag_t)
     elif isinstance(feat, InducingSequences):
         if feat.learn_weights:
-            Kzz, Kzx, Kxx = kern.K_seq_n_seq_covs(feat.Z, X_new, full_X2_cov=full_f_cov, return_levels=True)
+            Kzz, Kzx, Kxx = kern.K_seq_n_seq_covs(feat.Z, X_new, full_X2_cov=full_f_cov, return_levels=True, **rag_s)
             Kzz, Kzx, Kxx = _mix_square(feat.W, Kzz), _mix_left(feat.W, Kzx), Kxx.sum(0)
         else:
-            Kzz, Kzx, Kxx = kern.K_seq_n_seq_covs(feat.Z, X_new, full_X2_cov=full_f_cov)
+            Kzz, Kzx, Kxx = kern.K_seq_n_seq_covs(feat.Z, X_new, full_X2_cov=full_f_cov, **rag_s)
     else:
         raise NotImplementedError("Kuu_Kuf_Kff for %s" % type(feat).__name__)
     Kzz = Kzz + jitter * _eye_like(len(feat), Kzz)

@@ -193,28 +193,29 @@ class SVGPModule(torch.nn.Module if torch is not None else object):
     def _q_sqrt(self):
         return self.q_sqrt if self.q_diag else torch.tril(self.q_sqrt)                               # models.py:48/:66
 
-    def predict_f(self, X_new, full_cov=False, return_Kzz=False):
-        """models.py:62-73."""
-        Kzz, Kzx, Kxx = iv.Kuu_Kuf_Kff(self.feature(), self.kernel, X_new, jitter=JITTER, full_f_cov=full_cov)   # :65
+    def predict_f(self, X_new, full_cov=False, return_Kzz=False, lengths=None):
+        """models.py:62-73.  lengths: per-sequence lengths of a ragged X_new (low-rank mode: SignatureKernelModule.K)."""
+        Kzz, Kzx, Kxx = iv.Kuu_Kuf_Kff(self.feature(), self.kernel, X_new, jitter=JITTER, full_f_cov=full_cov, lengths=lengths)   # :65
         f_mean, f_var = base_conditional(Kzx, Kzz, Kxx, self.q_mu, full_cov=full_cov, q_sqrt=self._q_sqrt(), white=self.whiten)
         if self.mean_function is not None:
             f_mean = f_mean + self.mean_function(X_new)
         return (f_mean, f_var, Kzz) if return_Kzz else (f_mean, f_var)
 
-    def elbo(self, X, Y):
-        """models.py:40-59: sum of variational expectations, scaled to the full data set, minus the prior KL."""
+    def elbo(self, X, Y, lengths=None):
+        """models.py:40-59: sum of variational expectations, scaled to the full data set, minus the prior KL.  lengths: as in predict_f
+        (fit() takes none: a caller with ragged data writes their own loop)."""
         if self.whiten:
-            f_mean, f_var = self.predict_f(X)
+            f_mean, f_var = self.predict_f(X, lengths=lengths)
             KL = gauss_kl(self.q_mu, self._q_sqrt())                                                 # :47-48
         else:
-            f_mean, f_var, Kzz = self.predict_f(X, return_Kzz=True)
+            f_mean, f_var, Kzz = self.predict_f(X, return_Kzz=True, lengths=lengths)
             KL = gauss_kl(self.q_mu, self._q_sqrt(), K=Kzz)                                          # :50-51
         var_exp = self.likelihood.variational_expectations(f_mean, f_var, Y)                         # :54
         scale = float(self.num_data or X.shape[0]) / float(X.shape[0])                               # :57
         return var_exp.sum() * scale - KL
 
-    def predict_y(self, X_new):
-        f_mean, f_var = self.predict_f(X_new)
+    def predict_y(self, X_new, lengths=None):
+        f_mean, f_var = self.predict_f(X_new, lengths=lengths)
         return self.likelihood.predict_mean_and_var(f_mean, f_var)
 
     def fit(self, X, Y, iterations=100, lr=1e-2, minibatch_size=None, seed=0, callback=None, graph=False):

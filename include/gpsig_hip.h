@@ -365,6 +365,21 @@ int gpsig_lr_seq_features_dev(gpsig_ctx* ctx, const gpsig_params* p, int32_t num
 int gpsig_lr_seq_features_grad(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
                                const gpsig_sketch* sketches, const void* X, int64_t N, int32_t L, const double* S, const double* Wh,
                                const void* dPhi, void* gX, double* gS, double* gWh, double* g_base);
+/* The same pair for a RAGGED batch: sequence n has lengths[n] points, 1 <= lengths[n] <= L, in rows of room for L (`lengths`: N int32 on
+ * the DEVICE, directly after L).  Phi[n] is exactly the features of X[n, :lengths[n]] evaluated alone (with p->difference and lengths[n] = 1:
+ * no steps, Phi[n] = [1, 0, .., 0]); the rows X[n, lengths[n]:] are never read and may hold anything, NaN included; _grad writes every gX row
+ * exactly once, the padded points' rows as exact zeros, and stays deterministic.  Same checks, limits, typed refusals and plan as the pair above:
+ * whole-sequence or time-tiled form, tile length, LDS and scratch sizes follow from L alone (the host never reads the lengths); the kernels
+ * take each sequence's extent, tile count and scratch rows from its length, clamped to [1, L] on the device.  lengths == NULL with N > 0 is
+ * GPSIG_ERR_INVALID.  Float64, the families of the pair above (GPSIG_BASE_SPECTRAL: GPSIG_ERR_UNSUPPORTED).  They follow the option
+ * lr_fused_pad; the whole-sequence forms are built once each, at 512 threads, whatever lr_fused_variant and lr_grad_threads say (at 1024
+ * threads the ragged reverse instance would keep scratch memory). */
+int gpsig_lr_seq_features_ragged_dev(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
+                                     const gpsig_sketch* sketches, const void* X, int64_t N, int32_t L, const int32_t* lengths, const double* S,
+                                     const double* Wh, void* Phi);
+int gpsig_lr_seq_features_ragged_grad(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
+                                      const gpsig_sketch* sketches, const void* X, int64_t N, int32_t L, const int32_t* lengths, const double* S,
+                                      const double* Wh, const void* dPhi, void* gX, double* gS, double* gWh, double* g_base);
 /* The same pair for SignatureSpectral, whose parameters are trained: p->base_kernel = GPSIG_BASE_SPECTRAL, p->base_params = {Q, family};
  * alpha (Q), omega (Q, d), gamma (Q, d) are DEVICE pointers read on the device (p->base_table is ignored; no host round trip per step).
  * _grad: dPhi (N, F) -> gX (N, L, d), gS (c, d), gWh (c, c), dalpha (Q), domega (Q, d), dgamma (Q, d), all overwritten; deterministic
