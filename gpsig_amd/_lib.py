@@ -82,6 +82,9 @@ _KERNEL_FUNCS = {
     "gpsig_lr_seq_features_spectral_dev": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "gpsig_lr_seq_features_spectral_grad": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp],
+    "gpsig_lr_seq_features_spectral_ragged_dev": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gpsig_lr_seq_features_spectral_ragged_grad": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp, _vp, _vp, _vp],
     "gpsig_lr_tens_features_dev": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp],
     "gpsig_lr_tens_features_grad": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)],
     "gpsig_lr_tens_features_spectral_dev": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -901,6 +901,52 @@ class _LrSeqFeaturesSpectral(torch.autograd.Function):
         return tuple(t.to(dt) for t, dt in zip(grads, ctx.dt)) + (None, None, None, None)
 
 
+class _LrSeqFeaturesSpectralRagged(torch.autograd.Function):
+    """_LrSeqFeaturesSpectral for long and ragged batches: ``lengths`` (N,) int32 on the sequences' device, 1 <= lengths[n] <= L, or None (every
+    sequence has L points).  By gpsig_lr_seq_features_spectral_ragged_dev / _ragged_grad (csrc/lr_spectral_tiled_inst.hip: the lengths-aware
+    spectral instances of the whole-sequence and the time-tiled kernels, then the lengths-aware reverse kernels of the spectral cross op):
+    Phi[n] is the features of Xs[n, :lengths[n]] evaluated alone, the rows beyond a sequence's length are never read (they may hold NaN) and
+    their gradient rows are exact zeros.  Gradients of all six tensors.  Raises NotImplementedError outside the library's limits (the caller
+    falls back to torch ops)."""
+
+    @staticmethod
+    def forward(ctx, Xs, lengths, S, Wh, alpha, omega, gamma, spec, family, sketches, r):
+        X, Sd, Whd, a, o, g = (_c(t) for t in (Xs, S, Wh, alpha, omega, gamma))
+        n, l, d = X.shape
+        if lengths is not None and (lengths.dtype != torch.int32 or lengths.device != X.device or tuple(lengths.shape) != (n,)):
+            raise ValueError("lengths: an int32 tensor of shape (N,) on the sequences' device, or None")
+        lens = None if lengths is None else lengths.contiguous()
+        cc = Sd.shape[0]
+        keep = []
+        p = spec.params(d, float(a.shape[0]), keep)
+        p.base_params[1] = float(_SPECTRAL_FAMILY[family])
+        arr = _sketch_array(sketches, keep)
+        F = 1 + cc + (spec.num_levels - 1) * int(r)
+        out = torch.empty((n, F), dtype=torch.float64, device=X.device)
+        _ctx_for(X).call("gpsig_lr_seq_features_spectral_ragged_dev", p, cc, int(r), len(sketches), arr, _ptr(X), n, l,
+                         None if lens is None else _ptr(lens), _ptr(Sd), _ptr(Whd), _ptr(a), _ptr(o), _ptr(g), _ptr(out))
+        ctx.spec, ctx.family, ctx.sketches, ctx.r, ctx.has_lens = spec, family, sketches, int(r), lens is not None
+        ctx.dt = tuple(t.dtype for t in (Xs, S, Wh, alpha, omega, gamma))
+        ctx.save_for_backward(X, Sd, Whd, a, o, g, lens if lens is not None else X.new_empty(0))
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        X, Sd, Whd, a, o, g, lens = ctx.saved_tensors
+        n, l, d = X.shape
+        cc = Sd.shape[0]
+        keep = []
+        p = ctx.spec.params(d, float(a.shape[0]), keep)
+        p.base_params[1] = float(_SPECTRAL_FAMILY[ctx.family])
+        arr = _sketch_array(ctx.sketches, keep)
+        G = _c(G)
+        grads = [torch.empty_like(t) for t in (X, Sd, Whd, a, o, g)]
+        _ctx_for(X).call("gpsig_lr_seq_features_spectral_ragged_grad", p, cc, ctx.r, len(ctx.sketches), arr, _ptr(X), n, l,
+                         _ptr(lens) if ctx.has_lens else None, _ptr(Sd), _ptr(Whd), _ptr(a), _ptr(o), _ptr(g), _ptr(G), *(_ptr(t) for t in grads))
+        gX, rest = grads[0].to(ctx.dt[0]), tuple(t.to(dt) for t, dt in zip(grads[1:], ctx.dt[1:]))
+        return (gX, None) + rest + (None, None, None, None)
+
+
 class _LrTensFeatures(torch.autograd.Function):
     """_K_tens_lr_feat (kernels.py:285-311) given the landmarks and the whitening: scaled inducing tensors (lt, T[, 2], d), S (c, d), Wh (c, c)
     -> Phi (T, 1 + c + (M-1) r), by the fused HIP tensor kernel (gpsig_lr_tens_features_dev); the reverse pass by
@@ -1049,10 +1095,12 @@ class _LowRankScope:
     def seq(self, Xs, lengths=None):
         """signature_algs.py:162-192 (with :191 summing P, as evidently intended).  (N, L, d') -> [(N, 1), (N, c), (N, r), ...].
         Through the HIP feature kernel and its reverse pass (_LrSeqFeatures; SignatureSpectral: _LrSeqFeaturesSpectral) where they are
-        built (sequences beyond the LDS in time tiles; SignatureSpectral: whole sequences only); torch ops otherwise (more than 64
-        components, ranks beyond a 64-step tile, module option ``lr_hip = False``).
+        built (sequences beyond the LDS in time tiles; SignatureSpectral: whole sequences, and with the module option
+        ``lr_spectral_tiled`` longer ones in time tiles by _LrSeqFeaturesSpectralRagged); torch ops otherwise (more than 64 components, ranks
+        beyond a 64-step tile, module option ``lr_hip = False``).
         lengths: (N,) int32 on the sequences' device for a ragged batch (sequence n is Xs[n, :lengths[n]]; the rows beyond are not read):
-        _LrSeqFeaturesRagged within the same limits for the families other than SignatureSpectral, _seq_torch_ragged otherwise."""
+        _LrSeqFeaturesRagged within the same limits for the families other than SignatureSpectral, for which it is
+        _LrSeqFeaturesSpectralRagged with ``lr_spectral_tiled`` set; _seq_torch_ragged otherwise."""
         if lengths is not None:
             return self._seq_ragged(Xs, lengths)
         key = id(Xs)
@@ -1065,13 +1113,17 @@ class _LowRankScope:
             # arrays with its carry rows, three in the forward direction and four in the reverse pass -- longer sequences go in tiles;
             # SignatureSpectral: the four (width, L) arrays of a whole sequence
             rows, lp = max(cc, r, d, 16), (L + 63) // 64 * 64 + 1
-            if kern._base == "spectral":
-                fits = 8 * lp * 4 * rows <= 156 * 1024
-            else:
-                fits = max(8 * (65 * 4 * rows + 17 * rows), 8 * (65 * (cc + 2 * max(cc, r, d)) + 8 * max(cc, r, d))) <= 156 * 1024
+            tile_fits = max(8 * (65 * 4 * rows + 17 * rows), 8 * (65 * (cc + 2 * max(cc, r, d)) + 8 * max(cc, r, d))) <= 156 * 1024
+            whole_fits = 8 * lp * 4 * rows <= 156 * 1024
+            # SignatureSpectral beyond whole sequences: the lengths-aware tiled instances, where the module asks for them
+            spectral_tiled = kern._base == "spectral" and not whole_fits and getattr(mod, "lr_spectral_tiled", False)
+            fits = whole_fits if kern._base == "spectral" and not spectral_tiled else tile_fits
             if cc <= 64 and cc * d <= 4096 and fits and M - 1 <= 7:
                 try:
-                    if kern._base == "spectral":
+                    if spectral_tiled:
+                        Phi = _LrSeqFeaturesSpectralRagged.apply(Xs, None, self.S, self.Wh, positive(mod.raw_alpha), positive(mod.raw_omega),
+                                                                 positive(mod.raw_sgamma), mod._spec, kern.family, self.host_sketches, r)
+                    elif kern._base == "spectral":
                         Phi = _LrSeqFeaturesSpectral.apply(Xs, self.S, self.Wh, positive(mod.raw_alpha), positive(mod.raw_omega),
                                                            positive(mod.raw_sgamma), mod._spec, kern.family, self.host_sketches, r)
                     else:
@@ -1086,7 +1138,8 @@ class _LowRankScope:
 
     def _seq_ragged(self, Xs, lengths):
         key = (id(Xs), id(lengths))
-        if key not in self._seq and getattr(self.mod, "lr_hip", True) and Xs.is_cuda and self.mod.kern._base != "spectral":
+        spectral = self.mod.kern._base == "spectral"
+        if key not in self._seq and getattr(self.mod, "lr_hip", True) and Xs.is_cuda and (not spectral or getattr(self.mod, "lr_spectral_tiled", False)):
             mod, kern = self.mod, self.mod.kern
             M, cc = kern.num_levels, int(self.S.shape[0])
             r = int(self.host_sketches[0].r) if self.host_sketches else int(kern.rank_bound)
@@ -1095,7 +1148,11 @@ class _LowRankScope:
             fits = max(8 * (65 * 4 * max(cc, r, d, 16) + 17 * max(cc, r, d, 16)), 8 * (65 * (cc + 2 * max(cc, r, d)) + 8 * max(cc, r, d))) <= 156 * 1024
             if cc <= 64 and cc * d <= 4096 and fits and M - 1 <= 7:
                 try:
-                    Phi = _LrSeqFeaturesRagged.apply(Xs, lengths, self.S, self.Wh, mod.p0, mod._spec, self.host_sketches, r)
+                    if spectral:
+                        Phi = _LrSeqFeaturesSpectralRagged.apply(Xs, lengths, self.S, self.Wh, positive(mod.raw_alpha), positive(mod.raw_omega),
+                                                                 positive(mod.raw_sgamma), mod._spec, kern.family, self.host_sketches, r)
+                    else:
+                        Phi = _LrSeqFeaturesRagged.apply(Xs, lengths, self.S, self.Wh, mod.p0, mod._spec, self.host_sketches, r)
                     self._seq[key] = (Xs, lengths, list(torch.split(Phi, [1, cc] + [r] * (M - 1), dim=1)))
                 except NotImplementedError:
                     pass
@@ -1231,6 +1288,9 @@ class SignatureKernelModule(torch.nn.Module):
         # measured (minibatch of 50: 2.3 against 2.7 ms; 4,096 sequences: 2.1 against 51.6)
         self.feature_route_min_work_cosine = 0.0
         self.sum_route = True          # K(X [, X2]) of the linear / cosine kernel: level sum and gradient as one op where the library offers it
+        # low-rank SignatureSpectral: sequences beyond the whole-sequence kernels and ragged batches through the lengths-aware tiled instances
+        # (_LrSeqFeaturesSpectralRagged) instead of torch ops.  A plain switch, off until the default is flipped
+        self.lr_spectral_tiled = False
         d_cols = kern.num_features * (kern.num_lags + 1)
         # beyond 64 columns and for the spectral kernel: base-kernel tensors here (GEMMs, autograd), recursions in the library
         # (round 6: beyond 64 columns the library's wide route takes the primitives it is built for -- _mx below)

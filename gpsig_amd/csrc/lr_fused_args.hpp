@@ -63,9 +63,12 @@ __device__ __forceinline__ int lr_ragged_length(const int32_t* lengths, int64_t 
     const int v = __builtin_amdgcn_readfirstlane(lr_as_const(lengths)[n]);
     return v < 1 ? 1 : (v > L ? L : v);
 }
+// blocks whose `lengths` may be NULL, meaning L points for every sequence (the spectral instances, lr_spectral_tiled.hpp): one wave-uniform branch
+template <typename Args> struct lr_ragged_nullable { static constexpr bool value = false; };
 template <typename Args>
 __device__ __forceinline__ int lr_seq_points(const Args& A, int64_t n, int L) {
-    if constexpr (lr_ragged<Args>::value) return lr_ragged_length(A.lengths, n, L);
+    if constexpr (lr_ragged_nullable<Args>::value) return A.lengths ? lr_ragged_length(A.lengths, n, L) : L;
+    else if constexpr (lr_ragged<Args>::value) return lr_ragged_length(A.lengths, n, L);
     else return L;
 }
 
@@ -143,5 +146,11 @@ size_t spectral_cross_grad_part_doubles(int64_t n, int c, int d, int Q);
 int spectral_cross_grad_launch(hipStream_t stream, int Q, int family, int d, const double* P, int64_t n, const double* S, int c,
                                const double* alpha, const double* omega, const double* gamma, const double* G, double* dP, double* part,
                                double* dS, double* dalpha, double* domega, double* dgamma, bool accumulate);
+// ... and for the points of N sequences in rows of L (point p = n L + t), of which sequence n has
+// lengths[n] (N int32 on the device, clamped to [1, L]): a point with t >= lengths[n] is not read, its dP row is stored as exact zeros and it
+// adds nothing to dS, dalpha, domega, dgamma.  Same partial sums in the same order as spectral_cross_grad_launch on n = N L points.
+int spectral_cross_grad_len_launch(hipStream_t stream, int Q, int family, int d, const double* P, int64_t N, int L, const int32_t* lengths,
+                                   const double* S, int c, const double* alpha, const double* omega, const double* gamma, const double* G, double* dP,
+                                   double* part, double* dS, double* dalpha, double* domega, double* dgamma, bool accumulate);
 
 }  // namespace gpsig

@@ -85,6 +85,13 @@ __device__ __forceinline__ float lr_kappa_f32(int kind, float p0, float p1, int 
     return base_eval<T>(kind, ip, xs, ss, p0, p1);
 }
 
+// kappa(x, S_i) of the float64 spectral instances of the three-array form, on the packed table; overloaded on the argument block
+// (lr_spectral_tiled_inst.hip: its instances evaluate a component's exponential and cosine out of line)
+template <typename Args, class FX, class FY>
+__device__ __forceinline__ double lr_spectral_kappa(const Args& A, lr_const_ptr<double> tab, int Q, int d_eff, FX&& xf, FY&& yf) {
+    return spectral_pair(tab, tab + Q, tab + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff, xf, yf);
+}
+
 template <int THREADS, int UNROLL, bool SPEC, typename Args>
 __device__ __forceinline__ void lr_seq_features_fused_body(const Args& A) {
     using T = typename Args::value_type;
@@ -129,8 +136,7 @@ __device__ __forceinline__ void lr_seq_features_fused_body(const Args& A) {
                             bufA[i * lp + t] = spectral_pair_f32(tab, tab + Q, tab + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff,
                                                                  [&](int f) { return bufB[f * lp + t]; }, [&](int f) { return Si[f]; });
                         else
-                            bufA[i * lp + t] = spectral_pair(tab, tab + Q, tab + Q + Q * SPECTRAL_STRIDE, SPECTRAL_STRIDE, Q, int(A.p1), d_eff,
-                                                             [&](int f) { return bufB[f * lp + t]; }, [&](int f) { return Si[f]; });
+                            bufA[i * lp + t] = lr_spectral_kappa(A, tab, Q, d_eff, [&](int f) { return bufB[f * lp + t]; }, [&](int f) { return Si[f]; });
                         continue;
                     }
                     if constexpr (sizeof(T) == sizeof(float)) {

@@ -21,6 +21,11 @@
 // are added to the outputs in chunk order, the dWh partials of all chunks are reduced once in workgroup order -- deterministic either way.
 // Scratch: B_GR0 dWh partials, B_GR1 the per-workgroup E_i and kxs, B_LRDK dkxs, B_GR2 the cross op's partials (own buffers: none of them
 // can be resized while another one's reader is queued; ensure() waits for the stream before it frees anything anyway).
+// Long and ragged SignatureSpectral batches: gpsig_lr_seq_features_spectral_ragged_dev / _ragged_grad take the spectral pair's arguments and an
+// optional `lengths` (NULL: every sequence has L points).  Checks and plan follow from L alone, as for the other families; then the spectral
+// instances of lr_spectral_tiled_inst.hip, whole sequence or time-tiled, each direction on its own.  The reverse kernels stop at dkxs and keep kxs
+// of a whole sequence next to the E_i in B_GR1 (c L doubles more per workgroup, inside the plan's budget); dkxs goes to the lengths-aware
+// reverse kernels of the spectral cross op, in chunks of LR_SPECTRAL_DKXS_BUDGET as above.
 // The inducing tensors' feature map (_K_tens_lr_feat, kernels.py:285-311) has the same two pairs:
 //     gpsig_lr_tens_features_dev / _spectral_dev     Phi (T, F) by the fused tensor kernels of lr_fused_kernel.hpp (lr_tens_fused_launch)
 //     gpsig_lr_tens_features_grad / _spectral_grad   lr_tens_grad_kernel.hpp: dPhi -> dZ, dS, dWh, d base parameter; the spectral instance stops
@@ -32,6 +37,7 @@
 #include "ctx.hpp"
 #include "lr_grad_kernel.hpp"
 #include "lr_tens_grad_kernel.hpp"
+#include "lr_spectral_tiled.hpp"
 #include "lr_tiled_kernel.hpp"
 
 #include <algorithm>
@@ -146,20 +152,26 @@ __global__ __launch_bounds__(256) void lr_spectral_pack_kernel(const double* __r
     }
 }
 
+// the LrFusedArgs fields of a call on device-resident landmarks and whitening (the launchers derive F, lp and rows_b)
+void fused_args(const gpsig_params* p, int cc, int r, int nsk, const LrGradSketch* gs, const void* X, int64_t N, int L, const double* S,
+                const double* Wh, const double* spec, void* Phi, LrFusedArgs* A) {
+    A->X = static_cast<const double*>(X); A->N = N; A->L = L;
+    A->P.d_in = p->num_features;
+    A->S = S; A->Wh = Wh;
+    A->c = cc; A->r = r; A->M = p->num_levels; A->difference = p->difference; A->kind = int(p->base_kernel);
+    A->p0 = p->base_params[0]; A->p1 = p->base_params[1];
+    A->spec = spec;
+    for (int i = 0; i < nsk; ++i) A->sk[i] = LrFusedSketch{gs[i].colptr, gs[i].ent};
+    A->Phi = static_cast<double*>(Phi);
+}
+
 // the fused feature kernels (lr_fused_inst.hip) on device-resident landmarks and whitening: the caller scaled the inputs (no lengthscales,
 // no lags); `two` picks the two-array form, else the three-array instance of lr_fused_variant
 int fused_features(gpsig_ctx* c, const gpsig_params* p, int cc, int r, int nsk, const LrGradSketch* gs, const void* X, int64_t N, int L,
                    const double* S, const double* Wh, const double* spec, bool two, void* Phi, const char* what, const int32_t* lengths = nullptr) {
     LrFusedRaggedArgs A{};                       // (with `lengths` the ragged instance of the three-array form, lr_ragged_inst.hip)
     A.lengths = lengths;
-    A.X = static_cast<const double*>(X); A.N = N; A.L = L;
-    A.P.d_in = p->num_features;
-    A.S = S; A.Wh = Wh;
-    A.c = cc; A.r = r; A.M = p->num_levels; A.difference = p->difference; A.kind = int(p->base_kernel);
-    A.p0 = p->base_params[0]; A.p1 = p->base_params[1];
-    A.spec = spec;
-    for (int i = 0; i < nsk; ++i) A.sk[i] = LrFusedSketch{gs[i].colptr, gs[i].ent};
-    A.Phi = static_cast<double*>(Phi);
+    fused_args(p, cc, r, nsk, gs, X, N, L, S, Wh, spec, Phi, &A);
     const int rc = lengths ? lr_ragged_fused_launch(c->stream, A, c->lr_fused_pad)
                            : lr_fused_launch(c->stream, static_cast<const LrFusedArgs&>(A), c->lr_fused_pad, two, c->lr_fused_variant);
     if (rc != 0) return fail(c, GPSIG_ERR_HIP, "%s: %s", what, hipGetErrorString(hipError_t(rc)));
@@ -452,6 +464,125 @@ int gpsig_lr_seq_features_spectral_grad(gpsig_ctx* c, const gpsig_params* p, int
         const int rc = spectral_cross_grad_launch(c->stream, Q, family, d, Xc, nn * L, S, cc, alpha, omega, gamma, A.dkxs,
                                                   static_cast<double*>(gX) + n0 * int64_t(L) * d, static_cast<double*>(cpart), gS, dalpha, domega,
                                                   dgamma, n0 > 0);
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral cross reverse pass: %s", hipGetErrorString(hipError_t(rc)));
+        at += grid;
+    }
+    hipLaunchKernelGGL(lr_grad_reduce_kernel, dim3(unsigned((int64_t(cc) * cc + 255) / 256)), dim3(256), 0, c->stream, static_cast<const double*>(part),
+                       int(nparts), int64_t(cc) * cc, gS, int64_t(0), gWh, int64_t(cc) * cc, static_cast<double*>(nullptr));
+    HIPCHK(c, hipGetLastError());
+    return GPSIG_OK;
+}
+
+// ... of long and ragged batches: `lengths` directly after L (N int32 on the device, the kernels clamp to [1, L]; NULL: L points each).  Sequences
+// beyond the LDS go in time tiles; the plan follows from L alone.
+int gpsig_lr_seq_features_spectral_ragged_dev(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches,
+                                              const void* X, int64_t N, int32_t L, const int32_t* lengths, const double* S, const double* Wh,
+                                              const double* alpha, const double* omega, const double* gamma, void* Phi) {
+    CHK(check(c, p, cc, r, nsk, true));
+    if (N < 0 || L < 1 || (N > 0 && (!X || !S || !Wh || !alpha || !omega || !gamma || !Phi))) return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
+    const int d = p->num_features, Q = int(p->base_params[0]);
+    const LrTileDir D = lr_tile_dir(false, cc, r, d, L, p->difference ? L - 1 : L, c->lr_fused_pad);
+    if (!D.untiled && D.TL == 0)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "a %d-step tile of a sequence's low-rank arrays (%zu bytes) exceeds the LDS", LR_TILE_STEP,
+                    lr_tiled_fused_lds_bytes(cc, r, d, LR_TILE_STEP, c->lr_fused_pad));
+    LrGradSketch gs[LR_FUSED_MAX_SKETCHES];
+    CHK(upload_sketches(c, cc, r, nsk, sketches, gs));
+    if (N == 0) return GPSIG_OK;
+    void* tabv;
+    const int ntab = Q * (1 + 2 * SPECTRAL_STRIDE);
+    CHK(ensure(c, B_SPECD, sizeof(double) * size_t(ntab) + 64, &tabv));
+    const double* tab = static_cast<const double*>(tabv);
+    hipLaunchKernelGGL(lr_spectral_pack_kernel, dim3(unsigned((ntab + 255) / 256)), dim3(256), 0, c->stream, alpha, omega, gamma, Q, d,
+                       static_cast<double*>(tabv));
+    HIPCHK(c, hipGetLastError());
+    int rc;
+    if (D.untiled) {
+        LrFusedSpectralLenArgs A{};
+        fused_args(p, cc, r, nsk, gs, X, N, L, S, Wh, tab, Phi, &A);
+        A.lengths = lengths;
+        rc = lr_spectral_len_fused_launch(c->stream, A, c->lr_fused_pad);
+    } else {
+        LrTiledSpectralArgs A{};
+        tiled_args(c, p, cc, r, nsk, gs, L, S, Wh, D, false, &A);
+        A.X = static_cast<const double*>(X); A.N = N;
+        A.Phi = static_cast<double*>(Phi);
+        A.alpha = tab; A.omega = tab + Q; A.gamma = tab + Q + Q * SPECTRAL_STRIDE; A.ld = SPECTRAL_STRIDE;
+        A.lengths = lengths;
+        rc = lr_spectral_tiled_launch(c->stream, A, unsigned(N < (1 << 20) ? N : (1 << 20)), D.lds);
+    }
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "low-rank spectral feature kernel (lengths-aware): %s", hipGetErrorString(hipError_t(rc)));
+    return GPSIG_OK;
+}
+
+int gpsig_lr_seq_features_spectral_ragged_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches,
+                                               const void* X, int64_t N, int32_t L, const int32_t* lengths, const double* S, const double* Wh,
+                                               const double* alpha, const double* omega, const double* gamma, const void* dPhi, void* gX, double* gS,
+                                               double* gWh, double* dalpha, double* domega, double* dgamma) {
+    CHK(check(c, p, cc, r, nsk, true));
+    if (N < 0 || L < 1 || !gS || !gWh || !dalpha || !domega || !dgamma ||
+        (N > 0 && (!X || !S || !Wh || !alpha || !omega || !gamma || !dPhi || !gX)))
+        return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
+    const int M = p->num_levels, d = p->num_features, F = 1 + cc + (M - 1) * r, Q = int(p->base_params[0]), family = int(p->base_params[1]);
+    // sequences per chunk: dkxs of a chunk within the budget; the plan of a chunk, with kxs (c, L) in each workgroup's scratch
+    const int64_t per_seq = int64_t(L) * cc * int64_t(sizeof(double));
+    const int64_t nb = std::min<int64_t>(N, std::max<int64_t>(1, int64_t(LR_SPECTRAL_DKXS_BUDGET) / per_seq));
+    const LrTilePlan plan = lr_tile_plan(cc, r, d, L, M, p->difference, c->lr_fused_pad, nb, int64_t(cc) * L);
+    if (!plan.rev.untiled && plan.rev.TL == 0)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "a %d-step tile of a sequence's low-rank arrays (%zu bytes) exceeds the LDS in the reverse pass", LR_TILE_STEP,
+                    lr_tiled_grad_lds_bytes(cc, r, d, LR_TILE_STEP, c->lr_fused_pad));
+    if (N > 0 && plan.grid == 0)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "one workgroup's scratch for a sequence of %d steps (%lld bytes) exceeds the reverse pass's budget", plan.l,
+                    (long long)(plan.escr_stride * int64_t(sizeof(double))));
+    LrGradSketch gs[LR_FUSED_MAX_SKETCHES];
+    CHK(upload_sketches(c, cc, r, nsk, sketches, gs));
+    if (N == 0) {
+        CHK(zero_async(c, gS, sizeof(double) * size_t(cc) * d));
+        CHK(zero_async(c, gWh, sizeof(double) * size_t(cc) * cc));
+        CHK(zero_async(c, dalpha, sizeof(double) * size_t(Q)));
+        CHK(zero_async(c, domega, sizeof(double) * size_t(Q) * d));
+        CHK(zero_async(c, dgamma, sizeof(double) * size_t(Q) * d));
+        return GPSIG_OK;
+    }
+    const int64_t escr_stride = plan.escr_stride, kxs_off = escr_stride - int64_t(cc) * L - 8;
+    int64_t nparts = 0;                                                // workgroups over all chunks: one dWh partial each
+    for (int64_t n0 = 0; n0 < N; n0 += nb) nparts += std::min<int64_t>(std::min(nb, N - n0), plan.grid);
+    void *part, *escr, *dk, *cpart;
+    CHK(ensure(c, B_GR0, sizeof(double) * size_t(nparts) * size_t(cc) * cc + 64, &part));
+    CHK(ensure(c, B_GR1, sizeof(double) * size_t(plan.grid) * size_t(escr_stride) + 64, &escr));
+    CHK(ensure(c, B_LRDK, sizeof(double) * size_t(nb) * size_t(L) * cc + 64, &dk));
+    CHK(ensure(c, B_GR2, sizeof(double) * spectral_cross_grad_part_doubles(nb * L, cc, d, Q) + 64, &cpart));
+    LrGradSpectralLenArgs W{};                                          // whole sequences ...
+    LrTiledSpectralArgs T{};                                            // ... or time tiles
+    if (plan.rev.untiled) {
+        grad_args(c, p, cc, r, nsk, gs, L, S, Wh, escr, escr_stride, &W);
+        W.alpha = alpha; W.omega = omega; W.gamma = gamma;
+        W.dkxs = static_cast<double*>(dk); W.kxs_off = kxs_off;
+    } else {
+        tiled_args(c, p, cc, r, nsk, gs, L, S, Wh, plan.rev, true, &T);
+        T.escr = static_cast<double*>(escr); T.escr_stride = escr_stride;
+        T.alpha = alpha; T.omega = omega; T.gamma = gamma; T.ld = d;
+        T.dkxs = static_cast<double*>(dk); T.kxs_off = kxs_off;
+    }
+    int64_t at = 0;
+    for (int64_t n0 = 0; n0 < N; n0 += nb) {
+        const int64_t nn = std::min(nb, N - n0);
+        const unsigned grid = unsigned(std::min<int64_t>(nn, plan.grid));
+        const double* Xc = static_cast<const double*>(X) + n0 * int64_t(L) * d;
+        const int32_t* lc = lengths ? lengths + n0 : nullptr;
+        LrGradArgs& A = plan.rev.untiled ? static_cast<LrGradArgs&>(W) : static_cast<LrGradArgs&>(T);
+        A.X = Xc; A.N = nn;
+        A.dPhi = static_cast<const double*>(dPhi) + n0 * int64_t(F);
+        A.part = static_cast<double*>(part) + at * int64_t(cc) * cc;
+        W.lengths = T.lengths = lc;
+        int rc = plan.rev.untiled ? lr_spectral_len_grad_launch(c->stream, W, grid, plan.rev.lds)
+                                  : lr_spectral_grad_tiled_launch(c->stream, T, grid, plan.rev.lds);
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "low-rank spectral reverse kernel (lengths-aware): %s", hipGetErrorString(hipError_t(rc)));
+        double* gXc = static_cast<double*>(gX) + n0 * int64_t(L) * d;
+        double* dkp = static_cast<double*>(dk);
+        rc = lc ? spectral_cross_grad_len_launch(c->stream, Q, family, d, Xc, nn, L, lc, S, cc, alpha, omega, gamma, dkp, gXc,
+                                                 static_cast<double*>(cpart), gS, dalpha, domega, dgamma, n0 > 0)
+                : spectral_cross_grad_launch(c->stream, Q, family, d, Xc, nn * L, S, cc, alpha, omega, gamma, dkp, gXc, static_cast<double*>(cpart), gS,
+                                             dalpha, domega, dgamma, n0 > 0);
         if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral cross reverse pass: %s", hipGetErrorString(hipError_t(rc)));
         at += grid;
     }

@@ -304,7 +304,8 @@ __device__ __forceinline__ void lr_seq_features_grad_body(const Args& A) {
             Ln = lr_seq_points(A, n, L);
             ln = A.difference ? Ln - 1 : Ln;
             nch = (Ln + 63) / 64;
-            lr_zero_padded_rows<THREADS>(A.gX + n * int64_t(L) * d, Ln, L, d);
+            if constexpr (SPEC) lr_zero_padded_rows<THREADS>(A.dkxs + n * int64_t(L) * c, Ln, L, c);      // (its output is dkxs, not gX)
+            else lr_zero_padded_rows<THREADS>(A.gX + n * int64_t(L) * d, Ln, L, d);
         }
         __syncthreads();
         // ---- forward again: x -> B1, kxs -> BX, feat -> BY, U -> B0

@@ -85,13 +85,14 @@ inline LrTileDir lr_tile_dir(bool reverse, int c, int r, int d, int L, int l, in
 // the reverse pass's E_i scratch per workgroup, in doubles (what the whole-sequence kernel takes as well)
 constexpr int64_t lr_escr_stride(int c, int r, int M, int l) { return (int64_t(c) + int64_t(M > 2 ? M - 2 : 0) * r) * (l > 0 ? l : 1) + 8; }
 
-inline LrTilePlan lr_tile_plan(int c, int r, int d, int L, int M, int difference, int pad, int64_t N) {
+// (`extra`: further doubles of scratch per workgroup, under the same budget -- SignatureSpectral's reverse pass keeps kxs (c, L) there)
+inline LrTilePlan lr_tile_plan(int c, int r, int d, int L, int M, int difference, int pad, int64_t N, int64_t extra = 0) {
     LrTilePlan P{};
     P.halo = difference ? 1 : 0;
     P.l = L - P.halo;
     P.fwd = lr_tile_dir(false, c, r, d, L, P.l, pad);
     P.rev = lr_tile_dir(true, c, r, d, L, P.l, pad);
-    P.escr_stride = lr_escr_stride(c, r, M, P.l);
+    P.escr_stride = lr_escr_stride(c, r, M, P.l) + extra;
     int64_t g = N < LR_TILE_MAX_GRID ? N : LR_TILE_MAX_GRID;
     if (!P.rev.untiled) {                               // (whole sequences are short: their scratch stays small)
         const int64_t fit = int64_t(LR_TILE_SCRATCH_BUDGET / (sizeof(double) * size_t(P.escr_stride)));

@@ -15,7 +15,8 @@
 //              per-thread registers over tiles and sequences and leave as one partial per workgroup (lr_grad_reduce_kernel).
 // Layout, lane mappings and the loops themselves are the whole-sequence kernels' (lr_grad_kernel.hpp: lr_sketch_apply, lr_cross_base,
 // lr_grad_whiten_adjoint, lr_grad_base_phase): arrays [column][time] with the row stride of a tile, lane = time, thread = column for the
-// running sums, sketch entries through the scalar unit.  Non-spectral families, float64.
+// running sums, sketch entries through the scalar unit.  Float64; the kernels here serve the families of base_eval, SignatureSpectral's
+// instances of the same bodies are in lr_spectral_tiled_inst.hip.
 #pragma once
 
 #include "lr_grad_kernel.hpp"
@@ -33,18 +34,13 @@ struct LrTiledArgs : LrGradArgs {
 struct LrTiledRaggedArgs : LrTiledArgs { const int32_t* lengths; };
 template <> struct lr_ragged<LrTiledRaggedArgs> { static constexpr bool value = true; };
 
-// a tile's x -> xb, kxs -> kx, feat -> ft (may be xb), U -> u: `np` points at Xt, `tl` steps.  Ends with a barrier.
+// a tile's feat -> ft and U -> u from its kxs in kx: `np` points, `tl` steps.  Ends with a barrier.
 template <int THREADS>
-__device__ __forceinline__ void lr_tile_u(const LrTiledArgs& A, const double* Xt, int tl, int np, double* xb, double* kx, double* ft, double* u,
-                                          int lane, int wave) {
+__device__ __forceinline__ void lr_tile_feat_u(const LrTiledArgs& A, int tl, int np, const double* kx, double* ft, double* u, int lane, int wave) {
     constexpr int NW = THREADS / 64;
-    const int lp = A.lp, c = A.c, d = A.d;
+    const int lp = A.lp, c = A.c;
     const int nchunk = (np + 63) / 64;
     const lr_const_ptr<double> Whg = lr_as_const(A.Wh);
-    lr_load_points<THREADS>(Xt, np, d, lp, xb);
-    __syncthreads();
-    lr_cross_base<NW>(A.kind, A.p0, A.p1, lr_as_const(A.S), c, d, xb, kx, lp, np, nchunk, lane, wave);
-    __syncthreads();
     for (int ch = 0; ch < nchunk; ++ch) {
         const int t = ch * 64 + lane;
         if (t < np) {
@@ -66,6 +62,47 @@ __device__ __forceinline__ void lr_tile_u(const LrTiledArgs& A, const double* Xt
             }
         }
     }
+    __syncthreads();
+}
+
+// a tile's x -> xb, kxs -> kx, feat -> ft (may be xb), U -> u: `np` points at Xt, `tl` steps.  Ends with a barrier.
+template <int THREADS>
+__device__ __forceinline__ void lr_tile_u(const LrTiledArgs& A, const double* Xt, int tl, int np, double* xb, double* kx, double* ft, double* u,
+                                          int lane, int wave) {
+    constexpr int NW = THREADS / 64;
+    const int nchunk = (np + 63) / 64;
+    lr_load_points<THREADS>(Xt, np, A.d, A.lp, xb);
+    __syncthreads();
+    lr_cross_base<NW>(A.kind, A.p0, A.p1, lr_as_const(A.S), A.c, A.d, xb, kx, A.lp, np, nchunk, lane, wave);
+    __syncthreads();
+    lr_tile_feat_u<THREADS>(A, tl, np, kx, ft, u, lane, wave);
+}
+
+// ---- the phases of the reverse body that depend on the family, overloaded on the argument block: here the families of base_eval, which
+// evaluate kappa again wherever kxs is needed; SignatureSpectral's (lr_spectral_tiled_inst.hip) keep kxs of the sequence in the workgroup's
+// scratch (lr_keeps_kxs: pass A then runs for M = 1 as well) and write dkxs instead of the base-kernel phase.
+template <typename Args> struct lr_keeps_kxs { static constexpr bool value = false; };
+// the gX rows of a ragged sequence's padded points (it has Lp points) are zeros
+template <int THREADS>
+__device__ __forceinline__ void lr_tile_zero_padded(const LrTiledArgs& A, int64_t n, int Lp) {
+    lr_zero_padded_rows<THREADS>(A.gX + n * int64_t(A.L) * A.d, Lp, A.L, A.d);
+}
+// pass A, after lr_tile_u: nothing to keep
+template <int THREADS>
+__device__ __forceinline__ void lr_tile_keep_kxs(const LrTiledArgs&, const double*, double*, int, int, int) {}
+// pass B: lr_tile_u again
+template <int THREADS>
+__device__ __forceinline__ void lr_tile_u_again(const LrTiledArgs& A, const double* Xt, int tl, int np, double* xb, double* kx, double* ft, double* u,
+                                                int lane, int wave, const double*, int, int) {
+    lr_tile_u<THREADS>(A, Xt, tl, np, xb, kx, ft, u, lane, wave);
+}
+// ... and x -> xb, kxs -> kb once more for the tile's tail.  Ends with a barrier.
+template <int THREADS>
+__device__ __forceinline__ void lr_tile_kxs_again(const LrTiledArgs& A, lr_const_ptr<double> Sg, const double* Xt, int np, int pchunk, double* xb,
+                                                  double* kb, const double*, int, int, int lane, int wave) {
+    lr_load_points<THREADS>(Xt, np, A.d, A.lp, xb);
+    __syncthreads();
+    lr_cross_base<THREADS / 64>(A.kind, A.p0, A.p1, Sg, A.c, A.d, xb, kb, A.lp, np, pchunk, lane, wave);
     __syncthreads();
 }
 

@@ -1,6 +1,7 @@
 // lr_tiled_rev_body.inc -- the body of lr_seq_features_grad_tiled_kernel, included between the braces of a __global__ function template <int THREADS> whose
-// argument block is `A`: LrTiledArgs in lr_tiled_kernel.hpp, LrTiledRaggedArgs (per-sequence lengths) in lr_ragged_inst.hip.  A text shared by
-// inclusion, not a function: behind a reference or a by-value parameter the existing instance compiles to other code (more registers, or scratch).
+// argument block is `A`: LrTiledArgs in lr_tiled_kernel.hpp, LrTiledRaggedArgs (per-sequence lengths) in lr_ragged_inst.hip, LrTiledSpectralArgs in
+// lr_spectral_tiled_inst.hip.  A text shared by inclusion, not a function: behind a reference or a by-value parameter the existing instance compiles
+// to other code (more registers, or scratch).  The phases that depend on the family are overloaded on the block (lr_tiled_kernel.hpp).
     constexpr int NW = THREADS / 64, UNROLL = 8;
     constexpr bool RAGGED = lr_ragged<decltype(A)>::value;
     extern __shared__ double lrt_lds[];
@@ -35,7 +36,7 @@
         if constexpr (RAGGED) {                                  // the sequence's own steps and tiles, from lengths[n] (wave-uniform); the gX rows
             ln = lr_seq_points(A, n, L) - halo;                  // of its padded points are zeros
             ntiles = lr_tile_count(ln, TL);
-            lr_zero_padded_rows<THREADS>(A.gX + n * int64_t(L) * d, ln + halo, L, d);
+            lr_tile_zero_padded<THREADS>(A, n, ln + halo);
         }
         __syncthreads();
         // ---- the carries of this sequence: cf = 0;  cb_i = g_{i-1} (what the suffix sum of the last tile starts from);  dun = 0
@@ -46,10 +47,11 @@
         }
         for (int j = threadIdx.x; j < rows; j += THREADS) dun[j] = 0.0;
         // ---- pass A: E_2 = excumsum_t(U), E_{i+1} = excumsum_t(sketch_i(U, E_i)) of the whole sequence -> scratch, [column][l] per level
-        for (int k = 0; M >= 2 && k < ntiles; ++k) {
+        for (int k = 0; (M >= 2 || lr_keeps_kxs<decltype(A)>::value) && k < ntiles; ++k) {
             const int t0 = lr_tile_first(k, TL), tl = lr_tile_steps(ln, k, TL), np = tl + halo;
             const int nchunk = (tl + 63) / 64;
             lr_tile_u<THREADS>(A, Xn + int64_t(t0) * d, tl, np, B1, BX, BY, B0, lane, wave);
+            lr_tile_keep_kxs<THREADS>(A, BX, escr, ln + halo, t0, np);
             lr_tile_excumsum<THREADS>(B0, BX, c, lp, tl, cf, true, escr + t0, ln);
             __syncthreads();
             int64_t eo = int64_t(c) * ln;
@@ -70,7 +72,7 @@
             const int nchunk = (tl + 63) / 64, pchunk = (np + 63) / 64;
             const int q0 = halo && k > 0 ? 1 : 0;               // the tile's first point belongs to the tile before it
             __syncthreads();                                     // (the previous tile's dS sums read B1, BX and BY)
-            lr_tile_u<THREADS>(A, Xn + int64_t(t0) * d, tl, np, B1, BX, BY, B0, lane, wave);
+            lr_tile_u_again<THREADS>(A, Xn + int64_t(t0) * d, tl, np, B1, BX, BY, B0, lane, wave, escr, ln + halo, t0);
             for (int q = threadIdx.x; q < c * lp; q += THREADS) B1[q] = 0.0;                          // dU
             double* Y = BY;                                     // dP of the level being processed
             double* Xb = BX;                                    // E of that level, then dE
@@ -127,10 +129,7 @@
                 for (int j = threadIdx.x; j < c; j += THREADS) dun[j] = B1[j * lp];
             __syncthreads();
             // x -> B1 and kxs -> B0 once more (U and dU are done with)
-            lr_load_points<THREADS>(Xn + int64_t(t0) * d, np, d, lp, B1);
-            __syncthreads();
-            lr_cross_base<NW>(A.kind, A.p0, A.p1, Sg, c, d, B1, B0, lp, np, pchunk, lane, wave);
-            __syncthreads();
+            lr_tile_kxs_again<THREADS>(A, Sg, Xn + int64_t(t0) * d, np, pchunk, B1, B0, escr, ln + halo, t0, lane, wave);
             lr_grad_whiten_adjoint<THREADS>(c, lp, q0, np, B0, Xb, Whg, Y, accW, lane, wave);
             __syncthreads();
             lr_grad_base_phase<THREADS>(A, Sg, n, t0, q0, np, B0, B1, Xb, Y, accS, accP, lane, wave);

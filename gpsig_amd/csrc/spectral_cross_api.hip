@@ -9,8 +9,11 @@
 //     fixed order: no atomics, two runs agree bit for bit.  Per-pair arithmetic: spectral_pair.hpp.
 //   * spectral_cross_grad_launch: the same reverse pass for the low-rank training path's spectral entry points (lr_grad_api.hip), which
 //     hand over dkxs as G, partial sums in a buffer of their own and, for the second and later chunks of sequences, add to the outputs.
+//     spectral_cross_grad_len_launch: the same for sequences with per-sequence lengths, whose padded points take no part.
 #include "ctx.hpp"
 #include "lr_fused_args.hpp"
+
+#include <type_traits>
 #include "spectral_pair.hpp"
 
 using namespace gpsig;
@@ -59,6 +62,19 @@ struct SpecCrossArgs {
     int accumulate;                                                     // the combine pass adds dS and the parameters' sums to its outputs
 };
 
+// ... of N sequences in rows of L points (n = N L), of which sequence n has lengths[n]: the points beyond take no part
+struct SpecCrossLenArgs : SpecCrossArgs { int L; const int32_t* lengths; };
+template <typename Args>
+__device__ __forceinline__ bool spec_cross_live(const Args& A, int64_t pt) {
+    if constexpr (std::is_same<Args, SpecCrossLenArgs>::value) {
+        const int64_t n = pt / A.L;
+        const int v = A.lengths[n];
+        return int(pt - n * A.L) < (v < 1 ? 1 : v);             // (t < L always: the upper clamp of the length changes nothing)
+    } else {
+        return true;
+    }
+}
+
 constexpr int SC_THREADS = 256;
 
 __global__ __launch_bounds__(SC_THREADS) void spectral_cross_kernel(SpecCrossArgs A, double* __restrict__ K) {
@@ -75,42 +91,11 @@ __global__ __launch_bounds__(SC_THREADS) void spectral_cross_kernel(SpecCrossArg
 // dP: thread = point, the landmarks and the parameters wave-uniform (scalar loads); DMAX >= d columns in registers
 template <int DMAX>
 __global__ __launch_bounds__(SC_THREADS) void spectral_cross_grad_points_kernel(SpecCrossArgs A) {
-    const int d = A.d, Q = A.Q;
-    const lr_const_ptr<double> al = lr_as_const(A.alpha), om = lr_as_const(A.omega), ga = lr_as_const(A.gamma);
-    for (int64_t pt = blockIdx.x * int64_t(SC_THREADS) + threadIdx.x; pt < A.n; pt += int64_t(gridDim.x) * SC_THREADS) {
-        double x[DMAX], gx[DMAX];
-#pragma unroll
-        for (int f = 0; f < DMAX; ++f) {
-            x[f] = f < d ? A.P[pt * d + f] : 0.0;
-            gx[f] = 0.0;
-        }
-        for (int i = 0; i < A.c; ++i) {
-            const lr_const_ptr<double> y = lr_as_const(A.S) + size_t(i) * d;
-            const double g = A.G[pt * A.c + i];
-            for (int q = 0; q < Q; ++q) {
-                double w1 = 0.0, w2 = 0.0;
-#pragma unroll
-                for (int f = 0; f < DMAX; ++f)
-                    if (f < d) {
-                        const double diff = x[f] - y[f];
-                        const double gd = ga[q * d + f] * diff;
-                        w1 = fma(gd, gd, w1);
-                        w2 = fma(om[q * d + f], diff, w2);
-                    }
-                const SpectralTerm t = spectral_term(al[q], w1, w2, spectral_gauss(A.family, q, Q));
-                const double c1 = 2 * g * t.d_w1, c2 = g * t.d_w2;
-#pragma unroll
-                for (int f = 0; f < DMAX; ++f)
-                    if (f < d) {
-                        const double diff = x[f] - y[f], gq = ga[q * d + f];
-                        gx[f] += c1 * gq * gq * diff + c2 * om[q * d + f];
-                    }
-            }
-        }
-#pragma unroll
-        for (int f = 0; f < DMAX; ++f)
-            if (f < d) A.dP[pt * d + f] = gx[f];
-    }
+#include "spectral_cross_points_body.inc"
+}
+template <int DMAX>
+__global__ __launch_bounds__(SC_THREADS) void spectral_cross_grad_points_len_kernel(SpecCrossLenArgs A) {
+#include "spectral_cross_points_body.inc"
 }
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -123,76 +108,11 @@ __device__ __forceinline__ double wave_sum(double v) {
 // the 1 + 2d sums are reduced over the wavefront (butterfly), then over the four wavefronts in order; dS[i] at the end the same way.
 template <int DMAX>
 __global__ __launch_bounds__(SC_THREADS) void spectral_cross_grad_landmarks_kernel(SpecCrossArgs A) {
-    constexpr int NW = SC_THREADS / 64;
-    constexpr int W = 1 + 2 * DMAX;
-    __shared__ double red[NW][W];
-    const int d = A.d, Q = A.Q, i = blockIdx.y;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const lr_const_ptr<double> al = lr_as_const(A.alpha), om = lr_as_const(A.omega), ga = lr_as_const(A.gamma);
-    const lr_const_ptr<double> y = lr_as_const(A.S) + size_t(i) * d;
-    double* part = A.part + (size_t(i) * A.nchunk + blockIdx.x) * A.nv;
-    const int64_t step = int64_t(A.nchunk) * SC_THREADS;
-    double gs[DMAX];
-#pragma unroll
-    for (int f = 0; f < DMAX; ++f) gs[f] = 0.0;
-    for (int q = 0; q < Q; ++q) {
-        const bool gauss = spectral_gauss(A.family, q, Q);
-        double va = 0.0, vo[DMAX], vg[DMAX];
-#pragma unroll
-        for (int f = 0; f < DMAX; ++f) vo[f] = vg[f] = 0.0;
-        for (int64_t pt = int64_t(blockIdx.x) * SC_THREADS + threadIdx.x; pt < A.n; pt += step) {
-            const double g = A.G[pt * A.c + i];
-            double x[DMAX];
-            double w1 = 0.0, w2 = 0.0;
-#pragma unroll
-            for (int f = 0; f < DMAX; ++f)
-                if (f < d) {
-                    x[f] = A.P[pt * d + f];
-                    const double diff = x[f] - y[f];
-                    const double gd = ga[q * d + f] * diff;
-                    w1 = fma(gd, gd, w1);
-                    w2 = fma(om[q * d + f], diff, w2);
-                }
-            const SpectralTerm t = spectral_term(al[q], w1, w2, gauss);
-            const double c1 = 2 * g * t.d_w1, c2 = g * t.d_w2;
-            va = fma(g, t.d_alpha, va);
-#pragma unroll
-            for (int f = 0; f < DMAX; ++f)
-                if (f < d) {
-                    const double diff = x[f] - y[f], gq = ga[q * d + f];
-                    vo[f] = fma(c2, diff, vo[f]);
-                    vg[f] = fma(c1 * gq, diff * diff, vg[f]);
-                    gs[f] -= c1 * gq * gq * diff + c2 * om[q * d + f];
-                }
-        }
-        va = wave_sum(va);
-        if (lane == 0) red[wave][0] = va;
-#pragma unroll
-        for (int f = 0; f < DMAX; ++f)
-            if (f < d) {
-                const double so = wave_sum(vo[f]), sg = wave_sum(vg[f]);
-                if (lane == 0) { red[wave][1 + f] = so; red[wave][1 + d + f] = sg; }
-            }
-        __syncthreads();
-        if (threadIdx.x < 1 + 2 * d) {
-            double s = 0.0;
-            for (int w = 0; w < NW; ++w) s += red[w][threadIdx.x];
-            part[d + q * (1 + 2 * d) + threadIdx.x] = s;
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int f = 0; f < DMAX; ++f)
-        if (f < d) {
-            const double s = wave_sum(gs[f]);
-            if (lane == 0) red[wave][f] = s;
-        }
-    __syncthreads();
-    if (threadIdx.x < d) {
-        double s = 0.0;
-        for (int w = 0; w < NW; ++w) s += red[w][threadIdx.x];
-        part[threadIdx.x] = s;
-    }
+#include "spectral_cross_landmarks_body.inc"
+}
+template <int DMAX>
+__global__ __launch_bounds__(SC_THREADS) void spectral_cross_grad_landmarks_len_kernel(SpecCrossLenArgs A) {
+#include "spectral_cross_landmarks_body.inc"
 }
 
 // output o < c d: dS[o] = sum of the nchunk partials of landmark o / d; otherwise parameter v = o - c d: sum over every partial row
@@ -262,33 +182,57 @@ size_t spectral_cross_grad_part_doubles(int64_t n, int cc, int d, int Q) {
     return size_t(cc) * size_t(cross_grad_slices(n)) * size_t(d + Q * (1 + 2 * d));
 }
 
+// the three launches of the reverse pass on a filled argument block (SpecCrossArgs, or SpecCrossLenArgs: the lengths-aware kernels)
+template <typename Args>
+static int cross_grad_run(hipStream_t stream, Args A, double* dS, double* dalpha, double* domega, double* dgamma) {
+    constexpr bool LEN = std::is_same<Args, SpecCrossLenArgs>::value;
+    const int d = A.d;
+    A.nchunk = cross_grad_slices(A.n);
+    A.nv = d + A.Q * (1 + 2 * d);
+    const unsigned gp = unsigned(grid_for(A.n, SC_THREADS));
+    const dim3 gl(unsigned(A.nchunk), unsigned(A.c));
+    auto run = [&](auto dmax) {
+        constexpr int DMAX = decltype(dmax)::value;
+        if constexpr (LEN) {
+            hipLaunchKernelGGL(spectral_cross_grad_points_len_kernel<DMAX>, dim3(gp), dim3(SC_THREADS), 0, stream, A);
+            hipLaunchKernelGGL(spectral_cross_grad_landmarks_len_kernel<DMAX>, gl, dim3(SC_THREADS), 0, stream, A);
+        } else {
+            hipLaunchKernelGGL(spectral_cross_grad_points_kernel<DMAX>, dim3(gp), dim3(SC_THREADS), 0, stream, A);
+            hipLaunchKernelGGL(spectral_cross_grad_landmarks_kernel<DMAX>, gl, dim3(SC_THREADS), 0, stream, A);
+        }
+    };
+    if (d <= 8) run(std::integral_constant<int, 8>());
+    else if (d <= 16) run(std::integral_constant<int, 16>());
+    else run(std::integral_constant<int, 32>());
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return int(e);
+    const unsigned outs = unsigned(int64_t(A.c) * d + int64_t(A.Q) * (1 + 2 * d));
+    hipLaunchKernelGGL(spectral_cross_grad_combine_kernel, dim3(outs), dim3(SC_THREADS), 0, stream, static_cast<const SpecCrossArgs&>(A), dS, dalpha,
+                       domega, dgamma);
+    return int(hipGetLastError());
+}
+
 int spectral_cross_grad_launch(hipStream_t stream, int Q, int family, int d, const double* P, int64_t n, const double* S, int cc,
                                const double* alpha, const double* omega, const double* gamma, const double* G, double* dP, double* part,
                                double* dS, double* dalpha, double* domega, double* dgamma, bool accumulate) {
     SpecCrossArgs A{};
     A.P = P; A.n = n; A.S = S; A.c = cc; A.d = d; A.Q = Q; A.family = family; A.alpha = alpha; A.omega = omega; A.gamma = gamma;
     A.G = G; A.dP = dP;
-    A.nchunk = cross_grad_slices(n);
-    A.nv = d + Q * (1 + 2 * d);
     A.part = part;
     A.accumulate = accumulate ? 1 : 0;
-    const unsigned gp = unsigned(grid_for(n, SC_THREADS));
-    const dim3 gl(unsigned(A.nchunk), unsigned(cc));
-    if (d <= 8) {
-        hipLaunchKernelGGL(spectral_cross_grad_points_kernel<8>, dim3(gp), dim3(SC_THREADS), 0, stream, A);
-        hipLaunchKernelGGL(spectral_cross_grad_landmarks_kernel<8>, gl, dim3(SC_THREADS), 0, stream, A);
-    } else if (d <= 16) {
-        hipLaunchKernelGGL(spectral_cross_grad_points_kernel<16>, dim3(gp), dim3(SC_THREADS), 0, stream, A);
-        hipLaunchKernelGGL(spectral_cross_grad_landmarks_kernel<16>, gl, dim3(SC_THREADS), 0, stream, A);
-    } else {
-        hipLaunchKernelGGL(spectral_cross_grad_points_kernel<32>, dim3(gp), dim3(SC_THREADS), 0, stream, A);
-        hipLaunchKernelGGL(spectral_cross_grad_landmarks_kernel<32>, gl, dim3(SC_THREADS), 0, stream, A);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return int(e);
-    const unsigned outs = unsigned(int64_t(cc) * d + int64_t(Q) * (1 + 2 * d));
-    hipLaunchKernelGGL(spectral_cross_grad_combine_kernel, dim3(outs), dim3(SC_THREADS), 0, stream, A, dS, dalpha, domega, dgamma);
-    return int(hipGetLastError());
+    return cross_grad_run(stream, A, dS, dalpha, domega, dgamma);
+}
+
+int spectral_cross_grad_len_launch(hipStream_t stream, int Q, int family, int d, const double* P, int64_t N, int L, const int32_t* lengths,
+                                   const double* S, int cc, const double* alpha, const double* omega, const double* gamma, const double* G, double* dP,
+                                   double* part, double* dS, double* dalpha, double* domega, double* dgamma, bool accumulate) {
+    SpecCrossLenArgs A{};
+    A.P = P; A.n = N * L; A.S = S; A.c = cc; A.d = d; A.Q = Q; A.family = family; A.alpha = alpha; A.omega = omega; A.gamma = gamma;
+    A.G = G; A.dP = dP;
+    A.part = part;
+    A.accumulate = accumulate ? 1 : 0;
+    A.L = L; A.lengths = lengths;
+    return cross_grad_run(stream, A, dS, dalpha, domega, dgamma);
 }
 
 }  // namespace gpsig

@@ -384,8 +384,9 @@ int gpsig_lr_seq_features_ragged_grad(gpsig_ctx* ctx, const gpsig_params* p, int
  * alpha (Q), omega (Q, d), gamma (Q, d) are DEVICE pointers read on the device (p->base_table is ignored; no host round trip per step).
  * _grad: dPhi (N, F) -> gX (N, L, d), gS (c, d), gWh (c, c), dalpha (Q), domega (Q, d), dgamma (Q, d), all overwritten; deterministic
  * (no floating-point atomics, partial sums combined in a fixed order).  Limits: float64, device-pointer mode, num_lags = 0, order 1,
- * num_levels <= 8, Q <= 64, d <= 32, num_components <= 64, num_components x d <= 4096, a sequence's arrays within the LDS; outside them
- * GPSIG_ERR_UNSUPPORTED.  gpsig_lr_seq_features_dev / _grad keep refusing the spectral kernel. */
+ * num_levels <= 8, Q <= 64, d <= 32, num_components <= 64, num_components x d <= 4096, a sequence's arrays within the LDS (longer sequences
+ * and ragged batches: the _spectral_ragged pair below); outside them GPSIG_ERR_UNSUPPORTED.  gpsig_lr_seq_features_dev / _grad keep refusing the
+ * spectral kernel. */
 int gpsig_lr_seq_features_spectral_dev(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
                                        const gpsig_sketch* sketches, const void* X, int64_t N, int32_t L, const double* S, const double* Wh,
                                        const double* alpha, const double* omega, const double* gamma, void* Phi);
@@ -393,6 +394,25 @@ int gpsig_lr_seq_features_spectral_grad(gpsig_ctx* ctx, const gpsig_params* p, i
                                         const gpsig_sketch* sketches, const void* X, int64_t N, int32_t L, const double* S, const double* Wh,
                                         const double* alpha, const double* omega, const double* gamma, const void* dPhi, void* gX,
                                         double* gS, double* gWh, double* dalpha, double* domega, double* dgamma);
+/* The spectral pair for LONG and RAGGED batches: the same arguments with `lengths` directly after L, as the ragged pair above (N int32 on the
+ * DEVICE, clamped to [1, L] by the kernels) -- but lengths == NULL is valid here and means that every sequence has L points: that is how long
+ * dense batches are served.  Limits: those of the spectral pair except the sequence length.  Where a sequence's arrays fit the LDS the whole
+ * sequence is kept on chip, longer ones are walked in time tiles, each direction on its own; the plan follows from L alone (the host never
+ * reads the lengths).  GPSIG_ERR_UNSUPPORTED only where a single 64-step tile does not fit or where one workgroup's scratch -- the
+ * (c + (M-2) r) L doubles of the other families plus c L for kxs, which _grad keeps so that kappa is evaluated once per point -- exceeds
+ * 256 MB.  Phi[n] is the features of X[n, :lengths[n]] evaluated alone; the rows beyond a sequence's length are never read, by the feature
+ * kernels or by the spectral cross op's reverse kernels, and may hold NaN; _grad writes every gX row exactly once, the padded points' rows as
+ * exact zeros, and is bit-for-bit repeatable (fixed-order partial sums, no floating-point atomics).  N = 0: the summed outputs are zeroed.
+ * One instance per form (whole-sequence forward and reverse 512 threads, tiled forward 1024, tiled reverse 512), whatever lr_fused,
+ * lr_fused_variant and lr_grad_threads say; they follow lr_fused_pad. */
+int gpsig_lr_seq_features_spectral_ragged_dev(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
+                                              const gpsig_sketch* sketches, const void* X, int64_t N, int32_t L, const int32_t* lengths,
+                                              const double* S, const double* Wh, const double* alpha, const double* omega, const double* gamma,
+                                              void* Phi);
+int gpsig_lr_seq_features_spectral_ragged_grad(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
+                                               const gpsig_sketch* sketches, const void* X, int64_t N, int32_t L, const int32_t* lengths,
+                                               const double* S, const double* Wh, const double* alpha, const double* omega, const double* gamma,
+                                               const void* dPhi, void* gX, double* gS, double* gWh, double* dalpha, double* domega, double* dgamma);
 /* The inducing tensors' feature map for the TRAINING path: _K_tens_lr_feat (kernels.py:285-311: Nystrom_map + tensor_kern_lr_feature) given
  * landmarks S (c, d) and whitening Wh (c, c) on the device, like the four sequence entry points above.  Z: T inducing tensors of
  * lt = M (M + 1) / 2 components, (lt, T, d) or, with `increments`, (lt, T, 2, d) -- already scaled (no lengthscales inside, p->num_lags = 0),
