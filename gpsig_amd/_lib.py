@@ -73,6 +73,7 @@ _KERNEL_FUNCS = {
     "gpsig_base_kernel_matrix": [C.POINTER(C.c_double), C.POINTER(C.c_double), _i64, _i64, _i32, C.POINTER(C.c_double)],
     "gpsig_lr_whitening": [C.POINTER(C.c_double), _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "gpsig_lr_seq_features": [_LR, _vp, _i64, _i32, _vp],
+    "gpsig_lr_seq_features_ragged": [_LR, _vp, _i64, _i32, _vp, _vp],
     "gpsig_lr_tens_features": [_LR, _vp, _i64, _i32, _vp],
     "gpsig_lr_seq_features_dev": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp],
     "gpsig_lr_seq_features_grad": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)],
@@ -118,6 +119,7 @@ _PLAIN = {
     "gpsig_set_option": ([_vp, C.c_char_p, C.c_int], C.c_int),
     "gpsig_symmetrize_owned_rows": ([_vp, _i32, _vp, _i64, _vp], C.c_int),
     "gpsig_symmetrize_compact_rows": ([_vp, _i32, _vp, _i64, _vp], C.c_int),
+    "gpsig_scratch_bytes": ([_vp], _i64),
     "gpsig_timing_reset": ([_vp], C.c_int),
     "gpsig_timing_get": ([_vp, C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(_i64)], C.c_int),
     "gpsig_timing_info": ([_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double)], C.c_int),
@@ -228,6 +230,10 @@ class Context:
             g.launch()                                        # replays them with one launch
         """
         return Graph(self)
+
+    def scratch_bytes(self):
+        """Bytes of device memory in the context's scratch buffers now."""
+        return int(self._lib.gpsig_scratch_bytes(self._h))
 
     def timing_reset(self):
         self.check(self._lib.gpsig_timing_reset(self._h))

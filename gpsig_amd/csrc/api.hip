@@ -23,6 +23,7 @@
 #include "aux_kernels.hpp"
 #include "lowrank_kernels.hpp"
 #include "lr_fused_args.hpp"
+#include "lr_eval_tiled.hpp"
 #include "lr_draw_kernels.hpp"
 #include "seq_args.hpp"
 #include "seq_configs.hpp"
@@ -693,11 +694,15 @@ int lr_tens_features_passes(gpsig_ctx* c, const gpsig_params* p, const gpsig_low
     return finish(c);
 }
 
-// gpsig_lr_seq_features in T: the fused kernels (lr_fused_kernel.hpp: one workgroup per sequence, intermediates in LDS) where a sequence's
-// arrays fit, else the multi-pass route -- float64 only: for float32 that is UNSUPPORTED, and the Python layer computes the call in float64
-// and rounds it.  float64 tests the three-array footprint before it may pick either form, float32 the footprint of the form it picks.
+// gpsig_lr_seq_features / gpsig_lr_seq_features_ragged in T.  Whole sequences (`ragged` false): the fused kernels (lr_fused_kernel.hpp: one
+// workgroup per sequence, intermediates in LDS) where a sequence's arrays fit; beyond them, with lr_fused != 0, the time-tiled kernels of
+// lr_eval_tiled.hpp where at least one 64-step tile fits (float32: the families of base_eval only); else the multi-pass route -- float64
+// only: for float32 that is UNSUPPORTED, and the Python layer computes the call in float64 and rounds it.  float64 tests the three-array
+// footprint before it may pick either fused form, float32 the footprint of the form it picks.  Ragged (`lengths`: N int32 in the context's
+// pointer mode): the tiled kernels at every length -- a short batch is a one-tile walk -- whatever lr_fused says; there is no multi-pass form.
 template <typename T>
-int lr_seq_features_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L, void* Phi) {
+int lr_seq_features_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L, bool ragged,
+                      const int32_t* lengths, void* Phi) {
     constexpr bool f32 = std::is_same<T, float>::value;
     const int M = p->num_levels, cc = lr->num_components, r = lr->rank_bound;
     ScaleParams s;
@@ -707,29 +712,50 @@ int lr_seq_features_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* 
     const bool two = c->lr_fused == 1 && lr_fused2_ok(cc, r, L);
     const size_t lds = !f32 ? lr_fused_lds_bytes(cc, r, d_eff, L, c->lr_fused_pad)
                        : two ? lr_fused2_lds_bytes_f32(cc, r, d_eff, L, c->lr_fused_pad) : lr_fused_lds_bytes_f32(cc, r, d_eff, L, c->lr_fused_pad);
-    const bool fused = c->lr_fused != 0 && lds <= LR_FUSED_MAX_LDS && M - 1 <= LR_FUSED_MAX_SKETCHES;
-    if (f32 && !fused)
+    const bool levels_ok = M - 1 <= LR_FUSED_MAX_SKETCHES;
+    const bool fused = !ragged && c->lr_fused != 0 && lds <= LR_FUSED_MAX_LDS && levels_ok;
+    const LrTileDir TD = lr_eval_tile_dir(f32, cc, r, d_eff, L - (p->difference ? 1 : 0), c->lr_fused_pad);
+    const bool tiled = !fused && (ragged || c->lr_fused != 0) && TD.TL > 0 && levels_ok && !(f32 && p->base_kernel == GPSIG_BASE_SPECTRAL);
+    if (ragged && !tiled)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "ragged low-rank features need one 64-step tile of the tiled kernels in the LDS (%zu bytes), at most %d "
+                    "levels, and float64 for SignatureSpectral", lr_eval_tiled_lds_bytes(f32, cc, r, d_eff, LR_TILE_STEP, c->lr_fused_pad), LR_FUSED_MAX_SKETCHES + 1);
+    if (f32 && !fused && !tiled)
         return fail(c, GPSIG_ERR_UNSUPPORTED, "float32 low-rank features are built for the fused kernels only (lr_fused != 0, %zu bytes of LDS)", lds);
     LrDev D;
     CHK(lr_upload(c, lr, d_eff, &D));
     const int F = 1 + cc + (M - 1) * r;
     const void* dX;
     CHK(in_dev(c, B_IN0, X, sizeof(T) * size_t(N) * L * p->num_features, &dX));
+    const void* dlen = nullptr;
+    if (ragged) CHK(in_dev(c, B_IN1, lengths, sizeof(int32_t) * size_t(N), &dlen));
     void* dPhi;
     CHK(out_dev(c, B_OUT0, Phi, sizeof(T) * size_t(N) * F, &dPhi));
     double p0, p1;
     base_p(p, &p0, &p1);
     const double* spec = nullptr;        // BASE_SPECTRAL: its parameter table (p0 = Q, p1 = family), read by the spectral instances
     if (!f32 || N > 0) CHK(spectral_table(c, p, &spec));                     // (float32 uploads nothing for an empty call)
-    if (!fused) return lr_seq_features_passes(c, p, lr, s, D, static_cast<const double*>(dX), N, L, spec, Phi, dPhi);
+    if (!fused && !tiled) return lr_seq_features_passes(c, p, lr, s, D, static_cast<const double*>(dX), N, L, spec, Phi, dPhi);
     if (N <= 0) return finish(c);
-    std::conditional_t<f32, LrFusedArgsF32, LrFusedArgs> A{};
-    A.X = static_cast<const T*>(dX); A.N = N; A.L = L; A.P = s;
-    A.c = cc; A.r = r; A.M = M; A.difference = p->difference; A.kind = int(p->base_kernel); A.p0 = T(p0); A.p1 = T(p1);
-    A.Phi = static_cast<T*>(dPhi);
-    CHK(lr_state_args(c, p, D, d_eff, spec, &A));
-    const int rc = lr_fused_launch(c->stream, A, c->lr_fused_pad, two, c->lr_fused_variant);
-    if (rc != 0) return fail(c, GPSIG_ERR_HIP, f32 ? "fused float32 low-rank feature kernel: %s" : "fused low-rank feature kernel: %s", hipGetErrorString(hipError_t(rc)));
+    int rc;
+    if (tiled) {
+        std::conditional_t<f32, LrEvalTiledArgsF32, LrEvalTiledArgs> A{};
+        A.X = static_cast<const T*>(dX); A.N = N; A.L = L; A.P = s;
+        A.c = cc; A.r = r; A.M = M; A.difference = p->difference; A.kind = int(p->base_kernel); A.p0 = T(p0); A.p1 = T(p1);
+        A.Phi = static_cast<T*>(dPhi);
+        A.lengths = static_cast<const int32_t*>(dlen);
+        CHK(lr_state_args(c, p, D, d_eff, spec, &A));
+        rc = lr_eval_tiled_launch(c->stream, A, c->lr_fused_pad);
+    } else {
+        std::conditional_t<f32, LrFusedArgsF32, LrFusedArgs> A{};
+        A.X = static_cast<const T*>(dX); A.N = N; A.L = L; A.P = s;
+        A.c = cc; A.r = r; A.M = M; A.difference = p->difference; A.kind = int(p->base_kernel); A.p0 = T(p0); A.p1 = T(p1);
+        A.Phi = static_cast<T*>(dPhi);
+        CHK(lr_state_args(c, p, D, d_eff, spec, &A));
+        rc = lr_fused_launch(c->stream, A, c->lr_fused_pad, two, c->lr_fused_variant);
+    }
+    if (rc != 0)
+        return fail(c, GPSIG_ERR_HIP, f32 ? "%s float32 low-rank feature kernel: %s" : "%s low-rank feature kernel: %s", tiled ? "tiled" : "fused",
+                    hipGetErrorString(hipError_t(rc)));
     CHK(out_done(c, Phi, dPhi, sizeof(T) * size_t(N) * F));
     return finish(c);
 }
@@ -2465,6 +2491,13 @@ void gpsig_graph_destroy(gpsig_graph* G) {
     delete G;
 }
 
+int64_t gpsig_scratch_bytes(gpsig_ctx* c) {
+    if (!c) return 0;
+    size_t total = 0;
+    for (int i = 0; i < B_COUNT; ++i) total += c->buf[i].cap;
+    return int64_t(total);
+}
+
 int gpsig_timing_reset(gpsig_ctx* c) {
     if (!c) return GPSIG_ERR_INVALID;
     CHK(host_sync(c));
@@ -2831,8 +2864,19 @@ int gpsig_lr_whitening(gpsig_ctx* c, const gpsig_params* p, const double* S_host
 int gpsig_lr_seq_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L, void* Phi) {
     ENTER_LR(c, p);
     CHK(lr_check(c, p, lr));
-    if (p->dtype == GPSIG_F32) return lr_seq_features_t<float>(c, p, lr, X, N, L, Phi);
-    return lr_seq_features_t<double>(c, p, lr, X, N, L, Phi);
+    if (p->dtype == GPSIG_F32) return lr_seq_features_t<float>(c, p, lr, X, N, L, false, nullptr, Phi);
+    return lr_seq_features_t<double>(c, p, lr, X, N, L, false, nullptr, Phi);
+}
+
+int gpsig_lr_seq_features_ragged(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L,
+                                 const int32_t* lengths, void* Phi) {
+    ENTER_LR(c, p);
+    CHK(lr_check(c, p, lr));
+    if (p->num_lags > 0)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "per-sequence lengths are not built for num_lags > 0: the lag interpolation runs on the table's own time axis");
+    if (!lengths && N > 0) return fail(c, GPSIG_ERR_INVALID, "null lengths pointer");
+    if (p->dtype == GPSIG_F32) return lr_seq_features_t<float>(c, p, lr, X, N, L, true, lengths, Phi);
+    return lr_seq_features_t<double>(c, p, lr, X, N, L, true, lengths, Phi);
 }
 
 int gpsig_lr_tens_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* Z, int64_t T, int32_t increments,

@@ -1,6 +1,6 @@
 // lr_tile_plan.hpp -- LDS footprints of the low-rank sequence feature kernels and the time-tile plan of their tiled forms.
 // HIP-free (constexpr helpers are usable on the device): read by lr_fused_args.hpp / lr_grad_kernel.hpp (the whole-sequence kernels),
-// lr_tiled_kernel.hpp, the host path of lr_grad_api.hip and tests/emu/test_lr_tile_plan.cpp.
+// lr_tiled_kernel.hpp, lr_eval_tiled_inst.hip, the host paths of lr_grad_api.hip and api.hip, and tests/emu/test_lr_tile_plan.cpp.
 //
 // The whole-sequence kernels keep (width, L) arrays of a sequence in LDS: three in the forward direction (lr_fused_lds_bytes), four in the
 // reverse pass (lr_grad_lds_bytes).  Where those exceed LR_FUSED_MAX_LDS, the tiled kernels walk the sequence in tiles of TL time steps
@@ -79,6 +79,27 @@ inline LrTileDir lr_tile_dir(bool reverse, int c, int r, int d, int L, int l, in
     D.ntiles = TL ? lr_tile_count(l, TL) : 0;
     D.lp = D.untiled ? lr_fused_stride(L, pad) : lr_tile_stride(TL, pad);
     D.lds = D.untiled ? whole : TL ? (reverse ? lr_tiled_grad_lds_bytes(c, r, d, TL, pad) : lr_tiled_fused_lds_bytes(c, r, d, TL, pad)) : 0;
+    return D;
+}
+
+// ---- the evaluation side's tiled forward family (lr_eval_tiled.hpp): the forward layout -- U [c], two work arrays [rows], one carry row per
+// level -- in the element type of the call.  float32 keeps arrays and carries in float: its own footprint, about twice the tile length.
+constexpr size_t lr_eval_tiled_lds_bytes_f32(int c, int r, int d, int TL, int pad = 1) {
+    return sizeof(float) * (size_t(lr_tile_stride(TL, pad)) * (size_t(c) + 2 * size_t(lr_fused_rows(c, r, d))) + lr_tiled_fused_carry(c, r, d));
+}
+constexpr size_t lr_eval_tiled_lds_bytes(bool f32, int c, int r, int d, int TL, int pad = 1) {
+    return f32 ? lr_eval_tiled_lds_bytes_f32(c, r, d, TL, pad) : lr_tiled_fused_lds_bytes(c, r, d, TL, pad);
+}
+// the family's plan for sequences of l steps (as lr_tile_dir's tiled half: TL the largest multiple of 64 that fits, 0 where none does);
+// `untiled` is left false -- whether a whole-sequence kernel serves the call is the caller's decision
+inline LrTileDir lr_eval_tile_dir(bool f32, int c, int r, int d, int l, int pad) {
+    LrTileDir D{};
+    int TL = 0;
+    while (lr_eval_tiled_lds_bytes(f32, c, r, d, TL + LR_TILE_STEP, pad) <= LR_FUSED_MAX_LDS && TL < (1 << 20)) TL += LR_TILE_STEP;
+    D.TL = TL;
+    D.ntiles = TL ? lr_tile_count(l, TL) : 0;
+    D.lp = lr_tile_stride(TL, pad);
+    D.lds = TL ? lr_eval_tiled_lds_bytes(f32, c, r, d, TL, pad) : 0;
     return D;
 }
 

@@ -474,17 +474,22 @@ class SignatureKernel:
         return GraphedCall(g, tensors, out, side)
 
     @_f32_upcast
-    def K(self, X, X2=None, presliced=False, return_levels=False, presliced_X=False, presliced_X2=False, lr_state=None):
+    def K(self, X, X2=None, presliced=False, return_levels=False, presliced_X=False, presliced_X2=False, lr_state=None, lengths=None,
+          lengths2=None):
         """Reference: kernels.py:401-476.  (N1, N2) or (M+1, N1, N2).  lr_state: low-rank mode only, the random
-        objects to use (default: drawn afresh, as the reference does)."""
+        objects to use (default: drawn afresh, as the reference does).
+        lengths / lengths2 (low-rank mode): per-sequence lengths of a ragged X / X2 -- ints, a NumPy array or a torch tensor, 1 <= l <= L.
+        Sequence n is X[n, :lengths[n]]; what the rows beyond hold does not matter (NaN included)."""
         if presliced:
             presliced_X = presliced_X2 = True
         if not presliced_X:
             X, _ = self._slice(X, None)
         if not presliced_X2 and X2 is not None:
             X2, _ = self._slice(X2, None)
+        lengths = self._ragged_lengths(lengths, X)
+        lengths2 = self._ragged_lengths(lengths2, X2)
         if self.low_rank:
-            return self._K_lr(X, X2, return_levels, lr_state)
+            return self._K_lr(X, X2, return_levels, lr_state, lengths, lengths2)
         L_ = _Launch(X, X2)
         n1, l1 = self._seq_dims(X)
         n2, l2 = self._seq_dims(X2) if X2 is not None else (n1, l1)
@@ -494,16 +499,18 @@ class SignatureKernel:
         return out
 
     @_f32_upcast
-    def Kdiag(self, X, presliced=False, return_levels=False, lr_state=None):
-        """Reference: kernels.py:479-510.  (N,) or (M+1, N)."""
+    def Kdiag(self, X, presliced=False, return_levels=False, lr_state=None, lengths=None):
+        """Reference: kernels.py:479-510.  (N,) or (M+1, N).  lengths: as in K (normalised, the diagonal reads no features: they are
+        checked and ignored)."""
         if not presliced:
             X, _ = self._slice(X, None)
+        lengths = self._ragged_lengths(lengths, X)
         if self.low_rank and not self.normalization:
             L_ = _launch_lr(self, X)
-            st = lr_state or self.draw_low_rank(X=X, _implicit=True)
+            st = lr_state or self.draw_low_rank(X=self._real_points(X, lengths), _implicit=True)
             p = self._params(L_.keep, L_.dtype_id)
             lr = st.as_c(L_.keep)
-            Phi, pp, n = self._lr_features(L_, p, lr, X)
+            Phi, pp, n = self._lr_features(L_, p, lr, X, lengths=lengths)
             out, optr = L_.out((self.num_levels + 1, n) if return_levels else (n,))
             L_.ctx.call("gpsig_lr_kernel_diag", p, lr, pp, n, int(bool(return_levels)), optr)
             return out
@@ -534,17 +541,18 @@ class SignatureKernel:
         return out
 
     @_f32_upcast
-    def K_tens_vs_seq(self, Z, X, return_levels=False, increments=False, presliced=False, lr_state=None):
-        """Reference: kernels.py:539-588.  (T, N) or (M+1, T, N); normalised on the sequence axis only."""
+    def K_tens_vs_seq(self, Z, X, return_levels=False, increments=False, presliced=False, lr_state=None, lengths=None):
+        """Reference: kernels.py:539-588.  (T, N) or (M+1, T, N); normalised on the sequence axis only.  lengths: as in K."""
         if not presliced:
             X, _ = self._slice(X, None)
+        lengths = self._ragged_lengths(lengths, X)
         if self.low_rank:
             L_ = _launch_lr(self, Z, X)
-            st = lr_state or self.draw_low_rank(X=X, Z=Z, increments=increments, _implicit=True)
+            st = lr_state or self.draw_low_rank(X=self._real_points(X, lengths), Z=Z, increments=increments, _implicit=True)
             p = self._params(L_.keep, L_.dtype_id)
             lr = st.as_c(L_.keep)
             PZ, pz, t = self._lr_features(L_, p, lr, Z, tensors=True, increments=increments)
-            PX, px, n = self._lr_features(L_, p, lr, X)
+            PX, px, n = self._lr_features(L_, p, lr, X, lengths=lengths)
             out, optr = L_.out((self.num_levels + 1, t, n) if return_levels else (t, n))
             L_.ctx.call("gpsig_lr_kernel", p, lr, pz, px, t, n, 0, int(bool(self.normalization)), int(bool(return_levels)), optr)
             return out
@@ -558,13 +566,14 @@ class SignatureKernel:
         return out
 
     @_f32_upcast
-    def K_tens_n_seq_covs(self, Z, X, full_X_cov=False, return_levels=False, increments=False, presliced=False):
-        """Reference: kernels.py:591-671.  Returns (Kzz, Kzx, Kxx); Kxx is the diagonal unless full_X_cov."""
+    def K_tens_n_seq_covs(self, Z, X, full_X_cov=False, return_levels=False, increments=False, presliced=False, lengths=None):
+        """Reference: kernels.py:591-671.  Returns (Kzz, Kzx, Kxx); Kxx is the diagonal unless full_X_cov.  lengths: as in K."""
         if not presliced:
             X, _ = self._slice(X, None)
+        lengths = self._ragged_lengths(lengths, X)
         if self.low_rank:
             # one shared draw of landmarks / projections for all three matrices (kernels.py:613-621)
-            st = self.draw_low_rank(X=X, Z=Z, increments=increments)
+            st = self.draw_low_rank(X=self._real_points(X, lengths), Z=Z, increments=increments)
             L_ = _launch_lr(self, Z, X)
             p = self._params(L_.keep, L_.dtype_id)
             lr = st.as_c(L_.keep)
@@ -572,7 +581,7 @@ class SignatureKernel:
             m1 = (self.num_levels + 1,) if return_levels else ()
             # the two factor matrices once (kernels.py:613-621), then the three products of :623-661
             PZ, pz, t = self._lr_features(L_, p, lr, Z, tensors=True, increments=increments)
-            PX, px, n = self._lr_features(L_, p, lr, X)
+            PX, px, n = self._lr_features(L_, p, lr, X, lengths=lengths)
             Kzz, ozz = L_.out(m1 + (t, t))
             L_.ctx.call("gpsig_lr_kernel", p, lr, pz, None, t, t, 0, 0, lv, ozz)
             Kzx, ozx = L_.out(m1 + (t, n))
@@ -581,7 +590,7 @@ class SignatureKernel:
                 Kxx, oxx = L_.out(m1 + (n, n))
                 L_.ctx.call("gpsig_lr_kernel", p, lr, px, None, n, n, nrm, nrm, lv, oxx)
             elif self.normalization:
-                Kxx = self.Kdiag(X, presliced=True, return_levels=return_levels, lr_state=st)     # sigma * variances: no features needed
+                Kxx = self.Kdiag(X, presliced=True, return_levels=return_levels, lr_state=st, lengths=lengths)   # sigma * variances: no features needed
             else:
                 Kxx, oxx = L_.out(m1 + (n,))
                 L_.ctx.call("gpsig_lr_kernel_diag", p, lr, px, n, lv, oxx)
@@ -599,14 +608,15 @@ class SignatureKernel:
         return Kzz, Kzx, Kxx
 
     @_f32_upcast
-    def K_seq_n_seq_covs(self, X, X2, full_X2_cov=False, return_levels=False, presliced=False, lr_state=None):
+    def K_seq_n_seq_covs(self, X, X2, full_X2_cov=False, return_levels=False, presliced=False, lr_state=None, lengths2=None):
         """Reference: kernels.py:674-761 (X = inducing sequences, X2 = data).  Returns (Kxx, Kxx2, Kx2x2).
         The double division of Kxx2 by the X-side diagonal in the diagonal-only branch (:713 + :750) is
-        reproduced; the undefined names of :723-728 are read as the evident mirror of :709-712."""
+        reproduced; the undefined names of :723-728 are read as the evident mirror of :709-712.  lengths2: as in K, for X2."""
         if not presliced:
             X2, _ = self._slice(X2, None)
+        lengths2 = self._ragged_lengths(lengths2, X2)
         if self.low_rank:
-            return self._K_seq_n_seq_covs_lr(X, X2, full_X2_cov, return_levels, lr_state)
+            return self._K_seq_n_seq_covs_lr(X, X2, full_X2_cov, return_levels, lr_state, lengths2)
         L_ = _Launch(X, X2)
         n1, l1 = self._seq_dims(X)
         n2, l2 = self._seq_dims(X2)
@@ -631,12 +641,15 @@ class SignatureKernel:
                 Zf = Zf * np.asarray(self.gamma)[None, :, None]
         return Zf.reshape(-1, d_eff)
 
-    def draw_low_rank(self, X=None, X2=None, Z=None, increments=False, _implicit=False):
+    def draw_low_rank(self, X=None, X2=None, Z=None, increments=False, _implicit=False, lengths=None):
         """Draw the landmarks (uniformly, without replacement, from the scaled points of every given argument:
         kernels.py:444-446, :562-563), whiten their Gram (low_rank_calculations.py:50-57) and draw one projection
         per level (low_rank_calculations.py:76-193).  Returns a LowRankState that can be passed to K(..., lr_state=).
         A state returned to the caller is the caller's: later draws never write into it, for host arrays and CUDA tensors alike
-        (only the per-evaluation draws of K / Kdiag / K_tens / ... with lr_state=None reuse one device block of the kernel object)."""
+        (only the per-evaluation draws of K / Kdiag / K_tens / ... with lr_state=None reuse one device block of the kernel object).
+        lengths: per-sequence lengths of a ragged X (as in K): the pool the landmarks are drawn from holds real points only."""
+        if lengths is not None:
+            X = self._real_points(X, self._ragged_lengths(lengths, X))
         L_ = _launch_lr(self, X, X2, Z)
         if L_.device_mode and self.device_draw:
             return self._draw_low_rank_on_device(L_, X, X2, Z, increments, reuse=_implicit)
@@ -714,7 +727,43 @@ class SignatureKernel:
         rb = sk[0].r if sk else int(self.rank_bound)
         return LowRankState(S, Wh, sk, rb, jitter_diag=jd, eigenvalues=ev)
 
-    def _lr_features(self, L_, p, lr, A, tensors=False, increments=False):
+    def _ragged_lengths(self, lengths, X):
+        """``lengths=`` of a public evaluation -> (N,) int32 on the host, checked before any library call: a sequence of ints, a NumPy array or
+        a torch tensor on any device; integers, shape (N,), 1 <= l <= L (ValueError otherwise).  X: the sliced table."""
+        if lengths is None:
+            return None
+        if not self.low_rank:
+            raise NotImplementedError("lengths= is built for low-rank mode only: in exact mode pad each sequence by repeating its last "
+                                      "observation, which is exact there with difference=True (zero increments add nothing)")
+        if self.num_lags > 0:
+            raise NotImplementedError("lengths= is not built for num_lags > 0: the lag interpolation runs on the table's own time axis")
+        if X is None:
+            raise ValueError("lengths given without their sequences")
+        N, L = self._seq_dims(X)
+        host = lengths.detach().cpu().numpy() if _is_torch(lengths) else np.asarray(lengths)
+        if host.dtype.kind not in "iu":
+            raise ValueError("lengths must be integers, got %s" % host.dtype)
+        if host.shape != (N,):
+            raise ValueError("lengths must have shape (%d,), got %s" % (N, tuple(host.shape)))
+        if N and (int(host.min()) < 1 or int(host.max()) > L):
+            raise ValueError("lengths must lie in [1, %d], got [%d, %d]" % (L, int(host.min()), int(host.max())))
+        return np.ascontiguousarray(host, dtype=np.int32)
+
+    def _real_points(self, X, lengths):
+        """The table the landmarks are drawn from: each row beyond a sequence's length replaced by the sequence's last valid row (a gather of
+        valid rows: nothing, NaN included, comes from the padded ones), so that the pool holds real points only.  lengths: checked, or None."""
+        if lengths is None:
+            return X
+        N, L = self._seq_dims(X)
+        shp = _shape(X)
+        if _is_torch(X):
+            lens = torch.as_tensor(lengths, device=X.device).long()
+            idx = torch.minimum(torch.arange(L, device=X.device)[None, :], (lens - 1)[:, None])
+            return X.reshape(N, L, self.num_features)[torch.arange(N, device=X.device)[:, None], idx].reshape(shp)
+        idx = np.minimum(np.arange(L)[None, :], lengths.astype(np.int64)[:, None] - 1)
+        return np.asarray(X).reshape(N, L, self.num_features)[np.arange(N)[:, None], idx].reshape(shp)
+
+    def _lr_features(self, L_, p, lr, A, tensors=False, increments=False, lengths=None):
         F = 1 + lr.num_components + (self.num_levels - 1) * lr.rank_bound
         if tensors:
             t = self._tens_dims(A, increments)
@@ -723,36 +772,42 @@ class SignatureKernel:
             return Phi, pp, t
         n, l = self._seq_dims(A)
         Phi, pp = L_.out((n, F))
+        if lengths is not None:                     # checked host int32 (_ragged_lengths); the library reads them in the call's pointer mode
+            lens = torch.as_tensor(lengths, device=L_.dev) if L_.device_mode else lengths
+            L_.keep.append(lens)
+            lp = C.c_void_p(lens.data_ptr() if L_.device_mode else lens.ctypes.data)
+            L_.ctx.call("gpsig_lr_seq_features_ragged", p, lr, L_.inp(A), n, l, lp, pp)
+            return Phi, pp, n
         L_.ctx.call("gpsig_lr_seq_features", p, lr, L_.inp(A), n, l, pp)
         return Phi, pp, n
 
-    def _K_lr(self, X, X2, return_levels, lr_state):
+    def _K_lr(self, X, X2, return_levels, lr_state, lengths=None, lengths2=None):
         L_ = _launch_lr(self, X, X2)
-        st = lr_state or self.draw_low_rank(X=X, X2=X2, _implicit=True)
+        st = lr_state or self.draw_low_rank(X=self._real_points(X, lengths), X2=self._real_points(X2, lengths2), _implicit=True)
         p = self._params(L_.keep, L_.dtype_id)
         lr = st.as_c(L_.keep)
-        PA, pa, n1 = self._lr_features(L_, p, lr, X)
+        PA, pa, n1 = self._lr_features(L_, p, lr, X, lengths=lengths)
         if X2 is None:
             PB, pb, n2 = None, None, n1
         else:
-            PB, pb, n2 = self._lr_features(L_, p, lr, X2)
+            PB, pb, n2 = self._lr_features(L_, p, lr, X2, lengths=lengths2)
         out, optr = L_.out((self.num_levels + 1, n1, n2) if return_levels else (n1, n2))
         nrm = int(bool(self.normalization))
         L_.ctx.call("gpsig_lr_kernel", p, lr, pa, pb, n1, n2, nrm, nrm, int(bool(return_levels)), optr)
         return out
 
-    def _K_seq_n_seq_covs_lr(self, X, X2, full_X2_cov, return_levels, lr_state):
+    def _K_seq_n_seq_covs_lr(self, X, X2, full_X2_cov, return_levels, lr_state, lengths2=None):
         """kernels.py:696-761, low-rank branch: level Grams of the factor matrices (HIP: features + fp64-MFMA GEMMs), then the
         normalisation / weighting of :706-761 as elementwise torch ops on the device."""
         L_ = _launch_lr(self, X, X2)
-        st = lr_state or self.draw_low_rank(X=X, X2=X2, _implicit=True)
+        st = lr_state or self.draw_low_rank(X=X, X2=self._real_points(X2, lengths2), _implicit=True)
         p = self._params(L_.keep, L_.dtype_id)
         ones = np.ones(self.num_levels + 1)
         L_.keep.append(ones)
         p.sigma, p.variances = 1.0, ones.ctypes.data_as(C.POINTER(C.c_double))      # raw level Grams; weights are applied below
         lr = st.as_c(L_.keep)
         P1, pp1, n1 = self._lr_features(L_, p, lr, X)
-        P2, pp2, n2 = self._lr_features(L_, p, lr, X2)
+        P2, pp2, n2 = self._lr_features(L_, p, lr, X2, lengths=lengths2)
         M1 = self.num_levels + 1
         Kxx, o11 = L_.out((M1, n1, n1))
         Kxx2, o12 = L_.out((M1, n1, n2))

@@ -118,13 +118,14 @@ class SVGP:
             q_sqrt = np.ones((m, self.num_latent)) if q_diag else np.tile(np.eye(m)[None], [self.num_latent, 1, 1])
         self.q_sqrt = q_sqrt
 
-    def _covs(self, X_new, full_cov):
-        Kzz, Kzx, Kxx = iv.Kuu_Kuf_Kff(self.feature, self.kern, X_new, jitter=JITTER, full_f_cov=full_cov)   # models.py:65
+    def _covs(self, X_new, full_cov, lengths=None):
+        Kzz, Kzx, Kxx = iv.Kuu_Kuf_Kff(self.feature, self.kern, X_new, jitter=JITTER, full_f_cov=full_cov, lengths=lengths)   # models.py:65
         return _dev(Kzz, self.device), _dev(Kzx, self.device), _dev(Kxx, self.device)
 
-    def predict_f(self, X_new, full_cov=False, return_Kzz=False):
-        """models.py:62-73.  Returns (f_mean (N, R), f_var (N, R) or (R, N, N)) as torch tensors on the device."""
-        Kzz, Kzx, Kxx = self._covs(X_new, full_cov)
+    def predict_f(self, X_new, full_cov=False, return_Kzz=False, lengths=None):
+        """models.py:62-73.  Returns (f_mean (N, R), f_var (N, R) or (R, N, N)) as torch tensors on the device.
+        lengths: per-sequence lengths of a ragged X_new (low-rank mode: SignatureKernel.K)."""
+        Kzz, Kzx, Kxx = self._covs(X_new, full_cov, lengths)
         q_mu, q_sqrt = _dev(self.q_mu, self.device), _dev(self.q_sqrt, self.device)
         if not self.q_diag:
             q_sqrt = torch.tril(q_sqrt)                                                             # models.py:66

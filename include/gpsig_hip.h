@@ -180,6 +180,9 @@ int gpsig_set_shard(gpsig_ctx* ctx, int index, int count);
  *                 <= 5 levels, min(order, levels) <= 4, lattices of <= 512 columns): 0 scratch-free where the row totals fit LDS, 3 with
  *                 the prefixes in an HBM slot per pair group, any other value the lattice operations of rounds 2-5 (tests' A/B reference) */
 int gpsig_set_option(gpsig_ctx* ctx, const char* name, int value);
+/* Bytes of device memory the context holds in its scratch buffers now (staging, task lists, intermediates; they grow on demand and are
+ * kept until the context is destroyed).  No synchronisation, no device call. */
+int64_t gpsig_scratch_bytes(gpsig_ctx* ctx);
 /* HIP-event timing of the dominant kernel (the pair recursion) launched by the calls since the last
  * reset, measured on the ctx stream: total milliseconds and number of launches (the first 4096 timed
  * launches after a reset; none inside a graph capture). */
@@ -286,8 +289,8 @@ int gpsig_kernel_K_seq_n_seq_covs(gpsig_ctx* ctx, const gpsig_params* p, const v
 /* ---- low-rank mode (low_rank=True): gpsig/low_rank_calculations.py, gpsig/signature_algs.py:162-222,
  * gpsig/kernels.py:239-311, :424-426, :442-458, :499-501, :525-527, :560-574.
  * Float types: the state (landmarks, whitening, projections) is float64 always.  p->dtype = GPSIG_F32 (float32 points, features and
- * Grams) is accepted by gpsig_lr_seq_features / gpsig_lr_tens_features (the fused kernels only: option lr_fused != 0 and the float32
- * LDS footprint within bounds, else GPSIG_ERR_UNSUPPORTED), gpsig_lr_kernel / gpsig_lr_kernel_diag (float32 factors in, float32 out),
+ * Grams) is accepted by gpsig_lr_seq_features / gpsig_lr_seq_features_ragged / gpsig_lr_tens_features (the fused and the time-tiled kernels
+ * only: option lr_fused != 0 and the float32 LDS footprint within bounds, else GPSIG_ERR_UNSUPPORTED), gpsig_lr_kernel / gpsig_lr_kernel_diag (float32 factors in, float32 out),
  * and gpsig_lr_draw / gpsig_lr_gather_points (float32 points, widened before any arithmetic: the state drawn is bitwise that of the
  * widened points).  The spectral base kernel included.  Every other low-rank entry point is float64 only.
  *
@@ -448,8 +451,21 @@ int gpsig_spectral_cross(gpsig_ctx* ctx, int32_t Q, int32_t family, int32_t d, c
 int gpsig_spectral_cross_grad(gpsig_ctx* ctx, int32_t Q, int32_t family, int32_t d, const double* P, int64_t n, const double* S, int32_t c,
                               const double* alpha, const double* omega, const double* gamma, const double* G, double* dP, double* dS,
                               double* dalpha, double* domega, double* dgamma);
-/* SignatureKernel._K_seq_lr_feat (kernels.py:239-261): Nystrom_map + signature_kern_first_order_lr_feature.  Phi: (N, F). */
+/* SignatureKernel._K_seq_lr_feat (kernels.py:239-261): Nystrom_map + signature_kern_first_order_lr_feature.  Phi: (N, F).
+ * With option lr_fused != 0 (the default): one fused kernel where a sequence's three (width, L) arrays fit the LDS; beyond that the
+ * time-tiled kernels (csrc/lr_eval_tiled.hpp: tiles of a multiple of 64 time steps, one carried vector per level, the raw points scaled in
+ * the kernel -- lengthscales and lags included), in float64 and float32, where at least one 64-step tile fits; SignatureSpectral's tiled
+ * kernel is float64 only (float32: GPSIG_ERR_UNSUPPORTED there).  lr_fused = 0, or not even one tile: the multi-pass route (float64 only),
+ * which streams five (N, L, max(c, r)) arrays of context-owned scratch. */
 int gpsig_lr_seq_features(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L, void* Phi);
+/* ... for a RAGGED batch: lengths (N int32, in the context's pointer mode like X; host pointers are copied in), sequence n is
+ * X[n, :lengths[n]] and Phi[n] its features evaluated alone.  The rows beyond a sequence's length are never read (they may hold NaN);
+ * lengths are clamped to [1, L] on the device.  A sequence of one point with p->difference has no steps: Phi[n] = [1, 0, .., 0].  Served by
+ * the time-tiled kernels at every length, whatever lr_fused says; float64 and float32, SignatureSpectral in float64 only.
+ * GPSIG_ERR_UNSUPPORTED: p->num_lags > 0 (the lag interpolation runs on the table's own time axis), float32 SignatureSpectral, shapes
+ * whose 64-step tile exceeds the LDS. */
+int gpsig_lr_seq_features_ragged(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L,
+                                 const int32_t* lengths, void* Phi);
 /* SignatureKernel._K_tens_lr_feat (kernels.py:285-311): Nystrom_map + tensor_kern_lr_feature.  Phi: (T, F). */
 int gpsig_lr_tens_features(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_lowrank* lr, const void* Z, int64_t T,
                            int32_t increments, void* Phi);
