@@ -1395,7 +1395,9 @@ static int generic_levels(gpsig_ctx* c, const gpsig_params* p, bool apply_scalin
     CHK(scale_params(c, p, apply_scaling, &sp));
     const int d_eff = sp.d_eff(), M = p->num_levels;
     // wide route (wide_api.hip): the argument lattices by dgemm, one wavefront per lattice -- the distance kernels at order 1, up to 512 lattice columns
-    if (wide_lat_available(c, p, L1, L2) && sm == (diag ? N1 : N1 * N2) && si == (diag ? 1 : N2) && sj == (diag ? 0 : 1)) {
+    // (the dot-product families: beyond 32 columns, or by option -- up to there this fallback stays what it was for them)
+    if (wide_lat_available(c, p, L1, L2) && (!wide_dot_kind(p->base_kernel) || c->wide == 1 || d_eff > 32) && sm == (diag ? N1 : N1 * N2) && si == (diag ? 1 : N2) &&
+        sj == (diag ? 0 : 1)) {
         const bool same_ = diag || Y == nullptr || Y == X;
         void *xs, *ys = nullptr;
         CHK(ensure(c, B_GR0, sizeof(double) * size_t(N1) * L1 * d_eff + 8, &xs));
@@ -1556,7 +1558,8 @@ static int seq_K_device(gpsig_ctx* c, const gpsig_params* p, bool raw, const voi
     if (rc == GPSIG_OK && c->wide == 1 && generic_ok(p) && row_end == 0 && wide_lat_available(c, p, L1, L2)) rc = GPSIG_ERR_UNSUPPORTED;   // (option wide = 1)
     // 17 .. 32 columns, first order: the exact-shape kernels' 32-column instances hold four lattice columns x 32 features per lane at one wavefront per
     // SIMD -- a Gram of 384 sequences of 50 x 17 takes 10.8 ms there, 4.5 through the wide route's dgemm + lattice sweeps (tools/probe_shapes_rbf.py)
-    if (rc == GPSIG_OK && c->wide < 0 && sizeof(TT) == 8 && d_eff > 16 && pairs_hint >= 4096 && generic_ok(p) && row_end == 0 && !(p->order > 1 && p->num_levels > 1) &&
+    // (the dot-product families have no instance there to be pulled off: their rule reads "beyond 32 columns", where plan_seq has already said no)
+    if (rc == GPSIG_OK && c->wide < 0 && sizeof(TT) == 8 && d_eff > wide_auto_cols(p, 16) && pairs_hint >= 4096 && generic_ok(p) && row_end == 0 && !(p->order > 1 && p->num_levels > 1) &&
         wide_lat_available(c, p, L1, L2))
         rc = GPSIG_ERR_UNSUPPORTED;
     if (rc == GPSIG_ERR_UNSUPPORTED && generic_ok(p) && row_end == 0) {     // any-shape fallback (wide route where built; else orders of magnitude slower per pair)
@@ -1640,7 +1643,7 @@ static int tens_gram_device(gpsig_ctx* c, const gpsig_params* p, bool raw, const
     if (sizeof(TT) == 8 && Tn > 0) {        // wide state spaces (wide_api.hip): beyond 12 columns, or wherever built when the option says so
         ScaleParams s;
         CHK(scale_params(c, p, !raw, &s));
-        if (wide_tens_available(c, p, Tn) && (c->wide == 1 || s.d_eff() > 12)) {
+        if (wide_tens_available(c, p, Tn) && (c->wide == 1 || s.d_eff() > wide_auto_cols(p, 12))) {
             const double* w = nullptr;
             if (!raw) CHK(upload_weights(c, p, &w));
             return wide_tens_forward(c, p, s, s.d_eff(), static_cast<const double*>(Z), Tn, increments, w, (raw || return_levels) ? 0 : 1, static_cast<double*>(out));
@@ -1878,7 +1881,7 @@ static int tens_vs_seq_device(gpsig_ctx* c, const gpsig_params* p, bool raw, con
         // older mappings take -- 0.83 against 0.68 ms at UWave's shape --, the reverse pass saves its own forward sweep: 2.05 -> 1.59; option
         // wide_few_cols: the widest state space of this rule, A/B runs)
         const bool few = increments && d_eff > 4 && d_eff <= (c->wide_few_cols > 0 ? c->wide_few_cols : 8) && N <= 256 && p->base_kernel == GPSIG_BASE_RBF;
-        if (!wide_tvs_available(c, p, d_eff, Tn, N, L) || !(c->wide == 1 || d_eff > 8 || (few && c->wide != 0 && c->tvs_tile != 1))) return GPSIG_OK;
+        if (!wide_tvs_available(c, p, d_eff, Tn, N, L) || !(c->wide == 1 || d_eff > wide_auto_cols(p, 8) || (few && c->wide != 0 && c->tvs_tile != 1))) return GPSIG_OK;
         void* xs;
         CHK(ensure(c, B_XT, sizeof(double) * size_t(N) * L * d_eff + 8, &xs));
         hipLaunchKernelGGL(prep_seq_scaled_kernel<double>, dim3(grid_for(N * int64_t(L) * d_eff)), dim3(256), 0, c->stream,

@@ -512,3 +512,9 @@ inline int grid_for(int64_t n, int block = 256) {
     return int(g);
 }
 
+// ---- the wide route (wide_api.hip) and its automatic rules
+// The dot-product families (kappa = the dgemm's number itself).  Their automatic rules all read "beyond 32 columns": up to there the feature contraction and
+// the exact-shape kernels serve them (32 columns is the widest exact-shape lattice instance), and nothing has been measured that would move them.
+inline bool wide_dot_kind(int base_kernel) { return base_kernel == GPSIG_BASE_LINEAR || base_kernel == GPSIG_BASE_COSINE; }
+// the widest state space that the automatic rule of a call site keeps off the wide route (cols: the distance kernels' figure there)
+inline int wide_auto_cols(const gpsig_params* p, int cols) { return wide_dot_kind(p->base_kernel) ? 32 : cols; }

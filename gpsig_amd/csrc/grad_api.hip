@@ -847,7 +847,8 @@ int seq_grad(gpsig_ctx* c, const gpsig_params* p, const void* X, const void* Y, 
     // reference's shapes -- profiles/r06_ab_small_widths.txt; grad_impl != 0: A/B runs of the exact-shape kernels)
     // (higher order: the point route's dM and contraction kernels cost more than the sweeps -- ho_dm_kernel evaluates every kappa four times with the
     // library's exp --, so the wide route's dgemms take RBF and the Matern families at every width)
-    if (wide_ok && (c->wide == 1 || DP == 0 || wide_ho || (!ffn && c->grad_impl == 0 && (d > 8 || (!w2x && !lfn && !wfn))))) {
+    // (the dot-product families: beyond 32 columns, or by option -- up to there the feature route and the exact-shape kernels below keep them)
+    if (wide_ok && (c->wide == 1 || DP == 0 || wide_ho || (!ffn && c->grad_impl == 0 && (wide_dot_kind(p->base_kernel) ? d > 32 : (d > 8 || (!w2x && !lfn && !wfn)))))) {
         CHK(wide_lat_backward(c, p, d, static_cast<const double*>(dX), static_cast<const double*>((diag || sym) ? nullptr : dY), N1, N2, L1, L2, diag,
                               static_cast<const double*>(dG), static_cast<double*>(dgX), static_cast<double*>(dgY)));
         CHK(out_done(c, gX, dgX, xb));
@@ -1025,7 +1026,7 @@ int gpsig_tens_gram_levels_grad(gpsig_ctx* c, const gpsig_params* p, const void*
     int d, DP;
     CHK(grad_check(c, p, &d, &DP, 4096));
     if (T < 0 || T > 65535) return fail(c, GPSIG_ERR_INVALID, "bad number of tensors");
-    const bool wide = T > 0 && wide_tens_available(c, p, T) && (c->wide == 1 || d > 12);      // wide_api.hip
+    const bool wide = T > 0 && wide_tens_available(c, p, T) && (c->wide == 1 || d > wide_auto_cols(p, 12));      // wide_api.hip
     if (DP == 0 && !wide) return fail(c, GPSIG_ERR_UNSUPPORTED, "gradients are built for at most 64 feature columns here (got %d)", d);
     const int M = p->num_levels, lt = M * (M + 1) / 2, E = increments ? 2 : 1;
     const int64_t rows = int64_t(lt) * T * E;
@@ -1082,8 +1083,10 @@ int gpsig_tens_vs_seq_levels_grad(gpsig_ctx* c, const gpsig_params* p, const voi
     CHK(grad_check(c, p, &d, &DP, 4096));
     // wide state spaces (wide_api.hip): beyond the tile kernel's 8 columns, or wherever built when the option says so
     // (higher orders: at any width -- the tile kernel's reverse pass is first-order, the older kernels go through scratch memory operation by operation)
-    const bool wide = wide_tvs_available(c, p, d, T, N, L) && (c->wide == 1 || d > 8 || (p->num_levels > 6 && c->wide != 0) ||      /* (7 / 8 levels: no reverse tile instance -- 100 ms at T = 512, N = 2,048 on the older kernels) */
-                                                                (p->order > 1 && p->num_levels > 1 && c->wide != 0 && !tvs_grad_tile_ho_available(c, p, d, L, increments)));
+    // (the dot-product families: beyond 32 columns, or by option)
+    const bool wide = wide_tvs_available(c, p, d, T, N, L) && (wide_dot_kind(p->base_kernel) ? (c->wide == 1 || d > 32) :
+                                                               (c->wide == 1 || d > 8 || (p->num_levels > 6 && c->wide != 0) ||      /* (7 / 8 levels: no reverse tile instance -- 100 ms at T = 512, N = 2,048 on the older kernels) */
+                                                                (p->order > 1 && p->num_levels > 1 && c->wide != 0 && !tvs_grad_tile_ho_available(c, p, d, L, increments))));
     if (DP == 0 && !wide) return fail(c, GPSIG_ERR_UNSUPPORTED, "gradients are built for at most 64 feature columns here (got %d)", d);
     if (T < 0 || N < 0 || L < 1) return fail(c, GPSIG_ERR_INVALID, "bad sizes");
     if (N > 0x7fffffff || T > 0x7fffffff) return fail(c, GPSIG_ERR_UNSUPPORTED, "more than 2^31 items");
@@ -1428,8 +1431,10 @@ int gpsig_tens_vs_seq_weighted_grad(gpsig_ctx* c, const gpsig_params* p, const v
     int d, DP;
     CHK(grad_check(c, p, &d, &DP, 4096));
     // (higher orders: at any width -- the tile kernel's reverse pass is first-order, the older kernels go through scratch memory operation by operation)
-    const bool wide = wide_tvs_available(c, p, d, T, N, L) && (c->wide == 1 || d > 8 || (p->num_levels > 6 && c->wide != 0) ||      /* (7 / 8 levels: no reverse tile instance -- 100 ms at T = 512, N = 2,048 on the older kernels) */
-                                                                (p->order > 1 && p->num_levels > 1 && c->wide != 0 && !tvs_grad_tile_ho_available(c, p, d, L, increments)));
+    // (the dot-product families: beyond 32 columns, or by option)
+    const bool wide = wide_tvs_available(c, p, d, T, N, L) && (wide_dot_kind(p->base_kernel) ? (c->wide == 1 || d > 32) :
+                                                               (c->wide == 1 || d > 8 || (p->num_levels > 6 && c->wide != 0) ||      /* (7 / 8 levels: no reverse tile instance -- 100 ms at T = 512, N = 2,048 on the older kernels) */
+                                                                (p->order > 1 && p->num_levels > 1 && c->wide != 0 && !tvs_grad_tile_ho_available(c, p, d, L, increments))));
     if (DP == 0 && !wide) return fail(c, GPSIG_ERR_UNSUPPORTED, "gradients are built for at most 64 feature columns here (got %d)", d);
     if (T < 0 || N < 0 || L < 1) return fail(c, GPSIG_ERR_INVALID, "bad sizes");
     if (N > 0x7fffffff || T > 0x7fffffff) return fail(c, GPSIG_ERR_UNSUPPORTED, "more than 2^31 items");

@@ -1,7 +1,9 @@
 // wide_api.hip -- host side of the wide-state-space route (wide_kernels.hpp): augmented rows, the kernel-argument array by rocBLAS dgemm in chunks
 // of whole sequences, the fused map / difference / chain kernels, and for the reverse pass the adjoint array contracted back by two more dgemms.
 // Called from api.hip (evaluations, level primitives) and grad_api.hip (their gradients) with device pointers; *done = false leaves the call to the
-// exact-shape kernels.  float64, order 1, RBF and the Matern families (the distance kernels: kappa is a function of the ONE number the dgemm yields).
+// exact-shape kernels.  float64; RBF and the Matern families (the distance kernels: kappa is a function of the ONE number the dgemm yields) and the two
+// dot-product families, whose kappa IS that number: SignatureLinear on plain rows -- increments where the kernel takes differences, so that the kernels run in
+// their difference = 0 form on one row less and half the tensor columns --, SignatureCosine on unit rows.
 #include "ctx.hpp"
 #include "launchers.hpp"
 #include "aux_kernels.hpp"
@@ -13,8 +15,25 @@ namespace gpsig {
 namespace {
 
 bool wide_kind(int base_kernel) {
-    return base_kernel == GPSIG_BASE_RBF || base_kernel == GPSIG_BASE_MATERN12 || base_kernel == GPSIG_BASE_MATERN32 || base_kernel == GPSIG_BASE_MATERN52;
+    return base_kernel == GPSIG_BASE_RBF || base_kernel == GPSIG_BASE_MATERN12 || base_kernel == GPSIG_BASE_MATERN32 || base_kernel == GPSIG_BASE_MATERN52 ||
+           wide_dot_kind(base_kernel);
 }
+// the kernels' compile-time kind, and the form of the rows that go into the dgemm
+int kind_of(int base_kernel) { return base_kernel == GPSIG_BASE_RBF ? WIDE_KD_RBF : (wide_dot_kind(base_kernel) ? WIDE_KD_ID : WIDE_KD_MATERN); }
+int rows_mode(int base_kernel) { return base_kernel == GPSIG_BASE_LINEAR ? WIDE_ROWS_PLAIN : (base_kernel == GPSIG_BASE_COSINE ? WIDE_ROWS_UNIT : WIDE_ROWS_DIST); }
+// SignatureLinear: <.,.> is bilinear, so the differences along the sequences (signature_algs.py:26 / :114) and between a tensor's two points
+// (kernels.py:329-330) are taken on the ROWS -- exact to rounding under translation, like the exact-shape kernels' MODE_INC, where a four-term difference of
+// inner products of shifted paths is not -- and the kernels see difference = 0, one row less per sequence and one column per component
+bool rows_are_increments(const gpsig_params* p) { return p->base_kernel == GPSIG_BASE_LINEAR && p->difference; }
+bool tensors_collapse(const gpsig_params* p, int increments) { return p->base_kernel == GPSIG_BASE_LINEAR && increments; }
+
+// body with KD = the compile-time kind of base kernel `base`
+#define GPSIG_WIDE_KIND(base, ...)                                                            \
+    switch (kind_of(base)) {                                                                  \
+        case WIDE_KD_RBF: { constexpr int KD = WIDE_KD_RBF; __VA_ARGS__; } break;             \
+        case WIDE_KD_ID: { constexpr int KD = WIDE_KD_ID; __VA_ARGS__; } break;               \
+        default: { constexpr int KD = WIDE_KD_MATERN; __VA_ARGS__; } break;                   \
+    }
 
 size_t wide_chunk_bytes(const gpsig_ctx* c) {
     if (c->wide_chunk_mb > 0) return size_t(c->wide_chunk_mb) << 20;
@@ -45,35 +64,35 @@ int dgemm_batched(gpsig_ctx* c, bool ta, bool tb, int64_t m, int64_t n, int64_t 
     return GPSIG_OK;
 }
 
-int aug_rows(gpsig_ctx* c, const double* src, int64_t rows, int d, int right, double* dst) {
+int aug_rows(gpsig_ctx* c, const double* src, int64_t rows, int d, int right, int mode, int diff, double* dst) {
     if (rows == 0) return GPSIG_OK;
     ScaleParams none;
     memset(&none, 0, sizeof(none));
     none.d_in = d;
     hipLaunchKernelGGL(wide_aug_rows_kernel, dim3(unsigned(rows < 65535 ? rows : 65535)), dim3(64), 0, c->stream, src, rows, d, right, 0, int64_t(0), int64_t(0), 1,
-                       none, dst);
+                       none, mode, diff, dst);
     HIPCHK(c, hipGetLastError());
     return GPSIG_OK;
 }
 
 typedef void (*WideLatKernel)(const WideLatArgs);
-template <int LQ, bool RBF>
+template <int LQ, int KD>
 WideLatKernel lat_kernel_of(int C, bool bwd, int NW) {
-    if (NW == 2) return bwd ? wide_lattice_bwd_kernel<1, LQ, RBF, 2> : wide_lattice_fwd_kernel<1, LQ, RBF, 2>;
-    if (NW == 4) return bwd ? wide_lattice_bwd_kernel<1, LQ, RBF, 4> : wide_lattice_fwd_kernel<1, LQ, RBF, 4>;
-    if (NW == 8) return bwd ? wide_lattice_bwd_kernel<1, LQ, RBF, 8> : wide_lattice_fwd_kernel<1, LQ, RBF, 8>;
+    if (NW == 2) return bwd ? wide_lattice_bwd_kernel<1, LQ, KD, 2> : wide_lattice_fwd_kernel<1, LQ, KD, 2>;
+    if (NW == 4) return bwd ? wide_lattice_bwd_kernel<1, LQ, KD, 4> : wide_lattice_fwd_kernel<1, LQ, KD, 4>;
+    if (NW == 8) return bwd ? wide_lattice_bwd_kernel<1, LQ, KD, 8> : wide_lattice_fwd_kernel<1, LQ, KD, 8>;
     switch (C) {
-        case 1: return bwd ? wide_lattice_bwd_kernel<1, LQ, RBF> : wide_lattice_fwd_kernel<1, LQ, RBF>;
-        case 2: return bwd ? wide_lattice_bwd_kernel<2, LQ, RBF> : wide_lattice_fwd_kernel<2, LQ, RBF>;
-        case 4: return bwd ? wide_lattice_bwd_kernel<4, LQ, RBF> : wide_lattice_fwd_kernel<4, LQ, RBF>;
-        default: return bwd ? wide_lattice_bwd_kernel<8, LQ, RBF> : wide_lattice_fwd_kernel<8, LQ, RBF>;
+        case 1: return bwd ? wide_lattice_bwd_kernel<1, LQ, KD> : wide_lattice_fwd_kernel<1, LQ, KD>;
+        case 2: return bwd ? wide_lattice_bwd_kernel<2, LQ, KD> : wide_lattice_fwd_kernel<2, LQ, KD>;
+        case 4: return bwd ? wide_lattice_bwd_kernel<4, LQ, KD> : wide_lattice_fwd_kernel<4, LQ, KD>;
+        default: return bwd ? wide_lattice_bwd_kernel<8, LQ, KD> : wide_lattice_fwd_kernel<8, LQ, KD>;
     }
 }
-// levels kept by a lane: 3 (num_levels <= 4) or 7; the RBF kernel at compile time, the Matern families at run time.  NW > 1: NW wavefronts per
+// levels kept by a lane: 3 (num_levels <= 4) or 7; the RBF kernel and the identity (dot-product families) at compile time, the Matern families at run time.  NW > 1: NW wavefronts per
 // lattice with one column per lane (C is ignored)
-WideLatKernel lat_kernel(int M, int C, bool bwd, bool rbf, int NW = 1) {
-    if (M <= 4) return rbf ? lat_kernel_of<3, true>(C, bwd, NW) : lat_kernel_of<3, false>(C, bwd, NW);
-    return rbf ? lat_kernel_of<7, true>(C, bwd, NW) : lat_kernel_of<7, false>(C, bwd, NW);
+WideLatKernel lat_kernel(int M, int C, bool bwd, int base_kernel, int NW = 1) {
+    GPSIG_WIDE_KIND(base_kernel, return M <= 4 ? lat_kernel_of<3, KD>(C, bwd, NW) : lat_kernel_of<7, KD>(C, bwd, NW))
+    return nullptr;
 }
 // wavefronts per lattice: a launch of few lattices of more than 256 columns spreads each lattice's columns over eight wavefronts of one column per
 // lane instead of eight columns per lane of one (NetFlow's / CMUsubject16's level diagonals, 50 / 23 lattices of 499 x 499: reverse pass 3.5 -> 3.2 / 2.9 ms;
@@ -86,9 +105,11 @@ int lat_waves(const gpsig_ctx* c, int C, int64_t lattices) {
 }
 int lat_columns(int R2) { return R2 <= 64 ? 1 : (R2 <= 128 ? 2 : (R2 <= 256 ? 4 : 8)); }
 
-// the augmented rows of both sides: ZA (lt * E * Tpad, DA) left form, XA (N * L, DA) right form
-int wide_tvs_rows(gpsig_ctx* c, const ScaleParams& sz, const double* Z, const double* Xs, int lt, int E, int64_t Tn, int64_t Tpad, int64_t NL, int d,
-                  double** ZA, double** XA) {
+// the augmented rows of both sides: ZA (lt * E * Tpad, DA) left form, XA (NL, DA) right form.  E, NL: as the KERNELS see them -- SignatureLinear: E = 1 from
+// the caller's two points per tensor (zdiff), NL = N (L - 1) increment rows of sequences of xdiff = L observations
+int wide_tvs_rows(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz, const double* Z, const double* Xs, int lt, int E, int64_t Tn, int64_t Tpad, int64_t NL,
+                  int d, int zdiff, int xdiff, double** ZA, double** XA) {
+    const int mode = rows_mode(p->base_kernel);
     const int DA = d + 2;
     const int64_t zr = int64_t(lt) * E * Tpad;
     void *za, *xa;
@@ -98,10 +119,10 @@ int wide_tvs_rows(gpsig_ctx* c, const ScaleParams& sz, const double* Z, const do
     memset(&none, 0, sizeof(none));
     none.d_in = d;
     hipLaunchKernelGGL(wide_aug_rows_kernel, dim3(unsigned(zr < 65535 ? zr : 65535)), dim3(64), 0, c->stream, Z, zr, d, 0, lt, Tn, Tpad, E, sz,
-                       static_cast<double*>(za));
+                       mode, zdiff, static_cast<double*>(za));
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(wide_aug_rows_kernel, dim3(unsigned(NL < 65535 ? NL : 65535)), dim3(64), 0, c->stream, Xs, NL, d, 1, 0, int64_t(0), int64_t(0), 1,
-                       none, static_cast<double*>(xa));
+                       none, mode, xdiff, static_cast<double*>(xa));
     HIPCHK(c, hipGetLastError());
     *ZA = static_cast<double*>(za); *XA = static_cast<double*>(xa);
     return GPSIG_OK;
@@ -169,6 +190,7 @@ bool wide_tvs_available(const gpsig_ctx* c, const gpsig_params* p, int d, int64_
     if (c->wide == 0 || c->capturing) return false;
     if (!wide_kind(p->base_kernel) || (p->order > WIDE_MAX_ORDER && p->num_levels > WIDE_MAX_ORDER) || p->num_levels > WIDE_MAX_LEVELS || p->num_levels < 1) return false;
     if (Tn < 1 || N < 1 || L < 1 || d < 1) return false;
+    if (rows_are_increments(p) && L < 2) return false;        // (no increment rows)
     return true;
 }
 
@@ -176,10 +198,13 @@ bool wide_tvs_available(const gpsig_ctx* c, const gpsig_params* p, int d, int64_
 // sz.has_ls; Xs: (N, L, d) scaled sequences.  fx (N, M+1), w (M+1): factors or NULL.  out: (T, N) level sum or (M+1, T, N).  aux: chain totals or NULL.
 int wide_tvs_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz, int d, const double* Z, const double* Xs, int64_t Tn, int64_t N, int L,
                      int increments, const double* fx, const double* w, int sum_levels, double* out, double* aux) {
-    const int M = p->num_levels, lt = M * (M + 1) / 2, E = increments ? 2 : 1, DA = d + 2;
+    const bool xinc = rows_are_increments(p), zinc = tensors_collapse(p, increments);
+    const int xdiff = xinc ? L : 0;
+    if (xinc) L -= 1;                                            // the kernels' rows per sequence
+    const int M = p->num_levels, lt = M * (M + 1) / 2, E = (increments && !zinc) ? 2 : 1, DA = d + 2;
     const int64_t Tpad = (Tn + 63) / 64 * 64, CW = int64_t(lt) * E * Tpad, TB = Tpad / 64;
     double *ZA, *XA;
-    CHK(wide_tvs_rows(c, sz, Z, Xs, lt, E, Tn, Tpad, N * int64_t(L), d, &ZA, &XA));
+    CHK(wide_tvs_rows(c, p, sz, Z, Xs, lt, E, Tn, Tpad, N * int64_t(L), d, zinc ? 1 : 0, xdiff, &ZA, &XA));
     const size_t per_seq = sizeof(double) * size_t(L) * CW;
     int64_t chunk = int64_t(wide_chunk_bytes(c) / per_seq);
     if (chunk < 1) chunk = 1;
@@ -201,12 +226,12 @@ int wide_tvs_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz,
         WideTvsArgs A;
         memset(&A, 0, sizeof(A));
         A.arg = static_cast<const double*>(arg); A.CW = CW; A.Tpad = Tpad; A.Tn = Tn; A.n0 = n0; A.Nc = nc; A.N = N;
-        A.L = L; A.M = M; A.kind = p->base_kernel; A.difference = p->difference ? 1 : 0; A.sum_levels = sum_levels;
+        A.L = L; A.M = M; A.kind = p->base_kernel; A.difference = (p->difference && !xinc) ? 1 : 0; A.sum_levels = sum_levels;
         A.fx = fx; A.w = w; A.out = out; A.aux = aux; A.order = p->order < p->num_levels ? p->order : p->num_levels;
         const dim3 grid(unsigned(TB), unsigned(nc < 65535 ? nc : 65535), unsigned(M));
-        const bool rbf = p->base_kernel == GPSIG_BASE_RBF;
-        if (E == 2) { if (rbf) hipLaunchKernelGGL((wide_tvs_fwd_kernel<2, true>), grid, dim3(64), 0, c->stream, A); else hipLaunchKernelGGL((wide_tvs_fwd_kernel<2, false>), grid, dim3(64), 0, c->stream, A); }
-        else { if (rbf) hipLaunchKernelGGL((wide_tvs_fwd_kernel<1, true>), grid, dim3(64), 0, c->stream, A); else hipLaunchKernelGGL((wide_tvs_fwd_kernel<1, false>), grid, dim3(64), 0, c->stream, A); }
+        GPSIG_WIDE_KIND(p->base_kernel,
+                        if (E == 2) hipLaunchKernelGGL((wide_tvs_fwd_kernel<2, KD>), grid, dim3(64), 0, c->stream, A);
+                        else hipLaunchKernelGGL((wide_tvs_fwd_kernel<1, KD>), grid, dim3(64), 0, c->stream, A))
         HIPCHK(c, hipGetLastError());
         hipLaunchKernelGGL(wide_tvs_epilogue_kernel, dim3(grid_for(nc * Tn)), dim3(256), 0, c->stream, A);
         HIPCHK(c, hipGetLastError());
@@ -225,13 +250,17 @@ int wide_tvs_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz,
 // level array; fac (N, M+1): G (T, N), gradient of the weighted level sum, and gfac (N, M+1) receives the factors' gradient.
 int wide_tvs_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Z, const double* X, const double* G, int64_t Tn, int64_t N, int L,
                       int increments, const double* fac, const double* aux, double* gZ, double* gX, double* gfac) {
-    const int M = p->num_levels, lt = M * (M + 1) / 2, E = increments ? 2 : 1, DA = d + 2;
+    const bool xinc = rows_are_increments(p), zinc = tensors_collapse(p, increments);
+    const int xdiff = xinc ? L : 0, mode = rows_mode(p->base_kernel);
+    const int64_t NLx = N * int64_t(L);                          // the caller's rows
+    if (xinc) L -= 1;                                            // the kernels' rows per sequence
+    const int M = p->num_levels, lt = M * (M + 1) / 2, Ez = increments ? 2 : 1, E = zinc ? 1 : Ez, DA = d + 2;
     const int64_t Tpad = (Tn + 63) / 64 * 64, CW = int64_t(lt) * E * Tpad, TB = Tpad / 64, NL = N * int64_t(L);
     ScaleParams none;
     memset(&none, 0, sizeof(none));
     none.d_in = d;
     double *ZA, *XA;
-    CHK(wide_tvs_rows(c, none, Z, X, lt, E, Tn, Tpad, NL, d, &ZA, &XA));
+    CHK(wide_tvs_rows(c, p, none, Z, X, lt, E, Tn, Tpad, NL, d, zinc ? 1 : 0, xdiff, &ZA, &XA));
     const size_t per_seq = sizeof(double) * size_t(L) * CW;
     int64_t chunk = int64_t(wide_chunk_bytes(c) / per_seq);
     if (chunk < 1) chunk = 1;
@@ -248,24 +277,40 @@ int wide_tvs_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
         WideTvsArgs A;
         memset(&A, 0, sizeof(A));
         A.arg = static_cast<const double*>(arg); A.CW = CW; A.Tpad = Tpad; A.Tn = Tn; A.n0 = n0; A.Nc = nc; A.N = N;
-        A.L = L; A.M = M; A.kind = p->base_kernel; A.difference = p->difference ? 1 : 0;
+        A.L = L; A.M = M; A.kind = p->base_kernel; A.difference = (p->difference && !xinc) ? 1 : 0;
         A.fx = fac; A.w = nullptr; A.aux = const_cast<double*>(aux);
         A.G = G; A.W = static_cast<double*>(Wb); A.gfac_part = static_cast<double*>(gfp); A.weighted = fac ? 1 : 0;
         A.order = p->order < p->num_levels ? p->order : p->num_levels;
         const dim3 grid(unsigned(TB), unsigned(nc < 65535 ? nc : 65535), unsigned(M));
-        const bool rbf = p->base_kernel == GPSIG_BASE_RBF;
-        if (E == 2) { if (rbf) hipLaunchKernelGGL((wide_tvs_bwd_kernel<2, true>), grid, dim3(64), 0, c->stream, A); else hipLaunchKernelGGL((wide_tvs_bwd_kernel<2, false>), grid, dim3(64), 0, c->stream, A); }
-        else { if (rbf) hipLaunchKernelGGL((wide_tvs_bwd_kernel<1, true>), grid, dim3(64), 0, c->stream, A); else hipLaunchKernelGGL((wide_tvs_bwd_kernel<1, false>), grid, dim3(64), 0, c->stream, A); }
+        GPSIG_WIDE_KIND(p->base_kernel,
+                        if (E == 2) hipLaunchKernelGGL((wide_tvs_bwd_kernel<2, KD>), grid, dim3(64), 0, c->stream, A);
+                        else hipLaunchKernelGGL((wide_tvs_bwd_kernel<1, KD>), grid, dim3(64), 0, c->stream, A))
         HIPCHK(c, hipGetLastError());
         CHK(contract_both(c, static_cast<const double*>(Wb), XA + n0 * L * DA, ZA, nc * int64_t(L), CW, DA, n0 > 0, static_cast<double*>(gxa) + n0 * L * DA,
                           static_cast<double*>(gza)));
     }
-    const int64_t zrows = int64_t(lt) * Tn * E;
-    hipLaunchKernelGGL(wide_unaug_rows_kernel, dim3(grid_for(zrows * d)), dim3(256), 0, c->stream, static_cast<const double*>(gza), ZA, zrows, d, 0, lt, Tn,
-                       Tpad, E, gZ);
+    const int64_t zrows = int64_t(lt) * Tn * Ez;                // the caller's rows
+    // (plain rows -- SignatureLinear without increments / differences -- take the distance kernels' un-augmentation as it is: both extra columns of
+    // such rows are zero on BOTH sides, so the adjoint of the norm column, a product with the other side's zero column, is exactly 0 and g = ga)
+    if (mode == WIDE_ROWS_UNIT)
+        hipLaunchKernelGGL(wide_unaug_unit_kernel, dim3(unsigned(zrows < 65535 ? zrows : 65535)), dim3(64), 0, c->stream, static_cast<const double*>(gza), ZA,
+                           static_cast<const double*>(nullptr), static_cast<const double*>(nullptr), zrows, d, lt, Tn, Tpad, E, gZ);
+    else if (zinc)
+        hipLaunchKernelGGL(wide_unaug_inc_kernel, dim3(grid_for(zrows * d)), dim3(256), 0, c->stream, static_cast<const double*>(gza),
+                           static_cast<const double*>(nullptr), zrows, d, lt, Tn, Tpad, 0, gZ);
+    else
+        hipLaunchKernelGGL(wide_unaug_rows_kernel, dim3(grid_for(zrows * d)), dim3(256), 0, c->stream, static_cast<const double*>(gza), ZA, zrows, d, 0, lt, Tn,
+                           Tpad, E, gZ);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(wide_unaug_rows_kernel, dim3(grid_for(NL * d)), dim3(256), 0, c->stream, static_cast<const double*>(gxa), XA, NL, d, 1, 0, int64_t(1),
-                       int64_t(0), 1, gX);
+    if (mode == WIDE_ROWS_UNIT)
+        hipLaunchKernelGGL(wide_unaug_unit_kernel, dim3(unsigned(NLx < 65535 ? NLx : 65535)), dim3(64), 0, c->stream, static_cast<const double*>(nullptr),
+                           static_cast<const double*>(nullptr), static_cast<const double*>(gxa), XA, NLx, d, 0, int64_t(1), int64_t(0), 1, gX);
+    else if (xinc)
+        hipLaunchKernelGGL(wide_unaug_inc_kernel, dim3(grid_for(NLx * d)), dim3(256), 0, c->stream, static_cast<const double*>(nullptr),
+                           static_cast<const double*>(gxa), NLx, d, 0, int64_t(1), int64_t(0), xdiff, gX);
+    else
+        hipLaunchKernelGGL(wide_unaug_rows_kernel, dim3(grid_for(NL * d)), dim3(256), 0, c->stream, static_cast<const double*>(gxa), XA, NL, d, 1, 0, int64_t(1),
+                           int64_t(0), 1, gX);
     HIPCHK(c, hipGetLastError());
     if (fac) {
         hipLaunchKernelGGL(wide_gfac_reduce_kernel, dim3(grid_for(N * (M + 1))), dim3(256), 0, c->stream, static_cast<const double*>(gfp), int(TB),
@@ -284,22 +329,36 @@ bool wide_lat_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L
     if (!wide_kind(p->base_kernel) || p->num_levels > WIDE_MAX_LEVELS || p->num_levels < 1) return false;
     const int dr = p->difference ? 1 : 0;
     if (p->order > 1 && p->num_levels > 1) {      // higher orders: the forward and the reverse sweeps of grad_wave_ho_kernel.hpp (<= 5 levels, orders <= 4)
+        if (wide_dot_kind(p->base_kernel)) return false;      // (these families' higher orders: the feature contraction up to 32 columns, the any-shape kernel beyond)
         HoSweeps hf, hb;
         return L1 - dr >= 1 && L2 - dr >= 1 && ho_levels_plan(c, p, L1 - dr, L2 - dr, &hf) && ho_sweeps_plan(c, p, L1 - dr, L2 - dr, &hb);
     }
+    if (rows_are_increments(p) && (L1 < 2 || L2 < 2)) return false;      // (no increment rows)
     return L1 >= 1 && L2 >= 1 && L2 - dr <= WIDE_LAT_MAX_COLS;
 }
 
 // the reverse pass of the HIGHER-ORDER recursion on this route: argument lattices by dgemm -> dM lattices (wide_lattice_dm_kernel) -> both sweeps of a
 // pair in one wavefront (grad_wave_ho_kernel.hpp) -> the adjoint contracted back by dgemms; any number of columns
 bool wide_lat_ho_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L2) {
-    if (c->wide == 0 || c->capturing || !wide_kind(p->base_kernel) || !(p->order > 1 && p->num_levels > 1)) return false;
+    if (c->wide == 0 || c->capturing || !wide_kind(p->base_kernel) || wide_dot_kind(p->base_kernel) || !(p->order > 1 && p->num_levels > 1)) return false;
     const int dr = p->difference ? 1 : 0;
     HoSweeps hs;
     return L1 >= 1 && L2 >= 1 && ho_sweeps_plan(c, p, L1 - dr, L2 - dr, &hs);
 }
 
 namespace {
+
+// SignatureLinear with differences: the lattices of the INCREMENT rows, without differences (rows_are_increments)
+struct LatInc {
+    gpsig_params q;
+    int xd1 = 0, xd2 = 0;       // observations per sequence where the rows are increments, else 0
+    LatInc(const gpsig_params*& p, int& L1, int& L2) : q(*p) {
+        if (!rows_are_increments(p)) return;
+        xd1 = L1; xd2 = L2; L1 -= 1; L2 -= 1;
+        q.difference = 0;
+        p = &q;
+    }
+};
 
 struct LatPlan {
     int DA, dr, R1, R2, C;
@@ -308,14 +367,15 @@ struct LatPlan {
 };
 
 // augmented rows (left form of the left sequences, right form of the right ones) and the chunking of the argument lattices
+// (xd1, xd2 > 0: the rows are the increments of sequences of xd1 / xd2 observations, L1 / L2 of them per sequence -- LatInc)
 int lat_plan(gpsig_ctx* c, const gpsig_params* p, int d, const double* Xs, const double* Ys, int64_t N1, int64_t N2, int L1, int L2, bool diag, int bufs,
-             LatPlan* pl) {
+             int xd1, int xd2, LatPlan* pl) {
     pl->DA = d + 2; pl->dr = p->difference ? 1 : 0; pl->R1 = L1 - pl->dr; pl->R2 = L2 - pl->dr; pl->C = lat_columns(pl->R2);
     void *xl, *xr;
     CHK(ensure(c, B_WD0, sizeof(double) * size_t(N1) * L1 * pl->DA + 64, &xl));
     CHK(ensure(c, B_WD1, sizeof(double) * size_t(N2) * L2 * pl->DA + 64, &xr));
-    CHK(aug_rows(c, Xs, N1 * int64_t(L1), d, 0, static_cast<double*>(xl)));
-    CHK(aug_rows(c, Ys ? Ys : Xs, N2 * int64_t(L2), d, 1, static_cast<double*>(xr)));
+    CHK(aug_rows(c, Xs, N1 * int64_t(L1), d, 0, rows_mode(p->base_kernel), xd1, static_cast<double*>(xl)));
+    CHK(aug_rows(c, Ys ? Ys : Xs, N2 * int64_t(L2), d, 1, rows_mode(p->base_kernel), xd2, static_cast<double*>(xr)));
     pl->XL = static_cast<double*>(xl); pl->XR = static_cast<double*>(xr);
     const size_t per_i = sizeof(double) * size_t(L1) * L2 * size_t(diag ? 1 : N2) * size_t(bufs);
     int64_t chunk = int64_t(wide_chunk_bytes(c) / (per_i ? per_i : 1));
@@ -345,18 +405,19 @@ int lat_arguments(gpsig_ctx* c, const LatPlan& pl, int64_t i0, int64_t ni, int64
 // (Ys == NULL: Xs on both sides).  signature_algs.py:8-35 on kernels.py:188-237's tensors.
 int wide_lat_forward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Xs, const double* Ys, int64_t N1, int64_t N2, int L1, int L2, bool diag,
                      double* out) {
+    const LatInc inc(p, L1, L2);
     LatPlan pl;
     const bool ho = p->order > 1 && p->num_levels > 1;
     HoSweeps hs;
     if (ho && !ho_levels_plan(c, p, L1 - (p->difference ? 1 : 0), L2 - (p->difference ? 1 : 0), &hs))
         return fail(c, GPSIG_ERR_UNSUPPORTED, "no higher-order forward sweep for this shape");
-    CHK(lat_plan(c, p, d, Xs, Ys, N1, N2, L1, L2, diag, ho ? 2 : 1, &pl));
+    CHK(lat_plan(c, p, d, Xs, Ys, N1, N2, L1, L2, diag, ho ? 2 : 1, inc.xd1, inc.xd2, &pl));
     const int M = p->num_levels;
     void *arg, *dmat = nullptr;
     CHK(ensure(c, B_WD2, sizeof(double) * size_t(pl.chunk_i) * L1 * L2 * size_t(diag ? 1 : N2) + 64, &arg));
     if (ho) CHK(ensure(c, B_WD6, sizeof(double) * size_t(pl.chunk_i) * L1 * L2 * size_t(diag ? 1 : N2) + 64, &dmat));
     const int NW = ho ? 1 : lat_waves(c, pl.C, diag ? (N1 < pl.chunk_i ? N1 : pl.chunk_i) : (N1 < pl.chunk_i ? N1 : pl.chunk_i) * N2);
-    WideLatKernel fn = ho ? nullptr : lat_kernel(M, pl.C, false, p->base_kernel == GPSIG_BASE_RBF, NW);
+    WideLatKernel fn = ho ? nullptr : lat_kernel(M, pl.C, false, p->base_kernel, NW);
     hipEvent_t e0, e1;
     bool timed;
     CHK(wide_timing_begin(c, &e0, &e1, &timed));
@@ -371,10 +432,8 @@ int wide_lat_forward(gpsig_ctx* c, const gpsig_params* p, int d, const double* X
         A.out = out + (diag ? i0 : i0 * N2);              // (the kernel's pair index starts at 0 in this chunk's lattices)
         if (ho) {
             if (pl.R1 < 1 || pl.R2 < 1) return fail(c, GPSIG_ERR_UNSUPPORTED, "empty lattices");
-            if (p->base_kernel == GPSIG_BASE_RBF)
-                hipLaunchKernelGGL(wide_lattice_dm_kernel<true>, dim3(grid_for(A.P * int64_t(pl.R1) * pl.R2)), dim3(256), 0, c->stream, A, static_cast<double*>(dmat));
-            else
-                hipLaunchKernelGGL(wide_lattice_dm_kernel<false>, dim3(grid_for(A.P * int64_t(pl.R1) * pl.R2)), dim3(256), 0, c->stream, A, static_cast<double*>(dmat));
+            GPSIG_WIDE_KIND(p->base_kernel, hipLaunchKernelGGL(wide_lattice_dm_kernel<KD>, dim3(grid_for(A.P * int64_t(pl.R1) * pl.R2)), dim3(256), 0, c->stream, A,
+                                                               static_cast<double*>(dmat)))
             HIPCHK(c, hipGetLastError());
             CHK(ho_levels_launch(c, hs, M, pl.R1, pl.R2, static_cast<const double*>(dmat), out, pl.Ptot, diag ? 1 : N2, diag ? 0 : 1, diag ? 1 : N2, diag,
                                  diag ? i0 : i0 * N2, A.P));
@@ -396,6 +455,7 @@ int wide_lat_forward(gpsig_ctx* c, const gpsig_params* p, int d, const double* X
 // gradients land in gX (the symmetric Gram as the cross Gram of X with itself; the diagonal); else gX, gY.
 int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Xs, const double* Ys, int64_t N1, int64_t N2, int L1, int L2, bool diag,
                       const double* G, double* gX, double* gY) {
+    const LatInc inc(p, L1, L2);
     LatPlan pl;
     const bool ho = p->order > 1 && p->num_levels > 1;
     HoSweeps hs;
@@ -406,7 +466,7 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
     bool short_lat = false;
     if (!ho && c->wide_o1_sweeps != 0 && ((diag ? N1 : N1 * N2) >= 1024 || c->wide_o1_sweeps == 2))
         short_lat = o1_sweeps_plan(c, p, L1 - (p->difference ? 1 : 0), L2 - (p->difference ? 1 : 0), &hs);
-    CHK(lat_plan(c, p, d, Xs, Ys, N1, N2, L1, L2, diag, (ho || short_lat) ? 3 : 2, &pl));
+    CHK(lat_plan(c, p, d, Xs, Ys, N1, N2, L1, L2, diag, (ho || short_lat) ? 3 : 2, inc.xd1, inc.xd2, &pl));
     // the symmetric Gram (one array on both sides): the pairs i <= j with the upstream gradient folded onto them -- half the lattices
     const bool fold = !diag && Ys == nullptr && N1 == N2 && L1 == L2 && c->wide_sym_fold != 0;
     if (fold) {
@@ -438,7 +498,7 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
     if (groups > 4096) groups = 4096;
     if (ho || short_lat) groups = 1;      // (these sweeps bring their own slots, if any)
     CHK(ensure(c, B_WD7, per_group * size_t(groups) + 64, &scr));
-    WideLatKernel fn = (ho || short_lat) ? nullptr : lat_kernel(M, pl.C, true, p->base_kernel == GPSIG_BASE_RBF, NW);
+    WideLatKernel fn = (ho || short_lat) ? nullptr : lat_kernel(M, pl.C, true, p->base_kernel, NW);
     for (int64_t i0 = 0; i0 < N1; i0 += pl.chunk_i) {
         const int64_t ni = N1 - i0 < pl.chunk_i ? N1 - i0 : pl.chunk_i;
         const int64_t j0 = fold ? i0 : 0, N2e = N2 - j0;              // right sequences of this chunk
@@ -455,10 +515,8 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
         const int64_t ng = A.P < groups ? A.P : groups;
         A.ngroups = int(ng);
         if ((ho || short_lat) && pl.R1 > 0 && pl.R2 > 0) {
-            if (p->base_kernel == GPSIG_BASE_RBF)
-                hipLaunchKernelGGL(wide_lattice_dm_kernel<true>, dim3(grid_for(A.P * int64_t(pl.R1) * pl.R2)), dim3(256), 0, c->stream, A, static_cast<double*>(dmat));
-            else
-                hipLaunchKernelGGL(wide_lattice_dm_kernel<false>, dim3(grid_for(A.P * int64_t(pl.R1) * pl.R2)), dim3(256), 0, c->stream, A, static_cast<double*>(dmat));
+            GPSIG_WIDE_KIND(p->base_kernel, hipLaunchKernelGGL(wide_lattice_dm_kernel<KD>, dim3(grid_for(A.P * int64_t(pl.R1) * pl.R2)), dim3(256), 0, c->stream, A,
+                                                               static_cast<double*>(dmat)))
             HIPCHK(c, hipGetLastError());
             // (the sweeps address G by (i, j') = divmod(pair0 + pair, N2e): i absolute with pair0 = i0 N2e, j' relative to the chunk's first right sequence)
             CHK(ho_sweeps_launch(c, hs, M, pl.R1, pl.R2, static_cast<const double*>(dmat), static_cast<double*>(lam), G + j0, pl.Ptot, diag ? 1 : N2, diag ? 0 : 1,
@@ -468,10 +526,8 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
             HIPCHK(c, hipGetLastError());
         }
         // the adjoint of the arguments, in place of the arguments
-        if (p->base_kernel == GPSIG_BASE_RBF)
-            hipLaunchKernelGGL(wide_lattice_adjoint_kernel<true>, dim3(grid_for(A.P * int64_t(L1) * L2)), dim3(256), 0, c->stream, A, static_cast<double*>(arg));
-        else
-            hipLaunchKernelGGL(wide_lattice_adjoint_kernel<false>, dim3(grid_for(A.P * int64_t(L1) * L2)), dim3(256), 0, c->stream, A, static_cast<double*>(arg));
+        GPSIG_WIDE_KIND(p->base_kernel, hipLaunchKernelGGL(wide_lattice_adjoint_kernel<KD>, dim3(grid_for(A.P * int64_t(L1) * L2)), dim3(256), 0, c->stream, A,
+                                                           static_cast<double*>(arg)))
         HIPCHK(c, hipGetLastError());
         const double* W = static_cast<const double*>(arg);
         double* gl = static_cast<double*>(gxl) + i0 * L1 * DA;
@@ -488,12 +544,32 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
     // through the augmentation: left form into gX; right form into gX as well (one array on both sides) or into gY
     const int64_t xr_rows = N1 * int64_t(L1), yr_rows = N2 * int64_t(L2);
     const bool same = Ys == nullptr;
-    hipLaunchKernelGGL(wide_unaug_pair_kernel, dim3(grid_for(xr_rows * d)), dim3(256), 0, c->stream, static_cast<const double*>(gxl), pl.XL,
-                       same ? static_cast<const double*>(gxr) : nullptr, same ? pl.XR : nullptr, xr_rows, d, gX);
+    const double *gl = static_cast<const double*>(gxl), *gr = static_cast<const double*>(gxr), *none = nullptr;
+    if (rows_mode(p->base_kernel) == WIDE_ROWS_UNIT) {
+        hipLaunchKernelGGL(wide_unaug_unit_kernel, dim3(unsigned(xr_rows < 65535 ? xr_rows : 65535)), dim3(64), 0, c->stream, gl, pl.XL, same ? gr : none,
+                           same ? pl.XR : none, xr_rows, d, 0, int64_t(1), int64_t(0), 1, gX);
+        if (!same)
+            hipLaunchKernelGGL(wide_unaug_unit_kernel, dim3(unsigned(yr_rows < 65535 ? yr_rows : 65535)), dim3(64), 0, c->stream, none, none, gr, pl.XR, yr_rows, d,
+                               0, int64_t(1), int64_t(0), 1, gY);
+        HIPCHK(c, hipGetLastError());
+        return GPSIG_OK;
+    }
+    if (inc.xd1) {          // increment rows: N (L + 1) output rows from N L rows of adjoints
+        hipLaunchKernelGGL(wide_unaug_inc_kernel, dim3(grid_for(N1 * int64_t(inc.xd1) * d)), dim3(256), 0, c->stream, gl, same ? gr : none,
+                           N1 * int64_t(inc.xd1), d, 0, int64_t(1), int64_t(0), inc.xd1, gX);
+        if (!same)
+            hipLaunchKernelGGL(wide_unaug_inc_kernel, dim3(grid_for(N2 * int64_t(inc.xd2) * d)), dim3(256), 0, c->stream, none, gr, N2 * int64_t(inc.xd2), d, 0,
+                               int64_t(1), int64_t(0), inc.xd2, gY);
+        HIPCHK(c, hipGetLastError());
+        return GPSIG_OK;
+    }
+    // (plain rows of SignatureLinear too: their norm column's adjoint is exactly 0 -- see wide_tvs_backward)
+    hipLaunchKernelGGL(wide_unaug_pair_kernel, dim3(grid_for(xr_rows * d)), dim3(256), 0, c->stream, gl, pl.XL, same ? gr : none, same ? pl.XR : none, xr_rows, d,
+                       gX);
     HIPCHK(c, hipGetLastError());
     if (!same) {
-        hipLaunchKernelGGL(wide_unaug_rows_kernel, dim3(grid_for(yr_rows * d)), dim3(256), 0, c->stream, static_cast<const double*>(gxr), pl.XR, yr_rows, d, 1, 0,
-                           int64_t(1), int64_t(0), 1, gY);
+        hipLaunchKernelGGL(wide_unaug_rows_kernel, dim3(grid_for(yr_rows * d)), dim3(256), 0, c->stream, gr, pl.XR, yr_rows, d, 1, 0, int64_t(1), int64_t(0), 1,
+                           gY);
         HIPCHK(c, hipGetLastError());
     }
     return GPSIG_OK;
@@ -510,7 +586,9 @@ bool wide_tens_available(const gpsig_ctx* c, const gpsig_params* p, int64_t Tn) 
 
 namespace {
 // left- and right-form augmented rows of the tensors (B_WD0, B_WD6) and the argument blocks (B_WD2)
-int tens_arguments(gpsig_ctx* c, const ScaleParams& sz, int d, const double* Z, int lt, int E, int64_t Tn, int64_t Tpad, double** ZL, double** ZR, double** arg) {
+// (E as the kernels see it: SignatureLinear with increments has E = 1, rows z^1 - z^0 -- zdiff)
+int tens_arguments(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz, int d, const double* Z, int lt, int E, int zdiff, int64_t Tn, int64_t Tpad, double** ZL,
+                   double** ZR, double** arg) {
     const int DA = d + 2;
     const int64_t zr = int64_t(lt) * E * Tpad, R = int64_t(E) * Tpad;
     void *zl, *zrr, *ar;
@@ -519,7 +597,7 @@ int tens_arguments(gpsig_ctx* c, const ScaleParams& sz, int d, const double* Z, 
     CHK(ensure(c, B_WD2, sizeof(double) * size_t(lt) * R * R + 64, &ar));
     for (int right = 0; right < 2; ++right) {
         hipLaunchKernelGGL(wide_aug_rows_kernel, dim3(unsigned(zr < 65535 ? zr : 65535)), dim3(64), 0, c->stream, Z, zr, d, right, lt, Tn, Tpad, E, sz,
-                           static_cast<double*>(right ? zrr : zl));
+                           rows_mode(p->base_kernel), zdiff, static_cast<double*>(right ? zrr : zl));
         HIPCHK(c, hipGetLastError());
     }
     // block k, row-major (R, R) = ZL_k ZR_k^T  ==  column-major (R x R) = ZR_k,cm^T (R x DA) ZL_k,cm (DA x R)
@@ -533,28 +611,38 @@ int tens_arguments(gpsig_ctx* c, const ScaleParams& sz, int d, const double* Z, 
 // Kzz: Z the caller's (lt, T, E, d) array (scaled here when sz.has_ls); w (M+1) or NULL; out (T, T) weighted sum or (M+1, T, T)
 int wide_tens_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz, int d, const double* Z, int64_t Tn, int increments, const double* w,
                       int sum_levels, double* out) {
-    const int M = p->num_levels, lt = M * (M + 1) / 2, E = increments ? 2 : 1;
+    const bool zinc = tensors_collapse(p, increments);
+    const int M = p->num_levels, lt = M * (M + 1) / 2, E = (increments && !zinc) ? 2 : 1;
     const int64_t Tpad = (Tn + 63) / 64 * 64;
     double *ZL, *ZR, *arg;
-    CHK(tens_arguments(c, sz, d, Z, lt, E, Tn, Tpad, &ZL, &ZR, &arg));
+    hipEvent_t e0, e1;
+    bool timed;
+    CHK(wide_timing_begin(c, &e0, &e1, &timed));          // (around the rows, the batched dgemm and the kernel: what the record's name says)
+    CHK(tens_arguments(c, p, sz, d, Z, lt, E, zinc ? 1 : 0, Tn, Tpad, &ZL, &ZR, &arg));
     WideTensArgs A;
     memset(&A, 0, sizeof(A));
     A.arg = arg; A.Tpad = Tpad; A.Tn = Tn; A.M = M; A.E = E; A.kind = p->base_kernel; A.sum_levels = sum_levels; A.w = w; A.out = out;
-    if (p->base_kernel == GPSIG_BASE_RBF) hipLaunchKernelGGL(wide_tens_fwd_kernel<true>, dim3(unsigned(Tpad / 64), unsigned(Tn < 65535 ? Tn : 65535)), dim3(64), 0, c->stream, A);
-    else hipLaunchKernelGGL(wide_tens_fwd_kernel<false>, dim3(unsigned(Tpad / 64), unsigned(Tn < 65535 ? Tn : 65535)), dim3(64), 0, c->stream, A);
+    GPSIG_WIDE_KIND(p->base_kernel, hipLaunchKernelGGL(wide_tens_fwd_kernel<KD>, dim3(unsigned(Tpad / 64), unsigned(Tn < 65535 ? Tn : 65535)), dim3(64), 0, c->stream, A))
     HIPCHK(c, hipGetLastError());
+    if (timed) {
+        HIPCHK(c, hipEventRecord(e1, c->stream));
+        c->t_launches += 1;
+        c->t_pairs += Tn * Tn;
+        c->t_kernel = "wide_tens (dgemm + wide_tens_fwd_kernel)";
+    }
     return GPSIG_OK;
 }
 
 // gradient of sum_m G[m][t][t'] level_m[t][t'] with respect to the scaled tensors Z (lt, T, E, d)
 int wide_tens_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Z, int64_t Tn, int increments, const double* G, double* gZ) {
-    const int M = p->num_levels, lt = M * (M + 1) / 2, E = increments ? 2 : 1, DA = d + 2;
+    const bool zinc = tensors_collapse(p, increments);
+    const int M = p->num_levels, lt = M * (M + 1) / 2, Ez = increments ? 2 : 1, E = zinc ? 1 : Ez, DA = d + 2;
     const int64_t Tpad = (Tn + 63) / 64 * 64, R = int64_t(E) * Tpad, zr = int64_t(lt) * R;
     ScaleParams none;
     memset(&none, 0, sizeof(none));
     none.d_in = d;
     double *ZL, *ZR, *arg;
-    CHK(tens_arguments(c, none, d, Z, lt, E, Tn, Tpad, &ZL, &ZR, &arg));
+    CHK(tens_arguments(c, p, none, d, Z, lt, E, zinc ? 1 : 0, Tn, Tpad, &ZL, &ZR, &arg));
     void *Wb, *gzl, *gzr;
     CHK(ensure(c, B_WD3, sizeof(double) * size_t(lt) * R * R + 64, &Wb));
     CHK(ensure(c, B_WD4, sizeof(double) * size_t(zr) * DA + 64, &gzl));
@@ -562,15 +650,21 @@ int wide_tens_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double*
     WideTensArgs A;
     memset(&A, 0, sizeof(A));
     A.arg = arg; A.Tpad = Tpad; A.Tn = Tn; A.M = M; A.E = E; A.kind = p->base_kernel; A.G = G; A.W = static_cast<double*>(Wb);
-    if (p->base_kernel == GPSIG_BASE_RBF) hipLaunchKernelGGL(wide_tens_bwd_kernel<true>, dim3(unsigned(Tpad / 64), unsigned(Tpad < 65535 ? Tpad : 65535)), dim3(64), 0, c->stream, A);
-    else hipLaunchKernelGGL(wide_tens_bwd_kernel<false>, dim3(unsigned(Tpad / 64), unsigned(Tpad < 65535 ? Tpad : 65535)), dim3(64), 0, c->stream, A);
+    GPSIG_WIDE_KIND(p->base_kernel, hipLaunchKernelGGL(wide_tens_bwd_kernel<KD>, dim3(unsigned(Tpad / 64), unsigned(Tpad < 65535 ? Tpad : 65535)), dim3(64), 0, c->stream, A))
     HIPCHK(c, hipGetLastError());
     // gZL_k (R, DA) = W_k ZR_k: column-major (DA x R) = ZR_k,cm (DA x R) W_k,cm (R x R);   gZR_k = W_k^T ZL_k: (DA x R) = ZL_k,cm W_k,cm^T
     CHK(dgemm_batched(c, false, false, DA, R, R, ZR, DA, R * DA, static_cast<const double*>(Wb), R, R * R, static_cast<double*>(gzl), DA, R * DA, lt));
     CHK(dgemm_batched(c, false, true, DA, R, R, ZL, DA, R * DA, static_cast<const double*>(Wb), R, R * R, static_cast<double*>(gzr), DA, R * DA, lt));
-    const int64_t rows_out = int64_t(lt) * Tn * E;
-    hipLaunchKernelGGL(wide_unaug_tens_kernel, dim3(grid_for(rows_out * d)), dim3(256), 0, c->stream, static_cast<const double*>(gzl), ZL,
-                       static_cast<const double*>(gzr), ZR, rows_out, d, Tn, Tpad, E, gZ);
+    const int64_t rows_out = int64_t(lt) * Tn * Ez;             // the caller's rows
+    if (rows_mode(p->base_kernel) == WIDE_ROWS_UNIT)
+        hipLaunchKernelGGL(wide_unaug_unit_kernel, dim3(unsigned(rows_out < 65535 ? rows_out : 65535)), dim3(64), 0, c->stream, static_cast<const double*>(gzl), ZL,
+                           static_cast<const double*>(gzr), ZR, rows_out, d, lt, Tn, Tpad, E, gZ);
+    else if (zinc)
+        hipLaunchKernelGGL(wide_unaug_inc_kernel, dim3(grid_for(rows_out * d)), dim3(256), 0, c->stream, static_cast<const double*>(gzl),
+                           static_cast<const double*>(gzr), rows_out, d, lt, Tn, Tpad, 0, gZ);
+    else
+        hipLaunchKernelGGL(wide_unaug_tens_kernel, dim3(grid_for(rows_out * d)), dim3(256), 0, c->stream, static_cast<const double*>(gzl), ZL,
+                           static_cast<const double*>(gzr), ZR, rows_out, d, Tn, Tpad, E, gZ);
     HIPCHK(c, hipGetLastError());
     return GPSIG_OK;
 }

@@ -71,9 +71,29 @@ __device__ __forceinline__ WideKap wide_kap(int kind, const double* tab) {
     return K;
 }
 
-template <bool RBF>
+// The compile-time kind of a kernel instance.  WIDE_KD_ID: kappa(a) = a -- the dot-product families: SignatureLinear (kernels.py:798-808: rows are the
+// points or, with differences, their increments -- <.,.> is bilinear, so the differences are taken on the rows before the dgemm and the kernels run in
+// their difference = 0 form) and SignatureCosine (:820-828: unit rows, differences of kappa as for the distance kernels).  No exponential: these
+// instances neither fill nor read the table in LDS.
+constexpr int WIDE_KD_MATERN = 0, WIDE_KD_RBF = 1, WIDE_KD_ID = 2;
+
+// the exp table of a workgroup of n threads (nothing for the identity kind)
+template <int KD>
+__device__ __forceinline__ const double* wide_tab(double* etab, int tid, int n) {
+    if constexpr (KD == WIDE_KD_ID) {
+        return nullptr;
+    } else {
+        exp_tab_fill(etab, tid, n);
+        __syncthreads();
+        return etab;
+    }
+}
+
+template <int KD>
 __device__ __forceinline__ double wide_kappa(const WideKap& K, double a) {
-    if constexpr (RBF) {
+    if constexpr (KD == WIDE_KD_ID) {
+        return a;
+    } else if constexpr (KD == WIDE_KD_RBF) {
         return kexp_tab(a, K.tab);
     } else {
         double dist = -2.0 * a;
@@ -85,9 +105,12 @@ __device__ __forceinline__ double wide_kappa(const WideKap& K, double a) {
 
 // kappa and d kappa / d a  (a = -dist / 2: d/da = -2 d/ddist; r' = c sqrt(-2a): dr'/da = -c^2 / r'; the clamp of kernels.py:781 passes no gradient, as
 // grad_core.hpp: base_eval_grad)
-template <bool RBF>
+template <int KD>
 __device__ __forceinline__ void wide_kappa_grad(const WideKap& K, double a, double& k, double& dk) {
-    if constexpr (RBF) {
+    if constexpr (KD == WIDE_KD_ID) {
+        k = a;
+        dk = 1.0;
+    } else if constexpr (KD == WIDE_KD_RBF) {
         k = kexp_tab(a, K.tab);
         dk = k;
     } else {
@@ -109,10 +132,10 @@ __device__ __forceinline__ void wide_load_row(const double* __restrict__ r, int 
     for (int q = 0; q < I * E; ++q) raw[q] = r[(int64_t(k0) * E + q) * Tpad];
 }
 // the value of component j from them: kappa, or the difference of its two points' (kernels.py:330)
-template <int I, int E, bool RBF>
+template <int I, int E, int KD>
 __device__ __forceinline__ double wide_val(const double (&raw)[I * E], int j, const WideKap& K) {
-    if constexpr (E == 2) return wide_kappa<RBF>(K, raw[2 * j + 1]) - wide_kappa<RBF>(K, raw[2 * j]);
-    else return wide_kappa<RBF>(K, raw[j]);
+    if constexpr (E == 2) return wide_kappa<KD>(K, raw[2 * j + 1]) - wide_kappa<KD>(K, raw[2 * j]);
+    else return wide_kappa<KD>(K, raw[j]);
 }
 
 // the chains of ONE level (I components from k0) of one (tensor, sequence) pair: signature_algs.py:118-125 as one sweep; the arguments of the next
@@ -141,7 +164,7 @@ __device__ __forceinline__ void wide_ho_step(const double (&dk)[I], int order, d
     }
 }
 
-template <int I, int E, bool RBF>
+template <int I, int E, int KD>
 __device__ __forceinline__ void wide_chain_fwd(const double* __restrict__ col, int64_t CW, int64_t Tpad, int k0, int L, int difference, int order, const WideKap& K,
                                                double (&u)[I]) {
 #pragma unroll
@@ -152,7 +175,7 @@ __device__ __forceinline__ void wide_chain_fwd(const double* __restrict__ col, i
     wide_load_row<I, E>(r, k0, Tpad, cur);
     if (difference) {                                                              // signature_algs.py:114
 #pragma unroll
-        for (int j = 0; j < I; ++j) prev[j] = wide_val<I, E, RBF>(cur, j, K);
+        for (int j = 0; j < I; ++j) prev[j] = wide_val<I, E, KD>(cur, j, K);
         r += CW;
         steps = L - 1;
         if (steps > 0) wide_load_row<I, E>(r, k0, Tpad, cur);
@@ -164,7 +187,7 @@ __device__ __forceinline__ void wide_chain_fwd(const double* __restrict__ col, i
         double dk[I];
 #pragma unroll
         for (int j = 0; j < I; ++j) {
-            const double v = wide_val<I, E, RBF>(cur, j, K);
+            const double v = wide_val<I, E, KD>(cur, j, K);
             dk[j] = difference ? v - prev[j] : v;
             prev[j] = v;
         }
@@ -180,13 +203,13 @@ __device__ __forceinline__ void wide_chain_fwd(const double* __restrict__ col, i
     }
 }
 
-template <int E, bool RBF>
+template <int E, int KD>
 __device__ __forceinline__ void wide_level_fwd(int i, const double* col, const WideTvsArgs& A, const WideKap& K, double* u /* [i] */) {
     const int k0 = i * (i - 1) / 2;
 #define GPSIG_WIDE_CASE(I_)                                                                          \
     case I_: {                                                                                       \
         double v[I_];                                                                                \
-        wide_chain_fwd<I_, E, RBF>(col, A.CW, A.Tpad, k0, A.L, A.difference, A.order, K, v);                  \
+        wide_chain_fwd<I_, E, KD>(col, A.CW, A.Tpad, k0, A.L, A.difference, A.order, K, v);                  \
         _Pragma("unroll") for (int j = 0; j < I_; ++j) u[j] = v[j];                                 \
     } break;
     switch (i) {
@@ -200,12 +223,10 @@ __device__ __forceinline__ void wide_level_fwd(int i, const double* col, const W
 // grid: (Tpad / 64, sequences of the chunk (grid-stride), levels); block: one wavefront, lane = tensor.  A launch of few sequences is bound by the
 // serial sweep of one chain: the levels of a (tensor, sequence) pair go to different workgroups (blockIdx.z + 1 = level), each leaving its chain totals
 // in aux (N, lt, Tpad) -- tensors fastest --, and wide_tvs_epilogue_kernel forms the outputs from them.
-template <int E, bool RBF>
+template <int E, int KD>
 __global__ void __launch_bounds__(64) wide_tvs_fwd_kernel(const WideTvsArgs A) {
     __shared__ double etab[EXP_TAB_N];
-    exp_tab_fill(etab, threadIdx.x, 64);
-    __syncthreads();
-    const WideKap K = wide_kap(A.kind, etab);
+    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, 64));
     const int64_t t = int64_t(blockIdx.x) * 64 + threadIdx.x;
     const int M = A.M, lt = M * (M + 1) / 2;
     const int i = blockIdx.z + 1, k0 = i * (i - 1) / 2;
@@ -213,7 +234,7 @@ __global__ void __launch_bounds__(64) wide_tvs_fwd_kernel(const WideTvsArgs A) {
         const int64_t n = A.n0 + nl;
         const double* col = A.arg + nl * int64_t(A.L) * A.CW + t;
         double u[WIDE_MAX_LEVELS];
-        wide_level_fwd<E, RBF>(i, col, A, K, u);
+        wide_level_fwd<E, KD>(i, col, A, K, u);
         for (int j = 0; j < i; ++j) A.aux[(n * lt + k0 + j) * A.Tpad + t] = u[j];
     }
 }
@@ -242,7 +263,7 @@ __global__ void wide_tvs_epilogue_kernel(const WideTvsArgs A) {
 // by u_j <- u_j - m_j u_{j-1} (tvs_grad_tile_kernel.hpp, grad_ho_kernels.hpp: chain_levels_grad_kernel).  m_j[tau] = v_j[tau + 1] - v_j[tau]
 // (signature_algs.py:114), so the adjoint of the VALUE row rho is g[rho - 1] - g[rho]; times d kappa / d a of each endpoint it is the adjoint of the
 // argument.  u: the level's totals (destroyed).  c: the level's upstream gradient.  Columns of tensors beyond Tn get zeros (valid = false).
-template <int I, int E, bool RBF>
+template <int I, int E, int KD>
 __device__ __forceinline__ void wide_chain_bwd(const double* __restrict__ col, double* __restrict__ wcol, int64_t CW, int64_t Tpad, int k0, int L,
                                                int difference, int order, const WideKap& K, double (&u)[I], double c, bool valid) {
     double wv[I];
@@ -253,11 +274,11 @@ __device__ __forceinline__ void wide_chain_bwd(const double* __restrict__ col, d
         for (int j = 0; j < I; ++j) {
             if constexpr (E == 2) {
                 double k1, d1, k0v, d0;
-                wide_kappa_grad<RBF>(K, raw[2 * j + 1], k1, d1);
-                wide_kappa_grad<RBF>(K, raw[2 * j], k0v, d0);
+                wide_kappa_grad<KD>(K, raw[2 * j + 1], k1, d1);
+                wide_kappa_grad<KD>(K, raw[2 * j], k0v, d0);
                 v[j] = k1 - k0v; d[j][1] = d1; d[j][0] = -d0;
             } else {
-                wide_kappa_grad<RBF>(K, raw[j], v[j], d[j][0]);
+                wide_kappa_grad<KD>(K, raw[j], v[j], d[j][0]);
             }
         }
     };
@@ -384,12 +405,10 @@ __device__ __forceinline__ double wide_wave_sum(double v) {
     return v;
 }
 
-template <int E, bool RBF>
+template <int E, int KD>
 __global__ void __launch_bounds__(64) wide_tvs_bwd_kernel(const WideTvsArgs A) {
     __shared__ double etab[EXP_TAB_N];
-    exp_tab_fill(etab, threadIdx.x, 64);
-    __syncthreads();
-    const WideKap K = wide_kap(A.kind, etab);
+    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, 64));
     const int64_t t = int64_t(blockIdx.x) * 64 + threadIdx.x;
     const bool valid = t < A.Tn;
     const int M = A.M, lt = M * (M + 1) / 2;
@@ -410,7 +429,7 @@ __global__ void __launch_bounds__(64) wide_tvs_bwd_kernel(const WideTvsArgs A) {
         if (A.aux) {
             for (int j = 0; j < i; ++j) u[j] = A.aux[(n * lt + k0 + j) * A.Tpad + t];
         } else {
-            wide_level_fwd<E, RBF>(i, col, A, K, u);
+            wide_level_fwd<E, KD>(i, col, A, K, u);
         }
         if (A.gfac_part) {
             double ui = 0.0;
@@ -424,7 +443,7 @@ __global__ void __launch_bounds__(64) wide_tvs_bwd_kernel(const WideTvsArgs A) {
     case I_: {                                                                                               \
         double v[I_];                                                                                        \
         _Pragma("unroll") for (int j = 0; j < I_; ++j) v[j] = u[j];                                         \
-        wide_chain_bwd<I_, E, RBF>(col, wcol, A.CW, A.Tpad, k0, A.L, A.difference, A.order, K, v, c, valid);          \
+        wide_chain_bwd<I_, E, KD>(col, wcol, A.CW, A.Tpad, k0, A.L, A.difference, A.order, K, v, c, valid);          \
     } break;
         switch (i) {
             GPSIG_WIDE_CASE(1) GPSIG_WIDE_CASE(2) GPSIG_WIDE_CASE(3) GPSIG_WIDE_CASE(4)
@@ -448,38 +467,60 @@ __global__ void wide_gfac_reduce_kernel(const double* __restrict__ part, int TB,
 // dst row r (DA = d + 2 columns): the d values of the source row, then (-|v|^2/2, 1) [left form] or (1, -|v|^2/2) [right form].
 // Tensor rows are reordered on the way: dst row (k * E + e) * Tpad + t  <-  src row (k * Tn + t) * E + e (the caller's (lt, T, E, d) array), scaled by
 // lengthscales / lag weights where P.has_ls (kernels.py:367-398); rows of tensors beyond Tn are zero.  lt == 0: rows as they come (sequences, already scaled).
+// The dot-product families (mode; the argument is the inner product itself, the two extra columns stay out of it):
+//   WIDE_ROWS_PLAIN  [v, 0, 0] on both sides;
+//   WIDE_ROWS_UNIT   [v / |v|, 1 / |v|, 0] (left form), [v / |v|, 0, 1 / |v|] (right form): the norm's reciprocal rides in the column whose partner is
+//                    zero on the other side, for the adjoint (wide_unaug_unit_kernel); a row of zero norm is 0 / 0 as in base_eval (seq_core.hpp);
+// and with diff != 0 (SignatureLinear) the rows are INCREMENTS, taken before scaling:
+//   sequences (lt == 0): dst row n * (diff - 1) + t  <-  src rows n * diff + t + 1 minus n * diff + t   (diff = observations per sequence, rows = N (diff - 1));
+//   tensors (lt > 0, E == 1): dst row k * Tpad + t  <-  z^1 - z^0 of the caller's (lt, T, 2, d) array (kernels.py:329-330 collapsed: <z^1, x> - <z^0, x>).
 // One wavefront per row.
+constexpr int WIDE_ROWS_DIST = 0, WIDE_ROWS_PLAIN = 1, WIDE_ROWS_UNIT = 2;
+
 __global__ void __launch_bounds__(64) wide_aug_rows_kernel(const double* __restrict__ src, int64_t rows, int d, int right, int lt, int64_t Tn, int64_t Tpad,
-                                                           int E, ScaleParams P, double* __restrict__ dst) {
+                                                           int E, ScaleParams P, int mode, int diff, double* __restrict__ dst) {
     const int DA = d + 2;
     for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
-        const double* s = nullptr;
+        const double *s = nullptr, *s0 = nullptr;          // the row, and the row subtracted from it (increments)
         if (lt > 0) {
             const int64_t t = r % Tpad;
             const int ke = int(r / Tpad), k = ke / E, e = ke - k * E;
-            if (t < Tn) s = src + ((int64_t(k) * Tn + t) * E + e) * d;
+            if (t < Tn && diff) { s0 = src + (int64_t(k) * Tn + t) * 2 * d; s = s0 + d; }
+            else if (t < Tn) s = src + ((int64_t(k) * Tn + t) * E + e) * d;
+        } else if (diff) {
+            const int64_t n = r / (diff - 1), t = r - n * (diff - 1);
+            s0 = src + (n * diff + t) * d; s = s0 + d;
         } else {
             s = src + r * d;
         }
+        auto value = [&](int f) -> double {
+            if (!s) return 0.0;
+            double v = s0 ? s[f] - s0[f] : s[f];
+            if (lt > 0 && P.has_ls) {
+                const int lag = f / P.d_in, f0 = f - lag * P.d_in;
+                v = v / P.lsv(f0);
+                if (P.num_lags > 0) v = v * P.gamma[lag];
+            }
+            return v;
+        };
         double ss = 0.0;
         for (int f = threadIdx.x; f < d; f += 64) {
-            double v = 0.0;
-            if (s) {
-                v = s[f];
-                if (lt > 0 && P.has_ls) {
-                    const int lag = f / P.d_in, f0 = f - lag * P.d_in;
-                    v = v / P.lsv(f0);
-                    if (P.num_lags > 0) v = v * P.gamma[lag];
-                }
-            }
-            dst[r * DA + f] = v;
+            const double v = value(f);
+            if (mode != WIDE_ROWS_UNIT) dst[r * DA + f] = v;
             ss = fma(v, v, ss);
         }
         ss = wide_wave_sum(ss);
+        double inv = 0.0;
+        if (mode == WIDE_ROWS_UNIT) {
+            inv = s ? 1.0 / sqrt(ss) : 0.0;
+            for (int f = threadIdx.x; f < d; f += 64) dst[r * DA + f] = s ? value(f) * inv : 0.0;
+        }
         if (threadIdx.x == 0) {
-            const double h = s ? -0.5 * ss : 0.0, one = s ? 1.0 : 0.0;
-            dst[r * DA + d] = right ? one : h;
-            dst[r * DA + d + 1] = right ? h : one;
+            double own = s ? -0.5 * ss : 0.0, other = s ? 1.0 : 0.0;       // own: column d of the left form, d + 1 of the right form
+            if (mode == WIDE_ROWS_PLAIN) own = other = 0.0;
+            if (mode == WIDE_ROWS_UNIT) { own = inv; other = 0.0; }
+            dst[r * DA + d] = right ? other : own;
+            dst[r * DA + d + 1] = right ? own : other;
         }
     }
 }
@@ -501,6 +542,66 @@ __global__ void wide_unaug_rows_kernel(const double* __restrict__ ga, const doub
             r = (int64_t(k) * E + e) * Tpad + t;
         }
         g[idx] = fma(-ga[r * DA + nc], va[r * DA + f], ga[r * DA + f]);
+    }
+}
+
+// The adjoints of the dot-product families' rows.  Sources: the adjoint gl of left-form rows vl and / or gr of right-form rows vr (both: one array on both
+// sides of the lattices, the two forms of the tensors in Kzz -- the sum of the two); row mapping as wide_aug_rows_kernel.
+// WIDE_ROWS_UNIT:  g_v = (g_u - <g_u, u> u) / |v|   (u = v / |v|; 1 / |v| from the form's own column).  One wavefront per output row.
+__global__ void __launch_bounds__(64) wide_unaug_unit_kernel(const double* __restrict__ gl, const double* __restrict__ vl, const double* __restrict__ gr,
+                                                             const double* __restrict__ vr, int64_t rows_out, int d, int lt, int64_t Tn, int64_t Tpad, int E,
+                                                             double* __restrict__ g) {
+    const int DA = d + 2;
+    for (int64_t ro = blockIdx.x; ro < rows_out; ro += gridDim.x) {
+        int64_t r = ro;
+        if (lt > 0) {
+            const int e = int(ro % E);
+            const int64_t t = (ro / E) % Tn;
+            const int k = int(ro / (int64_t(E) * Tn));
+            r = (int64_t(k) * E + e) * Tpad + t;
+        }
+        double pl = 0.0, pr = 0.0;
+        for (int f = threadIdx.x; f < d; f += 64) {
+            if (gl) pl = fma(gl[r * DA + f], vl[r * DA + f], pl);
+            if (gr) pr = fma(gr[r * DA + f], vr[r * DA + f], pr);
+        }
+        pl = wide_wave_sum(pl);
+        pr = wide_wave_sum(pr);
+        const double il = gl ? vl[r * DA + d] : 0.0, ir = gr ? vr[r * DA + d + 1] : 0.0;
+        for (int f = threadIdx.x; f < d; f += 64) {
+            double v = 0.0;
+            if (gl) v = fma(-pl, vl[r * DA + f], gl[r * DA + f]) * il;
+            if (gr) v += fma(-pr, vr[r * DA + f], gr[r * DA + f]) * ir;
+            g[ro * d + f] = v;
+        }
+    }
+}
+
+// WIDE_ROWS_PLAIN rows that are increments (SignatureLinear): an increment's adjoint goes to its two points,
+//   sequences (lt == 0, diff = observations per sequence, rows_out = N diff):  gX[t] = gD[t - 1] - gD[t]   (zero outside 0 .. diff - 2),
+//   tensors (lt > 0, the caller's (lt, T, 2, d) array, rows_out = lt T 2):     gz^1 = gD,  gz^0 = -gD.
+// One thread per output element.
+__global__ void wide_unaug_inc_kernel(const double* __restrict__ gl, const double* __restrict__ gr, int64_t rows_out, int d, int lt, int64_t Tn, int64_t Tpad,
+                                      int diff, double* __restrict__ g) {
+    const int DA = d + 2;
+    const int64_t total = rows_out * d;
+    for (int64_t idx = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; idx < total; idx += int64_t(gridDim.x) * blockDim.x) {
+        const int f = int(idx % d);
+        const int64_t ro = idx / d;
+        auto at = [&](int64_t r) -> double { return (gl ? gl[r * DA + f] : 0.0) + (gr ? gr[r * DA + f] : 0.0); };
+        if (lt > 0) {
+            const int e = int(ro % 2);
+            const int64_t t = (ro / 2) % Tn;
+            const int64_t k = ro / (2 * Tn);
+            const double v = at(k * Tpad + t);
+            g[idx] = e ? v : -v;
+        } else {
+            const int64_t n = ro / diff, t = ro - n * diff, r0 = n * (diff - 1);
+            double v = 0.0;
+            if (t >= 1) v = at(r0 + t - 1);
+            if (t < diff - 1) v -= at(r0 + t);
+            g[idx] = v;
+        }
     }
 }
 
@@ -527,7 +628,7 @@ struct WideLatArgs {
 // argument rows (and, in the backward sweep, stored prefix rows) in flight ahead of a step: a step of few columns is shorter than a memory access
 constexpr int wide_lat_pf(int C) { return C >= 8 ? 1 : (C == 4 ? 2 : 4); }
 
-template <int C, bool RBF>
+template <int C, int KD>
 struct WideLatDm {
     double rd[C];
     int nvalid, b0, L2, diff;
@@ -544,7 +645,7 @@ struct WideLatDm {
     __device__ __forceinline__ void map(const double (&raw)[C + 1], double (&out)[C]) const {
         double k[C + 1];
 #pragma unroll
-        for (int c = 0; c <= C; ++c) k[c] = (c < C || diff) ? wide_kappa<RBF>(K, raw[c]) : 0.0;
+        for (int c = 0; c <= C; ++c) k[c] = (c < C || diff) ? wide_kappa<KD>(K, raw[c]) : 0.0;
 #pragma unroll
         for (int c = 0; c < C; ++c) out[c] = diff ? k[c + 1] - k[c] : k[c];
     }
@@ -582,12 +683,11 @@ __device__ __forceinline__ double wide_from_right(double v) {      // lane l <- 
 // NW > 1: NW wavefronts per lattice (a workgroup), lane lam = threadIdx.x of 64 NW; the hand-over across a wavefront boundary goes through LDS (two buffers
 // alternating by the step's parity, one barrier per step).  For a FEW long lattices (the level diagonals of a minibatch: 50 lattices of 499 x 499 keep
 // 50 of 1,024 SIMDs busy with eight columns per lane) -- more steps (R1 + 64 NW - 1), an eighth of the work per step, NW times the wavefronts.
-template <int C, int LQ, bool RBF, int NW = 1>
+template <int C, int LQ, int KD, int NW = 1>
 __global__ void __launch_bounds__(64 * NW) wide_lattice_fwd_kernel(const WideLatArgs A) {
     __shared__ double etab[EXP_TAB_N];
     __shared__ double xw[2][NW][LQ + 2];
-    exp_tab_fill(etab, threadIdx.x, 64 * NW);
-    __syncthreads();
+    const double* const ktab = wide_tab<KD>(etab, threadIdx.x, 64 * NW);
     constexpr int GL = 64 * NW, PF = wide_lat_pf(C);
     const int lam = threadIdx.x, M = A.M, wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
     const int dr = A.difference ? 1 : 0, R1 = A.L1 - dr, R2 = A.L2 - dr, TF = R1 + GL - 1;
@@ -601,9 +701,9 @@ __global__ void __launch_bounds__(64 * NW) wide_lattice_fwd_kernel(const WideLat
             __syncthreads();
         }
         const int64_t pg = A.p0 + pp;
-        WideLatDm<C, RBF> dmg;
+        WideLatDm<C, KD> dmg;
         dmg.lat = A.arg + (pg / A.N2) * A.si + (pg % A.N2) * A.sj;
-        dmg.ld = A.ld; dmg.b0 = C * lam; dmg.L2 = A.L2; dmg.K = wide_kap(A.kind, etab); dmg.diff = dr;
+        dmg.ld = A.ld; dmg.b0 = C * lam; dmg.L2 = A.L2; dmg.K = wide_kap(A.kind, ktab); dmg.diff = dr;
         { const int nv = R2 - C * lam; dmg.nvalid = nv < 0 ? 0 : (nv > C ? C : nv); }
         WaveFwd<C, LQ> fw;
         fw.reset();
@@ -662,12 +762,11 @@ __global__ void __launch_bounds__(64 * NW) wide_lattice_fwd_kernel(const WideLat
 
 // Both sweeps (grad_wave_kernel.hpp: seq_grad_wave_kernel with the argument lattice in place of the point rows): Lam[a][b] = dL/ddM[a][b] out.
 // grid: ngroups workgroups of one wavefront; a group's pairs one after the other through its scratch slot.
-template <int C, int LQ, bool RBF, int NW = 1>
+template <int C, int LQ, int KD, int NW = 1>
 __global__ void __launch_bounds__(64 * NW) wide_lattice_bwd_kernel(const WideLatArgs A) {
     __shared__ double etab[EXP_TAB_N];
     __shared__ double xw[2][NW][LQ + 2];
-    exp_tab_fill(etab, threadIdx.x, 64 * NW);
-    __syncthreads();
+    const double* const ktab = wide_tab<KD>(etab, threadIdx.x, 64 * NW);
     constexpr int GL = 64 * NW, PF = wide_lat_pf(C);
     const int lam = threadIdx.x, M = A.M, wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
     const int dr = A.difference ? 1 : 0, R1 = A.L1 - dr, R2 = A.L2 - dr, TF = R1 + GL - 1;
@@ -686,9 +785,9 @@ __global__ void __launch_bounds__(64 * NW) wide_lattice_bwd_kernel(const WideLat
     for (int64_t pp = blockIdx.x; pp < A.P; pp += gridDim.x) {
         xw_clear();
         const int64_t pg = A.p0 + pp;
-        WideLatDm<C, RBF> dmg;
+        WideLatDm<C, KD> dmg;
         dmg.lat = A.arg + (pg / A.N2) * A.si + (pg % A.N2) * A.sj;
-        dmg.ld = A.ld; dmg.b0 = C * lam; dmg.L2 = A.L2; dmg.K = wide_kap(A.kind, etab); dmg.diff = dr;
+        dmg.ld = A.ld; dmg.b0 = C * lam; dmg.L2 = A.L2; dmg.K = wide_kap(A.kind, ktab); dmg.diff = dr;
         { const int nv = R2 - C * lam; dmg.nvalid = nv < 0 ? 0 : (nv > C ? C : nv); }
         double clev[LQ + 2];
 #pragma unroll
@@ -818,12 +917,10 @@ __global__ void __launch_bounds__(64 * NW) wide_lattice_bwd_kernel(const WideLat
 // W[r][c] = adjoint of the argument at point pair (r, c): the adjoint of the double increment (signature_algs.py:26)
 //   Gam[r][c] = Lam[r-1][c-1] - Lam[r-1][c] - Lam[r][c-1] + Lam[r][c]   (zero outside the lattice; no differences: Gam = Lam)
 // times d kappa / d a.  One thread per point pair; W in the layout of arg.
-template <bool RBF>
+template <int KD>
 __global__ void wide_lattice_adjoint_kernel(const WideLatArgs A, double* __restrict__ W) {
     __shared__ double etab[EXP_TAB_N];
-    exp_tab_fill(etab, threadIdx.x, blockDim.x);
-    __syncthreads();
-    const WideKap K = wide_kap(A.kind, etab);
+    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, blockDim.x));
     const int dr = A.difference ? 1 : 0, R1 = A.L1 - dr, R2 = A.L2 - dr;
     const int64_t cells = int64_t(A.L1) * A.L2, total = A.P * cells;
     for (int64_t idx = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; idx < total; idx += int64_t(gridDim.x) * blockDim.x) {
@@ -834,7 +931,7 @@ __global__ void wide_lattice_adjoint_kernel(const WideLatArgs A, double* __restr
         const double gam = dr ? at(r - 1, c - 1) - at(r - 1, c) - at(r, c - 1) + at(r, c) : at(r, c);
         const int64_t off = (pg / A.N2) * A.si + (pg % A.N2) * A.sj + int64_t(r) * A.ld + c;
         double k, dk;
-        wide_kappa_grad<RBF>(K, A.arg[off], k, dk);
+        wide_kappa_grad<KD>(K, A.arg[off], k, dk);
         W[off] = gam * dk;
     }
 }
@@ -851,20 +948,18 @@ __global__ void wide_sym_upstream_kernel(const double* __restrict__ G, int64_t N
 
 // dM[pair][a][b] (signature_algs.py:26 / :56) from the argument lattices, for the sweeps that read it from memory (the higher-order reverse pass,
 // grad_wave_ho_kernel.hpp).  One thread per lattice cell.
-template <bool RBF>
+template <int KD>
 __global__ void wide_lattice_dm_kernel(const WideLatArgs A, double* __restrict__ dM) {
     __shared__ double etab[EXP_TAB_N];
-    exp_tab_fill(etab, threadIdx.x, blockDim.x);
-    __syncthreads();
-    const WideKap K = wide_kap(A.kind, etab);
+    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, blockDim.x));
     const int dr = A.difference ? 1 : 0, R1 = A.L1 - dr, R2 = A.L2 - dr;
     const int64_t cells = int64_t(R1) * R2, total = A.P * cells;
     for (int64_t idx = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; idx < total; idx += int64_t(gridDim.x) * blockDim.x) {
         const int64_t pp = idx / cells, pg = A.p0 + pp;
         const int a = int((idx % cells) / R2), b = int(idx % R2);
         const double* base = A.arg + (pg / A.N2) * A.si + (pg % A.N2) * A.sj + int64_t(a) * A.ld + b;
-        double v = wide_kappa<RBF>(K, base[0]);
-        if (dr) v = (wide_kappa<RBF>(K, base[A.ld + 1]) - wide_kappa<RBF>(K, base[A.ld])) - (wide_kappa<RBF>(K, base[1]) - v);
+        double v = wide_kappa<KD>(K, base[0]);
+        if (dr) v = (wide_kappa<KD>(K, base[A.ld + 1]) - wide_kappa<KD>(K, base[A.ld])) - (wide_kappa<KD>(K, base[1]) - v);
         dM[idx] = v;
     }
 }
@@ -898,20 +993,18 @@ struct WideTensArgs {
 };
 
 // value of component k at (t, t'): kappa, or the four-term difference of its two points on both sides (kernels.py:276-277)
-template <bool RBF>
+template <int KD>
 __device__ __forceinline__ double wide_tens_val(const double* __restrict__ blk, int64_t R, int64_t Tpad, int E, const WideKap& K, int64_t t, int64_t tp) {
     if (E == 2)
-        return wide_kappa<RBF>(K, blk[(Tpad + t) * R + Tpad + tp]) + wide_kappa<RBF>(K, blk[t * R + tp]) - wide_kappa<RBF>(K, blk[(Tpad + t) * R + tp]) -
-               wide_kappa<RBF>(K, blk[t * R + Tpad + tp]);
-    return wide_kappa<RBF>(K, blk[t * R + tp]);
+        return wide_kappa<KD>(K, blk[(Tpad + t) * R + Tpad + tp]) + wide_kappa<KD>(K, blk[t * R + tp]) - wide_kappa<KD>(K, blk[(Tpad + t) * R + tp]) -
+               wide_kappa<KD>(K, blk[t * R + Tpad + tp]);
+    return wide_kappa<KD>(K, blk[t * R + tp]);
 }
 
-template <bool RBF>
+template <int KD>
 __global__ void __launch_bounds__(64) wide_tens_fwd_kernel(const WideTensArgs A) {
     __shared__ double etab[EXP_TAB_N];
-    exp_tab_fill(etab, threadIdx.x, 64);
-    __syncthreads();
-    const WideKap K = wide_kap(A.kind, etab);
+    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, 64));
     const int64_t tp = int64_t(blockIdx.x) * 64 + threadIdx.x, R = int64_t(A.E) * A.Tpad;
     if (tp >= A.Tn) return;
     for (int64_t t = blockIdx.y; t < A.Tn; t += gridDim.y) {
@@ -920,7 +1013,7 @@ __global__ void __launch_bounds__(64) wide_tens_fwd_kernel(const WideTensArgs A)
         int k = 0;
         for (int i = 1; i <= A.M; ++i) {
             double prod = 1.0;
-            for (int j = 0; j < i; ++j, ++k) prod *= wide_tens_val<RBF>(A.arg + int64_t(k) * R * R, R, A.Tpad, A.E, K, t, tp);      // :91-97
+            for (int j = 0; j < i; ++j, ++k) prod *= wide_tens_val<KD>(A.arg + int64_t(k) * R * R, R, A.Tpad, A.E, K, t, tp);      // :91-97
             const double f = A.w ? A.w[i] : 1.0;
             if (A.sum_levels) acc = fma(prod, f, acc);
             else A.out[(int64_t(i) * A.Tn + t) * A.Tn + tp] = prod * f;
@@ -930,12 +1023,12 @@ __global__ void __launch_bounds__(64) wide_tens_fwd_kernel(const WideTensArgs A)
 }
 
 // grid (Tpad / 64, Tpad rows (grid-stride)): every entry of W is written (zeros at padded tensors)
-template <bool RBF>
-__global__ void __launch_bounds__(64) wide_tens_bwd_kernel(const WideTensArgs A) {
+// (the identity instance has no table and fewer vector registers, and would otherwise spend scalar registers on hoisted addresses to the point of
+// losing a wavefront per SIMD to them: it is held to the eight of the RBF instance)
+template <int KD>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KD == WIDE_KD_ID ? 8 : 1))) wide_tens_bwd_kernel(const WideTensArgs A) {
     __shared__ double etab[EXP_TAB_N];
-    exp_tab_fill(etab, threadIdx.x, 64);
-    __syncthreads();
-    const WideKap K = wide_kap(A.kind, etab);
+    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, 64));
     const int64_t tp = int64_t(blockIdx.x) * 64 + threadIdx.x, R = int64_t(A.E) * A.Tpad;
     for (int64_t t = blockIdx.y; t < A.Tpad; t += gridDim.y) {
         const bool valid = t < A.Tn && tp < A.Tn;
@@ -944,7 +1037,7 @@ __global__ void __launch_bounds__(64) wide_tens_bwd_kernel(const WideTensArgs A)
             const double c = valid ? A.G[(int64_t(i) * A.Tn + t) * A.Tn + tp] : 0.0;
             double v[WIDE_MAX_LEVELS];
 #pragma unroll
-            for (int j = 0; j < WIDE_MAX_LEVELS; ++j) v[j] = j < i ? wide_tens_val<RBF>(A.arg + int64_t(k0 + j) * R * R, R, A.Tpad, A.E, K, t, tp) : 1.0;
+            for (int j = 0; j < WIDE_MAX_LEVELS; ++j) v[j] = j < i ? wide_tens_val<KD>(A.arg + int64_t(k0 + j) * R * R, R, A.Tpad, A.E, K, t, tp) : 1.0;
 #pragma unroll
             for (int j = 0; j < WIDE_MAX_LEVELS; ++j) {
                 if (j >= i) continue;
@@ -956,12 +1049,12 @@ __global__ void __launch_bounds__(64) wide_tens_bwd_kernel(const WideTensArgs A)
                 double* wb = A.W + int64_t(k0 + j) * R * R;
                 double kk, dk;
                 if (A.E == 2) {
-                    wide_kappa_grad<RBF>(K, blk[(A.Tpad + t) * R + A.Tpad + tp], kk, dk); wb[(A.Tpad + t) * R + A.Tpad + tp] = g * dk;
-                    wide_kappa_grad<RBF>(K, blk[t * R + tp], kk, dk);                     wb[t * R + tp] = g * dk;
-                    wide_kappa_grad<RBF>(K, blk[(A.Tpad + t) * R + tp], kk, dk);          wb[(A.Tpad + t) * R + tp] = -g * dk;
-                    wide_kappa_grad<RBF>(K, blk[t * R + A.Tpad + tp], kk, dk);            wb[t * R + A.Tpad + tp] = -g * dk;
+                    wide_kappa_grad<KD>(K, blk[(A.Tpad + t) * R + A.Tpad + tp], kk, dk); wb[(A.Tpad + t) * R + A.Tpad + tp] = g * dk;
+                    wide_kappa_grad<KD>(K, blk[t * R + tp], kk, dk);                     wb[t * R + tp] = g * dk;
+                    wide_kappa_grad<KD>(K, blk[(A.Tpad + t) * R + tp], kk, dk);          wb[(A.Tpad + t) * R + tp] = -g * dk;
+                    wide_kappa_grad<KD>(K, blk[t * R + A.Tpad + tp], kk, dk);            wb[t * R + A.Tpad + tp] = -g * dk;
                 } else {
-                    wide_kappa_grad<RBF>(K, blk[t * R + tp], kk, dk);
+                    wide_kappa_grad<KD>(K, blk[t * R + tp], kk, dk);
                     wb[t * R + tp] = g * dk;
                 }
             }
