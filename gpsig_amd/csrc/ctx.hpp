@@ -44,7 +44,7 @@ enum BufId {
     B_LRF32,                                                   // low-rank mode, float32 calls: the state and the spectral table narrowed to float32
     B_TQ,                                                      // item counters of the Kzx tile kernel's persistent launch
     B_STASH,                                                   // what the fused reverse kernel needs of the forward recursion (gpsig_seq_gram_levels_stash)
-    B_WD0, B_WD1, B_WD2, B_WD3, B_WD4, B_WD5, B_WD6, B_WD7, B_WD8, B_WD9, B_WD10,   // wide state spaces (wide_api.hip): augmented rows, kernel-argument chunks, their adjoints, lattice states
+    B_WD0, B_WD1, B_WD2, B_WD3, B_WD4, B_WD5, B_WD6, B_WD7, B_WD8, B_WD9, B_WD10, B_WD11,   // wide state spaces (wide_api.hip): augmented rows, kernel-argument chunks, their adjoints, lattice states
     B_COUNT
 };
 
@@ -516,5 +516,13 @@ inline int grid_for(int64_t n, int block = 256) {
 // The dot-product families (kappa = the dgemm's number itself).  Their automatic rules all read "beyond 32 columns": up to there the feature contraction and
 // the exact-shape kernels serve them (32 columns is the widest exact-shape lattice instance), and nothing has been measured that would move them.
 inline bool wide_dot_kind(int base_kernel) { return base_kernel == GPSIG_BASE_LINEAR || base_kernel == GPSIG_BASE_COSINE; }
+// SignaturePoly there: the whole degrees 1 .. 8 (0: not served).  Its automatic rules all read "beyond 64 columns" -- where the exact-shape kernels and
+// their gradients end --, so no call of up to 64 columns changes route unless option wide = 1 says so; nothing below has been measured into a rule.
+inline int wide_poly_degree(const gpsig_params* p) {
+    if (p->base_kernel != GPSIG_BASE_POLY) return 0;
+    const double deg = p->base_params[1];
+    const int n = (deg >= 1.0 && deg <= 8.0) ? int(deg) : 0;
+    return double(n) == deg ? n : 0;
+}
 // the widest state space that the automatic rule of a call site keeps off the wide route (cols: the distance kernels' figure there)
-inline int wide_auto_cols(const gpsig_params* p, int cols) { return wide_dot_kind(p->base_kernel) ? 32 : cols; }
+inline int wide_auto_cols(const gpsig_params* p, int cols) { return p->base_kernel == GPSIG_BASE_POLY ? 64 : (wide_dot_kind(p->base_kernel) ? 32 : cols); }

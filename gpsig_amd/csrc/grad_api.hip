@@ -807,6 +807,10 @@ int seq_grad(gpsig_ctx* c, const gpsig_params* p, const void* X, const void* Y, 
     const bool wide_ho = N1 > 0 && N2 > 0 && wide_lat_ho_available(c, p, L1, (diag || Y == nullptr) ? L1 : L2);      // order > 1: the reverse pass only
     const bool wide_ok = wide_ho || (N1 > 0 && N2 > 0 && wide_lat_available(c, p, L1, (diag || Y == nullptr) ? L1 : L2));
     if (DP == 0 && !wide_ok) return fail(c, GPSIG_ERR_UNSUPPORTED, "gradients are built for at most 64 feature columns here (got %d)", d);
+    // SignaturePoly's sequence GRAM gradient beyond 64 columns stays refused although the wide lattices would take it (its level diagonals are served):
+    // tests/test_gpu_grad.py (the block at "beyond 64 columns ... an error for the others", poly at 65 columns) pins this answer
+    if (DP == 0 && !diag && p->base_kernel == GPSIG_BASE_POLY)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "gradients are built for at most 64 feature columns here (got %d)", d);
     if (N1 > 0x7fffffff || N2 > 0x7fffffff) return fail(c, GPSIG_ERR_UNSUPPORTED, "more than 2^31 sequences");
     const bool sym = !diag && Y == nullptr;
     if (sym) { N2 = N1; L2 = L1; }
@@ -847,10 +851,12 @@ int seq_grad(gpsig_ctx* c, const gpsig_params* p, const void* X, const void* Y, 
     // reference's shapes -- profiles/r06_ab_small_widths.txt; grad_impl != 0: A/B runs of the exact-shape kernels)
     // (higher order: the point route's dM and contraction kernels cost more than the sweeps -- ho_dm_kernel evaluates every kappa four times with the
     // library's exp --, so the wide route's dgemms take RBF and the Matern families at every width)
-    // (the dot-product families: beyond 32 columns, or by option -- up to there the feature route and the exact-shape kernels below keep them)
-    if (wide_ok && (c->wide == 1 || DP == 0 || wide_ho || (!ffn && c->grad_impl == 0 && (wide_dot_kind(p->base_kernel) ? d > 32 : (d > 8 || (!w2x && !lfn && !wfn)))))) {
+    // (the dot-product families: beyond 32 columns, or by option -- up to there the feature route and the exact-shape kernels below keep them;
+    // SignaturePoly: beyond 64 columns -- DP == 0 --, or by option)
+    const bool wide_rule = p->base_kernel == GPSIG_BASE_POLY ? false : (wide_dot_kind(p->base_kernel) ? d > 32 : (d > 8 || (!w2x && !lfn && !wfn)));
+    if (wide_ok && (c->wide == 1 || DP == 0 || wide_ho || (!ffn && c->grad_impl == 0 && wide_rule))) {
         CHK(wide_lat_backward(c, p, d, static_cast<const double*>(dX), static_cast<const double*>((diag || sym) ? nullptr : dY), N1, N2, L1, L2, diag,
-                              static_cast<const double*>(dG), static_cast<double*>(dgX), static_cast<double*>(dgY)));
+                              static_cast<const double*>(dG), static_cast<double*>(dgX), static_cast<double*>(dgY), kgb));
         CHK(out_done(c, gX, dgX, xb));
         if (!diag && !sym) CHK(out_done(c, gY, dgY, yb));
         CHK(gbase_end(c, dgb, g_base));
@@ -1041,7 +1047,7 @@ int gpsig_tens_gram_levels_grad(gpsig_ctx* c, const gpsig_params* p, const void*
     // kernels without a differentiable base parameter skip the accumulation (one same-address atomic per wavefront otherwise)
     double* const kgb = (p->base_kernel == GPSIG_BASE_POLY || p->base_kernel == GPSIG_BASE_MIX) ? dgb : nullptr;
     if (wide) {
-        CHK(wide_tens_backward(c, p, d, static_cast<const double*>(dZ), T, increments, static_cast<const double*>(dG), static_cast<double*>(dgZ)));
+        CHK(wide_tens_backward(c, p, d, static_cast<const double*>(dZ), T, increments, static_cast<const double*>(dG), static_cast<double*>(dgZ), kgb));
     } else if (T > 0) {
         void *zp, *gzp;
         CHK(ensure(c, B_GR0, sizeof(double) * size_t(rows) * DP, &zp));
@@ -1083,8 +1089,8 @@ int gpsig_tens_vs_seq_levels_grad(gpsig_ctx* c, const gpsig_params* p, const voi
     CHK(grad_check(c, p, &d, &DP, 4096));
     // wide state spaces (wide_api.hip): beyond the tile kernel's 8 columns, or wherever built when the option says so
     // (higher orders: at any width -- the tile kernel's reverse pass is first-order, the older kernels go through scratch memory operation by operation)
-    // (the dot-product families: beyond 32 columns, or by option)
-    const bool wide = wide_tvs_available(c, p, d, T, N, L) && (wide_dot_kind(p->base_kernel) ? (c->wide == 1 || d > 32) :
+    // (the dot-product families: beyond 32 columns, or by option; SignaturePoly: beyond 64)
+    const bool wide = wide_tvs_available(c, p, d, T, N, L) && ((wide_dot_kind(p->base_kernel) || p->base_kernel == GPSIG_BASE_POLY) ? (c->wide == 1 || d > wide_auto_cols(p, 32)) :
                                                                (c->wide == 1 || d > 8 || (p->num_levels > 6 && c->wide != 0) ||      /* (7 / 8 levels: no reverse tile instance -- 100 ms at T = 512, N = 2,048 on the older kernels) */
                                                                 (p->order > 1 && p->num_levels > 1 && c->wide != 0 && !tvs_grad_tile_ho_available(c, p, d, L, increments))));
     if (DP == 0 && !wide) return fail(c, GPSIG_ERR_UNSUPPORTED, "gradients are built for at most 64 feature columns here (got %d)", d);
@@ -1109,7 +1115,7 @@ int gpsig_tens_vs_seq_levels_grad(gpsig_ctx* c, const gpsig_params* p, const voi
     bool tiled = false;
     if (wide) {
         CHK(wide_tvs_backward(c, p, d, static_cast<const double*>(dZ), static_cast<const double*>(dX), static_cast<const double*>(dG), T, N, L, increments,
-                              nullptr, nullptr, static_cast<double*>(dgZ), static_cast<double*>(dgX), nullptr));
+                              nullptr, nullptr, static_cast<double*>(dgZ), static_cast<double*>(dgX), nullptr, kgb));
         tiled = true;
     }
     if (!tiled && T > 0 && N > 0 && c->grad_impl == 0 && c->tvs_grad_tile != 0)
@@ -1431,8 +1437,8 @@ int gpsig_tens_vs_seq_weighted_grad(gpsig_ctx* c, const gpsig_params* p, const v
     int d, DP;
     CHK(grad_check(c, p, &d, &DP, 4096));
     // (higher orders: at any width -- the tile kernel's reverse pass is first-order, the older kernels go through scratch memory operation by operation)
-    // (the dot-product families: beyond 32 columns, or by option)
-    const bool wide = wide_tvs_available(c, p, d, T, N, L) && (wide_dot_kind(p->base_kernel) ? (c->wide == 1 || d > 32) :
+    // (the dot-product families: beyond 32 columns, or by option; SignaturePoly: beyond 64)
+    const bool wide = wide_tvs_available(c, p, d, T, N, L) && ((wide_dot_kind(p->base_kernel) || p->base_kernel == GPSIG_BASE_POLY) ? (c->wide == 1 || d > wide_auto_cols(p, 32)) :
                                                                (c->wide == 1 || d > 8 || (p->num_levels > 6 && c->wide != 0) ||      /* (7 / 8 levels: no reverse tile instance -- 100 ms at T = 512, N = 2,048 on the older kernels) */
                                                                 (p->order > 1 && p->num_levels > 1 && c->wide != 0 && !tvs_grad_tile_ho_available(c, p, d, L, increments))));
     if (DP == 0 && !wide) return fail(c, GPSIG_ERR_UNSUPPORTED, "gradients are built for at most 64 feature columns here (got %d)", d);
@@ -1453,10 +1459,13 @@ int gpsig_tens_vs_seq_weighted_grad(gpsig_ctx* c, const gpsig_params* p, const v
     const bool has_base = p->base_kernel == GPSIG_BASE_POLY || p->base_kernel == GPSIG_BASE_MIX;
     bool tiled = false;
     if (wide) {
+        double* dgb = nullptr;
+        if (has_base) CHK(gbase_begin(c, &dgb));
         CHK(wide_tvs_backward(c, p, d, static_cast<const double*>(dZ), static_cast<const double*>(dX), static_cast<const double*>(dG), T, N, L, increments,
                               static_cast<const double*>(dF), c->ptr_mode == GPSIG_PTR_DEVICE ? static_cast<const double*>(aux) : nullptr,
-                              static_cast<double*>(dgZ), static_cast<double*>(dgX), static_cast<double*>(dgF)));
-        if (g_base && c->ptr_mode == GPSIG_PTR_HOST) g_base[0] = g_base[1] = 0.0;
+                              static_cast<double*>(dgZ), static_cast<double*>(dgX), static_cast<double*>(dgF), dgb));
+        if (has_base) CHK(gbase_end(c, dgb, g_base));
+        else if (g_base && c->ptr_mode == GPSIG_PTR_HOST) g_base[0] = g_base[1] = 0.0;              // (no base parameter: zeros, as before)
         else if (g_base) CHK(zero_async(c, g_base, 2 * sizeof(double)));
         tiled = true;
     }

@@ -181,17 +181,17 @@ bool wide_tvs_available(const gpsig_ctx* c, const gpsig_params* p, int d, int64_
 int wide_tvs_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz, int d, const double* Z, const double* Xs, int64_t Tn, int64_t N, int L,
                      int increments, const double* fx, const double* w, int sum_levels, double* out, double* aux);
 int wide_tvs_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Z, const double* X, const double* G, int64_t Tn, int64_t N, int L,
-                      int increments, const double* fac, const double* aux, double* gZ, double* gX, double* gfac);
+                      int increments, const double* fac, const double* aux, double* gZ, double* gX, double* gfac, double* g_base);
 bool wide_tens_available(const gpsig_ctx* c, const gpsig_params* p, int64_t Tn);
 int wide_tens_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz, int d, const double* Z, int64_t Tn, int increments, const double* w,
                       int sum_levels, double* out);
-int wide_tens_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Z, int64_t Tn, int increments, const double* G, double* gZ);
+int wide_tens_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Z, int64_t Tn, int increments, const double* G, double* gZ, double* g_base);
 bool wide_lat_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L2);
 bool wide_lat_ho_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L2);
 int wide_lat_forward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Xs, const double* Ys, int64_t N1, int64_t N2, int L1, int L2, bool diag,
                      double* out);
 int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Xs, const double* Ys, int64_t N1, int64_t N2, int L1, int L2, bool diag,
-                      const double* G, double* gX, double* gY);
+                      const double* G, double* gX, double* gY, double* g_base);
 
 // ---- lowrank_solver.hip: rocSOLVER / rocBLAS, opened at first use --------------------------------------------------------------------
 bool solver_dsyevd(void** handle_slot, hipStream_t stream, int n, double* A, double* ev, double* work, int* info, std::string* err);

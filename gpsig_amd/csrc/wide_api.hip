@@ -14,13 +14,23 @@
 namespace gpsig {
 namespace {
 
-bool wide_kind(int base_kernel) {
+// (SignaturePoly: the whole degrees 1 .. 8 of the kernels' repeated squaring -- any other degree is left to the routes that call the library's pow)
+bool wide_kind(const gpsig_params* p) {
+    const int base_kernel = p->base_kernel;
+    if (base_kernel == GPSIG_BASE_POLY) return wide_poly_degree(p) > 0;
     return base_kernel == GPSIG_BASE_RBF || base_kernel == GPSIG_BASE_MATERN12 || base_kernel == GPSIG_BASE_MATERN32 || base_kernel == GPSIG_BASE_MATERN52 ||
            wide_dot_kind(base_kernel);
 }
 // the kernels' compile-time kind, and the form of the rows that go into the dgemm
-int kind_of(int base_kernel) { return base_kernel == GPSIG_BASE_RBF ? WIDE_KD_RBF : (wide_dot_kind(base_kernel) ? WIDE_KD_ID : WIDE_KD_MATERN); }
-int rows_mode(int base_kernel) { return base_kernel == GPSIG_BASE_LINEAR ? WIDE_ROWS_PLAIN : (base_kernel == GPSIG_BASE_COSINE ? WIDE_ROWS_UNIT : WIDE_ROWS_DIST); }
+// (SignaturePoly: the points themselves as plain rows, a = <z, x>; it is non-linear, so its differences are taken on kappa inside the kernels)
+int kind_of(int base_kernel) {
+    if (base_kernel == GPSIG_BASE_POLY) return WIDE_KD_POLY;
+    return base_kernel == GPSIG_BASE_RBF ? WIDE_KD_RBF : (wide_dot_kind(base_kernel) ? WIDE_KD_ID : WIDE_KD_MATERN);
+}
+int rows_mode(int base_kernel) {
+    if (base_kernel == GPSIG_BASE_POLY) return WIDE_ROWS_PLAIN;
+    return base_kernel == GPSIG_BASE_LINEAR ? WIDE_ROWS_PLAIN : (base_kernel == GPSIG_BASE_COSINE ? WIDE_ROWS_UNIT : WIDE_ROWS_DIST);
+}
 // SignatureLinear: <.,.> is bilinear, so the differences along the sequences (signature_algs.py:26 / :114) and between a tensor's two points
 // (kernels.py:329-330) are taken on the ROWS -- exact to rounding under translation, like the exact-shape kernels' MODE_INC, where a four-term difference of
 // inner products of shifted paths is not -- and the kernels see difference = 0, one row less per sequence and one column per component
@@ -32,6 +42,7 @@ bool tensors_collapse(const gpsig_params* p, int increments) { return p->base_ke
     switch (kind_of(base)) {                                                                  \
         case WIDE_KD_RBF: { constexpr int KD = WIDE_KD_RBF; __VA_ARGS__; } break;             \
         case WIDE_KD_ID: { constexpr int KD = WIDE_KD_ID; __VA_ARGS__; } break;               \
+        case WIDE_KD_POLY: { constexpr int KD = WIDE_KD_POLY; __VA_ARGS__; } break;           \
         default: { constexpr int KD = WIDE_KD_MATERN; __VA_ARGS__; } break;                   \
     }
 
@@ -165,6 +176,18 @@ int contract_both(gpsig_ctx* c, const double* W, const double* XA, const double*
     return dgemm(c, false, false, DA, R, CW, ZA, DA, W, CW, 0.0, gXA, DA);
 }
 
+// SignaturePoly's offset: g_base[0] += the sum of the n partial sums that a reverse pass left in part (room for WIDE_GB_BLOCKS more doubles behind them), in
+// an order that depends on n alone (wide_sum_kernel)
+constexpr int WIDE_GB_BLOCKS = 1024;
+int gbase_reduce(gpsig_ctx* c, double* part, int64_t n, double* g_base) {
+    const int64_t nb = (n + 255) / 256;
+    const int blocks = int(nb < 1 ? 1 : (nb > WIDE_GB_BLOCKS ? WIDE_GB_BLOCKS : nb));
+    hipLaunchKernelGGL(wide_sum_kernel, dim3(blocks), dim3(256), 0, c->stream, static_cast<const double*>(part), n, 0, part + n);
+    hipLaunchKernelGGL(wide_sum_kernel, dim3(1), dim3(256), 0, c->stream, static_cast<const double*>(part + n), int64_t(blocks), 1, g_base);
+    HIPCHK(c, hipGetLastError());
+    return GPSIG_OK;
+}
+
 int wide_timing_begin(gpsig_ctx* c, hipEvent_t* e0, hipEvent_t* e1, bool* on) {
     *on = false;
     if (c->capturing || c->ev_used + 2 > 8192) return GPSIG_OK;
@@ -188,7 +211,7 @@ int wide_timing_begin(gpsig_ctx* c, hipEvent_t* e0, hipEvent_t* e1, bool* on) {
 // Is the route built for this call?  (float64 is the caller's business.)
 bool wide_tvs_available(const gpsig_ctx* c, const gpsig_params* p, int d, int64_t Tn, int64_t N, int L) {
     if (c->wide == 0 || c->capturing) return false;
-    if (!wide_kind(p->base_kernel) || (p->order > WIDE_MAX_ORDER && p->num_levels > WIDE_MAX_ORDER) || p->num_levels > WIDE_MAX_LEVELS || p->num_levels < 1) return false;
+    if (!wide_kind(p) || (p->order > WIDE_MAX_ORDER && p->num_levels > WIDE_MAX_ORDER) || p->num_levels > WIDE_MAX_LEVELS || p->num_levels < 1) return false;
     if (Tn < 1 || N < 1 || L < 1 || d < 1) return false;
     if (rows_are_increments(p) && L < 2) return false;        // (no increment rows)
     return true;
@@ -226,7 +249,7 @@ int wide_tvs_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz,
         WideTvsArgs A;
         memset(&A, 0, sizeof(A));
         A.arg = static_cast<const double*>(arg); A.CW = CW; A.Tpad = Tpad; A.Tn = Tn; A.n0 = n0; A.Nc = nc; A.N = N;
-        A.L = L; A.M = M; A.kind = p->base_kernel; A.difference = (p->difference && !xinc) ? 1 : 0; A.sum_levels = sum_levels;
+        A.L = L; A.M = M; A.kind = p->base_kernel; A.kp0 = p->base_params[0]; A.kp1 = p->base_params[1]; A.difference = (p->difference && !xinc) ? 1 : 0; A.sum_levels = sum_levels;
         A.fx = fx; A.w = w; A.out = out; A.aux = aux; A.order = p->order < p->num_levels ? p->order : p->num_levels;
         const dim3 grid(unsigned(TB), unsigned(nc < 65535 ? nc : 65535), unsigned(M));
         GPSIG_WIDE_KIND(p->base_kernel,
@@ -249,7 +272,7 @@ int wide_tvs_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz,
 // The reverse pass.  Z (lt, T, E, d), X (N, L, d): scaled operands as the gradient entry points take them.  fac == NULL: G (M+1, T, N), gradient of the
 // level array; fac (N, M+1): G (T, N), gradient of the weighted level sum, and gfac (N, M+1) receives the factors' gradient.
 int wide_tvs_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Z, const double* X, const double* G, int64_t Tn, int64_t N, int L,
-                      int increments, const double* fac, const double* aux, double* gZ, double* gX, double* gfac) {
+                      int increments, const double* fac, const double* aux, double* gZ, double* gX, double* gfac, double* g_base) {
     const bool xinc = rows_are_increments(p), zinc = tensors_collapse(p, increments);
     const int xdiff = xinc ? L : 0, mode = rows_mode(p->base_kernel);
     const int64_t NLx = N * int64_t(L);                          // the caller's rows
@@ -265,21 +288,44 @@ int wide_tvs_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
     int64_t chunk = int64_t(wide_chunk_bytes(c) / per_seq);
     if (chunk < 1) chunk = 1;
     if (chunk > N) chunk = N;
+    // SignaturePoly's offset (g_base: device, or NULL) is to come out with the same bits however the argument array is chunked.  Its partial sums are
+    // indexed by the global sequence (below), but the arguments themselves must not depend on the chunking either, and a dgemm's last bits depend on its
+    // shape (seen at 302 augmented columns).  So with the offset asked for, the arguments come from one dgemm per block of `blk` sequences -- a number
+    // that depends on L alone, at least 256 rows --, and chunks hold whole blocks (at least one: the budget yields to that), so that every dgemm has
+    // the same shape in every chunking.  (This rests on rocBLAS returning the same bits for dgemms of one shape whose outputs start at different
+    // offsets of the argument buffer.  Nothing in its interface promises that; tests/test_gpu_wide_poly.py holds it at the shapes it runs.)
+    const bool gb = g_base && p->base_kernel == GPSIG_BASE_POLY;
+    int64_t blk = chunk;                                         // sequences per dgemm
+    if (gb) {
+        blk = 1;
+        while (blk * L < 256) blk *= 2;
+        chunk = chunk / blk * blk;
+        if (chunk < blk) chunk = blk;
+        if (chunk > N) chunk = N;
+    }
     void *arg, *Wb, *gza, *gxa, *gfp = nullptr;
     CHK(ensure(c, B_WD2, per_seq * size_t(chunk) + 64, &arg));
     CHK(ensure(c, B_WD3, per_seq * size_t(chunk) + 64, &Wb));
     CHK(ensure(c, B_WD4, sizeof(double) * size_t(CW) * DA + 64, &gza));
     CHK(ensure(c, B_WD5, sizeof(double) * size_t(NL) * DA + 64, &gxa));
     if (fac) CHK(ensure(c, B_WD6, sizeof(double) * size_t(TB) * N * (M + 1) + 64, &gfp));
+    // ... every (tensor block, sequence, level) leaves the sum of its W entries in a slot of its own
+    void* gbp = nullptr;
+    const int64_t gbn = int64_t(TB) * N * M;
+    if (gb) CHK(ensure(c, B_WD11, sizeof(double) * size_t(gbn + WIDE_GB_BLOCKS) + 64, &gbp));
     for (int64_t n0 = 0; n0 < N; n0 += chunk) {
         const int64_t nc = N - n0 < chunk ? N - n0 : chunk;
-        CHK(dgemm(c, true, false, CW, nc * L, DA, ZA, DA, XA + n0 * L * DA, DA, 0.0, static_cast<double*>(arg), CW));
+        for (int64_t b0 = 0; b0 < nc; b0 += blk) {
+            const int64_t nb = nc - b0 < blk ? nc - b0 : blk;
+            CHK(dgemm(c, true, false, CW, nb * L, DA, ZA, DA, XA + (n0 + b0) * L * DA, DA, 0.0, static_cast<double*>(arg) + b0 * L * CW, CW));
+        }
         WideTvsArgs A;
         memset(&A, 0, sizeof(A));
         A.arg = static_cast<const double*>(arg); A.CW = CW; A.Tpad = Tpad; A.Tn = Tn; A.n0 = n0; A.Nc = nc; A.N = N;
-        A.L = L; A.M = M; A.kind = p->base_kernel; A.difference = (p->difference && !xinc) ? 1 : 0;
+        A.L = L; A.M = M; A.kind = p->base_kernel; A.kp0 = p->base_params[0]; A.kp1 = p->base_params[1]; A.difference = (p->difference && !xinc) ? 1 : 0;
         A.fx = fac; A.w = nullptr; A.aux = const_cast<double*>(aux);
         A.G = G; A.W = static_cast<double*>(Wb); A.gfac_part = static_cast<double*>(gfp); A.weighted = fac ? 1 : 0;
+        A.gb_part = static_cast<double*>(gbp);
         A.order = p->order < p->num_levels ? p->order : p->num_levels;
         const dim3 grid(unsigned(TB), unsigned(nc < 65535 ? nc : 65535), unsigned(M));
         GPSIG_WIDE_KIND(p->base_kernel,
@@ -317,6 +363,7 @@ int wide_tvs_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
                            N * int64_t(M + 1), gfac);
         HIPCHK(c, hipGetLastError());
     }
+    if (gb) CHK(gbase_reduce(c, static_cast<double*>(gbp), gbn, g_base));
     return GPSIG_OK;
 }
 
@@ -326,10 +373,10 @@ constexpr int WIDE_LAT_MAX_COLS = 512;            // 64 lanes x 8 columns
 
 bool wide_lat_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L2) {
     if (c->wide == 0 || c->capturing) return false;
-    if (!wide_kind(p->base_kernel) || p->num_levels > WIDE_MAX_LEVELS || p->num_levels < 1) return false;
+    if (!wide_kind(p) || p->num_levels > WIDE_MAX_LEVELS || p->num_levels < 1) return false;
     const int dr = p->difference ? 1 : 0;
     if (p->order > 1 && p->num_levels > 1) {      // higher orders: the forward and the reverse sweeps of grad_wave_ho_kernel.hpp (<= 5 levels, orders <= 4)
-        if (wide_dot_kind(p->base_kernel)) return false;      // (these families' higher orders: the feature contraction up to 32 columns, the any-shape kernel beyond)
+        if (wide_dot_kind(p->base_kernel) || p->base_kernel == GPSIG_BASE_POLY) return false;      // (these families' higher orders: the feature contraction / the exact-shape kernels, the any-shape kernel beyond)
         HoSweeps hf, hb;
         return L1 - dr >= 1 && L2 - dr >= 1 && ho_levels_plan(c, p, L1 - dr, L2 - dr, &hf) && ho_sweeps_plan(c, p, L1 - dr, L2 - dr, &hb);
     }
@@ -340,7 +387,7 @@ bool wide_lat_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L
 // the reverse pass of the HIGHER-ORDER recursion on this route: argument lattices by dgemm -> dM lattices (wide_lattice_dm_kernel) -> both sweeps of a
 // pair in one wavefront (grad_wave_ho_kernel.hpp) -> the adjoint contracted back by dgemms; any number of columns
 bool wide_lat_ho_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L2) {
-    if (c->wide == 0 || c->capturing || !wide_kind(p->base_kernel) || wide_dot_kind(p->base_kernel) || !(p->order > 1 && p->num_levels > 1)) return false;
+    if (c->wide == 0 || c->capturing || !wide_kind(p) || wide_dot_kind(p->base_kernel) || p->base_kernel == GPSIG_BASE_POLY || !(p->order > 1 && p->num_levels > 1)) return false;
     const int dr = p->difference ? 1 : 0;
     HoSweeps hs;
     return L1 >= 1 && L2 >= 1 && ho_sweeps_plan(c, p, L1 - dr, L2 - dr, &hs);
@@ -428,7 +475,7 @@ int wide_lat_forward(gpsig_ctx* c, const gpsig_params* p, int d, const double* X
         memset(&A, 0, sizeof(A));
         A.arg = static_cast<const double*>(arg); A.ld = pl.ld; A.si = pl.si; A.sj = pl.sj; A.N2 = pl.N2;
         A.P = diag ? ni : ni * N2; A.p0 = 0; A.Ptot = pl.Ptot;
-        A.L1 = L1; A.L2 = L2; A.M = M; A.kind = p->base_kernel; A.difference = pl.dr;
+        A.L1 = L1; A.L2 = L2; A.M = M; A.kind = p->base_kernel; A.kp0 = p->base_params[0]; A.kp1 = p->base_params[1]; A.difference = pl.dr;
         A.out = out + (diag ? i0 : i0 * N2);              // (the kernel's pair index starts at 0 in this chunk's lattices)
         if (ho) {
             if (pl.R1 < 1 || pl.R2 < 1) return fail(c, GPSIG_ERR_UNSUPPORTED, "empty lattices");
@@ -454,7 +501,7 @@ int wide_lat_forward(gpsig_ctx* c, const gpsig_params* p, int d, const double* X
 // Gradients of sum_m G[m][pair] level_m[pair] with respect to the scaled sequences.  G: (M+1, P).  Ys == NULL: Xs on both sides and both sides'
 // gradients land in gX (the symmetric Gram as the cross Gram of X with itself; the diagonal); else gX, gY.
 int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Xs, const double* Ys, int64_t N1, int64_t N2, int L1, int L2, bool diag,
-                      const double* G, double* gX, double* gY) {
+                      const double* G, double* gX, double* gY, double* g_base) {
     const LatInc inc(p, L1, L2);
     LatPlan pl;
     const bool ho = p->order > 1 && p->num_levels > 1;
@@ -499,6 +546,16 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
     if (ho || short_lat) groups = 1;      // (these sweeps bring their own slots, if any)
     CHK(ensure(c, B_WD7, per_group * size_t(groups) + 64, &scr));
     WideLatKernel fn = (ho || short_lat) ? nullptr : lat_kernel(M, pl.C, true, p->base_kernel, NW);
+    // SignaturePoly's offset (g_base: device, or NULL): every slice of every lattice leaves the sum of its W entries in a slot of its own, lattices in the
+    // order of G's pair axis (zero where the folded symmetric Gram visits no lattice)
+    void* gbp = nullptr;
+    const bool poly = p->base_kernel == GPSIG_BASE_POLY, gb = g_base && poly;
+    const int gbs = int((int64_t(L1) * L2 + WIDE_GB_SLICE - 1) / WIDE_GB_SLICE);
+    const int64_t gbn = (diag ? N1 : N1 * N2) * gbs;
+    if (gb) {
+        CHK(ensure(c, B_WD11, sizeof(double) * size_t(gbn + WIDE_GB_BLOCKS) + 64, &gbp));
+        CHK(zero_async(c, gbp, sizeof(double) * size_t(gbn)));
+    }
     for (int64_t i0 = 0; i0 < N1; i0 += pl.chunk_i) {
         const int64_t ni = N1 - i0 < pl.chunk_i ? N1 - i0 : pl.chunk_i;
         const int64_t j0 = fold ? i0 : 0, N2e = N2 - j0;              // right sequences of this chunk
@@ -508,10 +565,12 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
         A.arg = static_cast<const double*>(arg); A.ld = pl.ld; A.si = pl.si; A.sj = pl.sj; A.N2 = pl.N2;
         if (!diag) { A.ld = N2e * int64_t(L2); A.si = int64_t(L1) * A.ld; A.N2 = N2e; }
         A.P = diag ? ni : ni * N2e; A.p0 = 0; A.Ptot = pl.Ptot;
-        A.L1 = L1; A.L2 = L2; A.M = M; A.kind = p->base_kernel; A.difference = pl.dr;
+        A.L1 = L1; A.L2 = L2; A.M = M; A.kind = p->base_kernel; A.kp0 = p->base_params[0]; A.kp1 = p->base_params[1]; A.difference = pl.dr;
         A.G = G + (diag ? i0 : i0 * N2 + j0);
         A.g_i = diag ? 1 : N2; A.g_j = diag ? 0 : 1;
         A.scratch = static_cast<double*>(scr); A.lam = static_cast<double*>(lam);
+        A.gb_slices = gbs;
+        if (gb) A.gb_part = static_cast<double*>(gbp) + (diag ? i0 : i0 * N2 + j0) * gbs;
         const int64_t ng = A.P < groups ? A.P : groups;
         A.ngroups = int(ng);
         if ((ho || short_lat) && pl.R1 > 0 && pl.R2 > 0) {
@@ -526,8 +585,11 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
             HIPCHK(c, hipGetLastError());
         }
         // the adjoint of the arguments, in place of the arguments
-        GPSIG_WIDE_KIND(p->base_kernel, hipLaunchKernelGGL(wide_lattice_adjoint_kernel<KD>, dim3(grid_for(A.P * int64_t(L1) * L2)), dim3(256), 0, c->stream, A,
-                                                           static_cast<double*>(arg)))
+        if (poly)          // (a kernel of its own: one wavefront per slice of a lattice, with the slice's sum of W)
+            hipLaunchKernelGGL(wide_lattice_adjoint_poly_kernel, dim3(grid_for(A.P * gbs, 1)), dim3(64), 0, c->stream, A, static_cast<double*>(arg));
+        else
+            GPSIG_WIDE_KIND(p->base_kernel, hipLaunchKernelGGL(wide_lattice_adjoint_kernel<KD>, dim3(grid_for(A.P * int64_t(L1) * L2)), dim3(256), 0, c->stream, A,
+                                                               static_cast<double*>(arg)))
         HIPCHK(c, hipGetLastError());
         const double* W = static_cast<const double*>(arg);
         double* gl = static_cast<double*>(gxl) + i0 * L1 * DA;
@@ -541,6 +603,7 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
                               static_cast<double*>(gxr) + j0 * L2 * DA));
         }
     }
+    if (gb) CHK(gbase_reduce(c, static_cast<double*>(gbp), gbn, g_base));
     // through the augmentation: left form into gX; right form into gX as well (one array on both sides) or into gY
     const int64_t xr_rows = N1 * int64_t(L1), yr_rows = N2 * int64_t(L2);
     const bool same = Ys == nullptr;
@@ -578,7 +641,7 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
 // ---- inducing tensors vs inducing tensors ----------------------------------------------------------------------------------------------------
 bool wide_tens_available(const gpsig_ctx* c, const gpsig_params* p, int64_t Tn) {
     if (c->wide == 0 || c->capturing) return false;
-    if (!wide_kind(p->base_kernel) || p->num_levels > WIDE_MAX_LEVELS || p->num_levels < 1) return false;
+    if (!wide_kind(p) || p->num_levels > WIDE_MAX_LEVELS || p->num_levels < 1) return false;
     const int64_t Tpad = (Tn + 63) / 64 * 64;
     // the argument blocks of every component at once (10 components x 1,024^2 x 8 bytes = 84 MB at 500 tensors with increments)
     return Tn >= 1 && size_t(p->num_levels * (p->num_levels + 1) / 2) * size_t(4 * Tpad * Tpad) * sizeof(double) <= (size_t(2) << 30);
@@ -621,7 +684,7 @@ int wide_tens_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz
     CHK(tens_arguments(c, p, sz, d, Z, lt, E, zinc ? 1 : 0, Tn, Tpad, &ZL, &ZR, &arg));
     WideTensArgs A;
     memset(&A, 0, sizeof(A));
-    A.arg = arg; A.Tpad = Tpad; A.Tn = Tn; A.M = M; A.E = E; A.kind = p->base_kernel; A.sum_levels = sum_levels; A.w = w; A.out = out;
+    A.arg = arg; A.Tpad = Tpad; A.Tn = Tn; A.M = M; A.E = E; A.kind = p->base_kernel; A.kp0 = p->base_params[0]; A.kp1 = p->base_params[1]; A.sum_levels = sum_levels; A.w = w; A.out = out;
     GPSIG_WIDE_KIND(p->base_kernel, hipLaunchKernelGGL(wide_tens_fwd_kernel<KD>, dim3(unsigned(Tpad / 64), unsigned(Tn < 65535 ? Tn : 65535)), dim3(64), 0, c->stream, A))
     HIPCHK(c, hipGetLastError());
     if (timed) {
@@ -634,7 +697,7 @@ int wide_tens_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz
 }
 
 // gradient of sum_m G[m][t][t'] level_m[t][t'] with respect to the scaled tensors Z (lt, T, E, d)
-int wide_tens_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Z, int64_t Tn, int increments, const double* G, double* gZ) {
+int wide_tens_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Z, int64_t Tn, int increments, const double* G, double* gZ, double* g_base) {
     const bool zinc = tensors_collapse(p, increments);
     const int M = p->num_levels, lt = M * (M + 1) / 2, Ez = increments ? 2 : 1, E = zinc ? 1 : Ez, DA = d + 2;
     const int64_t Tpad = (Tn + 63) / 64 * 64, R = int64_t(E) * Tpad, zr = int64_t(lt) * R;
@@ -649,12 +712,19 @@ int wide_tens_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double*
     CHK(ensure(c, B_WD5, sizeof(double) * size_t(zr) * DA + 64, &gzr));
     WideTensArgs A;
     memset(&A, 0, sizeof(A));
-    A.arg = arg; A.Tpad = Tpad; A.Tn = Tn; A.M = M; A.E = E; A.kind = p->base_kernel; A.G = G; A.W = static_cast<double*>(Wb);
+    A.arg = arg; A.Tpad = Tpad; A.Tn = Tn; A.M = M; A.E = E; A.kind = p->base_kernel; A.kp0 = p->base_params[0]; A.kp1 = p->base_params[1]; A.G = G; A.W = static_cast<double*>(Wb);
+    // SignaturePoly's offset (g_base: device, or NULL): every (column block, row) leaves the sum of its W entries in a slot of its own
+    void* gbp = nullptr;
+    const bool gb = g_base && p->base_kernel == GPSIG_BASE_POLY;
+    const int64_t gbn = (Tpad / 64) * Tpad;
+    if (gb) CHK(ensure(c, B_WD11, sizeof(double) * size_t(gbn + WIDE_GB_BLOCKS) + 64, &gbp));
+    A.gb_part = static_cast<double*>(gbp);
     GPSIG_WIDE_KIND(p->base_kernel, hipLaunchKernelGGL(wide_tens_bwd_kernel<KD>, dim3(unsigned(Tpad / 64), unsigned(Tpad < 65535 ? Tpad : 65535)), dim3(64), 0, c->stream, A))
     HIPCHK(c, hipGetLastError());
     // gZL_k (R, DA) = W_k ZR_k: column-major (DA x R) = ZR_k,cm (DA x R) W_k,cm (R x R);   gZR_k = W_k^T ZL_k: (DA x R) = ZL_k,cm W_k,cm^T
     CHK(dgemm_batched(c, false, false, DA, R, R, ZR, DA, R * DA, static_cast<const double*>(Wb), R, R * R, static_cast<double*>(gzl), DA, R * DA, lt));
     CHK(dgemm_batched(c, false, true, DA, R, R, ZL, DA, R * DA, static_cast<const double*>(Wb), R, R * R, static_cast<double*>(gzr), DA, R * DA, lt));
+    if (gb) CHK(gbase_reduce(c, static_cast<double*>(gbp), gbn, g_base));
     const int64_t rows_out = int64_t(lt) * Tn * Ez;             // the caller's rows
     if (rows_mode(p->base_kernel) == WIDE_ROWS_UNIT)
         hipLaunchKernelGGL(wide_unaug_unit_kernel, dim3(unsigned(rows_out < 65535 ? rows_out : 65535)), dim3(64), 0, c->stream, static_cast<const double*>(gzl), ZL,

@@ -44,6 +44,8 @@ struct WideTvsArgs {
     double* gfac_part;      // reverse, weighted: (TB, N, M+1) partial sums of dL/dfac over the tensors of a block, or NULL
     int32_t weighted;
     int32_t order;          // > 1: the higher-order chains of signature_algs.py:129-160 (at most WIDE_MAX_ORDER)
+    double kp0, kp1;        // SignaturePoly: offset and degree (WIDE_KD_POLY)
+    double* gb_part;        // reverse, SignaturePoly: (TB, N, M) partial sums of W over the tensors of a block -- the offset's gradient --, or NULL
 };
 
 // The base kernel as a function of the argument a = -|z - x|^2 / 2, described by wavefront-uniform numbers so that the three Matern families share
@@ -59,11 +61,15 @@ constexpr double WIDE_M12_COINCIDE = 1e-13;
 struct WideKap {
     const double* tab;      // 2^(j/64) in LDS
     double c2, a1, a2, thr;
+    double p0;              // SignaturePoly: the offset ...
+    int pn;                 // ... and the whole degree, 1 .. 8
 };
 
-__device__ __forceinline__ WideKap wide_kap(int kind, const double* tab) {
+__device__ __forceinline__ WideKap wide_kap(int kind, const double* tab, double p0 = 0.0, double p1 = 0.0) {
     WideKap K;
     K.tab = tab;
+    K.p0 = p0;
+    K.pn = int(p1);
     K.c2 = kind == BASE_MATERN32 ? 3.0 : (kind == BASE_MATERN52 ? 5.0 : 1.0);
     K.a1 = kind == BASE_MATERN12 ? 0.0 : 1.0;
     K.a2 = kind == BASE_MATERN52 ? 1.0 / 3.0 : 0.0;
@@ -75,12 +81,27 @@ __device__ __forceinline__ WideKap wide_kap(int kind, const double* tab) {
 // points or, with differences, their increments -- <.,.> is bilinear, so the differences are taken on the rows before the dgemm and the kernels run in
 // their difference = 0 form) and SignatureCosine (:820-828: unit rows, differences of kappa as for the distance kernels).  No exponential: these
 // instances neither fill nor read the table in LDS.
-constexpr int WIDE_KD_MATERN = 0, WIDE_KD_RBF = 1, WIDE_KD_ID = 2;
+// WIDE_KD_POLY: SignaturePoly (kernels.py:844-848), kappa(a) = (a + p0)^p1 on plain rows (a = <z, x>) with a whole degree 1 .. 8; non-linear, so the
+// differences are taken on kappa as for the distance kernels.  d kappa / d p0 = d kappa / d a at every entry: the offset's gradient is the plain sum of
+// the adjoint array W that the reverse kernels write (their poly instances sum what they store: per lane, per wavefront, one partial per fixed slot, and
+// wide_sum_kernel adds the slots in a fixed order -- no atomics, the same bits from every call; across chunkings of the argument array too for Kzx,
+// whose host side keeps the dgemms' shapes fixed, not for the lattices).  No table either.
+constexpr int WIDE_KD_MATERN = 0, WIDE_KD_RBF = 1, WIDE_KD_ID = 2, WIDE_KD_POLY = 3;
 
-// the exp table of a workgroup of n threads (nothing for the identity kind)
+// b^n for a wavefront-uniform whole n in 0 .. 8, by repeated squaring (seq_core.hpp: poly_pow without its way out to the library's pow)
+__device__ __forceinline__ double wide_pow_n(double b, int n) {
+    double r = (n & 1) ? b : 1.0, x = b * b;
+    if (n & 2) r *= x;
+    x *= x;
+    if (n & 4) r *= x;
+    if (n & 8) r *= x * x;
+    return r;
+}
+
+// the exp table of a workgroup of n threads (nothing for the identity and the polynomial kind)
 template <int KD>
 __device__ __forceinline__ const double* wide_tab(double* etab, int tid, int n) {
-    if constexpr (KD == WIDE_KD_ID) {
+    if constexpr (KD == WIDE_KD_ID || KD == WIDE_KD_POLY) {
         return nullptr;
     } else {
         exp_tab_fill(etab, tid, n);
@@ -93,6 +114,8 @@ template <int KD>
 __device__ __forceinline__ double wide_kappa(const WideKap& K, double a) {
     if constexpr (KD == WIDE_KD_ID) {
         return a;
+    } else if constexpr (KD == WIDE_KD_POLY) {
+        return wide_pow_n(a + K.p0, K.pn);
     } else if constexpr (KD == WIDE_KD_RBF) {
         return kexp_tab(a, K.tab);
     } else {
@@ -110,6 +133,10 @@ __device__ __forceinline__ void wide_kappa_grad(const WideKap& K, double a, doub
     if constexpr (KD == WIDE_KD_ID) {
         k = a;
         dk = 1.0;
+    } else if constexpr (KD == WIDE_KD_POLY) {
+        const double b = a + K.p0, q = wide_pow_n(b, K.pn - 1);
+        k = b * q;
+        dk = double(K.pn) * q;
     } else if constexpr (KD == WIDE_KD_RBF) {
         k = kexp_tab(a, K.tab);
         dk = k;
@@ -226,7 +253,7 @@ __device__ __forceinline__ void wide_level_fwd(int i, const double* col, const W
 template <int E, int KD>
 __global__ void __launch_bounds__(64) wide_tvs_fwd_kernel(const WideTvsArgs A) {
     __shared__ double etab[EXP_TAB_N];
-    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, 64));
+    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, 64), A.kp0, A.kp1);
     const int64_t t = int64_t(blockIdx.x) * 64 + threadIdx.x;
     const int M = A.M, lt = M * (M + 1) / 2;
     const int i = blockIdx.z + 1, k0 = i * (i - 1) / 2;
@@ -265,7 +292,7 @@ __global__ void wide_tvs_epilogue_kernel(const WideTvsArgs A) {
 // argument.  u: the level's totals (destroyed).  c: the level's upstream gradient.  Columns of tensors beyond Tn get zeros (valid = false).
 template <int I, int E, int KD>
 __device__ __forceinline__ void wide_chain_bwd(const double* __restrict__ col, double* __restrict__ wcol, int64_t CW, int64_t Tpad, int k0, int L,
-                                               int difference, int order, const WideKap& K, double (&u)[I], double c, bool valid) {
+                                               int difference, int order, const WideKap& K, double (&u)[I], double c, bool valid, double& wsum) {
     double wv[I];
 #pragma unroll
     for (int j = 0; j < I; ++j) wv[j] = 0.0;
@@ -286,7 +313,11 @@ __device__ __forceinline__ void wide_chain_bwd(const double* __restrict__ col, d
 #pragma unroll
         for (int j = 0; j < I; ++j)
 #pragma unroll
-            for (int e = 0; e < E; ++e) wr[((k0 + j) * E + e) * Tpad] = valid ? g[j] * d[j][e] : 0.0;
+            for (int e = 0; e < E; ++e) {
+                const double w = valid ? g[j] * d[j][e] : 0.0;
+                wr[((k0 + j) * E + e) * Tpad] = w;
+                if constexpr (KD == WIDE_KD_POLY) wsum += w;               // (a padded lane stores and adds exactly zero)
+            }
     };
     // higher-order chains: the step's repeat-count vectors are rebuilt from the totals BEFORE the step (U_j - sum_l r_j[l], ascending in j), then the
     // adjoints run down: dL/dr_j[l] = W_j + m_{j+1} / (l+2) dL/dr_{j+1}[l+1],  dL/dm_j = dL/dr_j[0] U_{j-1} + sum_{l>=1} dL/dr_j[l] r_{j-1}[l-1] / (l+1),
@@ -408,7 +439,7 @@ __device__ __forceinline__ double wide_wave_sum(double v) {
 template <int E, int KD>
 __global__ void __launch_bounds__(64) wide_tvs_bwd_kernel(const WideTvsArgs A) {
     __shared__ double etab[EXP_TAB_N];
-    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, 64));
+    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, 64), A.kp0, A.kp1);
     const int64_t t = int64_t(blockIdx.x) * 64 + threadIdx.x;
     const bool valid = t < A.Tn;
     const int M = A.M, lt = M * (M + 1) / 2;
@@ -439,11 +470,12 @@ __global__ void __launch_bounds__(64) wide_tvs_bwd_kernel(const WideTvsArgs A) {
             const double s = wide_wave_sum(gsum * ui);
             if (threadIdx.x == 0) A.gfac_part[(int64_t(blockIdx.x) * A.N + n) * (M + 1) + i] = s;
         }
+        double wsum = 0.0;          // SignaturePoly: this lane's sum of the W entries of (tensor t, sequence n, level i)
 #define GPSIG_WIDE_CASE(I_)                                                                                  \
     case I_: {                                                                                               \
         double v[I_];                                                                                        \
         _Pragma("unroll") for (int j = 0; j < I_; ++j) v[j] = u[j];                                         \
-        wide_chain_bwd<I_, E, KD>(col, wcol, A.CW, A.Tpad, k0, A.L, A.difference, A.order, K, v, c, valid);          \
+        wide_chain_bwd<I_, E, KD>(col, wcol, A.CW, A.Tpad, k0, A.L, A.difference, A.order, K, v, c, valid, wsum);    \
     } break;
         switch (i) {
             GPSIG_WIDE_CASE(1) GPSIG_WIDE_CASE(2) GPSIG_WIDE_CASE(3) GPSIG_WIDE_CASE(4)
@@ -451,7 +483,29 @@ __global__ void __launch_bounds__(64) wide_tvs_bwd_kernel(const WideTvsArgs A) {
             default: break;
         }
 #undef GPSIG_WIDE_CASE
+        if constexpr (KD == WIDE_KD_POLY) {
+            if (A.gb_part) {            // the slot of (tensor block, GLOBAL sequence, level): the same partial however the sequences are chunked
+                const double s = wide_wave_sum(wsum);
+                if (threadIdx.x == 0) A.gb_part[(int64_t(blockIdx.x) * A.N + n) * M + (i - 1)] = s;
+            }
+        }
     }
+}
+
+// out[b] (+)= the sum of part[0 .. n) taken by block b of gridDim.x blocks of 256 threads: a thread adds its entries in ascending order, the block's 256
+// sums meet in a fixed tree.  Two launches -- (blocks, part -> tmp), (1, tmp -> g_base[0], add = 1) -- sum the offset's partials in an order that
+// depends on n alone (SignaturePoly's reverse passes).
+__global__ void __launch_bounds__(256) wide_sum_kernel(const double* __restrict__ part, int64_t n, int add, double* __restrict__ out) {
+    __shared__ double sh[256];
+    double s = 0.0;
+    for (int64_t idx = blockIdx.x * int64_t(256) + threadIdx.x; idx < n; idx += int64_t(gridDim.x) * 256) s += part[idx];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (int(threadIdx.x) < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = add ? out[blockIdx.x] + sh[0] : sh[0];
 }
 
 // gfac[n][m] = sum over the tensor blocks of the partial sums (a fixed order: the result does not depend on the schedule)
@@ -623,7 +677,11 @@ struct WideLatArgs {
     double* scratch;            // reverse: per group (M-1) * TF * 64 * C doubles (forward Q's, as grad_wave_kernel.hpp)
     double* lam;                // reverse: Lam = dL/ddM, (P, R1, R2) row-major
     int32_t ngroups;
+    double kp0, kp1;            // SignaturePoly: offset and degree (WIDE_KD_POLY; p0 above is a lattice index)
+    double* gb_part;            // reverse, SignaturePoly: gb_slices partial sums of W per lattice, lattices as G's pair axis (pg at (pg / N2) * g_i + (pg % N2) * g_j), or NULL
+    int32_t gb_slices;          // ... (L1 L2 + WIDE_GB_SLICE - 1) / WIDE_GB_SLICE
 };
+constexpr int WIDE_GB_SLICE = 1024;       // cells of a lattice per wavefront of the polynomial adjoint kernel (16 per lane)
 
 // argument rows (and, in the backward sweep, stored prefix rows) in flight ahead of a step: a step of few columns is shorter than a memory access
 constexpr int wide_lat_pf(int C) { return C >= 8 ? 1 : (C == 4 ? 2 : 4); }
@@ -703,7 +761,7 @@ __global__ void __launch_bounds__(64 * NW) wide_lattice_fwd_kernel(const WideLat
         const int64_t pg = A.p0 + pp;
         WideLatDm<C, KD> dmg;
         dmg.lat = A.arg + (pg / A.N2) * A.si + (pg % A.N2) * A.sj;
-        dmg.ld = A.ld; dmg.b0 = C * lam; dmg.L2 = A.L2; dmg.K = wide_kap(A.kind, ktab); dmg.diff = dr;
+        dmg.ld = A.ld; dmg.b0 = C * lam; dmg.L2 = A.L2; dmg.K = wide_kap(A.kind, ktab, A.kp0, A.kp1); dmg.diff = dr;
         { const int nv = R2 - C * lam; dmg.nvalid = nv < 0 ? 0 : (nv > C ? C : nv); }
         WaveFwd<C, LQ> fw;
         fw.reset();
@@ -787,7 +845,7 @@ __global__ void __launch_bounds__(64 * NW) wide_lattice_bwd_kernel(const WideLat
         const int64_t pg = A.p0 + pp;
         WideLatDm<C, KD> dmg;
         dmg.lat = A.arg + (pg / A.N2) * A.si + (pg % A.N2) * A.sj;
-        dmg.ld = A.ld; dmg.b0 = C * lam; dmg.L2 = A.L2; dmg.K = wide_kap(A.kind, ktab); dmg.diff = dr;
+        dmg.ld = A.ld; dmg.b0 = C * lam; dmg.L2 = A.L2; dmg.K = wide_kap(A.kind, ktab, A.kp0, A.kp1); dmg.diff = dr;
         { const int nv = R2 - C * lam; dmg.nvalid = nv < 0 ? 0 : (nv > C ? C : nv); }
         double clev[LQ + 2];
 #pragma unroll
@@ -920,7 +978,7 @@ __global__ void __launch_bounds__(64 * NW) wide_lattice_bwd_kernel(const WideLat
 template <int KD>
 __global__ void wide_lattice_adjoint_kernel(const WideLatArgs A, double* __restrict__ W) {
     __shared__ double etab[EXP_TAB_N];
-    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, blockDim.x));
+    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, blockDim.x), A.kp0, A.kp1);
     const int dr = A.difference ? 1 : 0, R1 = A.L1 - dr, R2 = A.L2 - dr;
     const int64_t cells = int64_t(A.L1) * A.L2, total = A.P * cells;
     for (int64_t idx = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; idx < total; idx += int64_t(gridDim.x) * blockDim.x) {
@@ -933,6 +991,36 @@ __global__ void wide_lattice_adjoint_kernel(const WideLatArgs A, double* __restr
         double k, dk;
         wide_kappa_grad<KD>(K, A.arg[off], k, dk);
         W[off] = gam * dk;
+    }
+}
+
+// The same for SignaturePoly, with the sum of what it stores (the offset's gradient): workgroups of ONE wavefront, each taking a slice of WIDE_GB_SLICE
+// cells of one lattice, so that a slice's sum of W is formed in an order that depends on the lattice's shape alone, and lands in the slice's own slot
+// (three 64-bit divisions: held to eight wavefronts per SIMD, which its scalar registers would otherwise miss by a few)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) wide_lattice_adjoint_poly_kernel(const WideLatArgs A, double* __restrict__ W) {
+    const WideKap K = wide_kap(A.kind, nullptr, A.kp0, A.kp1);
+    const int dr = A.difference ? 1 : 0, R1 = A.L1 - dr, R2 = A.L2 - dr;
+    const int64_t cells = int64_t(A.L1) * A.L2;
+    const int64_t S = A.gb_slices;
+    for (int64_t un = blockIdx.x; un < A.P * S; un += gridDim.x) {
+        const int64_t pp = un / S, sl = un - pp * S, pg = A.p0 + pp;
+        const double* lm = A.lam + pp * int64_t(R1) * R2;
+        auto at = [&](int a, int b) -> double { return (a >= 0 && a < R1 && b >= 0 && b < R2) ? lm[int64_t(a) * R2 + b] : 0.0; };
+        const int64_t base = (pg / A.N2) * A.si + (pg % A.N2) * A.sj;
+        const int64_t end = (sl + 1) * WIDE_GB_SLICE < cells ? (sl + 1) * WIDE_GB_SLICE : cells;
+        double wsum = 0.0;
+        for (int64_t cell = sl * WIDE_GB_SLICE + threadIdx.x; cell < end; cell += 64) {
+            const int r = int(cell / A.L2), c = int(cell % A.L2);
+            const double gam = dr ? at(r - 1, c - 1) - at(r - 1, c) - at(r, c - 1) + at(r, c) : at(r, c);
+            const int64_t off = base + int64_t(r) * A.ld + c;
+            double k, dk;
+            wide_kappa_grad<WIDE_KD_POLY>(K, A.arg[off], k, dk);
+            const double w = gam * dk;
+            W[off] = w;
+            wsum += w;
+        }
+        wsum = wide_wave_sum(wsum);
+        if (threadIdx.x == 0 && A.gb_part) A.gb_part[((pg / A.N2) * A.g_i + (pg % A.N2) * A.g_j) * S + sl] = wsum;
     }
 }
 
@@ -951,7 +1039,7 @@ __global__ void wide_sym_upstream_kernel(const double* __restrict__ G, int64_t N
 template <int KD>
 __global__ void wide_lattice_dm_kernel(const WideLatArgs A, double* __restrict__ dM) {
     __shared__ double etab[EXP_TAB_N];
-    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, blockDim.x));
+    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, blockDim.x), A.kp0, A.kp1);
     const int dr = A.difference ? 1 : 0, R1 = A.L1 - dr, R2 = A.L2 - dr;
     const int64_t cells = int64_t(R1) * R2, total = A.P * cells;
     for (int64_t idx = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; idx < total; idx += int64_t(gridDim.x) * blockDim.x) {
@@ -990,6 +1078,8 @@ struct WideTensArgs {
     double* out;            // forward: (T, T) weighted level sum or (M+1, T, T)
     const double* G;        // reverse: (M+1, T, T)
     double* W;              // reverse: adjoint of arg, same layout
+    double kp0, kp1;        // SignaturePoly: offset and degree (WIDE_KD_POLY)
+    double* gb_part;        // reverse, SignaturePoly: (Tpad / 64, Tpad) partial sums of W, one per (column block, row t), or NULL
 };
 
 // value of component k at (t, t'): kappa, or the four-term difference of its two points on both sides (kernels.py:276-277)
@@ -1004,7 +1094,7 @@ __device__ __forceinline__ double wide_tens_val(const double* __restrict__ blk, 
 template <int KD>
 __global__ void __launch_bounds__(64) wide_tens_fwd_kernel(const WideTensArgs A) {
     __shared__ double etab[EXP_TAB_N];
-    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, 64));
+    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, 64), A.kp0, A.kp1);
     const int64_t tp = int64_t(blockIdx.x) * 64 + threadIdx.x, R = int64_t(A.E) * A.Tpad;
     if (tp >= A.Tn) return;
     for (int64_t t = blockIdx.y; t < A.Tn; t += gridDim.y) {
@@ -1028,10 +1118,11 @@ __global__ void __launch_bounds__(64) wide_tens_fwd_kernel(const WideTensArgs A)
 template <int KD>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KD == WIDE_KD_ID ? 8 : 1))) wide_tens_bwd_kernel(const WideTensArgs A) {
     __shared__ double etab[EXP_TAB_N];
-    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, 64));
+    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, 64), A.kp0, A.kp1);
     const int64_t tp = int64_t(blockIdx.x) * 64 + threadIdx.x, R = int64_t(A.E) * A.Tpad;
     for (int64_t t = blockIdx.y; t < A.Tpad; t += gridDim.y) {
         const bool valid = t < A.Tn && tp < A.Tn;
+        double wsum = 0.0;          // SignaturePoly: this lane's sum of the W entries of (t, t'); a padded row or column adds exactly zero
         int k0 = 0;
         for (int i = 1; i <= A.M; ++i) {
             const double c = valid ? A.G[(int64_t(i) * A.Tn + t) * A.Tn + tp] : 0.0;
@@ -1049,16 +1140,29 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KD == W
                 double* wb = A.W + int64_t(k0 + j) * R * R;
                 double kk, dk;
                 if (A.E == 2) {
+                    double ws = 0.0;          // (the four entries' sum: +, +, -, -)
                     wide_kappa_grad<KD>(K, blk[(A.Tpad + t) * R + A.Tpad + tp], kk, dk); wb[(A.Tpad + t) * R + A.Tpad + tp] = g * dk;
+                    if constexpr (KD == WIDE_KD_POLY) ws += g * dk;
                     wide_kappa_grad<KD>(K, blk[t * R + tp], kk, dk);                     wb[t * R + tp] = g * dk;
+                    if constexpr (KD == WIDE_KD_POLY) ws += g * dk;
                     wide_kappa_grad<KD>(K, blk[(A.Tpad + t) * R + tp], kk, dk);          wb[(A.Tpad + t) * R + tp] = -g * dk;
+                    if constexpr (KD == WIDE_KD_POLY) ws -= g * dk;
                     wide_kappa_grad<KD>(K, blk[t * R + A.Tpad + tp], kk, dk);            wb[t * R + A.Tpad + tp] = -g * dk;
+                    if constexpr (KD == WIDE_KD_POLY) ws -= g * dk;
+                    if constexpr (KD == WIDE_KD_POLY) wsum += valid ? ws : 0.0;
                 } else {
                     wide_kappa_grad<KD>(K, blk[t * R + tp], kk, dk);
                     wb[t * R + tp] = g * dk;
+                    if constexpr (KD == WIDE_KD_POLY) wsum += valid ? g * dk : 0.0;
                 }
             }
             k0 += i;
+        }
+        if constexpr (KD == WIDE_KD_POLY) {
+            if (A.gb_part) {
+                const double s = wide_wave_sum(wsum);
+                if (threadIdx.x == 0) A.gb_part[int64_t(blockIdx.x) * A.Tpad + t] = s;
+            }
         }
     }
 }
