@@ -1065,7 +1065,9 @@ int sig_features_K(gpsig_ctx* c, const gpsig_params* p, bool raw, const void* X,
             c->t_launches += 1;
             c->t_pairs += NA * NB;
             c->t_kernel = used_dma ? "sig_gram_dma_kernel" : "sig_gram_kernel";
-            c->t_flops += 2.0 * double(ntiles) * SG_BM * SG_BN * double(nslab) * SG_BK;
+            // what is executed: the LDS-DMA form computes 36 of the 64 16 x 16 blocks of a symmetric product's diagonal tiles
+            const double tiles_done = double(ntiles) - ((used_dma && symtiles) ? double(nti) * 28.0 / 64.0 : 0.0);
+            c->t_flops += 2.0 * tiles_done * SG_BM * SG_BN * double(nslab) * SG_BK;
         }
         SigReduceArgs R;
         memset(&R, 0, sizeof(R));

@@ -510,6 +510,19 @@ __device__ inline void sig_tile_of(const SigGramArgs& G, int& split_out, int& bi
     {
         // tile -> (bi, bj): 8 x 8 blocks of tiles, block rows first; symmetric products keep the blocks and tiles with bi <= bj
         constexpr int SB = 8;
+        if (G.symmetric) {
+            // The diagonal tiles are dealt evenly over the sequence (tile t is one where floor(t ntj / ntiles) steps; the d-th of them is
+            // (d, d)), the tiles above the diagonal fill the places between in the block order below: a diagonal tile costs 36/64 of
+            // another (sig_gram_diag_tile), a workgroup's XCD is fixed by its index, and the launch ends with the slowest XCD -- in block
+            // order XCDs 1, 2 and 4 of configs[1] would hold no diagonal tile and the others' savings would end the launch no sooner.
+            const int d = int(int64_t(tile) * G.ntj / ntiles);
+            if (int(int64_t(tile + 1) * G.ntj / ntiles) > d) {
+                bi = bj = d;
+                split_out = split;
+                return;
+            }
+            tile -= d;
+        }
         const int nti = G.symmetric ? G.ntj : (ntiles / G.ntj), nbi = (nti + SB - 1) / SB, nbj = (G.ntj + SB - 1) / SB;
         int Bi = 0, Bj = 0, hi = 0, wj = 0;
         bool found = false;
@@ -517,18 +530,18 @@ __device__ inline void sig_tile_of(const SigGramArgs& G, int& split_out, int& bi
             hi = nti - Bi * SB < SB ? nti - Bi * SB : SB;
             for (Bj = G.symmetric ? Bi : 0; Bj < nbj; ++Bj) {
                 wj = G.ntj - Bj * SB < SB ? G.ntj - Bj * SB : SB;
-                const int cnt = (G.symmetric && Bj == Bi) ? hi * (hi + 1) / 2 : hi * wj;
+                const int cnt = (G.symmetric && Bj == Bi) ? hi * (hi - 1) / 2 : hi * wj;
                 if (tile < cnt) { found = true; break; }
                 tile -= cnt;
             }
             if (found) break;
         }
         int li_, lj_;
-        if (G.symmetric && Bj == Bi) {            // the upper triangle of a diagonal block, row by row
+        if (G.symmetric && Bj == Bi) {            // a diagonal block: the tiles above its diagonal, row by row
             li_ = 0;
-            int rowlen = hi;
+            int rowlen = hi - 1;
             while (tile >= rowlen) { tile -= rowlen; ++li_; --rowlen; }
-            lj_ = li_ + tile;
+            lj_ = li_ + 1 + tile;
         } else {
             li_ = tile / wj;
             lj_ = tile - li_ * wj;
@@ -646,7 +659,104 @@ static __global__ __launch_bounds__(256, 2) void sig_gram_kernel(const SigGramAr
 // depth step k+1 read while step k multiplies, ONE barrier in front of the last step's multiplies -- by then the wave holds that
 // step's fragments, and the next slab's first fragments are read right behind the barrier, under 16 MFMAs.  Same summation order as
 // sig_gram_kernel: bit-identical results.
+//
+// A DIAGONAL tile of a symmetric product (bi == bj) is its own transpose, entry for entry and bit for bit (a_i . a_j and a_j . a_i are
+// the same products added in the same order), and its A and B slabs are the same 128 feature rows.  sig_gram_diag_tile computes it as
+// an 8 x 8 grid of the 16 x 16 blocks of one MFMA and only the 36 blocks (sr <= sc) of it: wave W owns block rows W and 7 - W -- columns
+// W .. 7 of the first, 7 - W .. 7 of the second: 9 blocks, 9 MFMAs per depth step for every wave instead of 16 -- and reads the
+// 8 - W fragments of the block rows W .. 7 (its two row fragments are among them; a fragment is row and column operand alike) out of ONE
+// slab: 4 DMA instructions per wave and slab.  Swizzle, double buffering, the one barrier per slab and the place of the vmcnt(0) are
+// those of the whole-tile loop, and so is the order in which an entry's products are added: slabs in increasing order, the four depth
+// steps of a slab in increasing order, one MFMA per (block, step), from zero.  The blocks below are not stored (and no partial sum of
+// them is read: sig_gram_reduce_sym_kernel).  sig_gram_diag_owned is the rule the reduce kernel reads by
+// (restated in tests/test_gpu_gram_diag_tiles.py).
+__host__ __device__ inline bool sig_gram_diag_owned(int r, int c) { return (r >> 4) <= (c >> 4); }       // (r, c) inside the tile
+
 #ifdef GPSIG_KERNEL_DEFS          // defined once, in kernel_defs.hip; every other unit sees the declaration
+// As: the first of the two slab buffers of sig_gram_dma_kernel (the second one SG_BM * SG_BK doubles behind it).
+template <int W>
+__device__ __forceinline__ void sig_gram_diag_tile(const SigGramArgs& G, int split, int64_t tile_i, int s0, int nsl, double* As, int lane) {
+    constexpr int NF = 8 - W;                 // fragments: block rows W .. 7; [0] is row W, [NF - 1 - W] is row 7 - W
+    constexpr int RB = NF - 1 - W;
+    const int li = lane & 15, lk = lane >> 4;
+    const double* ga[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int r = (q * 4 + W) * 8 + (lane >> 3), p = (lane & 7) ^ ((r >> 1) & 7);
+        const int64_t ai = tile_i + r;
+        ga[q] = G.A + (ai < G.NA ? ai : 0) * G.lda + G.k_begin + int64_t(s0) * SG_BK + 2 * p;
+    }
+    auto dma = [&](auto buf_c, auto ahead_c) {
+        constexpr int BUF = decltype(buf_c)::value, OFF = decltype(ahead_c)::value * SG_BK * 8;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)ga[q],
+                                             (__attribute__((address_space(3))) void*)(As + BUF * SG_BM * SG_BK + (q * 4 + W) * 8 * SG_BK - OFF / 8), 16, OFF, 0);
+    };
+    const int swz = (lk >> 1) ^ ((li >> 1) & 7);
+    int fo[4];
+#pragma unroll
+    for (int kq = 0; kq < 4; ++kq) fo[kq] = (((2 * kq) ^ swz) << 1) + (lk & 1) + li * SG_BK;
+    const double* const Aw = As + W * 16 * SG_BK;
+    auto frag = [&](auto buf_c, int kq, double (&f)[NF]) {
+        constexpr int BUF = decltype(buf_c)::value;
+#pragma unroll
+        for (int t = 0; t < NF; ++t) f[t] = Aw[BUF * SG_BM * SG_BK + t * 16 * SG_BK + fo[kq]];
+    };
+    sig_f64x4 acc_a[NF], acc_b[W + 1];        // block row W, columns W + t; block row 7 - W, columns 7 - W + u
+#pragma unroll
+    for (int t = 0; t < NF; ++t) acc_a[t] = sig_f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int u = 0; u <= W; ++u) acc_b[u] = sig_f64x4{0.0, 0.0, 0.0, 0.0};
+    double f[2][NF];
+    using B0 = std::integral_constant<int, 0>;
+    using B1 = std::integral_constant<int, 1>;
+    if (nsl > 0) dma(B0{}, B0{});
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (nsl > 0) frag(B0{}, 0, f[0]);
+    auto slab = [&](auto buf_c, auto ahead_c, bool more) {
+        constexpr int BUF = decltype(buf_c)::value;
+        using OTHER = std::integral_constant<int, BUF ^ 1>;
+        if (more) dma(OTHER{}, ahead_c);
+#pragma unroll
+        for (int kq = 0; kq < 4; ++kq) {
+            const int cur = kq & 1, nxt = cur ^ 1;
+            if (kq < 3) {
+                frag(buf_c, kq + 1, f[nxt]);
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+                if (more) frag(OTHER{}, 0, f[nxt]);
+            }
+#pragma unroll
+            for (int t = 0; t < NF; ++t) acc_a[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[cur][0], f[cur][t], acc_a[t], 0, 0, 0);
+#pragma unroll
+            for (int u = 0; u <= W; ++u) acc_b[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[cur][RB], f[cur][RB + u], acc_b[u], 0, 0, 0);
+        }
+    };
+    int s = 0;
+    for (; s + 2 <= nsl; s += 2) {
+        slab(B0{}, std::integral_constant<int, 1>{}, true);
+        slab(B1{}, std::integral_constant<int, 2>{}, s + 2 < nsl);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ga[q] += 2 * SG_BK;
+    }
+    if (s < nsl) slab(B0{}, std::integral_constant<int, 1>{}, false);
+    double* const P = G.part + int64_t(split) * G.NA * G.NB;
+    auto store = [&](int sr, int sc, const sig_f64x4& a) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int64_t i = tile_i + sr * 16 + lk + 4 * r, j = tile_i + sc * 16 + li;
+            if (i < G.NA && j < G.NB) P[i * G.NB + j] = a[r];
+        }
+    };
+#pragma unroll
+    for (int t = 0; t < NF; ++t) store(W, W + t, acc_a[t]);
+#pragma unroll
+    for (int u = 0; u <= W; ++u) store(7 - W, 7 - W + u, acc_b[u]);
+}
+
 __global__ __launch_bounds__(256, 2) void sig_gram_dma_kernel(const SigGramArgs G) {
     // (1 KiB unused in front: an LDS-DMA load adds its immediate offset to the LDS address as well as to the global one, so the
     // destinations below are given minus that offset -- down to 1 KiB below the first buffer)
@@ -666,6 +776,13 @@ __global__ __launch_bounds__(256, 2) void sig_gram_dma_kernel(const SigGramArgs 
     if (G.band > 0 && (tile_j + SG_BN - 1 < tile_i || tile_j > tile_i + SG_BM - 1 + G.band)) return;      // nothing of this tile is owned
     const int s0 = G.bound[split], s1 = G.bound[split + 1];
     const int nsl = s1 - s0;
+    if (G.symmetric && bi == bj) {                  // a diagonal tile: its upper 16 x 16 blocks only, from one slab (see above)
+        if (wave == 0) sig_gram_diag_tile<0>(G, split, tile_i, s0, nsl, As[0], lane);
+        else if (wave == 1) sig_gram_diag_tile<1>(G, split, tile_i, s0, nsl, As[0], lane);
+        else if (wave == 2) sig_gram_diag_tile<2>(G, split, tile_i, s0, nsl, As[0], lane);
+        else sig_gram_diag_tile<3>(G, split, tile_i, s0, nsl, As[0], lane);
+        return;
+    }
     const double* ga[4];          // this lane's 16 bytes of the CURRENT slab, piece q; the next slab is 128 bytes on
     const double* gb[4];
 #pragma unroll
@@ -799,21 +916,25 @@ __global__ void sig_gram_reduce_sym_kernel(const SigReduceArgs R, int nt) {
     const int sbi = blockIdx.x / SB, sbj = blockIdx.x - sbi * SB;
     const int64_t i0 = int64_t(bi) * SG_BM + sbi * 32, j0 = int64_t(bj) * SG_BN + sbj * 32;
     const int64_t stride = R.NA * R.NB;
+    // A diagonal tile holds partial sums in its 16 x 16 blocks (sr <= sc) only (sig_gram_diag_tile; the staging kernel computes it whole,
+    // and a_i . a_j == a_j . a_i bit for bit): a 32 x 32 block above the diagonal is summed and mirrored like any other, one below is
+    // written by its mirror image, and one ON the diagonal sums its owned entries and mirrors them inside itself.
+    if (bi == bj && sbi > sbj) return;
+    const bool dblock = bi == bj && sbi == sbj;
     for (int r = threadIdx.y; r < 32; r += 8) {
         const int64_t i = i0 + r, j = j0 + threadIdx.x;
         double s = 0.0;
-        if (i < R.NA && j < R.NB) {
+        if (i < R.NA && j < R.NB && (!dblock || sig_gram_diag_owned(r, threadIdx.x))) {
             for (int k = 0; k < R.nsplit; ++k) s += R.part[int64_t(k) * stride + i * R.NB + j];
             if (i == j && R.diag_set) s = R.diag_value;
             R.out[i * R.so_i + j * R.so_j] = s;
         }
         tile[r][threadIdx.x] = s;
     }
-    if (bi == bj) return;                 // a diagonal tile was computed whole (and a_i . a_j == a_j . a_i bit for bit)
     __syncthreads();
     for (int r = threadIdx.y; r < 32; r += 8) {
         const int64_t j = j0 + r, i = i0 + threadIdx.x;
-        if (i < R.NA && j < R.NB) R.out[j * R.so_i + i * R.so_j] = tile[threadIdx.x][r];
+        if (i < R.NA && j < R.NB && (!dblock || !sig_gram_diag_owned(r, threadIdx.x))) R.out[j * R.so_i + i * R.so_j] = tile[threadIdx.x][r];
     }
 }
 #else
