@@ -782,256 +782,150 @@ def _sketch_array(sketches, keep):
     return arr
 
 
+_SPECTRAL_FAMILY = {"rbf": 0, "exp": 1, "mixed": 2}
+
+
+# The six low-rank feature ops below are one implementation (_lr_forward / _lr_backward) on different entry points of csrc/lr_grad_api.hip.  They
+# differ in the points -- sequences (N, L, d), passed with (N, L), or inducing tensors (lt, T[, 2], d), passed with (T, increments) --, in whether
+# per-sequence lengths follow the shape arguments, and in the base kernel's parameters: one scalar p0 (or none), whose gradient comes back in a
+# buffer of its own, or SignatureSpectral's alpha (Q), omega (Q, d), gamma (Q, d), which are three more inputs with three more gradients.
+def _lr_call(entry, ten, lens, spec, family, p0, sketches, r, increments, tail):
+    """One call of a low-rank feature entry point: params, the sketches, the points with their shape arguments, [lengths,] S, Wh[, alpha, omega,
+    gamma], then ``tail``.  ten: the contiguous float64 tensors (points, S, Wh[, alpha, omega, gamma]); lens: () or (int32 lengths or None,)."""
+    X, keep = ten[0], []
+    p = spec.params(X.shape[-1], _p0_value(p0) if family is None else float(ten[3].shape[0]), keep)
+    if family is not None:
+        p.base_params[1] = float(_SPECTRAL_FAMILY[family])
+    arr = _sketch_array(sketches, keep)
+    shape = (X.shape[0], X.shape[1]) if increments is None else (X.shape[1], int(increments))
+    _ctx_for(X).call(entry, p, ten[1].shape[0], r, len(sketches), arr, _ptr(X), *shape, *(None if t is None else _ptr(t) for t in lens),
+                     *(_ptr(t) for t in ten[1:]), *tail)
+
+
+def _lr_forward(ctx, entries, pts, lens, S, Wh, base, spec, family, sketches, r, increments=None):
+    """entries: the names of the forward and the reverse entry point; base: p0 (a tensor or None) where ``family`` is None, else (alpha, omega,
+    gamma); increments: None for sequences.  -> Phi (N or T, 1 + c + (M-1) r), float64."""
+    ins = (pts, S, Wh) + (() if family is None else tuple(base))
+    ten = tuple(_c(t) for t in ins)
+    p0 = base if family is None else None
+    increments = None if increments is None else bool(increments)
+    n = ten[0].shape[0] if increments is None else ten[0].shape[1]
+    out = torch.empty((n, 1 + ten[1].shape[0] + (spec.num_levels - 1) * int(r)), dtype=torch.float64, device=ten[0].device)
+    _lr_call(entries[0], ten, lens, spec, family, p0, sketches, int(r), increments, (_ptr(out),))
+    ctx.lr = (entries[1], spec, family, sketches, int(r), increments, p0 is not None, tuple(t is not None for t in lens))
+    ctx.dt = tuple(t.dtype for t in ins)
+    empty = ten[0].new_empty(0)
+    ctx.save_for_backward(*ten, *(() if family is not None else (p0 if p0 is not None else empty,)), *(empty if t is None else t for t in lens))
+    return out
+
+
+def _lr_backward(ctx, G):
+    """-> the gradients of the tensor inputs in the order of ``forward`` (None for lengths and for everything that is not a tensor)."""
+    entry, spec, family, sketches, r, increments, has_p0, has_lens = ctx.lr
+    saved, nt = ctx.saved_tensors, len(ctx.dt)
+    ten = saved[:nt]
+    p0 = saved[nt] if has_p0 else None
+    lens = tuple(t if given else None for t, given in zip(saved[len(saved) - len(has_lens):], has_lens))
+    G = _c(G)
+    grads = [torch.empty_like(t) for t in ten]
+    gb = torch.zeros(2, dtype=torch.float64, device=G.device) if family is None else None
+    _lr_call(entry, ten, lens, spec, family, p0, sketches, r, increments,
+             [_ptr(G)] + [_ptr(t) for t in grads] + ([] if gb is None else [C.cast(gb.data_ptr(), C.POINTER(C.c_double))]))
+    out = [t.to(dt) for t, dt in zip(grads, ctx.dt)]
+    if family is None:
+        out.append(gb[0].to(p0.device).reshape(p0.shape).to(p0.dtype) if has_p0 else None)
+    out[1:1] = [None] * len(has_lens)
+    return tuple(out) + (None,) * (3 + (family is not None) + (increments is not None))
+
+
+def _lr_lengths(lengths, Xs, optional=False):
+    """The lengths of a ragged batch as the entry points take them: (N,) int32 on the sequences' device (``optional``: or None)."""
+    if optional and lengths is None:
+        return None
+    if lengths.dtype != torch.int32 or lengths.device != Xs.device or tuple(lengths.shape) != (Xs.shape[0],):
+        raise ValueError("lengths: an int32 tensor of shape (N,) on the sequences' device" + (", or None" if optional else ""))
+    return lengths.contiguous()
+
+
 class _LrSeqFeatures(torch.autograd.Function):
     """_K_seq_lr_feat (kernels.py:239-261) given the landmarks and the whitening: scaled sequences (N, L, d), S (c, d), Wh (c, c) ->
     Phi (N, 1 + c + (M-1) r), by the fused HIP feature kernel; the reverse pass by lr_seq_features_grad_kernel (csrc/lr_grad_kernel.hpp):
     dPhi -> dX, dS, dWh, d base parameter.  Round 3 ran both directions as torch ops (_LowRankScope._seq_torch below: gather x gather x
-    value + index_add over every (point, entry) product), 9.1 s for the SVGP covariances of BASELINE configs[2]."""
+    value + index_add over every (point, entry) product), 9.1 s for the SVGP covariances of BASELINE configs[2].  Raises NotImplementedError
+    outside the library's limits, as all six ops do (the caller falls back to torch ops)."""
 
     @staticmethod
     def forward(ctx, Xs, S, Wh, p0, spec, sketches, r):
-        X, Sd, Whd = _c(Xs), _c(S), _c(Wh)
-        n, l, d = X.shape
-        cc = Sd.shape[0]
-        keep = []
-        p = spec.params(d, _p0_value(p0), keep)
-        arr = _sketch_array(sketches, keep)
-        F = 1 + cc + (spec.num_levels - 1) * int(r)
-        out = torch.empty((n, F), dtype=torch.float64, device=X.device)
-        _ctx_for(X).call("gpsig_lr_seq_features_dev", p, cc, int(r), len(sketches), arr, _ptr(X), n, l, _ptr(Sd), _ptr(Whd), _ptr(out))
-        ctx.spec, ctx.sketches, ctx.r, ctx.has_p0 = spec, sketches, int(r), p0 is not None
-        ctx.dt = (Xs.dtype, S.dtype, Wh.dtype)
-        ctx.save_for_backward(X, Sd, Whd, p0 if p0 is not None else X.new_empty(0))
-        return out
+        return _lr_forward(ctx, ("gpsig_lr_seq_features_dev", "gpsig_lr_seq_features_grad"), Xs, (), S, Wh, p0, spec, None, sketches, r)
 
-    @staticmethod
-    def backward(ctx, G):
-        X, Sd, Whd, p0 = ctx.saved_tensors
-        n, l, d = X.shape
-        cc = Sd.shape[0]
-        keep = []
-        p = ctx.spec.params(d, _p0_value(p0) if ctx.has_p0 else 0.0, keep)
-        arr = _sketch_array(ctx.sketches, keep)
-        G = _c(G)
-        gX, gS, gWh = torch.empty_like(X), torch.empty_like(Sd), torch.empty_like(Whd)
-        gb = torch.zeros(2, dtype=torch.float64, device=X.device)
-        _ctx_for(X).call("gpsig_lr_seq_features_grad", p, cc, ctx.r, len(ctx.sketches), arr, _ptr(X), n, l, _ptr(Sd), _ptr(Whd), _ptr(G),
-                         _ptr(gX), _ptr(gS), _ptr(gWh), C.cast(gb.data_ptr(), C.POINTER(C.c_double)))
-        gp0 = gb[0].to(p0.device).reshape(p0.shape).to(p0.dtype) if ctx.has_p0 else None
-        return gX.to(ctx.dt[0]), gS.to(ctx.dt[1]), gWh.to(ctx.dt[2]), gp0, None, None, None
+    backward = staticmethod(_lr_backward)
 
 
 class _LrSeqFeaturesRagged(torch.autograd.Function):
     """_LrSeqFeatures for a ragged batch: ``lengths`` (N,) int32 on the sequences' device, 1 <= lengths[n] <= L.  Phi[n] is the features of
     Xs[n, :lengths[n]] evaluated alone; the rows beyond a sequence's length are never read (they may hold NaN) and their gradient rows are exact
     zeros.  By gpsig_lr_seq_features_ragged_dev / _ragged_grad (csrc/lr_ragged_inst.hip: the ragged instances of the whole-sequence and the
-    time-tiled kernels).  Raises NotImplementedError outside the library's limits (the caller falls back to torch ops)."""
+    time-tiled kernels)."""
 
     @staticmethod
     def forward(ctx, Xs, lengths, S, Wh, p0, spec, sketches, r):
-        X, Sd, Whd = _c(Xs), _c(S), _c(Wh)
-        n, l, d = X.shape
-        if lengths.dtype != torch.int32 or lengths.device != X.device or tuple(lengths.shape) != (n,):
-            raise ValueError("lengths: an int32 tensor of shape (N,) on the sequences' device")
-        lens = lengths.contiguous()
-        cc = Sd.shape[0]
-        keep = []
-        p = spec.params(d, _p0_value(p0), keep)
-        arr = _sketch_array(sketches, keep)
-        F = 1 + cc + (spec.num_levels - 1) * int(r)
-        out = torch.empty((n, F), dtype=torch.float64, device=X.device)
-        _ctx_for(X).call("gpsig_lr_seq_features_ragged_dev", p, cc, int(r), len(sketches), arr, _ptr(X), n, l, _ptr(lens), _ptr(Sd), _ptr(Whd),
-                         _ptr(out))
-        ctx.spec, ctx.sketches, ctx.r, ctx.has_p0 = spec, sketches, int(r), p0 is not None
-        ctx.dt = (Xs.dtype, S.dtype, Wh.dtype)
-        ctx.save_for_backward(X, lens, Sd, Whd, p0 if p0 is not None else X.new_empty(0))
-        return out
+        return _lr_forward(ctx, ("gpsig_lr_seq_features_ragged_dev", "gpsig_lr_seq_features_ragged_grad"), Xs, (_lr_lengths(lengths, Xs),), S, Wh, p0,
+                           spec, None, sketches, r)
 
-    @staticmethod
-    def backward(ctx, G):
-        X, lens, Sd, Whd, p0 = ctx.saved_tensors
-        n, l, d = X.shape
-        cc = Sd.shape[0]
-        keep = []
-        p = ctx.spec.params(d, _p0_value(p0) if ctx.has_p0 else 0.0, keep)
-        arr = _sketch_array(ctx.sketches, keep)
-        G = _c(G)
-        gX, gS, gWh = torch.empty_like(X), torch.empty_like(Sd), torch.empty_like(Whd)
-        gb = torch.zeros(2, dtype=torch.float64, device=X.device)
-        _ctx_for(X).call("gpsig_lr_seq_features_ragged_grad", p, cc, ctx.r, len(ctx.sketches), arr, _ptr(X), n, l, _ptr(lens), _ptr(Sd), _ptr(Whd),
-                         _ptr(G), _ptr(gX), _ptr(gS), _ptr(gWh), C.cast(gb.data_ptr(), C.POINTER(C.c_double)))
-        gp0 = gb[0].to(p0.device).reshape(p0.shape).to(p0.dtype) if ctx.has_p0 else None
-        return gX.to(ctx.dt[0]), None, gS.to(ctx.dt[1]), gWh.to(ctx.dt[2]), gp0, None, None, None
-
-
-_SPECTRAL_FAMILY = {"rbf": 0, "exp": 1, "mixed": 2}
+    backward = staticmethod(_lr_backward)
 
 
 class _LrSeqFeaturesSpectral(torch.autograd.Function):
     """_LrSeqFeatures for SignatureSpectral, whose base-kernel parameters are trained: scaled sequences (N, L, d), S (c, d), Wh (c, c) and the
     positive alpha (Q), omega (Q, d), gamma (Q, d) -> Phi, by gpsig_lr_seq_features_spectral_dev (the spectral fused feature kernels on a
     table packed on the device); the reverse pass by gpsig_lr_seq_features_spectral_grad (csrc/lr_grad_api.hip: the spectral instance of
-    lr_seq_features_grad_kernel down to dkxs, then the spectral cross op's reverse kernels): gradients of all six tensors.  Raises
-    NotImplementedError outside the library's limits (the caller falls back to torch ops)."""
+    lr_seq_features_grad_kernel down to dkxs, then the spectral cross op's reverse kernels): gradients of all six tensors."""
 
     @staticmethod
     def forward(ctx, Xs, S, Wh, alpha, omega, gamma, spec, family, sketches, r):
-        X, Sd, Whd, a, o, g = (_c(t) for t in (Xs, S, Wh, alpha, omega, gamma))
-        n, l, d = X.shape
-        cc = Sd.shape[0]
-        keep = []
-        p = spec.params(d, float(a.shape[0]), keep)
-        p.base_params[1] = float(_SPECTRAL_FAMILY[family])
-        arr = _sketch_array(sketches, keep)
-        F = 1 + cc + (spec.num_levels - 1) * int(r)
-        out = torch.empty((n, F), dtype=torch.float64, device=X.device)
-        _ctx_for(X).call("gpsig_lr_seq_features_spectral_dev", p, cc, int(r), len(sketches), arr, _ptr(X), n, l, _ptr(Sd), _ptr(Whd), _ptr(a),
-                         _ptr(o), _ptr(g), _ptr(out))
-        ctx.spec, ctx.family, ctx.sketches, ctx.r = spec, family, sketches, int(r)
-        ctx.dt = tuple(t.dtype for t in (Xs, S, Wh, alpha, omega, gamma))
-        ctx.save_for_backward(X, Sd, Whd, a, o, g)
-        return out
+        return _lr_forward(ctx, ("gpsig_lr_seq_features_spectral_dev", "gpsig_lr_seq_features_spectral_grad"), Xs, (), S, Wh, (alpha, omega, gamma),
+                           spec, family, sketches, r)
 
-    @staticmethod
-    def backward(ctx, G):
-        X, Sd, Whd, a, o, g = ctx.saved_tensors
-        n, l, d = X.shape
-        cc = Sd.shape[0]
-        keep = []
-        p = ctx.spec.params(d, float(a.shape[0]), keep)
-        p.base_params[1] = float(_SPECTRAL_FAMILY[ctx.family])
-        arr = _sketch_array(ctx.sketches, keep)
-        G = _c(G)
-        grads = [torch.empty_like(t) for t in (X, Sd, Whd, a, o, g)]
-        _ctx_for(X).call("gpsig_lr_seq_features_spectral_grad", p, cc, ctx.r, len(ctx.sketches), arr, _ptr(X), n, l, _ptr(Sd), _ptr(Whd),
-                         _ptr(a), _ptr(o), _ptr(g), _ptr(G), *(_ptr(t) for t in grads))
-        return tuple(t.to(dt) for t, dt in zip(grads, ctx.dt)) + (None, None, None, None)
+    backward = staticmethod(_lr_backward)
 
 
 class _LrSeqFeaturesSpectralRagged(torch.autograd.Function):
-    """_LrSeqFeaturesSpectral for long and ragged batches: ``lengths`` (N,) int32 on the sequences' device, 1 <= lengths[n] <= L, or None (every
-    sequence has L points).  By gpsig_lr_seq_features_spectral_ragged_dev / _ragged_grad (csrc/lr_spectral_tiled_inst.hip: the lengths-aware
-    spectral instances of the whole-sequence and the time-tiled kernels, then the lengths-aware reverse kernels of the spectral cross op):
-    Phi[n] is the features of Xs[n, :lengths[n]] evaluated alone, the rows beyond a sequence's length are never read (they may hold NaN) and
-    their gradient rows are exact zeros.  Gradients of all six tensors.  Raises NotImplementedError outside the library's limits (the caller
-    falls back to torch ops)."""
+    """_LrSeqFeaturesSpectral for long and ragged batches: ``lengths`` as _LrSeqFeaturesRagged takes them, or None (every sequence has L points).
+    By gpsig_lr_seq_features_spectral_ragged_dev / _ragged_grad (csrc/lr_spectral_tiled_inst.hip: the lengths-aware spectral instances of the
+    whole-sequence and the time-tiled kernels, then the lengths-aware reverse kernels of the spectral cross op)."""
 
     @staticmethod
     def forward(ctx, Xs, lengths, S, Wh, alpha, omega, gamma, spec, family, sketches, r):
-        X, Sd, Whd, a, o, g = (_c(t) for t in (Xs, S, Wh, alpha, omega, gamma))
-        n, l, d = X.shape
-        if lengths is not None and (lengths.dtype != torch.int32 or lengths.device != X.device or tuple(lengths.shape) != (n,)):
-            raise ValueError("lengths: an int32 tensor of shape (N,) on the sequences' device, or None")
-        lens = None if lengths is None else lengths.contiguous()
-        cc = Sd.shape[0]
-        keep = []
-        p = spec.params(d, float(a.shape[0]), keep)
-        p.base_params[1] = float(_SPECTRAL_FAMILY[family])
-        arr = _sketch_array(sketches, keep)
-        F = 1 + cc + (spec.num_levels - 1) * int(r)
-        out = torch.empty((n, F), dtype=torch.float64, device=X.device)
-        _ctx_for(X).call("gpsig_lr_seq_features_spectral_ragged_dev", p, cc, int(r), len(sketches), arr, _ptr(X), n, l,
-                         None if lens is None else _ptr(lens), _ptr(Sd), _ptr(Whd), _ptr(a), _ptr(o), _ptr(g), _ptr(out))
-        ctx.spec, ctx.family, ctx.sketches, ctx.r, ctx.has_lens = spec, family, sketches, int(r), lens is not None
-        ctx.dt = tuple(t.dtype for t in (Xs, S, Wh, alpha, omega, gamma))
-        ctx.save_for_backward(X, Sd, Whd, a, o, g, lens if lens is not None else X.new_empty(0))
-        return out
+        return _lr_forward(ctx, ("gpsig_lr_seq_features_spectral_ragged_dev", "gpsig_lr_seq_features_spectral_ragged_grad"), Xs,
+                           (_lr_lengths(lengths, Xs, optional=True),), S, Wh, (alpha, omega, gamma), spec, family, sketches, r)
 
-    @staticmethod
-    def backward(ctx, G):
-        X, Sd, Whd, a, o, g, lens = ctx.saved_tensors
-        n, l, d = X.shape
-        cc = Sd.shape[0]
-        keep = []
-        p = ctx.spec.params(d, float(a.shape[0]), keep)
-        p.base_params[1] = float(_SPECTRAL_FAMILY[ctx.family])
-        arr = _sketch_array(ctx.sketches, keep)
-        G = _c(G)
-        grads = [torch.empty_like(t) for t in (X, Sd, Whd, a, o, g)]
-        _ctx_for(X).call("gpsig_lr_seq_features_spectral_ragged_grad", p, cc, ctx.r, len(ctx.sketches), arr, _ptr(X), n, l,
-                         _ptr(lens) if ctx.has_lens else None, _ptr(Sd), _ptr(Whd), _ptr(a), _ptr(o), _ptr(g), _ptr(G), *(_ptr(t) for t in grads))
-        gX, rest = grads[0].to(ctx.dt[0]), tuple(t.to(dt) for t, dt in zip(grads[1:], ctx.dt[1:]))
-        return (gX, None) + rest + (None, None, None, None)
+    backward = staticmethod(_lr_backward)
 
 
 class _LrTensFeatures(torch.autograd.Function):
     """_K_tens_lr_feat (kernels.py:285-311) given the landmarks and the whitening: scaled inducing tensors (lt, T[, 2], d), S (c, d), Wh (c, c)
     -> Phi (T, 1 + c + (M-1) r), by the fused HIP tensor kernel (gpsig_lr_tens_features_dev); the reverse pass by
     lr_tens_features_grad_kernel (csrc/lr_tens_grad_kernel.hpp): dPhi -> dZ, dS, dWh, d base parameter.  The twin of _LrSeqFeatures; the torch
-    route of the same map is _LowRankScope._tens_torch.  Raises NotImplementedError outside the library's limits."""
+    route of the same map is _LowRankScope._tens_torch."""
 
     @staticmethod
     def forward(ctx, Zs, S, Wh, p0, spec, sketches, r, increments):
-        Z, Sd, Whd = _c(Zs), _c(S), _c(Wh)
-        T, d = Z.shape[1], Z.shape[-1]
-        cc = Sd.shape[0]
-        keep = []
-        p = spec.params(d, _p0_value(p0), keep)
-        arr = _sketch_array(sketches, keep)
-        F = 1 + cc + (spec.num_levels - 1) * int(r)
-        out = torch.empty((T, F), dtype=torch.float64, device=Z.device)
-        _ctx_for(Z).call("gpsig_lr_tens_features_dev", p, cc, int(r), len(sketches), arr, _ptr(Z), T, int(bool(increments)), _ptr(Sd), _ptr(Whd),
-                         _ptr(out))
-        ctx.spec, ctx.sketches, ctx.r, ctx.has_p0, ctx.increments = spec, sketches, int(r), p0 is not None, bool(increments)
-        ctx.dt = (Zs.dtype, S.dtype, Wh.dtype)
-        ctx.save_for_backward(Z, Sd, Whd, p0 if p0 is not None else Z.new_empty(0))
-        return out
+        return _lr_forward(ctx, ("gpsig_lr_tens_features_dev", "gpsig_lr_tens_features_grad"), Zs, (), S, Wh, p0, spec, None, sketches, r, increments)
 
-    @staticmethod
-    def backward(ctx, G):
-        Z, Sd, Whd, p0 = ctx.saved_tensors
-        T, d = Z.shape[1], Z.shape[-1]
-        cc = Sd.shape[0]
-        keep = []
-        p = ctx.spec.params(d, _p0_value(p0) if ctx.has_p0 else 0.0, keep)
-        arr = _sketch_array(ctx.sketches, keep)
-        G = _c(G)
-        gZ, gS, gWh = torch.empty_like(Z), torch.empty_like(Sd), torch.empty_like(Whd)
-        gb = torch.zeros(2, dtype=torch.float64, device=Z.device)
-        _ctx_for(Z).call("gpsig_lr_tens_features_grad", p, cc, ctx.r, len(ctx.sketches), arr, _ptr(Z), T, int(ctx.increments), _ptr(Sd), _ptr(Whd),
-                         _ptr(G), _ptr(gZ), _ptr(gS), _ptr(gWh), C.cast(gb.data_ptr(), C.POINTER(C.c_double)))
-        gp0 = gb[0].to(p0.device).reshape(p0.shape).to(p0.dtype) if ctx.has_p0 else None
-        return gZ.to(ctx.dt[0]), gS.to(ctx.dt[1]), gWh.to(ctx.dt[2]), gp0, None, None, None, None
+    backward = staticmethod(_lr_backward)
 
 
 class _LrTensFeaturesSpectral(torch.autograd.Function):
     """_LrTensFeatures for SignatureSpectral: also the positive alpha (Q), omega (Q, d), gamma (Q, d), by gpsig_lr_tens_features_spectral_dev;
     the reverse pass by gpsig_lr_tens_features_spectral_grad (the spectral instance of lr_tens_features_grad_kernel down to dkx, then the spectral
-    cross op's reverse kernels on the tensors' points as they lie in memory): gradients of all six tensors.  Raises NotImplementedError
-    outside the library's limits (the caller falls back to torch ops)."""
+    cross op's reverse kernels on the tensors' points as they lie in memory): gradients of all six tensors."""
 
     @staticmethod
     def forward(ctx, Zs, S, Wh, alpha, omega, gamma, spec, family, sketches, r, increments):
-        Z, Sd, Whd, a, o, g = (_c(t) for t in (Zs, S, Wh, alpha, omega, gamma))
-        T, d = Z.shape[1], Z.shape[-1]
-        cc = Sd.shape[0]
-        keep = []
-        p = spec.params(d, float(a.shape[0]), keep)
-        p.base_params[1] = float(_SPECTRAL_FAMILY[family])
-        arr = _sketch_array(sketches, keep)
-        F = 1 + cc + (spec.num_levels - 1) * int(r)
-        out = torch.empty((T, F), dtype=torch.float64, device=Z.device)
-        _ctx_for(Z).call("gpsig_lr_tens_features_spectral_dev", p, cc, int(r), len(sketches), arr, _ptr(Z), T, int(bool(increments)), _ptr(Sd),
-                         _ptr(Whd), _ptr(a), _ptr(o), _ptr(g), _ptr(out))
-        ctx.spec, ctx.family, ctx.sketches, ctx.r, ctx.increments = spec, family, sketches, int(r), bool(increments)
-        ctx.dt = tuple(t.dtype for t in (Zs, S, Wh, alpha, omega, gamma))
-        ctx.save_for_backward(Z, Sd, Whd, a, o, g)
-        return out
+        return _lr_forward(ctx, ("gpsig_lr_tens_features_spectral_dev", "gpsig_lr_tens_features_spectral_grad"), Zs, (), S, Wh, (alpha, omega, gamma),
+                           spec, family, sketches, r, increments)
 
-    @staticmethod
-    def backward(ctx, G):
-        Z, Sd, Whd, a, o, g = ctx.saved_tensors
-        T, d = Z.shape[1], Z.shape[-1]
-        cc = Sd.shape[0]
-        keep = []
-        p = ctx.spec.params(d, float(a.shape[0]), keep)
-        p.base_params[1] = float(_SPECTRAL_FAMILY[ctx.family])
-        arr = _sketch_array(ctx.sketches, keep)
-        G = _c(G)
-        grads = [torch.empty_like(t) for t in (Z, Sd, Whd, a, o, g)]
-        _ctx_for(Z).call("gpsig_lr_tens_features_spectral_grad", p, cc, ctx.r, len(ctx.sketches), arr, _ptr(Z), T, int(ctx.increments), _ptr(Sd),
-                         _ptr(Whd), _ptr(a), _ptr(o), _ptr(g), _ptr(G), *(_ptr(t) for t in grads))
-        return tuple(t.to(dt) for t, dt in zip(grads, ctx.dt)) + (None, None, None, None, None)
+    backward = staticmethod(_lr_backward)
 
 
 class _SpectralCross(torch.autograd.Function):
@@ -1065,6 +959,15 @@ class _SpectralCross(torch.autograd.Function):
         lc.check(lc._lib.gpsig_spectral_cross_grad(lc._h, Q, _SPECTRAL_FAMILY[ctx.family], d, _ptr(Pd), n, _ptr(Sd), cc, _ptr(a), _ptr(o),
                                                    _ptr(g), _ptr(G), _ptr(gP), _ptr(gS), _ptr(ga), _ptr(go), _ptr(gg)))
         return tuple(t.to(dt) for t, dt in zip((gP, gS, ga, go, gg), ctx.dt)) + (None,)
+
+
+def _lr_limits(cc, r, d, M):
+    """What csrc/lr_grad_api.hip takes of a low-rank feature map -> (the sizes its reverse kernels are built for: at most 64 components, 4096
+    (component, column) pairs, 8 levels; whether one 64-step tile of a sequence's arrays fits the LDS with its carry rows (csrc/lr_tile_plan.hpp:
+    four arrays in the reverse pass, three in the forward direction -- longer sequences go in tiles))."""
+    rows = max(cc, r, d, 16)
+    tile_fits = max(8 * (65 * 4 * rows + 17 * rows), 8 * (65 * (cc + 2 * max(cc, r, d)) + 8 * max(cc, r, d))) <= 156 * 1024
+    return cc <= 64 and cc * d <= 4096 and M - 1 <= 7, tile_fits
 
 
 class _LowRankScope:
@@ -1101,71 +1004,48 @@ class _LowRankScope:
 
     def seq(self, Xs, lengths=None):
         """signature_algs.py:162-192 (with :191 summing P, as evidently intended).  (N, L, d') -> [(N, 1), (N, c), (N, r), ...].
-        Through the HIP feature kernel and its reverse pass (_LrSeqFeatures; SignatureSpectral: _LrSeqFeaturesSpectral) where they are
-        built (sequences beyond the LDS in time tiles; SignatureSpectral: whole sequences, and with the module option
-        ``lr_spectral_tiled`` longer ones in time tiles by _LrSeqFeaturesSpectralRagged); torch ops otherwise (more than 64 components, ranks
+        Through the HIP feature kernel and its reverse pass (_seq_hip) where they are built; torch ops otherwise (more than 64 components, ranks
         beyond a 64-step tile, module option ``lr_hip = False``).
-        lengths: (N,) int32 on the sequences' device for a ragged batch (sequence n is Xs[n, :lengths[n]]; the rows beyond are not read):
-        _LrSeqFeaturesRagged within the same limits for the families other than SignatureSpectral, for which it is
-        _LrSeqFeaturesSpectralRagged with ``lr_spectral_tiled`` set; _seq_torch_ragged otherwise."""
-        if lengths is not None:
-            return self._seq_ragged(Xs, lengths)
-        key = id(Xs)
-        if key not in self._seq and getattr(self.mod, "lr_hip", True) and Xs.is_cuda:
-            mod, kern = self.mod, self.mod.kern
-            M, cc = kern.num_levels, int(self.S.shape[0])
-            r = int(self.host_sketches[0].r) if self.host_sketches else int(kern.rank_bound)
-            L, d = int(Xs.shape[1]), int(Xs.shape[2])
-            # what csrc/lr_grad_api.hip takes: at most 64 components, and in LDS (csrc/lr_tile_plan.hpp) one 64-step tile of a sequence's
-            # arrays with its carry rows, three in the forward direction and four in the reverse pass -- longer sequences go in tiles;
-            # SignatureSpectral: the four (width, L) arrays of a whole sequence
-            rows, lp = max(cc, r, d, 16), (L + 63) // 64 * 64 + 1
-            tile_fits = max(8 * (65 * 4 * rows + 17 * rows), 8 * (65 * (cc + 2 * max(cc, r, d)) + 8 * max(cc, r, d))) <= 156 * 1024
-            whole_fits = 8 * lp * 4 * rows <= 156 * 1024
-            # SignatureSpectral beyond whole sequences: the lengths-aware tiled instances, where the module asks for them
-            spectral_tiled = kern._base == "spectral" and not whole_fits and getattr(mod, "lr_spectral_tiled", False)
-            fits = whole_fits if kern._base == "spectral" and not spectral_tiled else tile_fits
-            if cc <= 64 and cc * d <= 4096 and fits and M - 1 <= 7:
-                try:
-                    if spectral_tiled:
-                        Phi = _LrSeqFeaturesSpectralRagged.apply(Xs, None, self.S, self.Wh, positive(mod.raw_alpha), positive(mod.raw_omega),
-                                                                 positive(mod.raw_sgamma), mod._spec, kern.family, self.host_sketches, r)
-                    elif kern._base == "spectral":
-                        Phi = _LrSeqFeaturesSpectral.apply(Xs, self.S, self.Wh, positive(mod.raw_alpha), positive(mod.raw_omega),
-                                                           positive(mod.raw_sgamma), mod._spec, kern.family, self.host_sketches, r)
-                    else:
-                        Phi = _LrSeqFeatures.apply(Xs, self.S, self.Wh, mod.p0, mod._spec, self.host_sketches, r)
-                    cuts = [1, cc] + [r] * (M - 1)
-                    self._seq[key] = (Xs, list(torch.split(Phi, cuts, dim=1)))
-                except NotImplementedError:
-                    pass
+        lengths: (N,) int32 on the sequences' device for a ragged batch (sequence n is Xs[n, :lengths[n]]; the rows beyond are not read): the
+        ragged ops within the same limits, _seq_torch_ragged otherwise."""
+        key = id(Xs) if lengths is None else (id(Xs), id(lengths))
         if key not in self._seq:
-            self._seq[key] = (Xs, self._seq_torch(Xs))
-        return self._seq[key][1]
+            Phi = self._seq_hip(Xs, lengths) if getattr(self.mod, "lr_hip", True) and Xs.is_cuda else None
+            if Phi is None:
+                Phi = self._seq_torch(Xs) if lengths is None else self._seq_torch_ragged(Xs, lengths)
+            self._seq[key] = (Xs, Phi) if lengths is None else (Xs, lengths, Phi)
+        return self._seq[key][-1]
 
-    def _seq_ragged(self, Xs, lengths):
-        key = (id(Xs), id(lengths))
-        spectral = self.mod.kern._base == "spectral"
-        if key not in self._seq and getattr(self.mod, "lr_hip", True) and Xs.is_cuda and (not spectral or getattr(self.mod, "lr_spectral_tiled", False)):
-            mod, kern = self.mod, self.mod.kern
-            M, cc = kern.num_levels, int(self.S.shape[0])
-            r = int(self.host_sketches[0].r) if self.host_sketches else int(kern.rank_bound)
-            d = int(Xs.shape[2])
-            # the limits of seq() above: they follow from the table's L, not from the lengths
-            fits = max(8 * (65 * 4 * max(cc, r, d, 16) + 17 * max(cc, r, d, 16)), 8 * (65 * (cc + 2 * max(cc, r, d)) + 8 * max(cc, r, d))) <= 156 * 1024
-            if cc <= 64 and cc * d <= 4096 and fits and M - 1 <= 7:
-                try:
-                    if spectral:
-                        Phi = _LrSeqFeaturesSpectralRagged.apply(Xs, lengths, self.S, self.Wh, positive(mod.raw_alpha), positive(mod.raw_omega),
-                                                                 positive(mod.raw_sgamma), mod._spec, kern.family, self.host_sketches, r)
-                    else:
-                        Phi = _LrSeqFeaturesRagged.apply(Xs, lengths, self.S, self.Wh, mod.p0, mod._spec, self.host_sketches, r)
-                    self._seq[key] = (Xs, lengths, list(torch.split(Phi, [1, cc] + [r] * (M - 1), dim=1)))
-                except NotImplementedError:
-                    pass
-        if key not in self._seq:
-            self._seq[key] = (Xs, lengths, self._seq_torch_ragged(Xs, lengths))
-        return self._seq[key][2]
+    def _seq_hip(self, Xs, lengths):
+        """seq() by the HIP ops, or None where they are not built for the shape: _LrSeqFeatures (ragged: _LrSeqFeaturesRagged), sequences beyond
+        the LDS in time tiles.  SignatureSpectral: _LrSeqFeaturesSpectral for whole sequences; beyond them and for ragged batches
+        _LrSeqFeaturesSpectralRagged, with the module option ``lr_spectral_tiled`` alone.  The limits follow from the table's L, not from the
+        lengths."""
+        mod, kern = self.mod, self.mod.kern
+        M, cc = kern.num_levels, int(self.S.shape[0])
+        r = int(self.host_sketches[0].r) if self.host_sketches else int(kern.rank_bound)
+        L, d = int(Xs.shape[1]), int(Xs.shape[2])
+        sizes_ok, tile_fits = _lr_limits(cc, r, d, M)
+        spectral = kern._base == "spectral"
+        # the whole-sequence spectral pair keeps the four (width, L) arrays of a sequence in LDS
+        whole_fits = 8 * ((L + 63) // 64 * 64 + 1) * 4 * max(cc, r, d, 16) <= 156 * 1024
+        spectral_whole = spectral and lengths is None and whole_fits
+        if spectral and not spectral_whole and not getattr(mod, "lr_spectral_tiled", False):
+            return None
+        if not sizes_ok or not (spectral_whole or tile_fits):
+            return None
+        try:
+            if spectral:
+                base = (positive(mod.raw_alpha), positive(mod.raw_omega), positive(mod.raw_sgamma), mod._spec, kern.family, self.host_sketches, r)
+                Phi = (_LrSeqFeaturesSpectral.apply(Xs, self.S, self.Wh, *base) if spectral_whole else
+                       _LrSeqFeaturesSpectralRagged.apply(Xs, lengths, self.S, self.Wh, *base))
+            elif lengths is None:
+                Phi = _LrSeqFeatures.apply(Xs, self.S, self.Wh, mod.p0, mod._spec, self.host_sketches, r)
+            else:
+                Phi = _LrSeqFeaturesRagged.apply(Xs, lengths, self.S, self.Wh, mod.p0, mod._spec, self.host_sketches, r)
+        except NotImplementedError:
+            return None
+        return list(torch.split(Phi, [1, cc] + [r] * (M - 1), dim=1))
 
     def _seq_torch_ragged(self, Xs, lengths):
         """_seq_torch for a ragged batch (lengths (N,) integers on Xs's device, 1 <= lengths[n] <= L): the features of Xs[n, :lengths[n]]
@@ -1197,18 +1077,17 @@ class _LowRankScope:
     def _seq_torch(self, Xs):
         """The same feature map as torch ops (round 3's route; kept as the checker of the HIP reverse pass and for shapes it is not
         built for)."""
-        if True:
-            N, L, d = Xs.shape
-            U = self._nys(Xs.reshape(N * L, d)).reshape(N, L, -1)                                   # kernels.py:252-254
-            if self.mod.kern.difference:
-                U = U[:, 1:] - U[:, :-1]                                                            # :180
-            Phi = [torch.ones((N, 1), dtype=U.dtype, device=U.device), U.sum(dim=1)]                # :177, :182
-            P = U
-            for i in range(2, self.mod.kern.num_levels + 1):
-                P = torch.cumsum(P, dim=1) - P                                                      # :186 exclusive
-                P = _apply_sketch(self.sk[i - 2], U, P)                                             # :188 / :190
-                Phi.append(P.sum(dim=1))
-            return Phi
+        N, L, d = Xs.shape
+        U = self._nys(Xs.reshape(N * L, d)).reshape(N, L, -1)                                       # kernels.py:252-254
+        if self.mod.kern.difference:
+            U = U[:, 1:] - U[:, :-1]                                                                # :180
+        Phi = [torch.ones((N, 1), dtype=U.dtype, device=U.device), U.sum(dim=1)]                    # :177, :182
+        P = U
+        for i in range(2, self.mod.kern.num_levels + 1):
+            P = torch.cumsum(P, dim=1) - P                                                          # :186 exclusive
+            P = _apply_sketch(self.sk[i - 2], U, P)                                                 # :188 / :190
+            Phi.append(P.sum(dim=1))
+        return Phi
 
     def tens(self, Zs, increments):
         """signature_algs.py:194-222, kernels.py:285-311.  (lt, T[, 2], d') -> [(T, 1), (T, c), (T, r), ...].
@@ -1223,7 +1102,7 @@ class _LowRankScope:
             lt, d, E = int(Zs.shape[0]), int(Zs.shape[-1]), 2 if increments else 1
             # what csrc/lr_grad_api.hip takes (lr_tens_grad_lds_bytes): a tensor's arrays in LDS, at most 64 components
             lds = 8 * (lt * E * (d + 2 * cc) + 2 * lt * cc + M * (M - 1) // 2 * r + 2 * max(cc, r) + 16)
-            if cc <= 64 and cc * d <= 4096 and lds <= 156 * 1024 and M - 1 <= 7 and lt == M * (M + 1) // 2:
+            if _lr_limits(cc, r, d, M)[0] and lds <= 156 * 1024 and lt == M * (M + 1) // 2:
                 try:
                     if kern._base == "spectral":
                         Phi = _LrTensFeaturesSpectral.apply(Zs, self.S, self.Wh, positive(mod.raw_alpha), positive(mod.raw_omega),

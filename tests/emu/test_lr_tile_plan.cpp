@@ -67,6 +67,17 @@ int main() {
                                     else
                                         CHECK(P.grid == (N < LR_TILE_MAX_GRID ? N : LR_TILE_MAX_GRID));     // whole sequences: the grid as it was
                                     if (N > 0 && P.escr_stride * int64_t(sizeof(double)) <= int64_t(LR_TILE_SCRATCH_BUDGET)) CHECK(P.grid >= 1);
+                                    // SignatureSpectral's reverse pass keeps kxs (c, L) per workgroup too.  Where the plan of a chunk of N sequences is a
+                                    // whole-sequence one, it is the numbers gpsig_lr_seq_features_spectral_grad was written with: kxs behind the E_i, eight
+                                    // doubles of slack, min(N, 512) workgroups, the whole-sequence footprint
+                                    const LrTilePlan K = lr_tile_plan(c, r, d, L, M, difference, pad, N, int64_t(c) * L);
+                                    CHECK(K.rev.untiled == P.rev.untiled);
+                                    if (K.rev.untiled) {
+                                        const int64_t kxs_off = (int64_t(c) + int64_t(M > 2 ? M - 2 : 0) * r) * (l > 0 ? l : 1);
+                                        CHECK(K.escr_stride - int64_t(c) * L - 8 == kxs_off && K.escr_stride == kxs_off + int64_t(c) * L + 8);
+                                        CHECK(K.grid == (N < 512 ? N : 512));
+                                        CHECK(K.rev.lds == lr_grad_lds_bytes(c, r, d, L, pad));
+                                    }
                                     if (M == 4 && N == 3) {
                                         check_dir(P.fwd, false, c, r, d, L, l, halo, pad);
                                         check_dir(P.rev, true, c, r, d, L, l, halo, pad);
