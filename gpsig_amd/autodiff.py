@@ -72,9 +72,10 @@ class _Spec:
 # The library's "wide" option (state spaces beyond the exact-shape kernels' columns: kernel arguments by dgemm + fused map / difference / recursion
 # kernels, csrc/wide_api.hip): None = where the exact-shape kernels are not built (the library's default), True = wherever built, False = never.
 _WIDE = {"value": -1}
-WIDE_BASES = ("rbf", "matern12", "matern32", "matern52", "linear", "cosine", "poly")      # (poly: the whole degrees 1 .. 8 -- wide_poly_served)
+WIDE_BASES = ("rbf", "matern12", "matern32", "matern52", "linear", "cosine", "poly", "mix")      # (poly: the whole degrees 1 .. 8 -- wide_poly_served)
 WIDE_DOT_BASES = ("linear", "cosine")               # ... whose sequence lattices are first-order only there (their order > 1 beyond 64 columns: the matrix route)
 WIDE_SEQ_MATRIX_BASES = WIDE_DOT_BASES + ("poly",)   # ... and those whose sequence Grams / order > 1 level diagonals keep the matrix route beyond 64 columns
+WIDE_O1_LATTICE_BASES = WIDE_SEQ_MATRIX_BASES + ("mix",)      # ... those whose sequence lattices are first-order only there (mix: its first-order sequence Grams ARE served)
 WIDE_PRIMITIVES = {"tvs", "diag", "seq", "tens"}           # the level primitives the library has a wide route for
 def wide_poly_served(degree):
     """SignaturePoly on the wide route: the whole degrees 1 .. 8 (csrc/ctx.hpp: wide_poly_degree)."""
@@ -1314,7 +1315,7 @@ class SignatureKernelModule(torch.nn.Module):
             return True
         first = self._spec.order == 1 or self._spec.num_levels == 1 or prim == "tens"            # (Kzz has no order)
         # order > 1 on the wide route: the Kzx chains at orders <= 4; the sequence lattices' sweeps (csrc/grad_wave_ho_kernel.hpp) at <= 5 levels, orders <= 4
-        high = min(self._spec.order, self._spec.num_levels) <= 4 and (prim == "tvs" or (self._spec.num_levels <= 5 and self._spec.base not in WIDE_SEQ_MATRIX_BASES))
+        high = min(self._spec.order, self._spec.num_levels) <= 4 and (prim == "tvs" or (self._spec.num_levels <= 5 and self._spec.base not in WIDE_O1_LATTICE_BASES))
         wide = (prim in WIDE_PRIMITIVES and self._spec.base in WIDE_BASES and (first or high)
                 and _WIDE["value"] != 0 and cols - int(self._spec.difference) <= WIDE_LAT_MAX_COLS)
         return not wide

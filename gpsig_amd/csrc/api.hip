@@ -1398,8 +1398,8 @@ static int generic_levels(gpsig_ctx* c, const gpsig_params* p, bool apply_scalin
     const int d_eff = sp.d_eff(), M = p->num_levels;
     // wide route (wide_api.hip): the argument lattices by dgemm, one wavefront per lattice -- the distance kernels at order 1, up to 512 lattice columns
     // (the dot-product families: beyond 32 columns, or by option -- up to there this fallback stays what it was for them)
-    // (SignaturePoly: beyond 64 columns, or by option)
-    if (wide_lat_available(c, p, L1, L2) && (!(wide_dot_kind(p->base_kernel) || p->base_kernel == GPSIG_BASE_POLY) || c->wide == 1 || d_eff > wide_auto_cols(p, 32)) && sm == (diag ? N1 : N1 * N2) && si == (diag ? 1 : N2) &&
+    // (SignaturePoly, SignatureMix: beyond 64 columns, or by option)
+    if (wide_lat_available(c, p, L1, L2) && (!(wide_dot_kind(p->base_kernel) || wide_base_param_kind(p->base_kernel)) || c->wide == 1 || d_eff > wide_auto_cols(p, 32)) && sm == (diag ? N1 : N1 * N2) && si == (diag ? 1 : N2) &&
         sj == (diag ? 0 : 1)) {
         const bool same_ = diag || Y == nullptr || Y == X;
         void *xs, *ys = nullptr;

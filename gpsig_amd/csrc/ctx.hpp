@@ -44,7 +44,7 @@ enum BufId {
     B_LRF32,                                                   // low-rank mode, float32 calls: the state and the spectral table narrowed to float32
     B_TQ,                                                      // item counters of the Kzx tile kernel's persistent launch
     B_STASH,                                                   // what the fused reverse kernel needs of the forward recursion (gpsig_seq_gram_levels_stash)
-    B_WD0, B_WD1, B_WD2, B_WD3, B_WD4, B_WD5, B_WD6, B_WD7, B_WD8, B_WD9, B_WD10, B_WD11,   // wide state spaces (wide_api.hip): augmented rows, kernel-argument chunks, their adjoints, lattice states
+    B_WD0, B_WD1, B_WD2, B_WD3, B_WD4, B_WD5, B_WD6, B_WD7, B_WD8, B_WD9, B_WD10, B_WD11, B_WD12, B_WD13, B_WD14, B_WD15,   // wide state spaces (wide_api.hip): augmented rows, kernel-argument chunks, their adjoints, lattice states
     B_COUNT
 };
 
@@ -525,4 +525,6 @@ inline int wide_poly_degree(const gpsig_params* p) {
     return double(n) == deg ? n : 0;
 }
 // the widest state space that the automatic rule of a call site keeps off the wide route (cols: the distance kernels' figure there)
-inline int wide_auto_cols(const gpsig_params* p, int cols) { return p->base_kernel == GPSIG_BASE_POLY ? 64 : (wide_dot_kind(p->base_kernel) ? 32 : cols); }
+// SignaturePoly and SignatureMix: the families with a trainable base parameter, whose automatic rules all read "beyond 64 columns"
+inline bool wide_base_param_kind(int base_kernel) { return base_kernel == GPSIG_BASE_POLY || base_kernel == GPSIG_BASE_MIX; }
+inline int wide_auto_cols(const gpsig_params* p, int cols) { return wide_base_param_kind(p->base_kernel) ? 64 : (wide_dot_kind(p->base_kernel) ? 32 : cols); }

@@ -852,8 +852,8 @@ int seq_grad(gpsig_ctx* c, const gpsig_params* p, const void* X, const void* Y, 
     // (higher order: the point route's dM and contraction kernels cost more than the sweeps -- ho_dm_kernel evaluates every kappa four times with the
     // library's exp --, so the wide route's dgemms take RBF and the Matern families at every width)
     // (the dot-product families: beyond 32 columns, or by option -- up to there the feature route and the exact-shape kernels below keep them;
-    // SignaturePoly: beyond 64 columns -- DP == 0 --, or by option)
-    const bool wide_rule = p->base_kernel == GPSIG_BASE_POLY ? false : (wide_dot_kind(p->base_kernel) ? d > 32 : (d > 8 || (!w2x && !lfn && !wfn)));
+    // SignaturePoly, SignatureMix: beyond 64 columns -- DP == 0 --, or by option)
+    const bool wide_rule = wide_base_param_kind(p->base_kernel) ? false : (wide_dot_kind(p->base_kernel) ? d > 32 : (d > 8 || (!w2x && !lfn && !wfn)));
     if (wide_ok && (c->wide == 1 || DP == 0 || wide_ho || (!ffn && c->grad_impl == 0 && wide_rule))) {
         CHK(wide_lat_backward(c, p, d, static_cast<const double*>(dX), static_cast<const double*>((diag || sym) ? nullptr : dY), N1, N2, L1, L2, diag,
                               static_cast<const double*>(dG), static_cast<double*>(dgX), static_cast<double*>(dgY), kgb));
@@ -1089,8 +1089,8 @@ int gpsig_tens_vs_seq_levels_grad(gpsig_ctx* c, const gpsig_params* p, const voi
     CHK(grad_check(c, p, &d, &DP, 4096));
     // wide state spaces (wide_api.hip): beyond the tile kernel's 8 columns, or wherever built when the option says so
     // (higher orders: at any width -- the tile kernel's reverse pass is first-order, the older kernels go through scratch memory operation by operation)
-    // (the dot-product families: beyond 32 columns, or by option; SignaturePoly: beyond 64)
-    const bool wide = wide_tvs_available(c, p, d, T, N, L) && ((wide_dot_kind(p->base_kernel) || p->base_kernel == GPSIG_BASE_POLY) ? (c->wide == 1 || d > wide_auto_cols(p, 32)) :
+    // (the dot-product families: beyond 32 columns, or by option; SignaturePoly, SignatureMix: beyond 64)
+    const bool wide = wide_tvs_available(c, p, d, T, N, L) && ((wide_dot_kind(p->base_kernel) || wide_base_param_kind(p->base_kernel)) ? (c->wide == 1 || d > wide_auto_cols(p, 32)) :
                                                                (c->wide == 1 || d > 8 || (p->num_levels > 6 && c->wide != 0) ||      /* (7 / 8 levels: no reverse tile instance -- 100 ms at T = 512, N = 2,048 on the older kernels) */
                                                                 (p->order > 1 && p->num_levels > 1 && c->wide != 0 && !tvs_grad_tile_ho_available(c, p, d, L, increments))));
     if (DP == 0 && !wide) return fail(c, GPSIG_ERR_UNSUPPORTED, "gradients are built for at most 64 feature columns here (got %d)", d);
@@ -1437,8 +1437,8 @@ int gpsig_tens_vs_seq_weighted_grad(gpsig_ctx* c, const gpsig_params* p, const v
     int d, DP;
     CHK(grad_check(c, p, &d, &DP, 4096));
     // (higher orders: at any width -- the tile kernel's reverse pass is first-order, the older kernels go through scratch memory operation by operation)
-    // (the dot-product families: beyond 32 columns, or by option; SignaturePoly: beyond 64)
-    const bool wide = wide_tvs_available(c, p, d, T, N, L) && ((wide_dot_kind(p->base_kernel) || p->base_kernel == GPSIG_BASE_POLY) ? (c->wide == 1 || d > wide_auto_cols(p, 32)) :
+    // (the dot-product families: beyond 32 columns, or by option; SignaturePoly, SignatureMix: beyond 64)
+    const bool wide = wide_tvs_available(c, p, d, T, N, L) && ((wide_dot_kind(p->base_kernel) || wide_base_param_kind(p->base_kernel)) ? (c->wide == 1 || d > wide_auto_cols(p, 32)) :
                                                                (c->wide == 1 || d > 8 || (p->num_levels > 6 && c->wide != 0) ||      /* (7 / 8 levels: no reverse tile instance -- 100 ms at T = 512, N = 2,048 on the older kernels) */
                                                                 (p->order > 1 && p->num_levels > 1 && c->wide != 0 && !tvs_grad_tile_ho_available(c, p, d, L, increments))));
     if (DP == 0 && !wide) return fail(c, GPSIG_ERR_UNSUPPORTED, "gradients are built for at most 64 feature columns here (got %d)", d);

@@ -4,6 +4,7 @@
 // exact-shape kernels.  float64; RBF and the Matern families (the distance kernels: kappa is a function of the ONE number the dgemm yields) and the two
 // dot-product families, whose kappa IS that number: SignatureLinear on plain rows -- increments where the kernel takes differences, so that the kernels run in
 // their difference = 0 form on one row less and half the tensor columns --, SignatureCosine on unit rows.
+// SignaturePoly (whole degrees) on plain rows; SignatureMix on the distance kernels' rows, psi of the dgemm's number plus the one-sided norm terms (mix_sides).
 #include "ctx.hpp"
 #include "launchers.hpp"
 #include "aux_kernels.hpp"
@@ -18,6 +19,7 @@ namespace {
 bool wide_kind(const gpsig_params* p) {
     const int base_kernel = p->base_kernel;
     if (base_kernel == GPSIG_BASE_POLY) return wide_poly_degree(p) > 0;
+    if (base_kernel == GPSIG_BASE_MIX) return true;
     return base_kernel == GPSIG_BASE_RBF || base_kernel == GPSIG_BASE_MATERN12 || base_kernel == GPSIG_BASE_MATERN32 || base_kernel == GPSIG_BASE_MATERN52 ||
            wide_dot_kind(base_kernel);
 }
@@ -25,6 +27,7 @@ bool wide_kind(const gpsig_params* p) {
 // (SignaturePoly: the points themselves as plain rows, a = <z, x>; it is non-linear, so its differences are taken on kappa inside the kernels)
 int kind_of(int base_kernel) {
     if (base_kernel == GPSIG_BASE_POLY) return WIDE_KD_POLY;
+    if (base_kernel == GPSIG_BASE_MIX) return WIDE_KD_MIX;          // (the distance kernels' augmented rows: rows_mode falls through to WIDE_ROWS_DIST)
     return base_kernel == GPSIG_BASE_RBF ? WIDE_KD_RBF : (wide_dot_kind(base_kernel) ? WIDE_KD_ID : WIDE_KD_MATERN);
 }
 int rows_mode(int base_kernel) {
@@ -43,8 +46,26 @@ bool tensors_collapse(const gpsig_params* p, int increments) { return p->base_ke
         case WIDE_KD_RBF: { constexpr int KD = WIDE_KD_RBF; __VA_ARGS__; } break;             \
         case WIDE_KD_ID: { constexpr int KD = WIDE_KD_ID; __VA_ARGS__; } break;               \
         case WIDE_KD_POLY: { constexpr int KD = WIDE_KD_POLY; __VA_ARGS__; } break;           \
+        case WIDE_KD_MIX: { constexpr int KD = WIDE_KD_MIX; __VA_ARGS__; } break;             \
         default: { constexpr int KD = WIDE_KD_MATERN; __VA_ARGS__; } break;                   \
     }
+
+// SignatureMix: kappa = psi(a) + q (h_row + h_column) (wide_kernels.hpp: WIDE_KD_MIX).  Which of the two one-sided terms a primitive's kernels must add,
+// and its reverse pass must carry back -- the ONE place that decides it, for the forward and the reverse entry points alike.  A side's term is the same
+// number at both ends of any difference taken along the OTHER side, and cancels there:
+//   Kzx (rows = sequence points, columns = tensor points): the time difference runs along the rows and cancels the COLUMNS' term; increments subtract a
+//   tensor's two points and cancel the ROWS' term;
+//   sequence lattices: the double difference cancels both, without it both stay;   Kzz: the four-term difference of increments cancels both, without both stay.
+struct MixSides { bool rows, cols; };
+enum MixPrim { MIX_TVS, MIX_LAT, MIX_TENS };
+MixSides mix_sides(const gpsig_params* p, MixPrim prim, int increments) {
+    MixSides s = {false, false};
+    if (p->base_kernel != GPSIG_BASE_MIX) return s;
+    if (prim == MIX_TVS) { s.rows = !increments; s.cols = !p->difference; }
+    else if (prim == MIX_LAT) s.rows = s.cols = !p->difference;
+    else s.rows = s.cols = !increments;
+    return s;
+}
 
 size_t wide_chunk_bytes(const gpsig_ctx* c) {
     if (c->wide_chunk_mb > 0) return size_t(c->wide_chunk_mb) << 20;
@@ -251,6 +272,8 @@ int wide_tvs_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz,
         A.arg = static_cast<const double*>(arg); A.CW = CW; A.Tpad = Tpad; A.Tn = Tn; A.n0 = n0; A.Nc = nc; A.N = N;
         A.L = L; A.M = M; A.kind = p->base_kernel; A.kp0 = p->base_params[0]; A.kp1 = p->base_params[1]; A.difference = (p->difference && !xinc) ? 1 : 0; A.sum_levels = sum_levels;
         A.fx = fx; A.w = w; A.out = out; A.aux = aux; A.order = p->order < p->num_levels ? p->order : p->num_levels;
+        const MixSides ms = mix_sides(p, MIX_TVS, increments);          // (the rows' own norm column: d + 1 of the right form, d of the left form)
+        A.nrm_ld = DA; A.nrm_row = ms.rows ? XA + d + 1 : nullptr; A.nrm_col = ms.cols ? ZA + d : nullptr;
         const dim3 grid(unsigned(TB), unsigned(nc < 65535 ? nc : 65535), unsigned(M));
         GPSIG_WIDE_KIND(p->base_kernel,
                         if (E == 2) hipLaunchKernelGGL((wide_tvs_fwd_kernel<2, KD>), grid, dim3(64), 0, c->stream, A);
@@ -294,7 +317,9 @@ int wide_tvs_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
     // that depends on L alone, at least 256 rows --, and chunks hold whole blocks (at least one: the budget yields to that), so that every dgemm has
     // the same shape in every chunking.  (This rests on rocBLAS returning the same bits for dgemms of one shape whose outputs start at different
     // offsets of the argument buffer.  Nothing in its interface promises that; tests/test_gpu_wide_poly.py holds it at the shapes it runs.)
-    const bool gb = g_base && p->base_kernel == GPSIG_BASE_POLY;
+    // (SignatureMix's mixing: the same slots, the same dgemm blocks)
+    const bool gb = g_base && wide_base_param_kind(p->base_kernel);
+    const MixSides ms = mix_sides(p, MIX_TVS, increments);
     int64_t blk = chunk;                                         // sequences per dgemm
     if (gb) {
         blk = 1;
@@ -313,6 +338,17 @@ int wide_tvs_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
     void* gbp = nullptr;
     const int64_t gbn = int64_t(TB) * N * M;
     if (gb) CHK(ensure(c, B_WD11, sizeof(double) * size_t(gbn + WIDE_GB_BLOCKS) + 64, &gbp));
+    // SignatureMix, a side's term kept: the sums of the values' adjoints over the other side -- slots per (tensor block, level, row) / (sequence, column),
+    // added in a fixed order below (wide_gfac_reduce_kernel), and handed to the un-augmentation of that side
+    void *rap = nullptr, *cap = nullptr, *radj = nullptr, *cadj = nullptr;
+    if (ms.rows) {
+        CHK(ensure(c, B_WD12, sizeof(double) * size_t(TB) * M * size_t(NL) + 64, &rap));
+        CHK(ensure(c, B_WD14, sizeof(double) * size_t(NL) + 64, &radj));
+    }
+    if (ms.cols) {
+        CHK(ensure(c, B_WD13, sizeof(double) * size_t(N) * size_t(CW) + 64, &cap));
+        CHK(ensure(c, B_WD15, sizeof(double) * size_t(CW) + 64, &cadj));
+    }
     for (int64_t n0 = 0; n0 < N; n0 += chunk) {
         const int64_t nc = N - n0 < chunk ? N - n0 : chunk;
         for (int64_t b0 = 0; b0 < nc; b0 += blk) {
@@ -326,6 +362,8 @@ int wide_tvs_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
         A.fx = fac; A.w = nullptr; A.aux = const_cast<double*>(aux);
         A.G = G; A.W = static_cast<double*>(Wb); A.gfac_part = static_cast<double*>(gfp); A.weighted = fac ? 1 : 0;
         A.gb_part = static_cast<double*>(gbp);
+        A.nrm_ld = DA; A.nrm_row = ms.rows ? XA + d + 1 : nullptr; A.nrm_col = ms.cols ? ZA + d : nullptr;
+        A.radj_part = static_cast<double*>(rap); A.cadj_part = static_cast<double*>(cap);
         A.order = p->order < p->num_levels ? p->order : p->num_levels;
         const dim3 grid(unsigned(TB), unsigned(nc < 65535 ? nc : 65535), unsigned(M));
         GPSIG_WIDE_KIND(p->base_kernel,
@@ -336,6 +374,12 @@ int wide_tvs_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
                           static_cast<double*>(gza)));
     }
     const int64_t zrows = int64_t(lt) * Tn * Ez;                // the caller's rows
+    const double qmix = 1.0 - p->base_params[0];
+    if (ms.rows) hipLaunchKernelGGL(wide_gfac_reduce_kernel, dim3(grid_for(NL)), dim3(256), 0, c->stream, static_cast<const double*>(rap), int(TB * M), NL,
+                                    static_cast<double*>(radj));
+    if (ms.cols) hipLaunchKernelGGL(wide_gfac_reduce_kernel, dim3(grid_for(CW)), dim3(256), 0, c->stream, static_cast<const double*>(cap), int(N), CW,
+                                    static_cast<double*>(cadj));
+    HIPCHK(c, hipGetLastError());
     // (plain rows -- SignatureLinear without increments / differences -- take the distance kernels' un-augmentation as it is: both extra columns of
     // such rows are zero on BOTH sides, so the adjoint of the norm column, a product with the other side's zero column, is exactly 0 and g = ga)
     if (mode == WIDE_ROWS_UNIT)
@@ -346,7 +390,7 @@ int wide_tvs_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
                            static_cast<const double*>(nullptr), zrows, d, lt, Tn, Tpad, 0, gZ);
     else
         hipLaunchKernelGGL(wide_unaug_rows_kernel, dim3(grid_for(zrows * d)), dim3(256), 0, c->stream, static_cast<const double*>(gza), ZA, zrows, d, 0, lt, Tn,
-                           Tpad, E, gZ);
+                           Tpad, E, gZ, static_cast<const double*>(cadj), qmix);
     HIPCHK(c, hipGetLastError());
     if (mode == WIDE_ROWS_UNIT)
         hipLaunchKernelGGL(wide_unaug_unit_kernel, dim3(unsigned(NLx < 65535 ? NLx : 65535)), dim3(64), 0, c->stream, static_cast<const double*>(nullptr),
@@ -356,7 +400,7 @@ int wide_tvs_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
                            static_cast<const double*>(gxa), NLx, d, 0, int64_t(1), int64_t(0), xdiff, gX);
     else
         hipLaunchKernelGGL(wide_unaug_rows_kernel, dim3(grid_for(NL * d)), dim3(256), 0, c->stream, static_cast<const double*>(gxa), XA, NL, d, 1, 0, int64_t(1),
-                           int64_t(0), 1, gX);
+                           int64_t(0), 1, gX, static_cast<const double*>(radj), qmix);
     HIPCHK(c, hipGetLastError());
     if (fac) {
         hipLaunchKernelGGL(wide_gfac_reduce_kernel, dim3(grid_for(N * (M + 1))), dim3(256), 0, c->stream, static_cast<const double*>(gfp), int(TB),
@@ -376,7 +420,7 @@ bool wide_lat_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L
     if (!wide_kind(p) || p->num_levels > WIDE_MAX_LEVELS || p->num_levels < 1) return false;
     const int dr = p->difference ? 1 : 0;
     if (p->order > 1 && p->num_levels > 1) {      // higher orders: the forward and the reverse sweeps of grad_wave_ho_kernel.hpp (<= 5 levels, orders <= 4)
-        if (wide_dot_kind(p->base_kernel) || p->base_kernel == GPSIG_BASE_POLY) return false;      // (these families' higher orders: the feature contraction / the exact-shape kernels, the any-shape kernel beyond)
+        if (wide_dot_kind(p->base_kernel) || wide_base_param_kind(p->base_kernel)) return false;      // (these families' higher orders: the feature contraction / the exact-shape kernels, the any-shape kernel beyond)
         HoSweeps hf, hb;
         return L1 - dr >= 1 && L2 - dr >= 1 && ho_levels_plan(c, p, L1 - dr, L2 - dr, &hf) && ho_sweeps_plan(c, p, L1 - dr, L2 - dr, &hb);
     }
@@ -387,7 +431,7 @@ bool wide_lat_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L
 // the reverse pass of the HIGHER-ORDER recursion on this route: argument lattices by dgemm -> dM lattices (wide_lattice_dm_kernel) -> both sweeps of a
 // pair in one wavefront (grad_wave_ho_kernel.hpp) -> the adjoint contracted back by dgemms; any number of columns
 bool wide_lat_ho_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L2) {
-    if (c->wide == 0 || c->capturing || !wide_kind(p) || wide_dot_kind(p->base_kernel) || p->base_kernel == GPSIG_BASE_POLY || !(p->order > 1 && p->num_levels > 1)) return false;
+    if (c->wide == 0 || c->capturing || !wide_kind(p) || wide_dot_kind(p->base_kernel) || wide_base_param_kind(p->base_kernel) || !(p->order > 1 && p->num_levels > 1)) return false;
     const int dr = p->difference ? 1 : 0;
     HoSweeps hs;
     return L1 >= 1 && L2 >= 1 && ho_sweeps_plan(c, p, L1 - dr, L2 - dr, &hs);
@@ -477,6 +521,10 @@ int wide_lat_forward(gpsig_ctx* c, const gpsig_params* p, int d, const double* X
         A.P = diag ? ni : ni * N2; A.p0 = 0; A.Ptot = pl.Ptot;
         A.L1 = L1; A.L2 = L2; A.M = M; A.kind = p->base_kernel; A.kp0 = p->base_params[0]; A.kp1 = p->base_params[1]; A.difference = pl.dr;
         A.out = out + (diag ? i0 : i0 * N2);              // (the kernel's pair index starts at 0 in this chunk's lattices)
+        if (mix_sides(p, MIX_LAT, 0).rows) {              // (both sides or neither; the chunk's left sequences, every right sequence -- the diagonal: the chunk's)
+            A.nrm_ld = pl.DA; A.nrm_same = diag ? 1 : 0;
+            A.nrm_row = pl.XL + i0 * L1 * pl.DA + d; A.nrm_col = pl.XR + (diag ? i0 : 0) * L2 * pl.DA + d + 1;
+        }
         if (ho) {
             if (pl.R1 < 1 || pl.R2 < 1) return fail(c, GPSIG_ERR_UNSUPPORTED, "empty lattices");
             GPSIG_WIDE_KIND(p->base_kernel, hipLaunchKernelGGL(wide_lattice_dm_kernel<KD>, dim3(grid_for(A.P * int64_t(pl.R1) * pl.R2)), dim3(256), 0, c->stream, A,
@@ -549,7 +597,14 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
     // SignaturePoly's offset (g_base: device, or NULL): every slice of every lattice leaves the sum of its W entries in a slot of its own, lattices in the
     // order of G's pair axis (zero where the folded symmetric Gram visits no lattice)
     void* gbp = nullptr;
-    const bool poly = p->base_kernel == GPSIG_BASE_POLY, gb = g_base && poly;
+    const bool poly = p->base_kernel == GPSIG_BASE_POLY, mix = p->base_kernel == GPSIG_BASE_MIX, gb = g_base && (poly || mix);
+    // SignatureMix without differences: the row and the column sums of the Lam lattices, per point of the left / the right sequences
+    const bool sided = mix_sides(p, MIX_LAT, 0).rows;
+    void *radj = nullptr, *cadj = nullptr;
+    if (sided) {
+        CHK(ensure(c, B_WD14, sizeof(double) * size_t(N1) * L1 + 64, &radj));
+        CHK(ensure(c, B_WD15, sizeof(double) * size_t(N2) * L2 + 64, &cadj));
+    }
     const int gbs = int((int64_t(L1) * L2 + WIDE_GB_SLICE - 1) / WIDE_GB_SLICE);
     const int64_t gbn = (diag ? N1 : N1 * N2) * gbs;
     if (gb) {
@@ -570,6 +625,10 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
         A.g_i = diag ? 1 : N2; A.g_j = diag ? 0 : 1;
         A.scratch = static_cast<double*>(scr); A.lam = static_cast<double*>(lam);
         A.gb_slices = gbs;
+        if (sided) {              // (this chunk's left sequences and its right sequences j0 .. N2 - 1; the diagonal: the chunk's on both sides)
+            A.nrm_ld = DA; A.nrm_same = diag ? 1 : 0;
+            A.nrm_row = pl.XL + i0 * L1 * DA + d; A.nrm_col = pl.XR + (diag ? i0 : j0) * L2 * DA + d + 1;
+        }
         if (gb) A.gb_part = static_cast<double*>(gbp) + (diag ? i0 : i0 * N2 + j0) * gbs;
         const int64_t ng = A.P < groups ? A.P : groups;
         A.ngroups = int(ng);
@@ -585,8 +644,16 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
             HIPCHK(c, hipGetLastError());
         }
         // the adjoint of the arguments, in place of the arguments
+        if (sided) {
+            const int64_t units = ni * int64_t(L1) + (diag ? ni : N2e) * int64_t(L2);
+            hipLaunchKernelGGL(wide_lattice_sides_kernel, dim3(grid_for(units, 1)), dim3(64), 0, c->stream, static_cast<const double*>(lam), ni, diag ? int64_t(1) : N2e,
+                               L1, L2, diag ? 1 : 0, (!diag && i0 > 0) ? 1 : 0, static_cast<double*>(radj) + i0 * L1, static_cast<double*>(cadj) + (diag ? i0 : j0) * L2);
+            HIPCHK(c, hipGetLastError());
+        }
         if (poly)          // (a kernel of its own: one wavefront per slice of a lattice, with the slice's sum of W)
             hipLaunchKernelGGL(wide_lattice_adjoint_poly_kernel, dim3(grid_for(A.P * gbs, 1)), dim3(64), 0, c->stream, A, static_cast<double*>(arg));
+        else if (mix)
+            hipLaunchKernelGGL(wide_lattice_adjoint_mix_kernel, dim3(grid_for(A.P * gbs, 1)), dim3(64), 0, c->stream, A, static_cast<double*>(arg));
         else
             GPSIG_WIDE_KIND(p->base_kernel, hipLaunchKernelGGL(wide_lattice_adjoint_kernel<KD>, dim3(grid_for(A.P * int64_t(L1) * L2)), dim3(256), 0, c->stream, A,
                                                                static_cast<double*>(arg)))
@@ -627,12 +694,13 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
         return GPSIG_OK;
     }
     // (plain rows of SignatureLinear too: their norm column's adjoint is exactly 0 -- see wide_tvs_backward)
+    const double qmix = 1.0 - p->base_params[0];
     hipLaunchKernelGGL(wide_unaug_pair_kernel, dim3(grid_for(xr_rows * d)), dim3(256), 0, c->stream, gl, pl.XL, same ? gr : none, same ? pl.XR : none, xr_rows, d,
-                       gX);
+                       gX, static_cast<const double*>(radj), same ? static_cast<const double*>(cadj) : none, qmix);
     HIPCHK(c, hipGetLastError());
     if (!same) {
         hipLaunchKernelGGL(wide_unaug_rows_kernel, dim3(grid_for(yr_rows * d)), dim3(256), 0, c->stream, gr, pl.XR, yr_rows, d, 1, 0, int64_t(1), int64_t(0), 1,
-                           gY);
+                           gY, static_cast<const double*>(cadj), qmix);
         HIPCHK(c, hipGetLastError());
     }
     return GPSIG_OK;
@@ -685,6 +753,7 @@ int wide_tens_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz
     WideTensArgs A;
     memset(&A, 0, sizeof(A));
     A.arg = arg; A.Tpad = Tpad; A.Tn = Tn; A.M = M; A.E = E; A.kind = p->base_kernel; A.kp0 = p->base_params[0]; A.kp1 = p->base_params[1]; A.sum_levels = sum_levels; A.w = w; A.out = out;
+    if (mix_sides(p, MIX_TENS, increments).rows) { A.nrm = ZL + d; A.nrm_ld = d + 2; }          // (both sides are the tensors: one vector)
     GPSIG_WIDE_KIND(p->base_kernel, hipLaunchKernelGGL(wide_tens_fwd_kernel<KD>, dim3(unsigned(Tpad / 64), unsigned(Tn < 65535 ? Tn : 65535)), dim3(64), 0, c->stream, A))
     HIPCHK(c, hipGetLastError());
     if (timed) {
@@ -715,16 +784,31 @@ int wide_tens_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double*
     A.arg = arg; A.Tpad = Tpad; A.Tn = Tn; A.M = M; A.E = E; A.kind = p->base_kernel; A.kp0 = p->base_params[0]; A.kp1 = p->base_params[1]; A.G = G; A.W = static_cast<double*>(Wb);
     // SignaturePoly's offset (g_base: device, or NULL): every (column block, row) leaves the sum of its W entries in a slot of its own
     void* gbp = nullptr;
-    const bool gb = g_base && p->base_kernel == GPSIG_BASE_POLY;
+    const bool gb = g_base && wide_base_param_kind(p->base_kernel);
     const int64_t gbn = (Tpad / 64) * Tpad;
     if (gb) CHK(ensure(c, B_WD11, sizeof(double) * size_t(gbn + WIDE_GB_BLOCKS) + 64, &gbp));
     A.gb_part = static_cast<double*>(gbp);
+    // SignatureMix without increments: the values' adjoints (lt, Tpad, Tpad) next to W; their row sums go back with the left form's adjoint, their column
+    // sums with the right form's
+    const bool sided = mix_sides(p, MIX_TENS, increments).rows;
+    void *gval = nullptr, *radj = nullptr, *cadj = nullptr;
+    if (sided) {
+        CHK(ensure(c, B_WD12, sizeof(double) * size_t(lt) * Tpad * Tpad + 64, &gval));
+        CHK(ensure(c, B_WD14, sizeof(double) * size_t(zr) + 64, &radj));
+        CHK(ensure(c, B_WD15, sizeof(double) * size_t(zr) + 64, &cadj));
+        A.nrm = ZL + d; A.nrm_ld = DA; A.gval = static_cast<double*>(gval);
+    }
     GPSIG_WIDE_KIND(p->base_kernel, hipLaunchKernelGGL(wide_tens_bwd_kernel<KD>, dim3(unsigned(Tpad / 64), unsigned(Tpad < 65535 ? Tpad : 65535)), dim3(64), 0, c->stream, A))
     HIPCHK(c, hipGetLastError());
     // gZL_k (R, DA) = W_k ZR_k: column-major (DA x R) = ZR_k,cm (DA x R) W_k,cm (R x R);   gZR_k = W_k^T ZL_k: (DA x R) = ZL_k,cm W_k,cm^T
     CHK(dgemm_batched(c, false, false, DA, R, R, ZR, DA, R * DA, static_cast<const double*>(Wb), R, R * R, static_cast<double*>(gzl), DA, R * DA, lt));
     CHK(dgemm_batched(c, false, true, DA, R, R, ZL, DA, R * DA, static_cast<const double*>(Wb), R, R * R, static_cast<double*>(gzr), DA, R * DA, lt));
     if (gb) CHK(gbase_reduce(c, static_cast<double*>(gbp), gbn, g_base));
+    if (sided) {          // (lt "diagonal lattices" of Tpad x Tpad: one wavefront per row and per column)
+        hipLaunchKernelGGL(wide_lattice_sides_kernel, dim3(grid_for(2 * zr, 1)), dim3(64), 0, c->stream, static_cast<const double*>(gval), int64_t(lt), int64_t(1),
+                           int(Tpad), int(Tpad), 1, 0, static_cast<double*>(radj), static_cast<double*>(cadj));
+        HIPCHK(c, hipGetLastError());
+    }
     const int64_t rows_out = int64_t(lt) * Tn * Ez;             // the caller's rows
     if (rows_mode(p->base_kernel) == WIDE_ROWS_UNIT)
         hipLaunchKernelGGL(wide_unaug_unit_kernel, dim3(unsigned(rows_out < 65535 ? rows_out : 65535)), dim3(64), 0, c->stream, static_cast<const double*>(gzl), ZL,
@@ -734,7 +818,8 @@ int wide_tens_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double*
                            static_cast<const double*>(gzr), rows_out, d, lt, Tn, Tpad, 0, gZ);
     else
         hipLaunchKernelGGL(wide_unaug_tens_kernel, dim3(grid_for(rows_out * d)), dim3(256), 0, c->stream, static_cast<const double*>(gzl), ZL,
-                           static_cast<const double*>(gzr), ZR, rows_out, d, Tn, Tpad, E, gZ);
+                           static_cast<const double*>(gzr), ZR, rows_out, d, Tn, Tpad, E, gZ, static_cast<const double*>(radj), static_cast<const double*>(cadj),
+                           1.0 - p->base_params[0]);
     HIPCHK(c, hipGetLastError());
     return GPSIG_OK;
 }

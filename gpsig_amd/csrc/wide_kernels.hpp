@@ -46,6 +46,15 @@ struct WideTvsArgs {
     int32_t order;          // > 1: the higher-order chains of signature_algs.py:129-160 (at most WIDE_MAX_ORDER)
     double kp0, kp1;        // SignaturePoly: offset and degree (WIDE_KD_POLY)
     double* gb_part;        // reverse, SignaturePoly: (TB, N, M) partial sums of W over the tensors of a block -- the offset's gradient --, or NULL
+                            // (SignatureMix: the mixing's gradient, same slots)
+    // SignatureMix (WIDE_KD_MIX): kappa = psi(a) + q (hx[row] + hz[column]) with psi(a) = p0 exp(a) + q a, q = 1 - p0 and the half norms h = |v|^2 / 2.  A side's
+    // term cancels under a difference taken along the other side (the rows' under increments, the columns' under the time difference): NULL.  The half
+    // norms are read NEGATED from the augmented rows' own norm column (stride nrm_ld = d + 2 doubles).
+    const double* nrm_row;  // row (n L + tau) of ALL sequences at nrm_row[(n L + tau) * nrm_ld], or NULL
+    const double* nrm_col;  // column c at nrm_col[c * nrm_ld], or NULL
+    int64_t nrm_ld;
+    double* radj_part;      // reverse, rows' term kept: (TB * M, N L) sums of the values' adjoints over the tensors of a block and the components of a level
+    double* cadj_part;      // reverse, columns' term kept: (N, CW) sums of the values' adjoints over a sequence's rows
 };
 
 // The base kernel as a function of the argument a = -|z - x|^2 / 2, described by wavefront-uniform numbers so that the three Matern families share
@@ -63,6 +72,7 @@ struct WideKap {
     double c2, a1, a2, thr;
     double p0;              // SignaturePoly: the offset ...
     int pn;                 // ... and the whole degree, 1 .. 8
+    double q;               // SignatureMix: 1 - p0 (p0: the mixing)
 };
 
 __device__ __forceinline__ WideKap wide_kap(int kind, const double* tab, double p0 = 0.0, double p1 = 0.0) {
@@ -70,6 +80,7 @@ __device__ __forceinline__ WideKap wide_kap(int kind, const double* tab, double 
     K.tab = tab;
     K.p0 = p0;
     K.pn = int(p1);
+    K.q = 1.0 - p0;
     K.c2 = kind == BASE_MATERN32 ? 3.0 : (kind == BASE_MATERN52 ? 5.0 : 1.0);
     K.a1 = kind == BASE_MATERN12 ? 0.0 : 1.0;
     K.a2 = kind == BASE_MATERN52 ? 1.0 / 3.0 : 0.0;
@@ -86,7 +97,12 @@ __device__ __forceinline__ WideKap wide_kap(int kind, const double* tab, double 
 // the adjoint array W that the reverse kernels write (their poly instances sum what they store: per lane, per wavefront, one partial per fixed slot, and
 // wide_sum_kernel adds the slots in a fixed order -- no atomics, the same bits from every call; across chunkings of the argument array too for Kzx,
 // whose host side keeps the dgemms' shapes fixed, not for the lattices).  No table either.
-constexpr int WIDE_KD_MATERN = 0, WIDE_KD_RBF = 1, WIDE_KD_ID = 2, WIDE_KD_POLY = 3;
+// WIDE_KD_MIX: SignatureMix (kernels.py:881-892), kappa = p0 exp(-|z - x|^2 / 2) + (1 - p0) <z, x> on the distance kernels' augmented rows.  With a the
+// dgemm's number and h the half norms, <z, x> = a + hz + hx, so kappa = psi(a) + q (hz + hx), psi(a) = p0 exp(a) + q a: wide_kappa is psi, the one-sided
+// terms are added by the kernels where they survive the differences (the args' nrm_* vectors; NULL where they cancel).  d kappa / d p0 = exp(a) - a - hz - hx:
+// the reverse kernels sum it times the value's adjoint into poly's gb_part slots.  d kappa / d hz = q: where a side's term survives, the sums of the values'
+// adjoints over the other side go back through the un-augmentation (adj vectors there).
+constexpr int WIDE_KD_MATERN = 0, WIDE_KD_RBF = 1, WIDE_KD_ID = 2, WIDE_KD_POLY = 3, WIDE_KD_MIX = 4;
 
 // b^n for a wavefront-uniform whole n in 0 .. 8, by repeated squaring (seq_core.hpp: poly_pow without its way out to the library's pow)
 __device__ __forceinline__ double wide_pow_n(double b, int n) {
@@ -118,6 +134,8 @@ __device__ __forceinline__ double wide_kappa(const WideKap& K, double a) {
         return wide_pow_n(a + K.p0, K.pn);
     } else if constexpr (KD == WIDE_KD_RBF) {
         return kexp_tab(a, K.tab);
+    } else if constexpr (KD == WIDE_KD_MIX) {
+        return fma(K.p0, kexp_tab(a, K.tab), K.q * a);
     } else {
         double dist = -2.0 * a;
         dist = dist > K.thr ? dist : 0.0;
@@ -140,6 +158,10 @@ __device__ __forceinline__ void wide_kappa_grad(const WideKap& K, double a, doub
     } else if constexpr (KD == WIDE_KD_RBF) {
         k = kexp_tab(a, K.tab);
         dk = k;
+    } else if constexpr (KD == WIDE_KD_MIX) {
+        const double e = kexp_tab(a, K.tab);
+        k = fma(K.p0, e, K.q * a);
+        dk = fma(K.p0, e, K.q);
     } else {
         double dist = -2.0 * a;
         dist = dist > K.thr ? dist : 0.0;
@@ -151,6 +173,24 @@ __device__ __forceinline__ void wide_kappa_grad(const WideKap& K, double a, doub
         dk = clamped ? 0.0 : (K.c2 / rp) * (P - dP) * e;
     }
 }
+
+// SignatureMix: psi, psi' and d psi / d p0 = exp(a) - a
+__device__ __forceinline__ void wide_mix_grad(const WideKap& K, double a, double& k, double& dk, double& dp) {
+    const double e = kexp_tab(a, K.tab);
+    k = fma(K.p0, e, K.q * a);
+    dk = fma(K.p0, e, K.q);
+    dp = e - a;
+}
+
+// SignatureMix in the Kzx chain kernels: where the one-sided terms of a (lane, sequence, level) are read and where its adjoint sums go (all NULL / unused
+// for the other kinds: their instances compile to what they were)
+struct WideMixCtx {
+    const double* nrow;     // the sequence's rows: negated half norm of row tau at nrow[tau * ld] (wavefront-uniform), or NULL
+    const double* ncol;     // the lane's columns: component k, endpoint e at ncol[(k * E + e) * cs], or NULL
+    int64_t ld, cs;
+    double* radj;           // reverse: the slot of (tensor block, level, row tau) at radj[tau], or NULL
+    double* cadj;           // reverse: the slot of (sequence, component k, endpoint e, this lane's tensor) at cadj[(k * E + e) * Tpad], or NULL
+};
 
 // the raw arguments of I components at one argument row (r points at the lane's column 0 of that row): all loads first, so that they are in flight together
 template <int I, int E>
@@ -193,16 +233,34 @@ __device__ __forceinline__ void wide_ho_step(const double (&dk)[I], int order, d
 
 template <int I, int E, int KD>
 __device__ __forceinline__ void wide_chain_fwd(const double* __restrict__ col, int64_t CW, int64_t Tpad, int k0, int L, int difference, int order, const WideKap& K,
-                                               double (&u)[I]) {
+                                               double (&u)[I], const WideMixCtx& X) {
 #pragma unroll
     for (int j = 0; j < I; ++j) u[j] = 0.0;
     double prev[I], cur[I * E];
     const double* r = col;
     int steps = L;
+    // SignatureMix: the columns' half norms (an increment's: of its two points, subtracted) are lane-constant for the whole sweep, a row's is
+    // wavefront-uniform; value = psi + q (columns' + row's)
+    double hcm[I];
+    auto mixed = [&](int j, int tau, double v) -> double {
+        if constexpr (KD == WIDE_KD_MIX) {
+            const double hr = X.nrow ? -X.nrow[tau * X.ld] : 0.0;
+            return fma(K.q, hcm[j] + hr, v);
+        } else {
+            return v;
+        }
+    };
+    if constexpr (KD == WIDE_KD_MIX) {
+#pragma unroll
+        for (int j = 0; j < I; ++j) {
+            hcm[j] = 0.0;
+            if (X.ncol) hcm[j] = E == 2 ? X.ncol[((k0 + j) * 2) * X.cs] - X.ncol[((k0 + j) * 2 + 1) * X.cs] : -X.ncol[(k0 + j) * X.cs];
+        }
+    }
     wide_load_row<I, E>(r, k0, Tpad, cur);
     if (difference) {                                                              // signature_algs.py:114
 #pragma unroll
-        for (int j = 0; j < I; ++j) prev[j] = wide_val<I, E, KD>(cur, j, K);
+        for (int j = 0; j < I; ++j) prev[j] = mixed(j, 0, wide_val<I, E, KD>(cur, j, K));
         r += CW;
         steps = L - 1;
         if (steps > 0) wide_load_row<I, E>(r, k0, Tpad, cur);
@@ -214,7 +272,7 @@ __device__ __forceinline__ void wide_chain_fwd(const double* __restrict__ col, i
         double dk[I];
 #pragma unroll
         for (int j = 0; j < I; ++j) {
-            const double v = wide_val<I, E, KD>(cur, j, K);
+            const double v = mixed(j, difference ? s + 1 : s, wide_val<I, E, KD>(cur, j, K));
             dk[j] = difference ? v - prev[j] : v;
             prev[j] = v;
         }
@@ -231,12 +289,12 @@ __device__ __forceinline__ void wide_chain_fwd(const double* __restrict__ col, i
 }
 
 template <int E, int KD>
-__device__ __forceinline__ void wide_level_fwd(int i, const double* col, const WideTvsArgs& A, const WideKap& K, double* u /* [i] */) {
+__device__ __forceinline__ void wide_level_fwd(int i, const double* col, const WideTvsArgs& A, const WideKap& K, double* u /* [i] */, const WideMixCtx& X) {
     const int k0 = i * (i - 1) / 2;
 #define GPSIG_WIDE_CASE(I_)                                                                          \
     case I_: {                                                                                       \
         double v[I_];                                                                                \
-        wide_chain_fwd<I_, E, KD>(col, A.CW, A.Tpad, k0, A.L, A.difference, A.order, K, v);                  \
+        wide_chain_fwd<I_, E, KD>(col, A.CW, A.Tpad, k0, A.L, A.difference, A.order, K, v, X);               \
         _Pragma("unroll") for (int j = 0; j < I_; ++j) u[j] = v[j];                                 \
     } break;
     switch (i) {
@@ -245,6 +303,22 @@ __device__ __forceinline__ void wide_level_fwd(int i, const double* col, const W
         default: break;
     }
 #undef GPSIG_WIDE_CASE
+}
+
+// SignatureMix: the one-sided terms of (sequence n, tensor t) (the reverse kernel adds its slots)
+template <int KD>
+__device__ __forceinline__ WideMixCtx wide_mix_ctx(const WideTvsArgs& A, int64_t n, int64_t t) {
+    WideMixCtx X;
+    X.nrow = X.ncol = nullptr;
+    X.radj = X.cadj = nullptr;
+    X.ld = X.cs = 0;
+    if constexpr (KD == WIDE_KD_MIX) {
+        X.ld = A.nrm_ld;
+        X.cs = A.Tpad * A.nrm_ld;
+        if (A.nrm_row) X.nrow = A.nrm_row + n * int64_t(A.L) * A.nrm_ld;
+        if (A.nrm_col) X.ncol = A.nrm_col + t * A.nrm_ld;
+    }
+    return X;
 }
 
 // grid: (Tpad / 64, sequences of the chunk (grid-stride), levels); block: one wavefront, lane = tensor.  A launch of few sequences is bound by the
@@ -261,7 +335,7 @@ __global__ void __launch_bounds__(64) wide_tvs_fwd_kernel(const WideTvsArgs A) {
         const int64_t n = A.n0 + nl;
         const double* col = A.arg + nl * int64_t(A.L) * A.CW + t;
         double u[WIDE_MAX_LEVELS];
-        wide_level_fwd<E, KD>(i, col, A, K, u);
+        wide_level_fwd<E, KD>(i, col, A, K, u, wide_mix_ctx<KD>(A, n, t));
         for (int j = 0; j < i; ++j) A.aux[(n * lt + k0 + j) * A.Tpad + t] = u[j];
     }
 }
@@ -285,6 +359,12 @@ __global__ void wide_tvs_epilogue_kernel(const WideTvsArgs A) {
     }
 }
 
+__device__ __forceinline__ double wide_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 // ---- reverse pass ------------------------------------------------------------------------------------------------------------------
 // With u_j the chain values BEFORE a step and W_j = dL/du_j after it:  dL/dm_j = u_{j-1} W_j,  W_{j-1} += m_j W_j,  and the chain is undone
 // by u_j <- u_j - m_j u_{j-1} (tvs_grad_tile_kernel.hpp, grad_ho_kernels.hpp: chain_levels_grad_kernel).  m_j[tau] = v_j[tau + 1] - v_j[tau]
@@ -292,11 +372,42 @@ __global__ void wide_tvs_epilogue_kernel(const WideTvsArgs A) {
 // argument.  u: the level's totals (destroyed).  c: the level's upstream gradient.  Columns of tensors beyond Tn get zeros (valid = false).
 template <int I, int E, int KD>
 __device__ __forceinline__ void wide_chain_bwd(const double* __restrict__ col, double* __restrict__ wcol, int64_t CW, int64_t Tpad, int k0, int L,
-                                               int difference, int order, const WideKap& K, double (&u)[I], double c, bool valid, double& wsum) {
+                                               int difference, int order, const WideKap& K, double (&u)[I], double c, bool valid, double& wsum,
+                                               const WideMixCtx& X) {
     double wv[I];
 #pragma unroll
     for (int j = 0; j < I; ++j) wv[j] = 0.0;
-    auto eval = [&](const double (&raw)[I * E], double (&v)[I], double (&d)[I][E]) {
+    // SignatureMix: hc = the half norms of the lane's columns where their term survives (else 0), csum = the lane's sums of the values' adjoints over the
+    // rows, per component.  dp (the other kinds leave it alone) = d value / d p0 of an entry, with the entry's sign in the value: exp(a) - a - hz - hx
+    double hc[I][E], csum[I];
+    if constexpr (KD == WIDE_KD_MIX) {
+#pragma unroll
+        for (int j = 0; j < I; ++j) {
+            csum[j] = 0.0;
+#pragma unroll
+            for (int e = 0; e < E; ++e) hc[j][e] = X.ncol ? -X.ncol[((k0 + j) * E + e) * X.cs] : 0.0;
+        }
+    }
+    auto eval = [&](const double (&raw)[I * E], int tau, double (&v)[I], double (&d)[I][E], double (&dp)[I][E]) {
+        if constexpr (KD == WIDE_KD_MIX) {
+            const double hr = X.nrow ? -X.nrow[tau * X.ld] : 0.0;          // (wavefront-uniform; NULL with increments, where it cancels between the endpoints)
+#pragma unroll
+            for (int j = 0; j < I; ++j) {
+                if constexpr (E == 2) {
+                    double k1, d1, p1, k0v, d0, p0v;
+                    wide_mix_grad(K, raw[2 * j + 1], k1, d1, p1);
+                    wide_mix_grad(K, raw[2 * j], k0v, d0, p0v);
+                    v[j] = fma(K.q, hc[j][1] - hc[j][0], k1 - k0v); d[j][1] = d1; d[j][0] = -d0;
+                    dp[j][1] = p1 - hc[j][1]; dp[j][0] = hc[j][0] - p0v;
+                } else {
+                    double kk, pp;
+                    wide_mix_grad(K, raw[j], kk, d[j][0], pp);
+                    v[j] = fma(K.q, hc[j][0] + hr, kk);
+                    dp[j][0] = pp - hc[j][0] - hr;
+                }
+            }
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < I; ++j) {
             if constexpr (E == 2) {
@@ -309,7 +420,7 @@ __device__ __forceinline__ void wide_chain_bwd(const double* __restrict__ col, d
             }
         }
     };
-    auto store = [&](double* __restrict__ wr, const double (&g)[I], const double (&d)[I][E]) {
+    auto store = [&](double* __restrict__ wr, int tau, const double (&g)[I], const double (&d)[I][E], const double (&dp)[I][E]) {
 #pragma unroll
         for (int j = 0; j < I; ++j)
 #pragma unroll
@@ -317,7 +428,23 @@ __device__ __forceinline__ void wide_chain_bwd(const double* __restrict__ col, d
                 const double w = valid ? g[j] * d[j][e] : 0.0;
                 wr[((k0 + j) * E + e) * Tpad] = w;
                 if constexpr (KD == WIDE_KD_POLY) wsum += w;               // (a padded lane stores and adds exactly zero)
+                if constexpr (KD == WIDE_KD_MIX) wsum += valid ? g[j] * dp[j][e] : 0.0;
             }
+        if constexpr (KD == WIDE_KD_MIX) {
+            // g[j] IS the adjoint of the value of (row tau, component j): its sum over the level's components and the block's tensors to the row's slot,
+            // its sum over the rows stays in the lane
+            if (X.radj) {
+                double sr = 0.0;
+#pragma unroll
+                for (int j = 0; j < I; ++j) sr += valid ? g[j] : 0.0;
+                sr = wide_wave_sum(sr);
+                if (threadIdx.x == 0) X.radj[tau] = sr;
+            }
+            if (X.cadj) {
+#pragma unroll
+                for (int j = 0; j < I; ++j) csum[j] += valid ? g[j] : 0.0;
+            }
+        }
     };
     // higher-order chains: the step's repeat-count vectors are rebuilt from the totals BEFORE the step (U_j - sum_l r_j[l], ascending in j), then the
     // adjoints run down: dL/dr_j[l] = W_j + m_{j+1} / (l+2) dL/dr_{j+1}[l+1],  dL/dm_j = dL/dr_j[0] U_{j-1} + sum_{l>=1} dL/dr_j[l] r_{j-1}[l-1] / (l+1),
@@ -387,28 +514,31 @@ __device__ __forceinline__ void wide_chain_bwd(const double* __restrict__ col, d
     double raw[I * E], rnx[I * E];
     wide_load_row<I, E>(r, k0, Tpad, raw);
     if (difference) {
-        double nv[I], nd[I][E], gprev[I];
-        eval(raw, nv, nd);
+        double nv[I], nd[I][E], ndp[I][E], gprev[I];
+        eval(raw, L - 1, nv, nd, ndp);
 #pragma unroll
         for (int j = 0; j < I; ++j) gprev[j] = 0.0;
         if (L >= 2) wide_load_row<I, E>(r - CW, k0, Tpad, raw);
         for (int s = L - 2; s >= 0; --s) {
             r -= CW;
             if (s >= 1) wide_load_row<I, E>(r - CW, k0, Tpad, rnx);
-            double cv[I], cd[I][E], dk[I], g[I], gv[I];
-            eval(raw, cv, cd);
+            double cv[I], cd[I][E], cdp[I][E], dk[I], g[I], gv[I];
+            eval(raw, s, cv, cd, cdp);
 #pragma unroll
             for (int j = 0; j < I; ++j) dk[j] = nv[j] - cv[j];
             undo(dk, g);
 #pragma unroll
             for (int j = 0; j < I; ++j) gv[j] = g[j] - gprev[j];
-            store(wr, gv, nd);                                                         // row s + 1 is final
+            store(wr, s + 1, gv, nd, ndp);                                             // row s + 1 is final
             wr -= CW;
 #pragma unroll
             for (int j = 0; j < I; ++j) {
                 gprev[j] = g[j]; nv[j] = cv[j];
 #pragma unroll
-                for (int e = 0; e < E; ++e) nd[j][e] = cd[j][e];
+                for (int e = 0; e < E; ++e) {
+                    nd[j][e] = cd[j][e];
+                    if constexpr (KD == WIDE_KD_MIX) ndp[j][e] = cdp[j][e];
+                }
             }
 #pragma unroll
             for (int q = 0; q < I * E; ++q) raw[q] = rnx[q];
@@ -416,24 +546,26 @@ __device__ __forceinline__ void wide_chain_bwd(const double* __restrict__ col, d
         double gv[I];
 #pragma unroll
         for (int j = 0; j < I; ++j) gv[j] = -gprev[j];
-        store(wr, gv, nd);                                                             // row 0
+        store(wr, 0, gv, nd, ndp);                                                     // row 0
     } else {
         for (int s = L - 1; s >= 0; --s, r -= CW, wr -= CW) {
             if (s >= 1) wide_load_row<I, E>(r - CW, k0, Tpad, rnx);
-            double cv[I], cd[I][E], g[I];
-            eval(raw, cv, cd);
+            double cv[I], cd[I][E], cdp[I][E], g[I];
+            eval(raw, s, cv, cd, cdp);
             undo(cv, g);
-            store(wr, g, cd);
+            store(wr, s, g, cd, cdp);
 #pragma unroll
             for (int q = 0; q < I * E; ++q) raw[q] = rnx[q];
         }
     }
-}
-
-__device__ __forceinline__ double wide_wave_sum(double v) {
+    if constexpr (KD == WIDE_KD_MIX) {
+        if (X.cadj) {          // (an increment's value is its second point's minus its first's)
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
+            for (int j = 0; j < I; ++j)
+#pragma unroll
+                for (int e = 0; e < E; ++e) X.cadj[((k0 + j) * E + e) * Tpad] = (E == 2 && e == 0) ? -csum[j] : csum[j];
+        }
+    }
 }
 
 template <int E, int KD>
@@ -449,6 +581,11 @@ __global__ void __launch_bounds__(64) wide_tvs_bwd_kernel(const WideTvsArgs A) {
         const double* col = A.arg + nl * int64_t(A.L) * A.CW + t;
         double* wcol = A.W + nl * int64_t(A.L) * A.CW + t;
         const double gsum = (A.weighted && valid) ? A.G[t * A.N + n] : 0.0;
+        WideMixCtx X = wide_mix_ctx<KD>(A, n, t);
+        if constexpr (KD == WIDE_KD_MIX) {          // the slots of (tensor block, level, GLOBAL row) and of (GLOBAL sequence, column): the same partials in every chunking
+            if (A.radj_part) X.radj = A.radj_part + (int64_t(blockIdx.x) * M + (i - 1)) * (A.N * int64_t(A.L)) + n * int64_t(A.L);
+            if (A.cadj_part) X.cadj = A.cadj_part + n * A.CW + t;
+        }
         if (A.gfac_part && i == 1) {                                                   // level 0 == 1: dL/dfac[n][0] = sum_t G[t][n]
             const double s = wide_wave_sum(gsum);
             if (threadIdx.x == 0) A.gfac_part[(int64_t(blockIdx.x) * A.N + n) * (M + 1)] = s;
@@ -460,7 +597,7 @@ __global__ void __launch_bounds__(64) wide_tvs_bwd_kernel(const WideTvsArgs A) {
         if (A.aux) {
             for (int j = 0; j < i; ++j) u[j] = A.aux[(n * lt + k0 + j) * A.Tpad + t];
         } else {
-            wide_level_fwd<E, KD>(i, col, A, K, u);
+            wide_level_fwd<E, KD>(i, col, A, K, u, X);
         }
         if (A.gfac_part) {
             double ui = 0.0;
@@ -475,7 +612,7 @@ __global__ void __launch_bounds__(64) wide_tvs_bwd_kernel(const WideTvsArgs A) {
     case I_: {                                                                                               \
         double v[I_];                                                                                        \
         _Pragma("unroll") for (int j = 0; j < I_; ++j) v[j] = u[j];                                         \
-        wide_chain_bwd<I_, E, KD>(col, wcol, A.CW, A.Tpad, k0, A.L, A.difference, A.order, K, v, c, valid, wsum);    \
+        wide_chain_bwd<I_, E, KD>(col, wcol, A.CW, A.Tpad, k0, A.L, A.difference, A.order, K, v, c, valid, wsum, X); \
     } break;
         switch (i) {
             GPSIG_WIDE_CASE(1) GPSIG_WIDE_CASE(2) GPSIG_WIDE_CASE(3) GPSIG_WIDE_CASE(4)
@@ -483,7 +620,7 @@ __global__ void __launch_bounds__(64) wide_tvs_bwd_kernel(const WideTvsArgs A) {
             default: break;
         }
 #undef GPSIG_WIDE_CASE
-        if constexpr (KD == WIDE_KD_POLY) {
+        if constexpr (KD == WIDE_KD_POLY || KD == WIDE_KD_MIX) {
             if (A.gb_part) {            // the slot of (tensor block, GLOBAL sequence, level): the same partial however the sequences are chunked
                 const double s = wide_wave_sum(wsum);
                 if (threadIdx.x == 0) A.gb_part[(int64_t(blockIdx.x) * A.N + n) * M + (i - 1)] = s;
@@ -581,8 +718,10 @@ __global__ void __launch_bounds__(64) wide_aug_rows_kernel(const double* __restr
 
 // The chain rule through the augmentation: g[f] = ga[f] - ga[norm column] * v[f]   (d(-|v|^2/2)/dv = -v; the constant column carries nothing).
 // Tensor rows go back to the caller's (lt, T, E, d) order; sequences as they come.  One thread per output element.
+// adj (SignatureMix where this side's term q |v|^2 / 2 survives; else NULL, and the arithmetic is what it was): the sums of the values' adjoints over the
+// other side, per augmented row -- the norm column's adjoint becomes ga[norm column] - q adj[row].
 __global__ void wide_unaug_rows_kernel(const double* __restrict__ ga, const double* __restrict__ va, int64_t rows_out, int d, int right, int lt, int64_t Tn,
-                                       int64_t Tpad, int E, double* __restrict__ g) {
+                                       int64_t Tpad, int E, double* __restrict__ g, const double* __restrict__ adj = nullptr, double q = 0.0) {
     const int DA = d + 2, nc = right ? d + 1 : d;
     const int64_t total = rows_out * d;
     for (int64_t idx = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; idx < total; idx += int64_t(gridDim.x) * blockDim.x) {
@@ -595,7 +734,9 @@ __global__ void wide_unaug_rows_kernel(const double* __restrict__ ga, const doub
             const int k = int(ro / (int64_t(E) * Tn));
             r = (int64_t(k) * E + e) * Tpad + t;
         }
-        g[idx] = fma(-ga[r * DA + nc], va[r * DA + f], ga[r * DA + f]);
+        double gn = ga[r * DA + nc];
+        if (adj) gn = fma(-q, adj[r], gn);
+        g[idx] = fma(-gn, va[r * DA + f], ga[r * DA + f]);
     }
 }
 
@@ -680,7 +821,19 @@ struct WideLatArgs {
     double kp0, kp1;            // SignaturePoly: offset and degree (WIDE_KD_POLY; p0 above is a lattice index)
     double* gb_part;            // reverse, SignaturePoly: gb_slices partial sums of W per lattice, lattices as G's pair axis (pg at (pg / N2) * g_i + (pg % N2) * g_j), or NULL
     int32_t gb_slices;          // ... (L1 L2 + WIDE_GB_SLICE - 1) / WIDE_GB_SLICE
+    // SignatureMix without differences (with them both one-sided terms cancel: NULL): the NEGATED half norms of the launch's left / right sequences' points, from the
+    // augmented rows' own norm column (stride nrm_ld doubles); lattice pg = (i, j) reads rows i L1 + r and columns j L2 + c (nrm_same, the diagonal: i L2 + c)
+    const double* nrm_row;
+    const double* nrm_col;
+    int64_t nrm_ld;
+    int32_t nrm_same;
 };
+
+// SignatureMix: where lattice pg of a launch finds its rows' and its columns' half norms
+__device__ __forceinline__ const double* wide_lat_nrow(const WideLatArgs& A, int64_t pg) { return A.nrm_row + (pg / A.N2) * A.L1 * A.nrm_ld; }
+__device__ __forceinline__ const double* wide_lat_ncol(const WideLatArgs& A, int64_t pg) {
+    return A.nrm_col + (A.nrm_same ? pg / A.N2 : pg % A.N2) * A.L2 * A.nrm_ld;
+}
 constexpr int WIDE_GB_SLICE = 1024;       // cells of a lattice per wavefront of the polynomial adjoint kernel (16 per lane)
 
 // argument rows (and, in the backward sweep, stored prefix rows) in flight ahead of a step: a step of few columns is shorter than a memory access
@@ -693,11 +846,31 @@ struct WideLatDm {
     WideKap K;
     int64_t ld;
     const double* lat;
+    // SignatureMix without differences (mix_terms sets them; else unused): the row's term q hx[r] rides in raw[C], the slot that only differences use; the
+    // lane's columns' terms q hy[c] are kept
+    const double* nrow;
+    int64_t nld;
+    double cn[C];
 
+    __device__ __forceinline__ void mix_terms(const WideLatArgs& A, int64_t pg) {
+        nrow = nullptr;
+        nld = A.nrm_ld;
+        if constexpr (KD == WIDE_KD_MIX) {
+            if (!diff && A.nrm_row) {
+                nrow = wide_lat_nrow(A, pg);
+                const double* nc = wide_lat_ncol(A, pg);
+#pragma unroll
+                for (int c = 0; c < C; ++c) cn[c] = b0 + c < L2 ? -K.q * nc[(b0 + c) * nld] : 0.0;
+            }
+        }
+    }
     __device__ __forceinline__ void load(int r, bool ok, double (&raw)[C + 1]) const {
         const double* p = lat + int64_t(r) * ld + b0;
 #pragma unroll
         for (int c = 0; c <= C; ++c) raw[c] = (ok && b0 + c < L2 && (c < C || diff)) ? p[c] : 0.0;
+        if constexpr (KD == WIDE_KD_MIX) {
+            if (nrow) raw[C] = ok ? -K.q * nrow[r * nld] : 0.0;
+        }
     }
     // kappa differences along the row (diff) or kappa itself (no differences: signature_algs.py:18-19 with difference=False)
     __device__ __forceinline__ void map(const double (&raw)[C + 1], double (&out)[C]) const {
@@ -706,6 +879,12 @@ struct WideLatDm {
         for (int c = 0; c <= C; ++c) k[c] = (c < C || diff) ? wide_kappa<KD>(K, raw[c]) : 0.0;
 #pragma unroll
         for (int c = 0; c < C; ++c) out[c] = diff ? k[c + 1] - k[c] : k[c];
+        if constexpr (KD == WIDE_KD_MIX) {
+            if (nrow) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) out[c] += raw[C] + cn[c];
+            }
+        }
     }
     __device__ __forceinline__ void prime(const double (&raw)[C + 1]) { map(raw, rd); }
     // one lattice row from the raw arguments of its new point row (forward: a + 1, backward: a; no differences: a)
@@ -763,6 +942,7 @@ __global__ void __launch_bounds__(64 * NW) wide_lattice_fwd_kernel(const WideLat
         dmg.lat = A.arg + (pg / A.N2) * A.si + (pg % A.N2) * A.sj;
         dmg.ld = A.ld; dmg.b0 = C * lam; dmg.L2 = A.L2; dmg.K = wide_kap(A.kind, ktab, A.kp0, A.kp1); dmg.diff = dr;
         { const int nv = R2 - C * lam; dmg.nvalid = nv < 0 ? 0 : (nv > C ? C : nv); }
+        dmg.mix_terms(A, pg);
         WaveFwd<C, LQ> fw;
         fw.reset();
         // the argument rows of the coming PF steps are in flight while a step computes (a launch of a few lattices is one wavefront per
@@ -847,6 +1027,7 @@ __global__ void __launch_bounds__(64 * NW) wide_lattice_bwd_kernel(const WideLat
         dmg.lat = A.arg + (pg / A.N2) * A.si + (pg % A.N2) * A.sj;
         dmg.ld = A.ld; dmg.b0 = C * lam; dmg.L2 = A.L2; dmg.K = wide_kap(A.kind, ktab, A.kp0, A.kp1); dmg.diff = dr;
         { const int nv = R2 - C * lam; dmg.nvalid = nv < 0 ? 0 : (nv > C ? C : nv); }
+        dmg.mix_terms(A, pg);
         double clev[LQ + 2];
 #pragma unroll
         for (int p = 0; p < LQ + 2; ++p) clev[p] = (p >= 1 && p <= M) ? A.G[int64_t(p) * A.Ptot + (pg / A.N2) * A.g_i + (pg % A.N2) * A.g_j] : 0.0;
@@ -1024,6 +1205,69 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) wi
     }
 }
 
+// The same for SignatureMix, with the slice's sum of Gam d kappa / d p0 (the mixing's gradient): d kappa / d p0 = exp(a) - a, less the two half norms where
+// the one-sided terms survive (no differences).  Slices, slots and order of summation as above.
+__global__ void __launch_bounds__(64) wide_lattice_adjoint_mix_kernel(const WideLatArgs A, double* __restrict__ W) {
+    __shared__ double etab[EXP_TAB_N];
+    const WideKap K = wide_kap(A.kind, wide_tab<WIDE_KD_MIX>(etab, threadIdx.x, 64), A.kp0, A.kp1);
+    const int dr = A.difference ? 1 : 0, R1 = A.L1 - dr, R2 = A.L2 - dr;
+    const int64_t cells = int64_t(A.L1) * A.L2;
+    const int64_t S = A.gb_slices;
+    const bool sided = !dr && A.nrm_row;
+    for (int64_t un = blockIdx.x; un < A.P * S; un += gridDim.x) {
+        const int64_t pp = un / S, sl = un - pp * S, pg = A.p0 + pp;
+        const double* lm = A.lam + pp * int64_t(R1) * R2;
+        auto at = [&](int a, int b) -> double { return (a >= 0 && a < R1 && b >= 0 && b < R2) ? lm[int64_t(a) * R2 + b] : 0.0; };
+        const int64_t base = (pg / A.N2) * A.si + (pg % A.N2) * A.sj;
+        const int64_t end = (sl + 1) * WIDE_GB_SLICE < cells ? (sl + 1) * WIDE_GB_SLICE : cells;
+        const double *nr = sided ? wide_lat_nrow(A, pg) : nullptr, *nc = sided ? wide_lat_ncol(A, pg) : nullptr;
+        double psum = 0.0;
+        for (int64_t cell = sl * WIDE_GB_SLICE + threadIdx.x; cell < end; cell += 64) {
+            const int r = int(cell / A.L2), c = int(cell % A.L2);
+            const double gam = dr ? at(r - 1, c - 1) - at(r - 1, c) - at(r, c - 1) + at(r, c) : at(r, c);
+            const int64_t off = base + int64_t(r) * A.ld + c;
+            double k, dk, dp;
+            wide_mix_grad(K, A.arg[off], k, dk, dp);
+            if (sided) dp += nr[r * A.nrm_ld] + nc[c * A.nrm_ld];
+            W[off] = gam * dk;
+            psum = fma(gam, dp, psum);
+        }
+        psum = wide_wave_sum(psum);
+        if (threadIdx.x == 0 && A.gb_part) A.gb_part[((pg / A.N2) * A.g_i + (pg % A.N2) * A.g_j) * S + sl] = psum;
+    }
+}
+
+// SignatureMix without differences: Gam = Lam, and the sums of the values' adjoints over the other side are the row sums and the column sums of the
+// launch's Lam lattices.  One wavefront per unit, in an order fixed by the launch's shape: unit u < NI L1 is row r of left sequence il (sums over its lattices'
+// columns), the others column c of right sequence jl (over its lattices' rows).  NI x NJ lattices, pair il NJ + jl (the diagonal: NJ = 1 and jl = il).
+// radj (NI L1) is written; cadj (NJ L2; the diagonal: NI L2) is written or, acc, added to (the chunks of left sequences one after the other).
+__global__ void __launch_bounds__(64) wide_lattice_sides_kernel(const double* __restrict__ lam, int64_t NI, int64_t NJ, int L1, int L2, int diag, int acc,
+                                                                 double* __restrict__ radj, double* __restrict__ cadj) {
+    const int64_t rows = NI * L1, cols = (diag ? NI : NJ) * L2, cells = int64_t(L1) * L2;
+    for (int64_t un = blockIdx.x; un < rows + cols; un += gridDim.x) {
+        double s = 0.0;
+        if (un < rows) {
+            const int64_t il = un / L1;
+            const int r = int(un - il * L1);
+            for (int64_t jl = 0; jl < (diag ? 1 : NJ); ++jl) {
+                const double* lm = lam + (diag ? il : il * NJ + jl) * cells + int64_t(r) * L2;
+                for (int c = threadIdx.x; c < L2; c += 64) s += lm[c];
+            }
+            s = wide_wave_sum(s);
+            if (threadIdx.x == 0) radj[un] = s;
+        } else {
+            const int64_t uc = un - rows, jl = uc / L2;
+            const int c = int(uc - jl * L2);
+            for (int64_t il = diag ? jl : 0; il < (diag ? jl + 1 : NI); ++il) {
+                const double* lm = lam + (diag ? il : il * NJ + jl) * cells + c;
+                for (int r = threadIdx.x; r < L1; r += 64) s += lm[int64_t(r) * L2];
+            }
+            s = wide_wave_sum(s);
+            if (threadIdx.x == 0) cadj[uc] = acc ? cadj[uc] + s : s;
+        }
+    }
+}
+
 // The symmetric Gram's upstream gradient folded onto the pairs i <= j (the levels are symmetric functions of the two sequences):
 // Gs[m][i][j] = G[m][i][j] + G[m][j][i] (j > i),  G[m][i][i] (j == i),  0 (j < i).
 __global__ void wide_sym_upstream_kernel(const double* __restrict__ G, int64_t N, int M1, double* __restrict__ Gs) {
@@ -1048,20 +1292,31 @@ __global__ void wide_lattice_dm_kernel(const WideLatArgs A, double* __restrict__
         const double* base = A.arg + (pg / A.N2) * A.si + (pg % A.N2) * A.sj + int64_t(a) * A.ld + b;
         double v = wide_kappa<KD>(K, base[0]);
         if (dr) v = (wide_kappa<KD>(K, base[A.ld + 1]) - wide_kappa<KD>(K, base[A.ld])) - (wide_kappa<KD>(K, base[1]) - v);
+        if constexpr (KD == WIDE_KD_MIX) {
+            if (!dr && A.nrm_row) v -= K.q * (wide_lat_nrow(A, pg)[a * A.nrm_ld] + wide_lat_ncol(A, pg)[b * A.nrm_ld]);
+        }
         dM[idx] = v;
     }
 }
 
 // g[r][f] = left-form chain rule of (gl, vl) [+ right-form chain rule of (gr, vr) where given: one array on both sides of the lattices]
+// (adjl / adjr, q: as wide_unaug_rows_kernel)
 __global__ void wide_unaug_pair_kernel(const double* __restrict__ gl, const double* __restrict__ vl, const double* __restrict__ gr, const double* __restrict__ vr,
-                                       int64_t rows, int d, double* __restrict__ g) {
+                                       int64_t rows, int d, double* __restrict__ g, const double* __restrict__ adjl = nullptr,
+                                       const double* __restrict__ adjr = nullptr, double q = 0.0) {
     const int DA = d + 2;
     const int64_t total = rows * d;
     for (int64_t idx = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; idx < total; idx += int64_t(gridDim.x) * blockDim.x) {
         const int f = int(idx % d);
         const int64_t r = idx / d;
-        double v = fma(-gl[r * DA + d], vl[r * DA + f], gl[r * DA + f]);
-        if (gr) v += fma(-gr[r * DA + d + 1], vr[r * DA + f], gr[r * DA + f]);
+        double nl = gl[r * DA + d];
+        if (adjl) nl = fma(-q, adjl[r], nl);
+        double v = fma(-nl, vl[r * DA + f], gl[r * DA + f]);
+        if (gr) {
+            double nr = gr[r * DA + d + 1];
+            if (adjr) nr = fma(-q, adjr[r], nr);
+            v += fma(-nr, vr[r * DA + f], gr[r * DA + f]);
+        }
         g[idx] = v;
     }
 }
@@ -1079,7 +1334,12 @@ struct WideTensArgs {
     const double* G;        // reverse: (M+1, T, T)
     double* W;              // reverse: adjoint of arg, same layout
     double kp0, kp1;        // SignaturePoly: offset and degree (WIDE_KD_POLY)
-    double* gb_part;        // reverse, SignaturePoly: (Tpad / 64, Tpad) partial sums of W, one per (column block, row t), or NULL
+    double* gb_part;        // reverse, SignaturePoly: (Tpad / 64, Tpad) partial sums of W, one per (column block, row t), or NULL (SignatureMix: the mixing's gradient)
+    // SignatureMix without increments (E == 1; with them the four-term difference cancels both one-sided terms: NULL): the NEGATED half norm of tensor t of
+    // component k at nrm[(k * Tpad + t) * nrm_ld] (the left form's own norm column); value = psi(a) + q (hz[t] + hz[t'])
+    const double* nrm;
+    int64_t nrm_ld;
+    double* gval;           // reverse, nrm given: (lt, Tpad, Tpad) the values' adjoints (zeros at padded tensors); wide_lattice_sides_kernel takes their row and column sums
 };
 
 // value of component k at (t, t'): kappa, or the four-term difference of its two points on both sides (kernels.py:276-277)
@@ -1089,6 +1349,16 @@ __device__ __forceinline__ double wide_tens_val(const double* __restrict__ blk, 
         return wide_kappa<KD>(K, blk[(Tpad + t) * R + Tpad + tp]) + wide_kappa<KD>(K, blk[t * R + tp]) - wide_kappa<KD>(K, blk[(Tpad + t) * R + tp]) -
                wide_kappa<KD>(K, blk[t * R + Tpad + tp]);
     return wide_kappa<KD>(K, blk[t * R + tp]);
+}
+
+// ... of component k, with SignatureMix's one-sided terms where they survive
+template <int KD>
+__device__ __forceinline__ double wide_tens_val_k(const WideTensArgs& A, int k, int64_t R, const WideKap& K, int64_t t, int64_t tp) {
+    double v = wide_tens_val<KD>(A.arg + int64_t(k) * R * R, R, A.Tpad, A.E, K, t, tp);
+    if constexpr (KD == WIDE_KD_MIX) {
+        if (A.nrm) v -= K.q * (A.nrm[(k * A.Tpad + t) * A.nrm_ld] + A.nrm[(k * A.Tpad + tp) * A.nrm_ld]);
+    }
+    return v;
 }
 
 template <int KD>
@@ -1103,7 +1373,7 @@ __global__ void __launch_bounds__(64) wide_tens_fwd_kernel(const WideTensArgs A)
         int k = 0;
         for (int i = 1; i <= A.M; ++i) {
             double prod = 1.0;
-            for (int j = 0; j < i; ++j, ++k) prod *= wide_tens_val<KD>(A.arg + int64_t(k) * R * R, R, A.Tpad, A.E, K, t, tp);      // :91-97
+            for (int j = 0; j < i; ++j, ++k) prod *= wide_tens_val_k<KD>(A, k, R, K, t, tp);      // :91-97
             const double f = A.w ? A.w[i] : 1.0;
             if (A.sum_levels) acc = fma(prod, f, acc);
             else A.out[(int64_t(i) * A.Tn + t) * A.Tn + tp] = prod * f;
@@ -1128,7 +1398,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KD == W
             const double c = valid ? A.G[(int64_t(i) * A.Tn + t) * A.Tn + tp] : 0.0;
             double v[WIDE_MAX_LEVELS];
 #pragma unroll
-            for (int j = 0; j < WIDE_MAX_LEVELS; ++j) v[j] = j < i ? wide_tens_val<KD>(A.arg + int64_t(k0 + j) * R * R, R, A.Tpad, A.E, K, t, tp) : 1.0;
+            for (int j = 0; j < WIDE_MAX_LEVELS; ++j) {
+                if constexpr (KD == WIDE_KD_MIX) v[j] = j < i ? wide_tens_val_k<KD>(A, k0 + j, R, K, t, tp) : 1.0;
+                else v[j] = j < i ? wide_tens_val<KD>(A.arg + int64_t(k0 + j) * R * R, R, A.Tpad, A.E, K, t, tp) : 1.0;
+            }
 #pragma unroll
             for (int j = 0; j < WIDE_MAX_LEVELS; ++j) {
                 if (j >= i) continue;
@@ -1138,6 +1411,27 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KD == W
                     if (q != j && q < i) g *= v[q];
                 const double* blk = A.arg + int64_t(k0 + j) * R * R;
                 double* wb = A.W + int64_t(k0 + j) * R * R;
+                if constexpr (KD == WIDE_KD_MIX) {          // W = g psi', the mixing's partial g d value / d p0, and g itself where the one-sided terms survive
+                    double kk, dk, dp;
+                    if (A.E == 2) {
+                        double ps = 0.0;          // (the four entries: +, +, -, -)
+                        wide_mix_grad(K, blk[(A.Tpad + t) * R + A.Tpad + tp], kk, dk, dp); wb[(A.Tpad + t) * R + A.Tpad + tp] = g * dk; ps += dp;
+                        wide_mix_grad(K, blk[t * R + tp], kk, dk, dp);                     wb[t * R + tp] = g * dk; ps += dp;
+                        wide_mix_grad(K, blk[(A.Tpad + t) * R + tp], kk, dk, dp);          wb[(A.Tpad + t) * R + tp] = -g * dk; ps -= dp;
+                        wide_mix_grad(K, blk[t * R + A.Tpad + tp], kk, dk, dp);            wb[t * R + A.Tpad + tp] = -g * dk; ps -= dp;
+                        wsum += valid ? g * ps : 0.0;
+                    } else {
+                        wide_mix_grad(K, blk[t * R + tp], kk, dk, dp);
+                        wb[t * R + tp] = g * dk;
+                        const double gv = valid ? g : 0.0;
+                        if (A.nrm) {
+                            dp += A.nrm[((k0 + j) * A.Tpad + t) * A.nrm_ld] + A.nrm[((k0 + j) * A.Tpad + tp) * A.nrm_ld];
+                            A.gval[((k0 + j) * A.Tpad + t) * A.Tpad + tp] = gv;
+                        }
+                        wsum += gv * dp;
+                    }
+                    continue;
+                }
                 double kk, dk;
                 if (A.E == 2) {
                     double ws = 0.0;          // (the four entries' sum: +, +, -, -)
@@ -1158,7 +1452,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KD == W
             }
             k0 += i;
         }
-        if constexpr (KD == WIDE_KD_POLY) {
+        if constexpr (KD == WIDE_KD_POLY || KD == WIDE_KD_MIX) {
             if (A.gb_part) {
                 const double s = wide_wave_sum(wsum);
                 if (threadIdx.x == 0) A.gb_part[int64_t(blockIdx.x) * A.Tpad + t] = s;
@@ -1169,7 +1463,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KD == W
 
 // gZ in the caller's (lt, T, E, d) order from the adjoints of the left-form and the right-form augmented rows (rows (k * E + e) * Tpad + t)
 __global__ void wide_unaug_tens_kernel(const double* __restrict__ gl, const double* __restrict__ vl, const double* __restrict__ gr, const double* __restrict__ vr,
-                                       int64_t rows_out, int d, int64_t Tn, int64_t Tpad, int E, double* __restrict__ g) {
+                                       int64_t rows_out, int d, int64_t Tn, int64_t Tpad, int E, double* __restrict__ g,
+                                       const double* __restrict__ adjl = nullptr, const double* __restrict__ adjr = nullptr, double q = 0.0) {
     const int DA = d + 2;
     const int64_t total = rows_out * d;
     for (int64_t idx = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; idx < total; idx += int64_t(gridDim.x) * blockDim.x) {
@@ -1179,7 +1474,9 @@ __global__ void wide_unaug_tens_kernel(const double* __restrict__ gl, const doub
         const int64_t t = (ro / E) % Tn;
         const int k = int(ro / (int64_t(E) * Tn));
         const int64_t r = (int64_t(k) * E + e) * Tpad + t;
-        g[idx] = fma(-gl[r * DA + d], vl[r * DA + f], gl[r * DA + f]) + fma(-gr[r * DA + d + 1], vr[r * DA + f], gr[r * DA + f]);
+        double nl = gl[r * DA + d], nr = gr[r * DA + d + 1];
+        if (adjl) { nl = fma(-q, adjl[r], nl); nr = fma(-q, adjr[r], nr); }          // (SignatureMix: as wide_unaug_rows_kernel; both or neither)
+        g[idx] = fma(-nl, vl[r * DA + f], gl[r * DA + f]) + fma(-nr, vr[r * DA + f], gr[r * DA + f]);
     }
 }
 
