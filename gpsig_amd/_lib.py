@@ -91,6 +91,12 @@ _KERNEL_FUNCS = {
     "gpsig_lr_tens_features_spectral_dev": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "gpsig_lr_tens_features_spectral_grad": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                              _vp, _vp, _vp],
+    "gpsig_lr_cross": [_vp, _i64, _vp, _i32, _vp],
+    "gpsig_lr_cross_grad": [_vp, _i64, _vp, _i32, _vp, _vp, _vp, C.POINTER(C.c_double)],
+    "gpsig_lr_seq_features_kx_dev": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp],
+    "gpsig_lr_seq_features_kx_grad": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
+    "gpsig_lr_tens_features_kx_dev": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp],
+    "gpsig_lr_tens_features_kx_grad": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp, _vp],
     "gpsig_lr_kernel": [_LR, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
     "gpsig_lr_kernel_diag": [_LR, _vp, _i64, _i32, _vp],
     "gpsig_seq_gram_levels_grad": [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(C.c_double)],

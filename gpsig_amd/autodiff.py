@@ -786,13 +786,16 @@ def _sketch_array(sketches, keep):
 _SPECTRAL_FAMILY = {"rbf": 0, "exp": 1, "mixed": 2}
 
 
-# The six low-rank feature ops below are one implementation (_lr_forward / _lr_backward) on different entry points of csrc/lr_grad_api.hip.  They
+# The low-rank feature ops below are one implementation (_lr_forward / _lr_backward) on different entry points of csrc/lr_grad_api.hip.  They
 # differ in the points -- sequences (N, L, d), passed with (N, L), or inducing tensors (lt, T[, 2], d), passed with (T, increments) --, in whether
 # per-sequence lengths follow the shape arguments, and in the base kernel's parameters: one scalar p0 (or none), whose gradient comes back in a
-# buffer of its own, or SignatureSpectral's alpha (Q), omega (Q, d), gamma (Q, d), which are three more inputs with three more gradients.
+# buffer of its own, or SignatureSpectral's alpha (Q), omega (Q, d), gamma (Q, d), which are three more inputs with three more gradients.  The two
+# `Kx` ops are the maps behind the Nystrom cross matrix (_LrCross): their "points" are kxs (N, L, c) or kzs (lt, T[, 2], c), there are no landmarks
+# (S is None) and no base parameter -- the tensors are (kxs, Wh), whose gradients the reverse entry points return in that order.
 def _lr_call(entry, ten, lens, spec, family, p0, sketches, r, increments, tail):
     """One call of a low-rank feature entry point: params, the sketches, the points with their shape arguments, [lengths,] S, Wh[, alpha, omega,
-    gamma], then ``tail``.  ten: the contiguous float64 tensors (points, S, Wh[, alpha, omega, gamma]); lens: () or (int32 lengths or None,)."""
+    gamma], then ``tail``.  ten: the contiguous float64 tensors (points, S, Wh[, alpha, omega, gamma]) -- the Kx ops': (kxs, Wh), no S in the call
+    either; lens: () or (int32 lengths or None,)."""
     X, keep = ten[0], []
     p = spec.params(X.shape[-1], _p0_value(p0) if family is None else float(ten[3].shape[0]), keep)
     if family is not None:
@@ -806,14 +809,14 @@ def _lr_call(entry, ten, lens, spec, family, p0, sketches, r, increments, tail):
 def _lr_forward(ctx, entries, pts, lens, S, Wh, base, spec, family, sketches, r, increments=None):
     """entries: the names of the forward and the reverse entry point; base: p0 (a tensor or None) where ``family`` is None, else (alpha, omega,
     gamma); increments: None for sequences.  -> Phi (N or T, 1 + c + (M-1) r), float64."""
-    ins = (pts, S, Wh) + (() if family is None else tuple(base))
+    ins = ((pts, Wh) if S is None else (pts, S, Wh)) + (() if family is None else tuple(base))
     ten = tuple(_c(t) for t in ins)
     p0 = base if family is None else None
     increments = None if increments is None else bool(increments)
     n = ten[0].shape[0] if increments is None else ten[0].shape[1]
     out = torch.empty((n, 1 + ten[1].shape[0] + (spec.num_levels - 1) * int(r)), dtype=torch.float64, device=ten[0].device)
     _lr_call(entries[0], ten, lens, spec, family, p0, sketches, int(r), increments, (_ptr(out),))
-    ctx.lr = (entries[1], spec, family, sketches, int(r), increments, p0 is not None, tuple(t is not None for t in lens))
+    ctx.lr = (entries[1], spec, family, sketches, int(r), increments, p0 is not None, tuple(t is not None for t in lens), S is None)
     ctx.dt = tuple(t.dtype for t in ins)
     empty = ten[0].new_empty(0)
     ctx.save_for_backward(*ten, *(() if family is not None else (p0 if p0 is not None else empty,)), *(empty if t is None else t for t in lens))
@@ -822,21 +825,49 @@ def _lr_forward(ctx, entries, pts, lens, S, Wh, base, spec, family, sketches, r,
 
 def _lr_backward(ctx, G):
     """-> the gradients of the tensor inputs in the order of ``forward`` (None for lengths and for everything that is not a tensor)."""
-    entry, spec, family, sketches, r, increments, has_p0, has_lens = ctx.lr
+    entry, spec, family, sketches, r, increments, has_p0, has_lens, kx = ctx.lr
     saved, nt = ctx.saved_tensors, len(ctx.dt)
     ten = saved[:nt]
     p0 = saved[nt] if has_p0 else None
     lens = tuple(t if given else None for t, given in zip(saved[len(saved) - len(has_lens):], has_lens))
     G = _c(G)
     grads = [torch.empty_like(t) for t in ten]
-    gb = torch.zeros(2, dtype=torch.float64, device=G.device) if family is None else None
+    gb = torch.zeros(2, dtype=torch.float64, device=G.device) if family is None and not kx else None
     _lr_call(entry, ten, lens, spec, family, p0, sketches, r, increments,
              [_ptr(G)] + [_ptr(t) for t in grads] + ([] if gb is None else [C.cast(gb.data_ptr(), C.POINTER(C.c_double))]))
     out = [t.to(dt) for t, dt in zip(grads, ctx.dt)]
-    if family is None:
+    if gb is not None:
         out.append(gb[0].to(p0.device).reshape(p0.shape).to(p0.dtype) if has_p0 else None)
     out[1:1] = [None] * len(has_lens)
     return tuple(out) + (None,) * (3 + (family is not None) + (increments is not None))
+
+
+class _LrCross(torch.autograd.Function):
+    """kappa(P, S) of the families of base_kernel_matrix other than SignatureSpectral's, for points P (n, d) and landmarks S (c, d) -> (n, c), by
+    gpsig_lr_cross (csrc/lr_cross_kernel.hpp: the d-deep contraction on the float64 matrix cores, up to 4096 columns, at most 64 landmarks); the
+    reverse pass by gpsig_lr_cross_grad: d points, d landmarks and d p0 (SignaturePoly's offset, SignatureMix's mixing; None for the others),
+    bit-for-bit repeatable.  The squared norms are accumulated in the inner product's own order, so a landmark gathered from the points is at
+    distance exactly 0 from its point (the clamped square root of the Matern families passes no gradient there, as in the fused kernels).  A
+    point whose upstream gradients are all zero gets an exactly zero gradient row whatever it holds (the padded rows of a ragged batch)."""
+
+    @staticmethod
+    def forward(ctx, P, S, p0, spec):
+        Pd, Sd = _c(P), _c(S)
+        out = torch.empty((Pd.shape[0], Sd.shape[0]), dtype=torch.float64, device=Pd.device)
+        _ctx_for(Pd).call("gpsig_lr_cross", spec.params(Pd.shape[1], _p0_value(p0), []), _ptr(Pd), Pd.shape[0], _ptr(Sd), Sd.shape[0], _ptr(out))
+        ctx.spec, ctx.dt, ctx.has_p0 = spec, (P.dtype, S.dtype), p0 is not None
+        ctx.save_for_backward(Pd, Sd, p0 if p0 is not None else Pd.new_empty(0))
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        Pd, Sd, p0 = ctx.saved_tensors
+        G = _c(G)
+        gP, gS = torch.empty_like(Pd), torch.empty_like(Sd)
+        gb = torch.zeros(2, dtype=torch.float64, device=G.device)
+        _ctx_for(Pd).call("gpsig_lr_cross_grad", ctx.spec.params(Pd.shape[1], _p0_value(p0) if ctx.has_p0 else 0.0, []), _ptr(Pd), Pd.shape[0],
+                          _ptr(Sd), Sd.shape[0], _ptr(G), _ptr(gP), _ptr(gS), C.cast(gb.data_ptr(), C.POINTER(C.c_double)))
+        return gP.to(ctx.dt[0]), gS.to(ctx.dt[1]), gb[0].to(p0.device).reshape(p0.shape).to(p0.dtype) if ctx.has_p0 else None, None
 
 
 def _lr_lengths(lengths, Xs, optional=False):
@@ -899,6 +930,31 @@ class _LrSeqFeaturesSpectralRagged(torch.autograd.Function):
     def forward(ctx, Xs, lengths, S, Wh, alpha, omega, gamma, spec, family, sketches, r):
         return _lr_forward(ctx, ("gpsig_lr_seq_features_spectral_ragged_dev", "gpsig_lr_seq_features_spectral_ragged_grad"), Xs,
                            (_lr_lengths(lengths, Xs, optional=True),), S, Wh, (alpha, omega, gamma), spec, family, sketches, r)
+
+    backward = staticmethod(_lr_backward)
+
+
+class _LrSeqFeaturesKx(torch.autograd.Function):
+    """_LrSeqFeatures behind the cross matrix, for state spaces too wide for it: kxs (N, L, c) = kappa(sequences, landmarks) (_LrCross), ``lengths``
+    as _LrSeqFeaturesRagged takes them or None, Wh (c, c) -> Phi, by gpsig_lr_seq_features_kx_dev; the reverse pass by gpsig_lr_seq_features_kx_grad:
+    dPhi -> dkxs (the rows beyond a sequence's length exact zeros) and dWh (csrc/lr_kx_inst.hip: the time-tiled kernels with kxs from memory)."""
+
+    @staticmethod
+    def forward(ctx, kxs, lengths, Wh, spec, sketches, r):
+        return _lr_forward(ctx, ("gpsig_lr_seq_features_kx_dev", "gpsig_lr_seq_features_kx_grad"), kxs, (_lr_lengths(lengths, kxs, optional=True),),
+                           None, Wh, None, spec, None, sketches, r)
+
+    backward = staticmethod(_lr_backward)
+
+
+class _LrTensFeaturesKx(torch.autograd.Function):
+    """_LrTensFeatures behind the cross matrix: kzs (lt, T[, 2], c) = kappa(the tensors' points, landmarks) (_LrCross), Wh (c, c) -> Phi, by
+    gpsig_lr_tens_features_kx_dev / _kx_grad (dPhi -> dkzs, dWh)."""
+
+    @staticmethod
+    def forward(ctx, kzs, Wh, spec, sketches, r, increments):
+        return _lr_forward(ctx, ("gpsig_lr_tens_features_kx_dev", "gpsig_lr_tens_features_kx_grad"), kzs, (), None, Wh, None, spec, None, sketches, r,
+                           increments)
 
     backward = staticmethod(_lr_backward)
 
@@ -971,6 +1027,30 @@ def _lr_limits(cc, r, d, M):
     return cc <= 64 and cc * d <= 4096 and M - 1 <= 7, tile_fits
 
 
+def _lr_route(cc, r, d, M, L, spectral, dense, tens=None):
+    """Which ops compute a low-rank feature map of cc components, rank r, d columns, M levels: of sequences of L points (``dense``: no per-sequence
+    lengths), or with ``tens`` = (lt, E) of inducing tensors of lt components of E points (L and dense are not used).
+      "fused"  the ops that take the points (_LrSeqFeatures ..., _LrTensFeatures ...): exactly the shapes they served before "kx" existed
+      "kx"     _LrCross, then _LrSeqFeaturesKx / _LrTensFeaturesKx: the families of base_kernel_matrix other than SignatureSpectral's, at most 64
+               components and 8 levels, where "fused" is out only because of d -- cc d > 4096, or a 64-step tile (a tensor's arrays) exceeds the LDS
+               with d columns but not without
+      "torch"  everything else (_seq_torch, _seq_torch_ragged, _tens_torch)"""
+    sizes_ok, tile_fits = _lr_limits(cc, r, d, M)
+    if tens is not None:
+        lt, E = tens
+        fits = [8 * (lt * E * (w + 2 * cc) + 2 * lt * cc + M * (M - 1) // 2 * r + 2 * max(cc, r) + 16) <= 156 * 1024 for w in (d, 0)]
+        if lt != M * (M + 1) // 2:
+            return "torch"
+        if sizes_ok and fits[0]:
+            return "fused"
+        return "kx" if not spectral and _lr_limits(cc, r, 0, M)[0] and fits[1] else "torch"
+    # the whole-sequence spectral pair keeps the four (width, L) arrays of a sequence in LDS
+    whole_fits = 8 * ((L + 63) // 64 * 64 + 1) * 4 * max(cc, r, d, 16) <= 156 * 1024
+    if sizes_ok and (tile_fits or (spectral and dense and whole_fits)):
+        return "fused"
+    return "kx" if not spectral and all(_lr_limits(cc, r, 0, M)) else "torch"
+
+
 class _LowRankScope:
     """One low-rank evaluation: landmarks gathered from the evaluation's scaled points, their whitening, and the level features of
     every input asked for (kept per tensor: Kzz, Kzx and Kxx of one call share them)."""
@@ -1005,8 +1085,9 @@ class _LowRankScope:
 
     def seq(self, Xs, lengths=None):
         """signature_algs.py:162-192 (with :191 summing P, as evidently intended).  (N, L, d') -> [(N, 1), (N, c), (N, r), ...].
-        Through the HIP feature kernel and its reverse pass (_seq_hip) where they are built; torch ops otherwise (more than 64 components, ranks
-        beyond a 64-step tile, module option ``lr_hip = False``).
+        Through the HIP feature kernel and its reverse pass (_seq_hip) where they are built -- state spaces too wide for them through the cross
+        op and the kernels that take kxs from memory (_lr_route) --; torch ops otherwise (more than 64 components, ranks beyond a 64-step tile,
+        module option ``lr_hip = False``).
         lengths: (N,) int32 on the sequences' device for a ragged batch (sequence n is Xs[n, :lengths[n]]; the rows beyond are not read): the
         ragged ops within the same limits, _seq_torch_ragged otherwise."""
         key = id(Xs) if lengths is None else (id(Xs), id(lengths))
@@ -1019,24 +1100,28 @@ class _LowRankScope:
 
     def _seq_hip(self, Xs, lengths):
         """seq() by the HIP ops, or None where they are not built for the shape: _LrSeqFeatures (ragged: _LrSeqFeaturesRagged), sequences beyond
-        the LDS in time tiles.  SignatureSpectral: _LrSeqFeaturesSpectral for whole sequences; beyond them and for ragged batches
+        the LDS in time tiles; where only the number of columns keeps them out (_lr_route: "kx") _LrCross and _LrSeqFeaturesKx, with ``lengths`` or
+        without.  SignatureSpectral: _LrSeqFeaturesSpectral for whole sequences; beyond them and for ragged batches
         _LrSeqFeaturesSpectralRagged, with the module option ``lr_spectral_tiled`` alone.  The limits follow from the table's L, not from the
         lengths."""
         mod, kern = self.mod, self.mod.kern
         M, cc = kern.num_levels, int(self.S.shape[0])
         r = int(self.host_sketches[0].r) if self.host_sketches else int(kern.rank_bound)
         L, d = int(Xs.shape[1]), int(Xs.shape[2])
-        sizes_ok, tile_fits = _lr_limits(cc, r, d, M)
         spectral = kern._base == "spectral"
         # the whole-sequence spectral pair keeps the four (width, L) arrays of a sequence in LDS
         whole_fits = 8 * ((L + 63) // 64 * 64 + 1) * 4 * max(cc, r, d, 16) <= 156 * 1024
         spectral_whole = spectral and lengths is None and whole_fits
         if spectral and not spectral_whole and not getattr(mod, "lr_spectral_tiled", False):
             return None
-        if not sizes_ok or not (spectral_whole or tile_fits):
+        route = _lr_route(cc, r, d, M, L, spectral, lengths is None)
+        if route == "torch":
             return None
         try:
-            if spectral:
+            if route == "kx":                                                                       # wide state spaces: the cross matrix as an op of its own
+                kxs = _LrCross.apply(Xs.reshape(-1, d), self.S, mod.p0, mod._spec).reshape(Xs.shape[0], L, cc)
+                Phi = _LrSeqFeaturesKx.apply(kxs, lengths, self.Wh, mod._spec, self.host_sketches, r)
+            elif spectral:
                 base = (positive(mod.raw_alpha), positive(mod.raw_omega), positive(mod.raw_sgamma), mod._spec, kern.family, self.host_sketches, r)
                 Phi = (_LrSeqFeaturesSpectral.apply(Xs, self.S, self.Wh, *base) if spectral_whole else
                        _LrSeqFeaturesSpectralRagged.apply(Xs, lengths, self.S, self.Wh, *base))
@@ -1093,7 +1178,8 @@ class _LowRankScope:
     def tens(self, Zs, increments):
         """signature_algs.py:194-222, kernels.py:285-311.  (lt, T[, 2], d') -> [(T, 1), (T, c), (T, r), ...].
         Through the fused HIP tensor kernel and its reverse pass (_LrTensFeatures; SignatureSpectral: _LrTensFeaturesSpectral) where they are
-        built; torch ops otherwise (more than 64 components, a tensor's arrays beyond the LDS, module option ``lr_hip = False`` or, for the
+        built, wide state spaces through _LrCross and _LrTensFeaturesKx (_lr_route); torch ops otherwise (more than 64 components, a tensor's
+        arrays beyond the LDS whatever the number of columns, module option ``lr_hip = False`` or, for the
         tensors alone, ``lr_tens_hip = False``: A/B runs, tools/bench_lr_tens_train.py)."""
         key = id(Zs)
         if key not in self._tens and getattr(self.mod, "lr_hip", True) and getattr(self.mod, "lr_tens_hip", True) and Zs.is_cuda:
@@ -1101,11 +1187,13 @@ class _LowRankScope:
             M, cc = kern.num_levels, int(self.S.shape[0])
             r = int(self.host_sketches[0].r) if self.host_sketches else int(kern.rank_bound)
             lt, d, E = int(Zs.shape[0]), int(Zs.shape[-1]), 2 if increments else 1
-            # what csrc/lr_grad_api.hip takes (lr_tens_grad_lds_bytes): a tensor's arrays in LDS, at most 64 components
-            lds = 8 * (lt * E * (d + 2 * cc) + 2 * lt * cc + M * (M - 1) // 2 * r + 2 * max(cc, r) + 16)
-            if _lr_limits(cc, r, d, M)[0] and lds <= 156 * 1024 and lt == M * (M + 1) // 2:
+            route = _lr_route(cc, r, d, M, 0, kern._base == "spectral", True, tens=(lt, E))
+            if route != "torch":
                 try:
-                    if kern._base == "spectral":
+                    if route == "kx":                                                               # wide state spaces: the cross matrix as an op of its own
+                        kzs = _LrCross.apply(Zs.reshape(-1, d), self.S, mod.p0, mod._spec).reshape(*Zs.shape[:-1], cc)
+                        Phi = _LrTensFeaturesKx.apply(kzs, self.Wh, mod._spec, self.host_sketches, r, increments)
+                    elif kern._base == "spectral":
                         Phi = _LrTensFeaturesSpectral.apply(Zs, self.S, self.Wh, positive(mod.raw_alpha), positive(mod.raw_omega),
                                                             positive(mod.raw_sgamma), mod._spec, kern.family, self.host_sketches, r, increments)
                     else:

@@ -96,6 +96,9 @@ struct LrTensFusedFields {
 };
 struct LrTensFusedArgs : LrTensFusedFields<double, LrEntry> {};
 struct LrTensFusedArgsF32 : LrTensFusedFields<float, LrEntryF32> {};
+// blocks of the tensor kernels, forward and reverse, that carry `kzs` (lt T E, c): kappa of the tensors' points against the landmarks comes from
+// memory in Z's flat point order instead of being evaluated (lr_kx.hpp; their d is 0: no point is read).  One compile-time branch.
+template <typename Args> struct lr_tens_kx { static constexpr bool value = false; };
 inline size_t lr_tens_fused_lds_bytes(int c, int r, int d_eff, int lt, int E) {
     const size_t rows = size_t(lt) * E, w = size_t(c > r ? c : r);
     return sizeof(double) * (rows * (size_t(d_eff) + 2 * size_t(c)) + size_t(lt) * c + 2 * w);

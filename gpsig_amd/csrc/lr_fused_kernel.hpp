@@ -439,6 +439,11 @@ __device__ __forceinline__ void lr_tens_features_fused_body(const Args& A) {
     __syncthreads();
     for (int q = threadIdx.x; q < rows * c; q += LR_TENS_THREADS) {
         const int row = q / c, i = q - row * c;
+        if constexpr (lr_tens_kx<Args>::value) {         // kappa from memory (lr_kx_inst.hip)
+            const int k = row / E, e = row - k * E;
+            kx[q] = A.kzs[((int64_t(k) * A.T + t) * E + e) * c + i];
+            continue;
+        }
         if constexpr (SPEC) {
             const int Q = int(A.p0);
             if constexpr (sizeof(T) == sizeof(float))

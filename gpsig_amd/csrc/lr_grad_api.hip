@@ -18,6 +18,10 @@
 //                                                         instances of lr_spectral_tiled_inst.hip, whole sequence or time-tiled
 //     gpsig_lr_tens_features_dev / _grad                  inducing tensors (lt, T, E, d) (_K_tens_lr_feat, kernels.py:285-311): the fused tensor
 //     gpsig_lr_tens_features_spectral_dev / _grad         kernels of lr_fused_kernel.hpp (lr_tens_fused_launch) / lr_tens_grad_kernel.hpp
+//     gpsig_lr_seq_features_kx_dev / _kx_grad             the maps BEHIND the Nystrom cross matrix, for state spaces too wide for the kernels above:
+//     gpsig_lr_tens_features_kx_dev / _kx_grad            kxs (N, L, c) / kzs (lt T E, c) come from memory (gpsig_lr_cross, lr_cross_inst.hip), the
+//                                                         reverse passes stop at dkxs / dkzs and sum dWh alone (lr_kx.hpp, lr_kx_inst.hip); the
+//                                                         width d enters neither a plan nor a table
 // What they share:
 //     LrCall, open()      the call's sizes, landmarks, whitening and projections; check() and the entry's own size / NULL test.  An entry's
 //                         plan and LDS refusals follow, then upload_sketches: the projections are value-independent random objects that come from
@@ -37,6 +41,7 @@
 // queued; ensure() waits for the stream before it frees anything anyway).
 #include "ctx.hpp"
 #include "lr_grad_kernel.hpp"
+#include "lr_kx.hpp"
 #include "lr_tens_grad_kernel.hpp"
 #include "lr_spectral_tiled.hpp"
 #include "lr_tiled_kernel.hpp"
@@ -534,6 +539,34 @@ int spectral_seq_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r
         });
 }
 
+// ---- the entry points behind the cross matrix (lr_kx.hpp): what open() leaves to them.  p->num_features is the width of the points kxs was
+// computed from and is not used: the plans have max(c, r) rows.
+int kx_open(LrCall* k, gpsig_ctx* c, const gpsig_params* p, int cc, int r, int nsk, const double* Wh, bool bad) {
+    CHK(open(k, c, p, cc, r, nsk, nullptr, Wh, false, false));
+    k->d = 0;
+    if (k->M - 1 > LR_FUSED_MAX_SKETCHES) return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank mode is built for num_levels <= %d", LR_FUSED_MAX_SKETCHES + 1);
+    if (cc > 64) return fail(c, GPSIG_ERR_UNSUPPORTED, "the low-rank training path is built for num_components <= 64");
+    if (bad) return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
+    return GPSIG_OK;
+}
+int kx_plan(const LrCall& k, bool reverse, int L, LrTileDir* D) {
+    *D = lr_kx_tile_dir(reverse, k.cc, k.r, L, k.p->difference ? L - 1 : L, k.c->lr_fused_pad);
+    if (D->TL == 0)
+        return fail(k.c, GPSIG_ERR_UNSUPPORTED, "a %d-step tile of a sequence's low-rank arrays (%zu bytes) exceeds the LDS", LR_TILE_STEP,
+                    reverse ? lr_tiled_grad_lds_bytes(k.cc, k.r, 0, LR_TILE_STEP, k.c->lr_fused_pad)
+                            : lr_tiled_fused_lds_bytes(k.cc, k.r, 0, LR_TILE_STEP, k.c->lr_fused_pad));
+    return GPSIG_OK;
+}
+int kx_tens_open(LrCall* k, gpsig_ctx* c, const gpsig_params* p, int cc, int r, int nsk, const double* Wh, int64_t T, int E, bool bad) {
+    CHK(kx_open(k, c, p, cc, r, nsk, Wh, false));
+    const int lt = k->M * (k->M + 1) / 2;
+    if (T < 0 || T > 0x7fffffff) return fail(c, GPSIG_ERR_INVALID, "bad number of tensors");
+    const size_t lds = std::max(lr_tens_grad_lds_bytes(cc, r, 0, lt, E, k->M), lr_tens_fused_lds_bytes(cc, r, 0, lt, E));
+    if (lds > LR_FUSED_MAX_LDS) return fail(c, GPSIG_ERR_UNSUPPORTED, "a tensor's low-rank arrays (%zu bytes) exceed the LDS", lds);
+    if (bad) return fail(c, GPSIG_ERR_INVALID, "bad sizes / NULL pointer");
+    return GPSIG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -701,6 +734,93 @@ int gpsig_lr_tens_features_spectral_grad(gpsig_ctx* c, const gpsig_params* p, in
             }
             return GPSIG_OK;
         });
+}
+
+// ---- behind the cross matrix: kxs (N, L, c) = kappa(X, S) from gpsig_lr_cross; `lengths` may be NULL (L points each)
+int gpsig_lr_seq_features_kx_dev(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches, const double* kxs,
+                                 int64_t N, int32_t L, const int32_t* lengths, const double* Wh, void* Phi) {
+    LrCall k;
+    CHK(kx_open(&k, c, p, cc, r, nsk, Wh, N < 0 || L < 1 || (N > 0 && (!kxs || !Wh || !Phi))));
+    LrTileDir D;
+    CHK(kx_plan(k, false, L, &D));
+    CHK(upload_sketches(c, cc, r, nsk, sketches, k.gs));
+    if (N == 0) return GPSIG_OK;
+    LrTiledKxArgs A{};
+    tiled_args(k, L, D, false, &A);
+    A.X = kxs; A.d = cc; A.N = N;                    // (the bodies step through X in rows of d: lr_kx.hpp)
+    A.Phi = static_cast<double*>(Phi);
+    A.lengths = lengths;
+    const int rc = lr_kx_tiled_launch(c->stream, A, unsigned(N < (1 << 20) ? N : (1 << 20)), D.lds);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "tiled low-rank feature kernel (kxs from memory): %s", hipGetErrorString(hipError_t(rc)));
+    return GPSIG_OK;
+}
+
+int gpsig_lr_seq_features_kx_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches, const double* kxs,
+                                  int64_t N, int32_t L, const int32_t* lengths, const double* Wh, const void* dPhi, double* dkxs, double* gWh) {
+    LrCall k;
+    CHK(kx_open(&k, c, p, cc, r, nsk, Wh, N < 0 || L < 1 || !gWh || (N > 0 && (!kxs || !Wh || !dPhi || !dkxs))));
+    LrTileDir D;
+    CHK(kx_plan(k, true, L, &D));
+    // min(N, 512) workgroups, fewer where their E_i scratch would exceed its budget (lr_tile_plan's rule, here for every length)
+    const int64_t escr_stride = lr_escr_stride(cc, r, k.M, p->difference ? L - 1 : L);
+    const int64_t grid = std::min<int64_t>(std::min<int64_t>(N, LR_TILE_MAX_GRID), int64_t(LR_TILE_SCRATCH_BUDGET / (sizeof(double) * size_t(escr_stride))));
+    if (N > 0 && grid == 0)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "one workgroup's scratch for a sequence of %d points (%lld bytes) exceeds the reverse pass's budget", L,
+                    (long long)(escr_stride * int64_t(sizeof(double))));
+    CHK(upload_sketches(c, cc, r, nsk, sketches, k.gs));
+    if (N == 0) return zero_async(c, gWh, sizeof(double) * size_t(cc) * cc);
+    void *part, *escr;
+    CHK(ensure(c, B_GR0, sizeof(double) * size_t(grid) * size_t(cc) * cc + 64, &part));
+    CHK(ensure(c, B_GR1, sizeof(double) * size_t(grid) * size_t(escr_stride) + 64, &escr));
+    LrTiledKxArgs A{};
+    tiled_args(k, L, D, true, &A);
+    A.escr = static_cast<double*>(escr); A.escr_stride = escr_stride;
+    A.X = kxs; A.d = cc; A.N = N;
+    A.dPhi = static_cast<const double*>(dPhi);
+    A.dkxs = dkxs;
+    A.part = static_cast<double*>(part);
+    A.lengths = lengths;
+    const int rc = lr_kx_grad_tiled_launch(c->stream, A, unsigned(grid), D.lds);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "tiled low-rank reverse kernel (kxs from memory): %s", hipGetErrorString(hipError_t(rc)));
+    return reduce_partials(k, part, grid, true, nullptr, gWh, nullptr);
+}
+
+// ... and the inducing tensors': kzs (lt T E, c) = kappa of Z's points in their flat order
+int gpsig_lr_tens_features_kx_dev(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches, const double* kzs,
+                                  int64_t T, int32_t increments, const double* Wh, void* Phi) {
+    LrCall k;
+    const int E = increments ? 2 : 1;
+    CHK(kx_tens_open(&k, c, p, cc, r, nsk, Wh, T, E, T > 0 && (!kzs || !Wh || !Phi)));
+    CHK(upload_sketches(c, cc, r, nsk, sketches, k.gs));
+    if (T == 0) return GPSIG_OK;
+    LrTensKxArgs A{};
+    A.T = T; A.lt = k.M * (k.M + 1) / 2; A.E = E;
+    forward_fields(k, nullptr, Phi, &A);
+    A.kzs = kzs;
+    const int rc = lr_kx_tens_launch(c->stream, A);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "fused low-rank tensor feature kernel (kzs from memory): %s", hipGetErrorString(hipError_t(rc)));
+    return GPSIG_OK;
+}
+
+int gpsig_lr_tens_features_kx_grad(gpsig_ctx* c, const gpsig_params* p, int32_t cc, int32_t r, int32_t nsk, const gpsig_sketch* sketches, const double* kzs,
+                                   int64_t T, int32_t increments, const double* Wh, const void* dPhi, double* dkzs, double* gWh) {
+    LrCall k;
+    const int E = increments ? 2 : 1;
+    CHK(kx_tens_open(&k, c, p, cc, r, nsk, Wh, T, E, !gWh || (T > 0 && (!kzs || !Wh || !dPhi || !dkzs))));
+    CHK(upload_sketches(c, cc, r, nsk, sketches, k.gs));
+    if (T == 0) return zero_async(c, gWh, sizeof(double) * size_t(cc) * cc);
+    const unsigned grid = unsigned(T < 512 ? T : 512);                 // as gpsig_lr_tens_features_grad
+    void* part;
+    CHK(ensure(c, B_GR0, sizeof(double) * size_t(grid) * size_t(cc) * cc + 64, &part));
+    LrTensGradKxArgs A{};
+    tens_grad_args(k, nullptr, T, E, dPhi, &A);
+    A.t0 = 0; A.nt = T;                                                // one launch: dkzs is in the flat point order of Z
+    A.part = static_cast<double*>(part);
+    A.dkx = dkzs;
+    A.kzs = kzs;
+    const int rc = lr_kx_tens_grad_launch(c->stream, A, grid);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "low-rank tensor reverse kernel (kzs from memory): %s", hipGetErrorString(hipError_t(rc)));
+    return reduce_partials(k, part, grid, true, nullptr, gWh, nullptr);
 }
 
 }  // extern "C"

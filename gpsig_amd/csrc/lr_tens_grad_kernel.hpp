@@ -102,7 +102,10 @@ __device__ __forceinline__ void lr_tens_features_grad_body(const Args& A) {
         __syncthreads();
         for (int q = threadIdx.x; q < rows * c; q += THREADS) {
             const int row = q / c, i = q - row * c;
-            if constexpr (SPEC) {
+            if constexpr (lr_tens_kx<Args>::value) {     // kappa from memory (lr_kx_inst.hip: a SPEC instance, dkx out)
+                const int k = row / E, e = row - k * E;
+                kx[q] = A.kzs[((int64_t(k) * A.T + t) * E + e) * c + i];
+            } else if constexpr (SPEC) {
                 kx[q] = spectral_pair(lr_as_const(A.alpha), lr_as_const(A.omega), lr_as_const(A.gamma), d, int(A.p0), int(A.p1), d,
                                       [&](int f) { return zs[row * d + f]; }, [&](int f) { return Sg[size_t(i) * d + f]; });
             } else {
@@ -293,9 +296,12 @@ __device__ __forceinline__ void lr_tens_features_grad_body(const Args& A) {
     }
 }
 
+// (no templates: defined once, in lr_grad_api.hip; lr_kx_inst.hip takes the body alone)
+#ifndef GPSIG_LR_BODIES_ONLY
 __global__ __launch_bounds__(LR_TENS_GRAD_THREADS) void lr_tens_features_grad_kernel(LrTensGradArgs A) { lr_tens_features_grad_body<false>(A); }
 
 // SignatureSpectral: kappa by spectral_pair, dkx out instead of the base-kernel phase (above)
 __global__ __launch_bounds__(LR_TENS_GRAD_THREADS) void lr_tens_features_grad_spectral_kernel(LrTensGradSpectralArgs A) { lr_tens_features_grad_body<true>(A); }
+#endif
 
 }  // namespace gpsig

@@ -1,6 +1,6 @@
 // lr_tiled_fwd_body.inc -- the body of lr_seq_features_tiled_kernel, included between the braces of a __global__ function template <int THREADS> whose
 // argument block is `A`: LrTiledArgs in lr_tiled_kernel.hpp, LrTiledRaggedArgs (per-sequence lengths) in lr_ragged_inst.hip, LrTiledSpectralArgs
-// (lr_tile_u evaluates spectral_pair) in lr_spectral_tiled_inst.hip.  A text shared by inclusion, not a function: behind a reference or a
+// (lr_tile_u evaluates spectral_pair) in lr_spectral_tiled_inst.hip, LrTiledKxArgs (lr_tile_u loads kxs) in lr_kx_inst.hip.  A text shared by inclusion, not a function: behind a reference or a
 // by-value parameter the existing instance compiles to other code (more registers, or scratch).
     constexpr int NW = THREADS / 64, UNROLL = 8;
     constexpr bool RAGGED = lr_ragged<decltype(A)>::value;

@@ -1,6 +1,6 @@
 // lr_tiled_rev_body.inc -- the body of lr_seq_features_grad_tiled_kernel, included between the braces of a __global__ function template <int THREADS> whose
 // argument block is `A`: LrTiledArgs in lr_tiled_kernel.hpp, LrTiledRaggedArgs (per-sequence lengths) in lr_ragged_inst.hip, LrTiledSpectralArgs in
-// lr_spectral_tiled_inst.hip.  A text shared by inclusion, not a function: behind a reference or a by-value parameter the existing instance compiles
+// lr_spectral_tiled_inst.hip, LrTiledKxArgs (kxs from memory) in lr_kx_inst.hip.  A text shared by inclusion, not a function: behind a reference or a by-value parameter the existing instance compiles
 // to other code (more registers, or scratch).  The phases that depend on the family are overloaded on the block (lr_tiled_kernel.hpp).
     constexpr int NW = THREADS / 64, UNROLL = 8;
     constexpr bool RAGGED = lr_ragged<decltype(A)>::value;

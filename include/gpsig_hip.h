@@ -451,6 +451,40 @@ int gpsig_spectral_cross(gpsig_ctx* ctx, int32_t Q, int32_t family, int32_t d, c
 int gpsig_spectral_cross_grad(gpsig_ctx* ctx, int32_t Q, int32_t family, int32_t d, const double* P, int64_t n, const double* S, int32_t c,
                               const double* alpha, const double* omega, const double* gamma, const double* G, double* dP, double* dS,
                               double* dalpha, double* domega, double* dgamma);
+/* The Nystrom cross matrix of the other families for the TRAINING path on WIDE state spaces (low_rank_calculations.py:59): K (n, c) =
+ * kappa(P, S) for points P (n, d) and landmarks S (c, d), p->base_kernel in GPSIG_BASE_LINEAR .. GPSIG_BASE_MATERN52 with p->base_params as
+ * the fused feature kernels read them, d = p->num_features; the d-deep contraction runs on the float64 matrix cores.  Device pointers,
+ * device-pointer mode, float64, asynchronous on the context's stream.  Limits: 1 <= c <= 64, 1 <= d <= 4096, any n >= 0; outside them
+ * GPSIG_ERR_UNSUPPORTED.  |P_t|^2 and |S_i|^2 are diagonals of matrix-core products with the inner product's own order of additions, so a
+ * landmark that IS one of the points is at distance exactly 0 from it.
+ * _grad: G = dL/dK (n, c) -> dP (n, d), dS (c, d), g_base[0] (the base kernel's own parameter, or NULL), overwritten; partial sums combined
+ * in a fixed order, no floating-point atomics: two calls return the same bits (the number of partial sums of dS follows the option
+ * wide_chunk_mb).  The Matern families take no gradient through a zero distance, as the feature pairs above.  An element with G == 0
+ * contributes nothing whatever its point holds, and a point whose G are all zero gets a dP row of exact zeros: the padded rows of a ragged
+ * batch may hold NaN.  n = 0: dS and g_base are zeroed.  Scratch: n (c + 1) doubles of the context's. */
+int gpsig_lr_cross(gpsig_ctx* ctx, const gpsig_params* p, const double* P, int64_t n, const double* S, int32_t c, double* K);
+int gpsig_lr_cross_grad(gpsig_ctx* ctx, const gpsig_params* p, const double* P, int64_t n, const double* S, int32_t c, const double* G, double* dP,
+                        double* dS, double* g_base);
+/* The training path's feature maps BEHIND that cross matrix: gpsig_lr_seq_features_dev / _grad and gpsig_lr_tens_features_dev / _grad without
+ * their first phase.  kxs (N, L, c) = kappa(X, S) and kzs (lt T E, c) = kappa of Z's points in their flat order come from memory
+ * (gpsig_lr_cross); the reverse passes return dkxs / dkzs in the same layouts (for gpsig_lr_cross_grad, which carries them on to the points,
+ * the landmarks and the base parameter) and gWh (c, c), all overwritten and bit-for-bit repeatable.  p->num_features (the width the cross
+ * matrix was computed at) is not used: the width enters neither the LDS plan nor a table, which have max(c, r) rows.  `lengths`: N int32 on
+ * the DEVICE as the ragged pair takes them, or NULL (every sequence has L points); the kxs rows beyond a sequence's length are never read and
+ * their dkxs rows are exact zeros.  Sequences go in time tiles (one tile where they fit).  Checks and refusals are those of the pairs above
+ * (float64, device-pointer mode, order 1, num_levels <= 8, num_components <= 64, else GPSIG_ERR_UNSUPPORTED); the sequence pair also refuses
+ * a 64-step tile that exceeds the LDS, the tensor pair a tensor's arrays that do.  N = 0 / T = 0: gWh is zeroed. */
+int gpsig_lr_seq_features_kx_dev(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
+                                 const gpsig_sketch* sketches, const double* kxs, int64_t N, int32_t L, const int32_t* lengths, const double* Wh,
+                                 void* Phi);
+int gpsig_lr_seq_features_kx_grad(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
+                                  const gpsig_sketch* sketches, const double* kxs, int64_t N, int32_t L, const int32_t* lengths, const double* Wh,
+                                  const void* dPhi, double* dkxs, double* gWh);
+int gpsig_lr_tens_features_kx_dev(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
+                                  const gpsig_sketch* sketches, const double* kzs, int64_t T, int32_t increments, const double* Wh, void* Phi);
+int gpsig_lr_tens_features_kx_grad(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t num_sketches,
+                                   const gpsig_sketch* sketches, const double* kzs, int64_t T, int32_t increments, const double* Wh,
+                                   const void* dPhi, double* dkzs, double* gWh);
 /* SignatureKernel._K_seq_lr_feat (kernels.py:239-261): Nystrom_map + signature_kern_first_order_lr_feature.  Phi: (N, F).
  * With option lr_fused != 0 (the default): one fused kernel where a sequence's three (width, L) arrays fit the LDS; beyond that the
  * time-tiled kernels (csrc/lr_eval_tiled.hpp: tiles of a multiple of 64 time steps, one carried vector per level, the raw points scaled in
