@@ -24,6 +24,7 @@
 #include "lowrank_kernels.hpp"
 #include "lr_fused_args.hpp"
 #include "lr_eval_tiled.hpp"
+#include "lr_eval_wide.hpp"
 #include "lr_draw_kernels.hpp"
 #include "seq_args.hpp"
 #include "seq_configs.hpp"
@@ -694,12 +695,104 @@ int lr_tens_features_passes(gpsig_ctx* c, const gpsig_params* p, const gpsig_low
     return finish(c);
 }
 
+// ---- The wide routes: state spaces beyond every kernel that holds the points in LDS (which calls: lr_eval_route / lr_eval_tens_route,
+// lr_tile_plan.hpp).  The Nystrom cross matrix comes from the float64 matrix cores, straight from the caller's raw points (lr_cross_eval_kernel,
+// lr_cross_kernel.hpp), into B_LR2 in the call's element type; the feature kernels that take it from memory follow (lr_eval_wide.hpp).  Sequences
+// (tensors) go in chunks whose kxs stay within the wide route's chunk budget, each a cross launch and a feature launch on its slice: they are
+// independent, so the result does not depend on the chunk count.
+size_t lr_wide_chunk_bytes(const gpsig_ctx* c) {     // (as lr_cross_inst.hip: chunk_budget)
+    if (c->wide_chunk_mb > 0) return size_t(c->wide_chunk_mb) << 20;
+    return size_t(c->grad_scratch_mb > 0 ? c->grad_scratch_mb : 4096) << 20;
+}
+
+// what both wide routes set up: the feature kernels' view of the state (lr_state_args: float32 narrowed once per call), |S_i|^2 in B_LR3, the
+// chunk (objects of `per` bytes of kxs each) and its buffer
+template <typename T, typename Entry>
+int lr_wide_open(gpsig_ctx* c, const gpsig_params* p, const LrDev& D, int d_eff, int64_t count, size_t per, LrEvalWideFeat<T, Entry>* W,
+                 LrCrossEvalArgs<T>* A, int64_t* chunk) {
+    std::conditional_t<std::is_same<T, float>::value, LrEvalTiledArgsF32, LrEvalTiledArgs> st{};
+    CHK(lr_state_args(c, p, D, d_eff, nullptr, &st));
+    W->Wh = st.Wh;
+    for (int i = 0; i < D.nsk; ++i) W->sk[i] = st.sk[i];
+    W->c = D.c; W->r = D.r; W->M = p->num_levels; W->difference = p->difference;
+    const int64_t fit = int64_t(lr_wide_chunk_bytes(c) / per);
+    *chunk = std::max<int64_t>(1, std::min<int64_t>(fit, count));
+    void *kxs, *sn;
+    CHK(ensure(c, B_LR2, per * size_t(*chunk) + 64, &kxs));
+    CHK(ensure(c, B_LR3, sizeof(double) * LR_EVAL_WIDE_MAX_C + 64, &sn));
+    double p0, p1;
+    base_p(p, &p0, &p1);
+    A->S = D.S; A->c = D.c; A->kind = int(p->base_kernel); A->p0 = p0; A->p1 = p1;
+    A->sn = static_cast<const double*>(sn);
+    A->K = static_cast<T*>(kxs);
+    W->kxs = static_cast<const T*>(kxs);
+    if (count > 0) {
+        const int rc = lr_cross_norms_launch(c->stream, D.S, D.c, d_eff, static_cast<double*>(sn));
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "Nystrom cross kernel (landmark norms): %s", hipGetErrorString(hipError_t(rc)));
+    }
+    return GPSIG_OK;
+}
+
+template <typename T>
+int lr_seq_features_wide(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& s, const LrDev& D, const T* dX, int64_t N, int32_t L,
+                         const int32_t* dlen, void* Phi, void* dPhi) {
+    using Entry = std::conditional_t<std::is_same<T, float>::value, LrEntryF32, LrEntry>;
+    const int F = 1 + D.c + (p->num_levels - 1) * D.r;
+    LrEvalWideFeat<T, Entry> W{};
+    LrCrossEvalArgs<T> A{};
+    int64_t chunk;
+    CHK(lr_wide_open(c, p, D, s.d_eff(), N, sizeof(T) * size_t(L) * D.c, &W, &A, &chunk));
+    A.L = L; A.P = s;
+    W.L = L;
+    for (int64_t n0 = 0; n0 < N; n0 += chunk) {
+        const int64_t nn = std::min<int64_t>(chunk, N - n0);
+        A.X = dX + n0 * int64_t(L) * p->num_features; A.n = nn * L;
+        A.lengths = dlen ? dlen + n0 : nullptr;
+        int rc = lr_cross_eval_seq_launch(c->stream, A);
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "Nystrom cross kernel (evaluation form): %s", hipGetErrorString(hipError_t(rc)));
+        W.N = nn; W.lengths = A.lengths;
+        W.Phi = static_cast<T*>(dPhi) + n0 * int64_t(F);
+        rc = lr_eval_wide_seq_launch(c->stream, W, c->lr_fused_pad);
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "tiled low-rank feature kernel (kxs from memory): %s", hipGetErrorString(hipError_t(rc)));
+    }
+    CHK(out_done(c, Phi, dPhi, sizeof(T) * size_t(N) * F));
+    return finish(c);
+}
+
+template <typename T>
+int lr_tens_features_wide(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& s, const LrDev& D, const T* dZ, int64_t T_, int lt, int E, void* Phi,
+                          void* dPhi) {
+    using Entry = std::conditional_t<std::is_same<T, float>::value, LrEntryF32, LrEntry>;
+    const int F = 1 + D.c + (p->num_levels - 1) * D.r;
+    LrEvalWideFeat<T, Entry> W{};
+    LrCrossEvalArgs<T> A{};
+    int64_t chunk;
+    CHK(lr_wide_open(c, p, D, s.d_eff(), T_, sizeof(T) * size_t(lt) * E * D.c, &W, &A, &chunk));
+    A.X = dZ; A.P = s; A.T = T_; A.E = E;
+    W.L = lt; W.E = E;
+    for (int64_t t0 = 0; t0 < T_; t0 += chunk) {
+        const int64_t nt = std::min<int64_t>(chunk, T_ - t0);
+        A.t0 = t0; A.nt = nt; A.n = int64_t(lt) * nt * E;
+        int rc = lr_cross_eval_tens_launch(c->stream, A);
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "Nystrom cross kernel (evaluation form, tensors): %s", hipGetErrorString(hipError_t(rc)));
+        W.N = nt;
+        W.Phi = static_cast<T*>(dPhi) + t0 * int64_t(F);
+        rc = lr_eval_wide_tens_launch(c->stream, W);
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "fused low-rank tensor feature kernel (kzs from memory): %s", hipGetErrorString(hipError_t(rc)));
+    }
+    CHK(out_done(c, Phi, dPhi, sizeof(T) * size_t(T_) * F));
+    return finish(c);
+}
+
 // gpsig_lr_seq_features / gpsig_lr_seq_features_ragged in T.  Whole sequences (`ragged` false): the fused kernels (lr_fused_kernel.hpp: one
 // workgroup per sequence, intermediates in LDS) where a sequence's arrays fit; beyond them, with lr_fused != 0, the time-tiled kernels of
-// lr_eval_tiled.hpp where at least one 64-step tile fits (float32: the families of base_eval only); else the multi-pass route -- float64
-// only: for float32 that is UNSUPPORTED, and the Python layer computes the call in float64 and rounds it.  float64 tests the three-array
+// lr_eval_tiled.hpp where at least one 64-step tile fits (float32: the families of base_eval only); beyond those the wide route above (the
+// families of base_eval, c <= 64, both float types); else the multi-pass route -- float64
+// only: for float32 that is UNSUPPORTED, and the Python layer computes the call in float64 and rounds it.  lr_fused = 0 is the multi-pass route at
+// every shape.  The rule is lr_eval_route (lr_tile_plan.hpp).  float64 tests the three-array
 // footprint before it may pick either fused form, float32 the footprint of the form it picks.  Ragged (`lengths`: N int32 in the context's
-// pointer mode): the tiled kernels at every length -- a short batch is a one-tile walk -- whatever lr_fused says; there is no multi-pass form.
+// pointer mode): the tiled kernels at every length -- a short batch is a one-tile walk --, the wide route beyond them, whatever lr_fused says;
+// there is no multi-pass form.
 template <typename T>
 int lr_seq_features_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L, bool ragged,
                       const int32_t* lengths, void* Phi) {
@@ -712,14 +805,13 @@ int lr_seq_features_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* 
     const bool two = c->lr_fused == 1 && lr_fused2_ok(cc, r, L);
     const size_t lds = !f32 ? lr_fused_lds_bytes(cc, r, d_eff, L, c->lr_fused_pad)
                        : two ? lr_fused2_lds_bytes_f32(cc, r, d_eff, L, c->lr_fused_pad) : lr_fused_lds_bytes_f32(cc, r, d_eff, L, c->lr_fused_pad);
-    const bool levels_ok = M - 1 <= LR_FUSED_MAX_SKETCHES;
-    const bool fused = !ragged && c->lr_fused != 0 && lds <= LR_FUSED_MAX_LDS && levels_ok;
-    const LrTileDir TD = lr_eval_tile_dir(f32, cc, r, d_eff, L - (p->difference ? 1 : 0), c->lr_fused_pad);
-    const bool tiled = !fused && (ragged || c->lr_fused != 0) && TD.TL > 0 && levels_ok && !(f32 && p->base_kernel == GPSIG_BASE_SPECTRAL);
-    if (ragged && !tiled)
+    const LrEvalRoute route = lr_eval_route(f32, cc, r, d_eff, L, M, p->difference, ragged, c->lr_fused, p->base_kernel == GPSIG_BASE_SPECTRAL,
+                                            c->lr_fused_pad);
+    const bool fused = route == LR_EVAL_FUSED, tiled = route == LR_EVAL_TILED;
+    if (ragged && route == LR_EVAL_REFUSE)
         return fail(c, GPSIG_ERR_UNSUPPORTED, "ragged low-rank features need one 64-step tile of the tiled kernels in the LDS (%zu bytes), at most %d "
                     "levels, and float64 for SignatureSpectral", lr_eval_tiled_lds_bytes(f32, cc, r, d_eff, LR_TILE_STEP, c->lr_fused_pad), LR_FUSED_MAX_SKETCHES + 1);
-    if (f32 && !fused && !tiled)
+    if (route == LR_EVAL_REFUSE)
         return fail(c, GPSIG_ERR_UNSUPPORTED, "float32 low-rank features are built for the fused kernels only (lr_fused != 0, %zu bytes of LDS)", lds);
     LrDev D;
     CHK(lr_upload(c, lr, d_eff, &D));
@@ -733,6 +825,8 @@ int lr_seq_features_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* 
     double p0, p1;
     base_p(p, &p0, &p1);
     const double* spec = nullptr;        // BASE_SPECTRAL: its parameter table (p0 = Q, p1 = family), read by the spectral instances
+    if (route == LR_EVAL_WIDE)
+        return lr_seq_features_wide<T>(c, p, s, D, static_cast<const T*>(dX), N, L, static_cast<const int32_t*>(dlen), Phi, dPhi);
     if (!f32 || N > 0) CHK(spectral_table(c, p, &spec));                     // (float32 uploads nothing for an empty call)
     if (!fused && !tiled) return lr_seq_features_passes(c, p, lr, s, D, static_cast<const double*>(dX), N, L, spec, Phi, dPhi);
     if (N <= 0) return finish(c);
@@ -760,7 +854,8 @@ int lr_seq_features_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* 
     return finish(c);
 }
 
-// gpsig_lr_tens_features in T: the fused kernel where a tensor's arrays fit 64 KB of LDS, else the multi-pass route (float64 only, as above)
+// gpsig_lr_tens_features in T: the fused kernel where a tensor's arrays fit 64 KB of LDS; where they do without the points, the wide route;
+// else the multi-pass route (float64 only, as above).  The rule is lr_eval_tens_route (lr_tile_plan.hpp).
 template <typename T>
 int lr_tens_features_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* Z, int64_t T_, int32_t increments, void* Phi) {
     constexpr bool f32 = std::is_same<T, float>::value;
@@ -769,8 +864,9 @@ int lr_tens_features_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank*
     CHK(scale_params(c, p, true, &s));
     const int d_eff = s.d_eff();
     const size_t lds = f32 ? lr_tens_fused_lds_bytes_f32(cc, r, d_eff, lt, E) : lr_tens_fused_lds_bytes(cc, r, d_eff, lt, E);
-    const bool fused = c->lr_fused != 0 && lds <= 64 * 1024 && M - 1 <= LR_FUSED_MAX_SKETCHES && T_ <= 0x7fffffff;
-    if (f32 && !fused)
+    const LrEvalRoute route = lr_eval_tens_route(f32, cc, r, d_eff, M, E, c->lr_fused, p->base_kernel == GPSIG_BASE_SPECTRAL, T_);
+    const bool fused = route == LR_EVAL_FUSED;
+    if (route == LR_EVAL_REFUSE)
         return fail(c, GPSIG_ERR_UNSUPPORTED, "float32 low-rank tensor features are built for the fused kernel only (lr_fused != 0, %zu bytes of LDS)", lds);
     LrDev D;
     CHK(lr_upload(c, lr, d_eff, &D));
@@ -780,6 +876,7 @@ int lr_tens_features_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank*
     void* dPhi;
     CHK(out_dev(c, B_OUT0, Phi, sizeof(T) * size_t(T_) * F, &dPhi));
     if (T_ <= 0) return finish(c);
+    if (route == LR_EVAL_WIDE) return lr_tens_features_wide<T>(c, p, s, D, static_cast<const T*>(dZ), T_, lt, E, Phi, dPhi);
     double p0, p1;
     base_p(p, &p0, &p1);
     const double* spec;

@@ -54,6 +54,13 @@ int norms(gpsig_ctx* c, const LrCrossArgs& A, double* sn) {
 
 }  // namespace
 
+namespace gpsig {
+int lr_cross_norms_launch(hipStream_t stream, const double* S, int c, int d, double* sn) {
+    hipLaunchKernelGGL(lr_cross_norms_kernel, dim3(unsigned((c + 15) / 16)), dim3(64), 0, stream, S, c, d, sn);
+    return int(hipGetLastError());
+}
+}  // namespace gpsig
+
 extern "C" {
 
 int gpsig_lr_cross(gpsig_ctx* c, const gpsig_params* p, const double* P, int64_t n, const double* S, int32_t cc, double* K) {

@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "grad_core.hpp"
+#include "lr_eval_wide.hpp"
 #include "lr_fused_args.hpp"
 #include "seq_core.hpp"
 
@@ -91,6 +92,33 @@ __device__ __forceinline__ void lr_cross_inner(const double* __restrict__ P, int
         }
     }
 }
+// The same walk with the tile's loader as a parameter, for the evaluation form (lr_cross_eval_kernel): `load(col)` fills column `lane` of the
+// tile's 16 rows with column col of the wavefront's points, zeros beyond their end.  (A text of its own: behind a callable the training kernels
+// above compile to other code -- the reverse kernel's register allocation moved.)
+template <class Load>
+__device__ __forceinline__ void lr_cross_walk(Load&& load, int d, const double* __restrict__ S, int c, int nt, double* pt, lr_cross_f64x4 (&ip)[4],
+                                              lr_cross_f64x4& xx, int lane) {
+    const int m = lane & 15, kq = lane >> 4;
+    for (int k0 = 0; k0 < d; k0 += LR_CROSS_KC) {
+        __syncthreads();                            // (the previous columns' readers are done)
+        load(k0 + lane);
+        __syncthreads();
+        const int steps = (d - k0 < LR_CROSS_KC ? d - k0 + 3 : LR_CROSS_KC) / 4;
+        for (int kk = 0; kk < steps; ++kk) {
+            const int f = k0 + kk * 4 + kq;
+            const double a = pt[m * LR_CROSS_LD + kk * 4 + kq];
+            xx = __builtin_amdgcn_mfma_f64_16x16x4f64(a, a, xx, 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j < nt) {
+                    const int i = j * 16 + m;
+                    const double b = (i < c && f < d) ? S[size_t(i) * d + f] : 0.0;
+                    ip[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, ip[j], 0, 0, 0);
+                }
+            }
+        }
+    }
+}
 
 // the diagonal of a wavefront's 16 x 16 tile -> xs[g] = the entry of row (l >> 4) + 4 g, through 16 doubles of the wavefront's LDS tile
 // (between two workgroup barriers of the caller's own)
@@ -100,6 +128,138 @@ __device__ __forceinline__ void lr_cross_diag_put(const lr_cross_f64x4& xx, doub
         if ((lane & 15) == (lane >> 4) + 4 * g) pt[lane & 15] = xx[g];
 }
 
+// ---- the evaluation form: kxs of the CALLER'S points, for gpsig_lr_seq_features / _ragged / gpsig_lr_tens_features on state spaces too wide for
+// the kernels that hold the points in LDS (lr_eval_wide_inst.hip; the feature kernels that take kxs from memory follow it).  The walk and the
+// wavefront layout are lr_cross_kernel's; loader and store differ:
+//   loader   the table as the caller gives it, double or float, widened value by value and scaled in float64 as scaled_point<double, In> does
+//            (sequences: lengthscales, lags and lag weights on the sequence's own time axis, the interpolation bracket found once per (row, lag)
+//            into the wavefront's LDS, not once per element) or as lr_tens_cross_kernel does (tensors: Z (lt, T, E, d) in its flat order,
+//            lengthscales and lag weights).  The landmarks of a state are float64 values gathered from widened, scaled points: the loader
+//            reproduces those bits, so a landmark that is one of the points is at distance exactly 0 in float32 calls too.
+//   rows     sequences: point q of the launch is point q % L of sequence q / L; with `lengths` (clamped to [1, L]) the points beyond a
+//            sequence's length are never read -- zeros in the operand -- and their kxs rows are not written.  Tensors: the launch takes the
+//            tensors [t0, t0 + nt) of T: its point (k nt + tt) E + e is Z's row (k T + t0 + tt) E + e, so that K is kzs of nt tensors.
+//   store    in the call's element type: double, or float rounded once.  Arithmetic is float64 for both.
+// (LrCrossEvalArgs<In>: lr_eval_wide.hpp)
+
+// the lag interpolation of scaled_point (aux_kernels.hpp; gpsig/lags.py:7-57) in two steps: the bracket of (point t, lag) ...
+__device__ __forceinline__ int lr_cross_lag_bracket(int L, int t, double lag, double jitter, double* tq_out) {
+    const double denom = double(L - 1);
+    const double tq = fmax(double(t) / denom - lag, 0.0);
+    int left = 0;
+    for (int i = L - 1; i >= 0; --i)
+        if (!(double(i) / denom - tq > jitter)) { left = i; break; }
+    *tq_out = tq;
+    return left;
+}
+// ... and the value of column f between its two rows: the same operations on the same values as scaled_point<double, In>
+template <typename In>
+__device__ __forceinline__ double lr_cross_lag_value(const In* __restrict__ Xn, int L, int d_in, int f, int left, double tq) {
+    const double denom = double(L - 1);
+    const int right = left + 1 < L ? left + 1 : L - 1;
+    const double xl = double(Xn[int64_t(left) * d_in + f]), xr = double(Xn[int64_t(right) * d_in + f]);
+    const double tl = double(left) / denom, tr = double(right) / denom;
+    return xl + (tq - tl) * (xr - xl) / (tr - tl);
+}
+
+template <typename In, bool TENS>
+__global__ __launch_bounds__(LR_CROSS_THREADS) void lr_cross_eval_kernel(LrCrossEvalArgs<In> A) {
+    __shared__ double tiles[LR_CROSS_WAVES][16 * LR_CROSS_LD];
+    __shared__ int64_t roff[LR_CROSS_WAVES][16];                            // a row's sequence (tensors: the row itself) in X, in elements
+    __shared__ int rtime[LR_CROSS_WAVES][16];                               // its point in the sequence; -1: the row is not read
+    __shared__ int bleft[LR_CROSS_WAVES][16 * MAX_LAGS];                    // the lag brackets of the wavefront's rows
+    __shared__ double btq[LR_CROSS_WAVES][16 * MAX_LAGS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 15, kq = lane >> 4;
+    double* const pt = tiles[wave];
+    const int c = A.c, nt = (c + 15) / 16, d = A.P.d_eff(), d_in = A.P.d_in, L = A.L, nlags = TENS ? 0 : A.P.num_lags;
+    const int64_t nblk = (A.n + 16 * LR_CROSS_WAVES - 1) / (16 * LR_CROSS_WAVES);
+    double ss[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ss[j] = j * 16 + m < c ? A.sn[j * 16 + m] : 0.0;
+    for (int64_t b = blockIdx.x; b < nblk; b += gridDim.x) {                // (the same number of rounds for every wavefront: barriers inside)
+        const int64_t row0 = (b * LR_CROSS_WAVES + wave) * 16;
+        __syncthreads();                                                    // (the previous round's readers of the row tables are done)
+        if (lane < 16) {
+            const int64_t row = row0 + lane;
+            int64_t off = 0;
+            int t = -1;
+            if (row < A.n) {
+                if constexpr (TENS) {
+                    const int64_t per = A.nt * A.E, k = row / per;
+                    off = ((k * A.T + A.t0) * A.E + (row - k * per)) * d;
+                    t = 0;
+                } else {
+                    const int64_t nq = row / L;
+                    const int tt = int(row - nq * L);
+                    int len = L;
+                    if (A.lengths) {
+                        len = A.lengths[nq];
+                        len = len < 1 ? 1 : (len > L ? L : len);
+                    }
+                    if (tt < len) { off = nq * int64_t(L) * d_in; t = tt; }
+                }
+            }
+            roff[wave][lane] = off;
+            rtime[wave][lane] = t;
+        }
+        __syncthreads();
+        if constexpr (!TENS) {
+            for (int q = lane; q < 16 * nlags; q += 64) {                   // once per (row, lag)
+                const int rr = q / nlags, lg = q - rr * nlags, t = rtime[wave][rr];
+                double tq = 0.0;
+                bleft[wave][q] = t >= 0 ? lr_cross_lag_bracket(L, t, A.P.lags[lg], A.P.jitter, &tq) : 0;
+                btq[wave][q] = tq;
+            }
+        }
+        lr_cross_f64x4 ip[4], xx = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ip[j] = lr_cross_f64x4{0.0, 0.0, 0.0, 0.0};
+        lr_cross_walk(
+            [&](int col) {                                                  // (its first barrier orders the tables above)
+                const bool in = col < d;
+                const int lag = in ? col / d_in : 0, f = in ? col - lag * d_in : 0;
+                const double ls = A.P.has_ls ? A.P.lsv(f) : 1.0, gm = A.P.num_lags > 0 ? A.P.gamma[lag] : 1.0;
+                for (int rr = 0; rr < 16; ++rr) {
+                    const int t = rtime[wave][rr];
+                    double v = 0.0;
+                    if (in && t >= 0) {
+                        const In* Xn = A.X + roff[wave][rr];
+                        if constexpr (TENS) {
+                            v = double(Xn[col]);
+                            if (A.P.has_ls) {
+                                v = v / ls;
+                                if (A.P.num_lags > 0) v = v * gm;
+                            }
+                        } else {
+                            v = lag == 0 ? double(Xn[int64_t(t) * d_in + f])
+                                         : lr_cross_lag_value(Xn, L, d_in, f, bleft[wave][rr * nlags + lag - 1], btq[wave][rr * nlags + lag - 1]);
+                            if (A.P.has_ls) v = v / ls;
+                            if (A.P.num_lags > 0) v = v * gm;
+                        }
+                    }
+                    pt[rr * LR_CROSS_LD + lane] = v;
+                }
+            },
+            d, A.S, c, nt, pt, ip, xx, lane);
+        __syncthreads();
+        lr_cross_diag_put(xx, pt, lane);
+        __syncthreads();
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int64_t row = row0 + kq + 4 * g;
+            const double xs = pt[kq + 4 * g];
+            const bool live = rtime[wave][kq + 4 * g] >= 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int i = j * 16 + m;
+                if (j < nt && live && i < c) A.K[row * c + i] = In(base_eval<double>(A.kind, ip[j][g], xs, ss[j], A.p0, A.p1));
+            }
+        }
+    }
+}
+
+// (the kernels below are no templates: defined once, in lr_cross_inst.hip; lr_eval_wide_inst.hip takes the templates above alone)
+#ifndef GPSIG_LR_CROSS_TEMPLATES_ONLY
 // |S_i|^2 by the walk of lr_cross_inner on S itself: one wavefront per 16 landmarks
 __global__ __launch_bounds__(64) void lr_cross_norms_kernel(const double* __restrict__ S, int c, int d, double* __restrict__ sn) {
     const int lane = threadIdx.x, m = lane & 15, kq = lane >> 4;
@@ -296,5 +456,7 @@ __global__ __launch_bounds__(256) void lr_cross_grad_reduce_kernel(const double*
     const double cs = colsum[q / d];
     dS[q] = cs != 0.0 ? fma(cs, S[q], s) : s;
 }
+
+#endif  // GPSIG_LR_CROSS_TEMPLATES_ONLY
 
 }  // namespace gpsig

@@ -27,11 +27,21 @@ template <> struct lr_ragged<LrEvalTiledArgsF32> { static constexpr bool value =
 template <> struct lr_ragged_nullable<LrEvalTiledArgs> { static constexpr bool value = true; };
 template <> struct lr_ragged_nullable<LrEvalTiledArgsF32> { static constexpr bool value = true; };
 
+// The float32 kernel BEHIND the Nystrom cross matrix (the wide route of api.hip; float64 takes lr_seq_features_tiled_kx_kernel, lr_kx.hpp): X is
+// kxs (N, L, c) in float, from lr_cross_eval_kernel; phases 0 and 1 are a load, the rest is the kernel above.  S and kind are not read.
+struct LrEvalTiledKxArgsF32 : LrEvalTiledArgsF32 {};
+template <typename Args> struct lr_eval_kx { static constexpr bool value = false; };
+template <> struct lr_eval_kx<LrEvalTiledKxArgsF32> { static constexpr bool value = true; };
+template <> struct lr_ragged<LrEvalTiledKxArgsF32> { static constexpr bool value = true; };
+template <> struct lr_ragged_nullable<LrEvalTiledKxArgsF32> { static constexpr bool value = true; };
+
 // The caller fills the arguments except F, rows_b, lp, TL and ntiles, which the launcher derives from lr_eval_tile_dir (with the LDS row
 // padding `pad`); one workgroup of 1024 threads per sequence (at most 2^20: the kernel strides over the rest).  A.kind == BASE_SPECTRAL
 // launches the spectral instance (float64 only: the float32 launcher returns hipErrorInvalidValue for it, as both do where not even a
 // 64-step tile fits the LDS -- callers test lr_eval_tile_dir(...).TL first).  Return the hipError_t of the launch.
 int lr_eval_tiled_launch(hipStream_t stream, LrEvalTiledArgs A, int pad);
 int lr_eval_tiled_launch(hipStream_t stream, LrEvalTiledArgsF32 A, int pad);
+// ... and the kx instance: P is set here (d_in = c, no scaling), the plan is lr_eval_tile_dir's with max(c, r) rows
+int lr_eval_tiled_kx_launch(hipStream_t stream, LrEvalTiledKxArgsF32 A, int pad);
 
 }  // namespace gpsig

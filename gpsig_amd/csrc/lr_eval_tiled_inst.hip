@@ -44,33 +44,41 @@ __device__ __forceinline__ void lr_tile_u(const Args& A, const T* Xn, int t0, in
     constexpr int NW = THREADS / 64;
     const int lp = A.lp, c = A.c, L = A.L, d_eff = A.P.d_eff();
     const int pchunk = (np + 63) / 64, nchunk = (tl + 63) / 64;
-    // ---- phase 0: scaled observations, xb[fe][t]
-    for (int q = threadIdx.x; q < np * d_eff; q += THREADS) {
-        const int t = q / d_eff, fe = q - t * d_eff;
-        xb[fe * lp + t] = scaled_point<T>(Xn, L, t0 + t, fe, A.P);
-    }
-    __syncthreads();
-    // ---- phase 1: kxs, kx[i][t]
-    for (int ch = 0; ch < pchunk; ++ch) {
-        const int t = ch * 64 + lane;
-        if (t < np) {
-            T xs = T(0);
-            for (int fe = 0; fe < d_eff; ++fe) { const T x = xb[fe * lp + t]; xs = fma(x, x, xs); }
-            for (int i = wave; i < c; i += NW) {
-                const lr_const_ptr<T> Si = lr_as_const(A.S) + size_t(i) * d_eff;
-                if constexpr (SPEC) {
-                    kx[i * lp + t] = lr_eval_spectral_pair(lr_as_const(A.spec), int(A.p0), int(A.p1), d_eff, [&](int f) { return xb[f * lp + t]; },
-                                                           [&](int f) { return Si[f]; });
-                } else if constexpr (sizeof(T) == sizeof(float)) {
-                    kx[i * lp + t] = lr_kappa_f32(A.kind, A.p0, A.p1, d_eff, xs, [&](int f) { return xb[f * lp + t]; }, [&](int f) { return Si[f]; });
-                } else {
-                    T ip = T(0), ss = T(0);
-                    for (int fe = 0; fe < d_eff; ++fe) {
-                        const T y = Si[fe];
-                        ip = fma(xb[fe * lp + t], y, ip);
-                        ss = fma(y, y, ss);
+    if constexpr (lr_eval_kx<Args>::value) {
+        // ---- instead of phases 0 and 1: the tile's kxs rows from memory (the wide route: X is kxs (N, L, c), P.d_in = c)
+        for (int q = threadIdx.x; q < np * c; q += THREADS) {
+            const int t = q / c, i = q - t * c;
+            kx[i * lp + t] = Xn[int64_t(t0) * c + q];
+        }
+    } else {
+        // ---- phase 0: scaled observations, xb[fe][t]
+        for (int q = threadIdx.x; q < np * d_eff; q += THREADS) {
+            const int t = q / d_eff, fe = q - t * d_eff;
+            xb[fe * lp + t] = scaled_point<T>(Xn, L, t0 + t, fe, A.P);
+        }
+        __syncthreads();
+        // ---- phase 1: kxs, kx[i][t]
+        for (int ch = 0; ch < pchunk; ++ch) {
+            const int t = ch * 64 + lane;
+            if (t < np) {
+                T xs = T(0);
+                for (int fe = 0; fe < d_eff; ++fe) { const T x = xb[fe * lp + t]; xs = fma(x, x, xs); }
+                for (int i = wave; i < c; i += NW) {
+                    const lr_const_ptr<T> Si = lr_as_const(A.S) + size_t(i) * d_eff;
+                    if constexpr (SPEC) {
+                        kx[i * lp + t] = lr_eval_spectral_pair(lr_as_const(A.spec), int(A.p0), int(A.p1), d_eff, [&](int f) { return xb[f * lp + t]; },
+                                                               [&](int f) { return Si[f]; });
+                    } else if constexpr (sizeof(T) == sizeof(float)) {
+                        kx[i * lp + t] = lr_kappa_f32(A.kind, A.p0, A.p1, d_eff, xs, [&](int f) { return xb[f * lp + t]; }, [&](int f) { return Si[f]; });
+                    } else {
+                        T ip = T(0), ss = T(0);
+                        for (int fe = 0; fe < d_eff; ++fe) {
+                            const T y = Si[fe];
+                            ip = fma(xb[fe * lp + t], y, ip);
+                            ss = fma(y, y, ss);
+                        }
+                        kx[i * lp + t] = base_eval<T>(A.kind, ip, xs, ss, A.p0, A.p1);
                     }
-                    kx[i * lp + t] = base_eval<T>(A.kind, ip, xs, ss, A.p0, A.p1);
                 }
             }
         }
@@ -184,6 +192,8 @@ __device__ __forceinline__ void lr_seq_features_eval_tiled_body(const Args& A) {
 __global__ __launch_bounds__(1024) void lr_seq_features_eval_tiled_kernel(LrEvalTiledArgs A) { lr_seq_features_eval_tiled_body<1024, 8, false>(A); }
 __global__ __launch_bounds__(1024) void lr_seq_features_eval_tiled_spectral_kernel(LrEvalTiledArgs A) { lr_seq_features_eval_tiled_body<1024, 8, true>(A); }
 __global__ __launch_bounds__(1024) void lr_seq_features_eval_tiled_f32_kernel(LrEvalTiledArgsF32 A) { lr_seq_features_eval_tiled_body<1024, 8, false>(A); }
+// ... behind the cross matrix (the wide route): everything after phase 1 is the code above
+__global__ __launch_bounds__(1024) void lr_seq_features_eval_tiled_kx_f32_kernel(LrEvalTiledKxArgsF32 A) { lr_seq_features_eval_tiled_body<1024, 8, false>(A); }
 
 namespace {
 // F, the work arrays' rows and the tile plan of L points; false where not even one 64-step tile fits
@@ -213,6 +223,15 @@ int lr_eval_tiled_launch(hipStream_t stream, LrEvalTiledArgsF32 A, int pad) {
     size_t lds;
     if (A.kind == BASE_SPECTRAL || !eval_tiled_fields(A, true, pad, &grid, &lds)) return int(hipErrorInvalidValue);
     return lr_launch(lr_seq_features_eval_tiled_f32_kernel, grid, 1024, lds, stream, A);
+}
+
+int lr_eval_tiled_kx_launch(hipStream_t stream, LrEvalTiledKxArgsF32 A, int pad) {
+    unsigned grid;
+    size_t lds;
+    A.P = ScaleParams{};
+    A.P.d_in = A.c;                                  // rows of kxs: the plan is that of max(c, r) rows
+    if (!eval_tiled_fields(A, true, pad, &grid, &lds)) return int(hipErrorInvalidValue);
+    return lr_launch(lr_seq_features_eval_tiled_kx_f32_kernel, grid, 1024, lds, stream, A);
 }
 
 }  // namespace gpsig

@@ -27,7 +27,7 @@ struct LrSketch { const int32_t* colptr; const Entry* ent; };
 using LrFusedSketch = LrSketch<LrEntry>;
 using LrFusedSketchF32 = LrSketch<LrEntryF32>;
 
-constexpr int LR_FUSED_MAX_SKETCHES = 7;            // levels 2 .. 8
+// (LR_FUSED_MAX_SKETCHES = 7, levels 2 .. 8: lr_tile_plan.hpp)
 
 // The float32 forms run the same bodies on float: points, landmarks, whitening, sketch values, spectral table and features in float32,
 // phase 1 on the hardware transcendentals.  The state stays float64 (drawn and whitened in float64); lr_narrow_launch converts what the
@@ -72,13 +72,8 @@ __device__ __forceinline__ int lr_seq_points(const Args& A, int64_t n, int L) {
     else return L;
 }
 
-// two-array form (lr_seq_features_fused2_kernel): usable for L <= 64 and at most 8 output columns per wavefront of the 512-thread workgroup
-inline bool lr_fused2_ok(int c, int r, int L) { return L <= 64 && c <= 64 && r <= 64; }
-inline size_t lr_fused2_lds_bytes(int c, int r, int d_eff, int L, int pad = 1) {
-    int kb = c > r ? c : r;
-    if (d_eff > kb) kb = d_eff;
-    return sizeof(double) * size_t(lr_fused_stride(L, pad)) * 2 * size_t(kb);
-}
+// (the two-array form's lr_fused2_ok / lr_fused2_lds_bytes, the tensor kernel's lr_tens_fused_lds_bytes and the float32 footprints are HIP-free
+// and live in lr_tile_plan.hpp, next to the route predicates that read them)
 
 // Feature map of inducing tensors (gpsig/kernels.py:285-311 _K_tens_lr_feat, signature_algs.py:194-222 tensor_kern_lr_feature),
 // one workgroup per tensor: its lt * E components are whitened and chained through the sketches in LDS.
@@ -99,14 +94,6 @@ struct LrTensFusedArgsF32 : LrTensFusedFields<float, LrEntryF32> {};
 // blocks of the tensor kernels, forward and reverse, that carry `kzs` (lt T E, c): kappa of the tensors' points against the landmarks comes from
 // memory in Z's flat point order instead of being evaluated (lr_kx.hpp; their d is 0: no point is read).  One compile-time branch.
 template <typename Args> struct lr_tens_kx { static constexpr bool value = false; };
-inline size_t lr_tens_fused_lds_bytes(int c, int r, int d_eff, int lt, int E) {
-    const size_t rows = size_t(lt) * E, w = size_t(c > r ? c : r);
-    return sizeof(double) * (rows * (size_t(d_eff) + 2 * size_t(c)) + size_t(lt) * c + 2 * w);
-}
-
-inline size_t lr_fused_lds_bytes_f32(int c, int r, int d_eff, int L, int pad = 1) { return lr_fused_lds_bytes(c, r, d_eff, L, pad) / 2; }
-inline size_t lr_fused2_lds_bytes_f32(int c, int r, int d_eff, int L, int pad = 1) { return lr_fused2_lds_bytes(c, r, d_eff, L, pad) / 2; }
-inline size_t lr_tens_fused_lds_bytes_f32(int c, int r, int d_eff, int lt, int E) { return lr_tens_fused_lds_bytes(c, r, d_eff, lt, E) / 2; }
 
 // lr_fused_inst.hip: the sequence route's launchers.  The caller fills the arguments except F, lp and rows_b, which the launcher derives
 // (with the LDS row padding `pad`), and launches one workgroup per sequence (at most 2^20: the kernel strides over the rest).

@@ -68,6 +68,7 @@ __global__ __launch_bounds__(THREADS) void lr_seq_features_grad_tiled_kx_kernel(
 #include "lr_tiled_rev_body.inc"
 }
 __global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_kx_kernel(LrTensKxArgs A) { lr_tens_features_fused_body<false>(A); }
+__global__ __launch_bounds__(LR_TENS_THREADS) void lr_tens_features_kx_f32_kernel(LrTensKxArgsF32 A) { lr_tens_features_fused_body<false>(A); }
 __global__ __launch_bounds__(LR_TENS_GRAD_THREADS) void lr_tens_features_grad_kx_kernel(LrTensGradKxArgs A) { lr_tens_features_grad_body<true>(A); }
 
 int lr_kx_tiled_launch(hipStream_t stream, const LrTiledKxArgs& A, unsigned grid, size_t lds) {
@@ -81,6 +82,11 @@ int lr_kx_grad_tiled_launch(hipStream_t stream, const LrTiledKxArgs& A, unsigned
 int lr_kx_tens_launch(hipStream_t stream, LrTensKxArgs A) {
     A.F = 1 + A.c + (A.M - 1) * A.r;
     return lr_launch(lr_tens_features_kx_kernel, unsigned(A.T), LR_TENS_THREADS, lr_tens_fused_lds_bytes(A.c, A.r, 0, A.lt, A.E), stream, A);
+}
+
+int lr_kx_tens_launch(hipStream_t stream, LrTensKxArgsF32 A) {
+    A.F = 1 + A.c + (A.M - 1) * A.r;
+    return lr_launch(lr_tens_features_kx_f32_kernel, unsigned(A.T), LR_TENS_THREADS, lr_tens_fused_lds_bytes_f32(A.c, A.r, 0, A.lt, A.E), stream, A);
 }
 
 int lr_kx_tens_grad_launch(hipStream_t stream, const LrTensGradKxArgs& A, unsigned grid) {

@@ -1,6 +1,8 @@
 // lr_tile_plan.hpp -- LDS footprints of the low-rank sequence feature kernels and the time-tile plan of their tiled forms.
+// Also: the footprints of the other evaluation kernels and the predicates that pick an evaluation call's route (lr_eval_route, lr_eval_tens_route).
 // HIP-free (constexpr helpers are usable on the device): read by lr_fused_args.hpp / lr_grad_kernel.hpp (the whole-sequence kernels),
-// lr_tiled_kernel.hpp, lr_eval_tiled_inst.hip, the host paths of lr_grad_api.hip and api.hip, and tests/emu/test_lr_tile_plan.cpp.
+// lr_tiled_kernel.hpp, lr_eval_tiled_inst.hip, the host paths of lr_grad_api.hip and api.hip, tests/emu/test_lr_tile_plan.cpp and
+// tests/emu/test_lr_eval_route.cpp.
 //
 // The whole-sequence kernels keep (width, L) arrays of a sequence in LDS: three in the forward direction (lr_fused_lds_bytes), four in the
 // reverse pass (lr_grad_lds_bytes).  Where those exceed LR_FUSED_MAX_LDS, the tiled kernels walk the sequence in tiles of TL time steps
@@ -101,6 +103,66 @@ inline LrTileDir lr_eval_tile_dir(bool f32, int c, int r, int d, int l, int pad)
     D.lp = lr_tile_stride(TL, pad);
     D.lds = TL ? lr_eval_tiled_lds_bytes(f32, c, r, d, TL, pad) : 0;
     return D;
+}
+
+// ---- the other evaluation kernels' footprints (their argument blocks: lr_fused_args.hpp)
+constexpr int LR_FUSED_MAX_SKETCHES = 7;            // levels 2 .. 8
+// two-array form (lr_seq_features_fused2_kernel): usable for L <= 64 and at most 8 output columns per wavefront of the 512-thread workgroup
+inline bool lr_fused2_ok(int c, int r, int L) { return L <= 64 && c <= 64 && r <= 64; }
+inline size_t lr_fused2_lds_bytes(int c, int r, int d_eff, int L, int pad = 1) {
+    int kb = c > r ? c : r;
+    if (d_eff > kb) kb = d_eff;
+    return sizeof(double) * size_t(lr_fused_stride(L, pad)) * 2 * size_t(kb);
+}
+// the fused tensor kernel: a tensor's lt E points (d_eff), their kxs and features (c each), U (lt, c) and two chain rows
+inline size_t lr_tens_fused_lds_bytes(int c, int r, int d_eff, int lt, int E) {
+    const size_t rows = size_t(lt) * E, w = size_t(c > r ? c : r);
+    return sizeof(double) * (rows * (size_t(d_eff) + 2 * size_t(c)) + size_t(lt) * c + 2 * w);
+}
+inline size_t lr_fused_lds_bytes_f32(int c, int r, int d_eff, int L, int pad = 1) { return lr_fused_lds_bytes(c, r, d_eff, L, pad) / 2; }
+inline size_t lr_fused2_lds_bytes_f32(int c, int r, int d_eff, int L, int pad = 1) { return lr_fused2_lds_bytes(c, r, d_eff, L, pad) / 2; }
+inline size_t lr_tens_fused_lds_bytes_f32(int c, int r, int d_eff, int lt, int E) { return lr_tens_fused_lds_bytes(c, r, d_eff, lt, E) / 2; }
+constexpr size_t LR_TENS_FUSED_MAX_LDS = 64 * 1024; // what the evaluation side gives the fused tensor kernel (several workgroups per CU)
+
+// ---- which route serves an evaluation call (api.hip: lr_seq_features_t, lr_tens_features_t; tests/emu/test_lr_eval_route.cpp)
+//   FUSED    the whole-sequence kernels (lr_fused_kernel.hpp) / the fused tensor kernel: the object's arrays, points included, in LDS
+//   TILED    the time-tiled kernels on raw points (lr_eval_tiled.hpp): a 64-step tile of max(c, r, d) rows fits
+//   WIDE     beyond those: the Nystrom cross matrix on the float64 matrix cores from the raw points (lr_cross_kernel.hpp, evaluation form), then
+//            the feature kernels that take it from memory (lr_kx.hpp; float32: the kx instances of the evaluation kernels).  The width d
+//            enters no LDS plan: the kx plan is that of d = 0.  Families of base_eval, c <= 64, d <= 4096.
+//   PASSES   the multi-pass route (float64): lr_fused = 0 at every shape, and what none of the above serves
+//   REFUSE   GPSIG_ERR_UNSUPPORTED: float32 or ragged where only the multi-pass route is left
+// A shape a fused or tiled kernel serves keeps it; WIDE only takes calls that were PASSES or REFUSE before it existed.
+enum LrEvalRoute { LR_EVAL_FUSED = 0, LR_EVAL_TILED = 1, LR_EVAL_WIDE = 2, LR_EVAL_PASSES = 3, LR_EVAL_REFUSE = 4 };
+constexpr int LR_EVAL_WIDE_MAX_C = 64;               // the cross kernel's four 16-landmark accumulator tiles
+constexpr int LR_EVAL_WIDE_MAX_D = 4096;             // MAX_FEATURES_WIDE
+
+inline bool lr_eval_wide_common(int c, int d, int M, bool spectral) {
+    return !spectral && c <= LR_EVAL_WIDE_MAX_C && M - 1 <= LR_FUSED_MAX_SKETCHES && d <= LR_EVAL_WIDE_MAX_D;
+}
+// sequences: (N, L) points of d columns after lags; `ragged`: the call carries lengths; `spectral`: GPSIG_BASE_SPECTRAL
+inline LrEvalRoute lr_eval_route(bool f32, int c, int r, int d, int L, int M, int difference, bool ragged, int lr_fused, bool spectral, int pad) {
+    // two arrays in LDS instead of three where a wavefront can hold its output columns in registers: float32 tests the footprint of the
+    // form it picks, float64 the three-array footprint before it may pick either
+    const bool two = lr_fused == 1 && lr_fused2_ok(c, r, L);
+    const size_t lds = !f32 ? lr_fused_lds_bytes(c, r, d, L, pad) : two ? lr_fused2_lds_bytes_f32(c, r, d, L, pad) : lr_fused_lds_bytes_f32(c, r, d, L, pad);
+    const bool levels_ok = M - 1 <= LR_FUSED_MAX_SKETCHES;
+    if (!ragged && lr_fused != 0 && lds <= LR_FUSED_MAX_LDS && levels_ok) return LR_EVAL_FUSED;
+    const bool beyond = ragged || lr_fused != 0;     // ragged batches take the tiled forms whatever lr_fused says: there is no multi-pass form
+    const int l = L - (difference ? 1 : 0);
+    if (beyond && levels_ok && !(f32 && spectral) && lr_eval_tile_dir(f32, c, r, d, l, pad).TL > 0) return LR_EVAL_TILED;
+    if (beyond && lr_eval_wide_common(c, d, M, spectral) && lr_eval_tile_dir(f32, c, r, 0, l, pad).TL > 0) return LR_EVAL_WIDE;
+    return ragged || f32 ? LR_EVAL_REFUSE : LR_EVAL_PASSES;
+}
+// inducing tensors: T tensors of lt = M (M + 1) / 2 components of E points
+inline LrEvalRoute lr_eval_tens_route(bool f32, int c, int r, int d, int M, int E, int lr_fused, bool spectral, int64_t T) {
+    const int lt = M * (M + 1) / 2;
+    const bool ok = lr_fused != 0 && M - 1 <= LR_FUSED_MAX_SKETCHES && T <= 0x7fffffff;
+    if (ok && (f32 ? lr_tens_fused_lds_bytes_f32(c, r, d, lt, E) : lr_tens_fused_lds_bytes(c, r, d, lt, E)) <= LR_TENS_FUSED_MAX_LDS) return LR_EVAL_FUSED;
+    if (ok && lr_eval_wide_common(c, d, M, spectral) &&
+        (f32 ? lr_tens_fused_lds_bytes_f32(c, r, 0, lt, E) : lr_tens_fused_lds_bytes(c, r, 0, lt, E)) <= LR_TENS_FUSED_MAX_LDS)
+        return LR_EVAL_WIDE;
+    return f32 ? LR_EVAL_REFUSE : LR_EVAL_PASSES;
 }
 
 // the reverse pass's E_i scratch per workgroup, in doubles (what the whole-sequence kernel takes as well)

@@ -489,18 +489,30 @@ int gpsig_lr_tens_features_kx_grad(gpsig_ctx* ctx, const gpsig_params* p, int32_
  * With option lr_fused != 0 (the default): one fused kernel where a sequence's three (width, L) arrays fit the LDS; beyond that the
  * time-tiled kernels (csrc/lr_eval_tiled.hpp: tiles of a multiple of 64 time steps, one carried vector per level, the raw points scaled in
  * the kernel -- lengthscales and lags included), in float64 and float32, where at least one 64-step tile fits; SignatureSpectral's tiled
- * kernel is float64 only (float32: GPSIG_ERR_UNSUPPORTED there).  lr_fused = 0, or not even one tile: the multi-pass route (float64 only),
- * which streams five (N, L, max(c, r)) arrays of context-owned scratch. */
+ * kernel is float64 only (float32: GPSIG_ERR_UNSUPPORTED there).  Where not even one tile holds the points -- 65 c + 138 max(c, r, d') doubles
+ * exceed 156 KB: d' > 121 at c = r = 50, twice that in float32 -- the WIDE route: the Nystrom cross matrix on the float64 matrix cores from the
+ * raw points (csrc/lr_cross_kernel.hpp, evaluation form; float32 points are widened value by value, so a landmark that is one of the points
+ * stays at distance exactly 0), written to context scratch in the call's element type, then the feature kernels that take it from memory
+ * (csrc/lr_kx.hpp; float32: the kx instance of the tiled kernel); sequences go in chunks whose cross matrix stays within wide_chunk_mb (else
+ * grad_scratch_mb), and the result does not depend on the chunk count.  It serves the families of base_eval at num_components <= 64,
+ * num_levels <= 8 and d' <= 4096 wherever max(c, r) rows fit a tile.  lr_fused = 0, SignatureSpectral or num_components > 64 beyond the
+ * tiled kernels: the multi-pass route (float64 only; float32: GPSIG_ERR_UNSUPPORTED), which streams five (N, L, max(c, r)) arrays of
+ * context-owned scratch.  The rule is csrc/lr_tile_plan.hpp: lr_eval_route. */
 int gpsig_lr_seq_features(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L, void* Phi);
 /* ... for a RAGGED batch: lengths (N int32, in the context's pointer mode like X; host pointers are copied in), sequence n is
  * X[n, :lengths[n]] and Phi[n] its features evaluated alone.  The rows beyond a sequence's length are never read (they may hold NaN);
  * lengths are clamped to [1, L] on the device.  A sequence of one point with p->difference has no steps: Phi[n] = [1, 0, .., 0].  Served by
- * the time-tiled kernels at every length, whatever lr_fused says; float64 and float32, SignatureSpectral in float64 only.
- * GPSIG_ERR_UNSUPPORTED: p->num_lags > 0 (the lag interpolation runs on the table's own time axis), float32 SignatureSpectral, shapes
- * whose 64-step tile exceeds the LDS. */
+ * the time-tiled kernels at every length and, where not even one tile holds the points, by the wide route (above: the padded rows are zeros
+ * in the cross kernel's operand and their rows of the cross matrix are never written), whatever lr_fused says; float64 and float32,
+ * SignatureSpectral in float64 only.
+ * GPSIG_ERR_UNSUPPORTED: p->num_lags > 0 (the lag interpolation runs on the table's own time axis), float32 SignatureSpectral, and shapes
+ * whose 64-step tile exceeds the LDS where the wide route does not apply (SignatureSpectral, num_components > 64, max(c, r) rows beyond a tile). */
 int gpsig_lr_seq_features_ragged(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L,
                                  const int32_t* lengths, void* Phi);
-/* SignatureKernel._K_tens_lr_feat (kernels.py:285-311): Nystrom_map + tensor_kern_lr_feature.  Phi: (T, F). */
+/* SignatureKernel._K_tens_lr_feat (kernels.py:285-311): Nystrom_map + tensor_kern_lr_feature.  Phi: (T, F).  With lr_fused != 0 one fused kernel
+ * where a tensor's arrays -- 8 (lt E (d' + 2 c) + lt c + 2 max(c, r)) bytes, half in float32 -- fit 64 KB of LDS; where they do without the
+ * points (d' = 0) the wide route as for sequences (the cross matrix of Z's points in their flat order, then the kx instance of the fused
+ * kernel; tensors in chunks), for the families of base_eval at num_components <= 64; else the multi-pass route (float64 only). */
 int gpsig_lr_tens_features(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_lowrank* lr, const void* Z, int64_t T,
                            int32_t increments, void* Phi);
 /* Kernel matrix from factors: level Grams PhiA_m PhiB_m^T (fp64 MFMA; float32 factors: v_mfma_f32_16x16x4_f32), optional per-side level normalisation
