@@ -989,7 +989,11 @@ class _SpectralCross(torch.autograd.Function):
     """SignatureSpectral's kappa(P, S) (kernels.py:921-942) for points P (n, d) and landmarks S (c, d) -> (n, c), by gpsig_spectral_cross; the
     reverse pass by gpsig_spectral_cross_grad: d points, d landmarks, d alpha, d omega, d gamma, the parameters read from device memory.
     What base_kernel_matrix computes for this family without the (n, c, d) difference tensor per component under autograd; the same
-    convention at zero distance (_SqrtZeroGrad)."""
+    convention at zero distance (_SqrtZeroGrad).  Up to 32 columns a thread per pair; from 33 to 4096 columns, with at most 64 landmarks, the
+    d-deep contractions run on the float64 matrix cores (csrc/lr_cross_spectral_kernel.hpp): a landmark gathered from the points is at distance
+    and phase exactly 0 from its point, the reverse pass repeats bit for bit, and a point whose upstream gradients are all zero gets an exactly
+    zero gradient row and takes no part in the other four gradients whatever it holds (the padded rows of a ragged batch).  NotImplementedError
+    beyond those limits."""
 
     @staticmethod
     def forward(ctx, P, S, alpha, omega, gamma, family):
@@ -1051,6 +1055,22 @@ def _lr_route(cc, r, d, M, L, spectral, dense, tens=None):
     return "kx" if not spectral and all(_lr_limits(cc, r, 0, M)) else "torch"
 
 
+def _lr_spectral_wide(cc, r, d, M, tens=None):
+    """Whether a low-rank SignatureSpectral feature map of d columns takes _SpectralCross and then _LrSeqFeaturesKx / _LrTensFeaturesKx (``tens`` =
+    (lt, E): of inducing tensors): 33 .. 4096 columns -- up to 32 the fused spectral ops and _lr_route decide, as they did -- within the limits of
+    the ops behind the cross matrix, which are _lr_route's for "kx": at most 64 components and 8 levels, a 64-step tile (a tensor's arrays) of
+    max(cc, r) rows inside the LDS.  With per-sequence lengths or without, whatever ``lr_spectral_tiled`` says (that option selects the tiled
+    spectral instances, which stay at 32 columns).  No shape class is sent back to torch ops: tools/bench_lr_spectral_wide.py,
+    profiles/lowrank_spectral_wide.txt."""
+    if not 32 < d <= 4096:
+        return False
+    if tens is not None:
+        lt, E = tens
+        fits = 8 * (lt * E * 2 * cc + 2 * lt * cc + M * (M - 1) // 2 * r + 2 * max(cc, r) + 16) <= 156 * 1024
+        return lt == M * (M + 1) // 2 and _lr_limits(cc, r, 0, M)[0] and fits
+    return all(_lr_limits(cc, r, 0, M))
+
+
 class _LowRankScope:
     """One low-rank evaluation: landmarks gathered from the evaluation's scaled points, their whitening, and the level features of
     every input asked for (kept per tensor: Kzz, Kzx and Kxx of one call share them)."""
@@ -1073,12 +1093,19 @@ class _LowRankScope:
         self._seq, self._tens = {}, {}
 
     def _cross(self, pts):
-        """kappa(pts, landmarks): SignatureSpectral's through the HIP op (_SpectralCross) for CUDA tensors unless the module option
-        ``lr_hip`` is False; torch ops (_kappa) otherwise -- the in-tree checker of that op."""
+        """kappa(pts, landmarks): SignatureSpectral's through the HIP op (_SpectralCross: a thread per pair up to 32 columns, the matrix cores
+        from 33 to 4096 with at most 64 landmarks) for CUDA tensors unless the module option ``lr_hip`` is False; torch ops (_kappa) otherwise
+        -- the in-tree checker of that op."""
         mod = self.mod
         if mod.kern._base == "spectral" and getattr(mod, "lr_hip", True) and pts.is_cuda:
             return _SpectralCross.apply(pts, self.S, positive(mod.raw_alpha), positive(mod.raw_omega), positive(mod.raw_sgamma), mod.kern.family)
         return mod._kappa(pts, self.S)
+
+    def _kx_spec(self):
+        """What the ops behind the cross matrix read of the kernel: levels, difference and order.  Their entry points refuse the spectral base
+        kernel (it has no scalar parameter to hand them); they get the same levels under a family they take."""
+        s = self.mod._spec
+        return _Spec("rbf", s.num_levels, s.difference, order=s.order) if s.base == "spectral" else s
 
     def _nys(self, pts):
         return self._cross(pts) @ self.Wh                                                           # :59-61
@@ -1102,13 +1129,20 @@ class _LowRankScope:
         """seq() by the HIP ops, or None where they are not built for the shape: _LrSeqFeatures (ragged: _LrSeqFeaturesRagged), sequences beyond
         the LDS in time tiles; where only the number of columns keeps them out (_lr_route: "kx") _LrCross and _LrSeqFeaturesKx, with ``lengths`` or
         without.  SignatureSpectral: _LrSeqFeaturesSpectral for whole sequences; beyond them and for ragged batches
-        _LrSeqFeaturesSpectralRagged, with the module option ``lr_spectral_tiled`` alone.  The limits follow from the table's L, not from the
-        lengths."""
+        _LrSeqFeaturesSpectralRagged, with the module option ``lr_spectral_tiled`` alone; beyond 32 columns (_lr_spectral_wide) _SpectralCross
+        and _LrSeqFeaturesKx, with ``lengths`` or without.  The limits follow from the table's L, not from the lengths."""
         mod, kern = self.mod, self.mod.kern
         M, cc = kern.num_levels, int(self.S.shape[0])
         r = int(self.host_sketches[0].r) if self.host_sketches else int(kern.rank_bound)
         L, d = int(Xs.shape[1]), int(Xs.shape[2])
         spectral = kern._base == "spectral"
+        if spectral and _lr_spectral_wide(cc, r, d, M):                                             # wide state spaces: the spectral cross op, then the kx op
+            try:
+                kxs = self._cross(Xs.reshape(-1, d)).reshape(Xs.shape[0], L, cc)
+                Phi = _LrSeqFeaturesKx.apply(kxs, lengths, self.Wh, self._kx_spec(), self.host_sketches, r)
+            except NotImplementedError:
+                return None
+            return list(torch.split(Phi, [1, cc] + [r] * (M - 1), dim=1))
         # the whole-sequence spectral pair keeps the four (width, L) arrays of a sequence in LDS
         whole_fits = 8 * ((L + 63) // 64 * 64 + 1) * 4 * max(cc, r, d, 16) <= 156 * 1024
         spectral_whole = spectral and lengths is None and whole_fits
@@ -1178,7 +1212,8 @@ class _LowRankScope:
     def tens(self, Zs, increments):
         """signature_algs.py:194-222, kernels.py:285-311.  (lt, T[, 2], d') -> [(T, 1), (T, c), (T, r), ...].
         Through the fused HIP tensor kernel and its reverse pass (_LrTensFeatures; SignatureSpectral: _LrTensFeaturesSpectral) where they are
-        built, wide state spaces through _LrCross and _LrTensFeaturesKx (_lr_route); torch ops otherwise (more than 64 components, a tensor's
+        built, wide state spaces through _LrCross (SignatureSpectral beyond 32 columns: _SpectralCross, _lr_spectral_wide) and _LrTensFeaturesKx
+        (_lr_route); torch ops otherwise (more than 64 components, a tensor's
         arrays beyond the LDS whatever the number of columns, module option ``lr_hip = False`` or, for the
         tensors alone, ``lr_tens_hip = False``: A/B runs, tools/bench_lr_tens_train.py)."""
         key = id(Zs)
@@ -1188,9 +1223,14 @@ class _LowRankScope:
             r = int(self.host_sketches[0].r) if self.host_sketches else int(kern.rank_bound)
             lt, d, E = int(Zs.shape[0]), int(Zs.shape[-1]), 2 if increments else 1
             route = _lr_route(cc, r, d, M, 0, kern._base == "spectral", True, tens=(lt, E))
+            if kern._base == "spectral" and _lr_spectral_wide(cc, r, d, M, tens=(lt, E)):
+                route = "spectral-kx"
             if route != "torch":
                 try:
-                    if route == "kx":                                                               # wide state spaces: the cross matrix as an op of its own
+                    if route == "spectral-kx":                                                      # wide state spaces: the spectral cross op, then the kx op
+                        kzs = self._cross(Zs.reshape(-1, d)).reshape(*Zs.shape[:-1], cc)
+                        Phi = _LrTensFeaturesKx.apply(kzs, self.Wh, self._kx_spec(), self.host_sketches, r, increments)
+                    elif route == "kx":                                                             # wide state spaces: the cross matrix as an op of its own
                         kzs = _LrCross.apply(Zs.reshape(-1, d), self.S, mod.p0, mod._spec).reshape(*Zs.shape[:-1], cc)
                         Phi = _LrTensFeaturesKx.apply(kzs, self.Wh, mod._spec, self.host_sketches, r, increments)
                     elif kern._base == "spectral":

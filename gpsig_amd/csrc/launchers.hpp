@@ -193,6 +193,13 @@ int wide_lat_forward(gpsig_ctx* c, const gpsig_params* p, int d, const double* X
 int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Xs, const double* Ys, int64_t N1, int64_t N2, int L1, int L2, bool diag,
                       const double* G, double* gX, double* gY, double* g_base);
 
+// ---- lr_cross_spectral_inst.hip: gpsig_spectral_cross / gpsig_spectral_cross_grad beyond 32 columns (the entry points: spectral_cross_api.hip)
+int spectral_cross_wide(gpsig_ctx* c, int Q, int family, int d, const double* P, int64_t n, const double* S, int cc, const double* alpha,
+                        const double* omega, const double* gamma, double* K);
+int spectral_cross_wide_grad(gpsig_ctx* c, int Q, int family, int d, const double* P, int64_t n, const double* S, int cc, const double* alpha,
+                             const double* omega, const double* gamma, const double* G, double* dP, double* dS, double* dalpha, double* domega,
+                             double* dgamma);
+
 // ---- lowrank_solver.hip: rocSOLVER / rocBLAS, opened at first use --------------------------------------------------------------------
 bool solver_dsyevd(void** handle_slot, hipStream_t stream, int n, double* A, double* ev, double* work, int* info, std::string* err);
 bool solver_dgemm(void** handle_slot, hipStream_t stream, bool transA, bool transB, int m, int n, int k, double alpha, const double* A, int lda,

@@ -7,10 +7,13 @@
 //     The reverse pass: dP by one thread per point (landmarks wave-uniform); dS and the parameters -- sums over every pair -- by
 //     workgroups of (landmark, slice of the points) that reduce in LDS into per-workgroup partial sums, combined by a second pass in a
 //     fixed order: no atomics, two runs agree bit for bit.  Per-pair arithmetic: spectral_pair.hpp.
+//     These kernels serve d <= 32.  Beyond, up to 4096 columns and 64 landmarks, the two entry points hand over -- before anything else -- to the
+//     kernels on the float64 matrix cores (lr_cross_spectral_inst.hip, lr_cross_spectral_kernel.hpp).
 //   * spectral_cross_grad_launch: the same reverse pass for the low-rank training path's spectral entry points (lr_grad_api.hip), which
 //     hand over dkxs as G, partial sums in a buffer of their own and, for the second and later chunks of sequences, add to the outputs.
 //     spectral_cross_grad_len_launch: the same for sequences with per-sequence lengths, whose padded points take no part.
 #include "ctx.hpp"
+#include "launchers.hpp"
 #include "lr_fused_args.hpp"
 
 #include <type_traits>
@@ -241,6 +244,7 @@ extern "C" {
 
 int gpsig_spectral_cross(gpsig_ctx* c, int32_t Q, int32_t family, int32_t d, const double* P, int64_t n, const double* S, int32_t cc,
                          const double* alpha, const double* omega, const double* gamma, double* K) {
+    if (c && d > SPECTRAL_STRIDE) return spectral_cross_wide(c, Q, family, d, P, n, S, cc, alpha, omega, gamma, K);       // lr_cross_spectral_inst.hip
     CHK(cross_check(c, Q, family, d, n, cc));
     if (n == 0) return GPSIG_OK;
     if (!P || !S || !alpha || !omega || !gamma || !K) return fail(c, GPSIG_ERR_INVALID, "NULL pointer");
@@ -254,6 +258,7 @@ int gpsig_spectral_cross(gpsig_ctx* c, int32_t Q, int32_t family, int32_t d, con
 int gpsig_spectral_cross_grad(gpsig_ctx* c, int32_t Q, int32_t family, int32_t d, const double* P, int64_t n, const double* S, int32_t cc,
                               const double* alpha, const double* omega, const double* gamma, const double* G, double* dP, double* dS,
                               double* dalpha, double* domega, double* dgamma) {
+    if (c && d > SPECTRAL_STRIDE) return spectral_cross_wide_grad(c, Q, family, d, P, n, S, cc, alpha, omega, gamma, G, dP, dS, dalpha, domega, dgamma);
     CHK(cross_check(c, Q, family, d, n, cc));
     if (!dS || !dalpha || !domega || !dgamma) return fail(c, GPSIG_ERR_INVALID, "NULL pointer");
     if (n == 0) {

@@ -442,10 +442,17 @@ int gpsig_lr_tens_features_spectral_grad(gpsig_ctx* ctx, const gpsig_params* p, 
                                          void* gZ, double* gS, double* gWh, double* dalpha, double* domega, double* dgamma);
 /* SignatureSpectral's Nystrom cross matrix for the TRAINING path (kernels.py:921-942, low_rank_calculations.py:59): K (n, c) = kappa(P, S)
  * for points P (n, d) and landmarks S (c, d), the parameters alpha (Q), omega (Q, d), gamma (Q, d) read from DEVICE memory (they change at
- * every optimiser step: no trip through the host), family 0 = rbf, 1 = exp, 2 = mixed; 1 <= Q <= 64, d <= 32.  Device pointers, device-pointer
- * mode; asynchronous on the context's stream.
+ * every optimiser step: no trip through the host), family 0 = rbf, 1 = exp, 2 = mixed; 1 <= Q <= 64.  Device pointers, device-pointer
+ * mode; asynchronous on the context's stream.  Limits: d <= 32 with any c >= 1 (a thread per pair); 33 <= d <= 4096 with c <= 64 (the d-deep
+ * contractions on the float64 matrix cores: the squared distance of a component is xs + ss - 2 ip from three products accumulated in one
+ * order, the phase a difference of two, so a landmark that IS one of the points is at distance and phase exactly 0 from it); outside them
+ * GPSIG_ERR_UNSUPPORTED.
  * _grad: G = dL/dK (n, c) -> dP (n, d), dS (c, d), dalpha (Q), domega (Q, d), dgamma (Q, d), overwritten; deterministic (partial sums
- * combined in a fixed order).  The exponential envelope's sqrt has derivative 0 at zero distance (a point paired with itself). */
+ * combined in a fixed order, no floating-point atomics: two calls return the same bits).  The exponential envelope's sqrt has derivative 0 at
+ * zero distance (a point paired with itself).  n = 0 zeroes the four sums.  Beyond 32 columns also: scratch stays inside the context's chunk
+ * budget (wide_chunk_mb, else grad_scratch_mb) -- the points go in chunks whose sums are added in chunk order; the bits of dP do not depend
+ * on the budget --, and an element with G == 0 contributes nothing whatever its point holds: a point all of whose G are zero (the padded rows
+ * of a ragged batch: NaN in P, zeros in G) gets a dP row of exact zeros and takes no part in dS, dalpha, domega, dgamma. */
 int gpsig_spectral_cross(gpsig_ctx* ctx, int32_t Q, int32_t family, int32_t d, const double* P, int64_t n, const double* S, int32_t c,
                          const double* alpha, const double* omega, const double* gamma, double* K);
 int gpsig_spectral_cross_grad(gpsig_ctx* ctx, int32_t Q, int32_t family, int32_t d, const double* P, int64_t n, const double* S, int32_t c,
