@@ -119,6 +119,15 @@ def test_reverse_pass_repeats_bit_for_bit():
     e = relerr(capped[1], first[1])
     print("dS, eight shares against nine", e)
     assert e <= 1e-12, e
+    # and against something independent: the host reference of tests/cross_reference.py (np.longdouble closed forms)
+    import cross_reference
+    want = cross_reference.cross_grad("mix", Pn, Sn, G.cpu().numpy(), P0["mix"], 0.0)
+    for tag, got in (("nine shares", first), ("eight shares", capped)):
+        for name, a, b in zip(("dP", "dS", "g_base"), (got[0], got[1], got[2][0]), want):
+            a, b = a.cpu().numpy().astype(np.longdouble), np.asarray(b)
+            e = float(np.abs(a - b).max() / np.abs(b).max())
+            print("gradient against the host reference,", tag, name, e)
+            assert np.isfinite(a).all() and e <= 1e-9, (tag, name, e)
 
 
 def test_empty_batch_and_refusals():
