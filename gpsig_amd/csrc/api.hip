@@ -25,6 +25,7 @@
 #include "lr_fused_args.hpp"
 #include "lr_eval_tiled.hpp"
 #include "lr_eval_wide.hpp"
+#include "lr_eval_spectral_wide.hpp"
 #include "lr_draw_kernels.hpp"
 #include "seq_args.hpp"
 #include "seq_configs.hpp"
@@ -99,8 +100,9 @@ SeqLaunchFn seq_lookup_ho_matern_exact(int kind, int G, int C, int D, int M, int
 
 namespace {
 
-// low_rank: the low-rank entry points, whose float32 forms carry the spectral base kernel too
-int check_params(gpsig_ctx* c, const gpsig_params* p, bool low_rank = false) {
+// low_rank: the low-rank entry points, whose float32 forms carry the spectral base kernel too.  lr_wide: the entry points of low-rank mode that
+// serve SignatureSpectral beyond the SPECTRAL_STRIDE columns of its packed table for a kernel object that opts in (base_params[2] != 0)
+int check_params(gpsig_ctx* c, const gpsig_params* p, bool low_rank = false, bool lr_wide = false) {
     if (!c) return GPSIG_ERR_INVALID;
     if (!p) return fail(c, GPSIG_ERR_INVALID, "params is NULL");
     if (p->dtype != GPSIG_F64 && p->dtype != GPSIG_F32) return fail(c, GPSIG_ERR_INVALID, "unknown dtype %d", p->dtype);
@@ -112,7 +114,8 @@ int check_params(gpsig_ctx* c, const gpsig_params* p, bool low_rank = false) {
     if (p->base_kernel == GPSIG_BASE_SPECTRAL) {
         const int Q = int(p->base_params[0]), fam = int(p->base_params[1]);
         if (Q < 1 || Q > 64 || fam < 0 || fam > 2) return fail(c, GPSIG_ERR_INVALID, "spectral kernel: bad number of components / family");
-        if (p->num_features > SPECTRAL_STRIDE) return fail(c, GPSIG_ERR_UNSUPPORTED, "the spectral base kernel is built for at most %d features", int(SPECTRAL_STRIDE));
+        if (p->num_features > SPECTRAL_STRIDE && !(lr_wide && p->base_params[2] != 0.0))
+            return fail(c, GPSIG_ERR_UNSUPPORTED, "the spectral base kernel is built for at most %d features", int(SPECTRAL_STRIDE));
         if (!p->base_table || p->base_table_len != int64_t(Q) * (1 + 2 * p->num_features))
             return fail(c, GPSIG_ERR_INVALID, "spectral kernel: base_table must hold alpha[Q], omega[Q][d], gamma[Q][d]");
         if (p->lengthscales || p->num_lags != 0)
@@ -163,6 +166,7 @@ int spectral_table(gpsig_ctx* c, const gpsig_params* p, const double** dev) {
     *dev = nullptr;
     if (p->base_kernel != GPSIG_BASE_SPECTRAL) return GPSIG_OK;
     const int Q = int(p->base_params[0]), d = p->num_features;
+    if (d > SPECTRAL_STRIDE) return fail(c, GPSIG_ERR_UNSUPPORTED, "the spectral base kernel's packed table holds at most %d features", int(SPECTRAL_STRIDE));
     std::vector<double> h(size_t(Q) * (1 + 2 * SPECTRAL_STRIDE), 0.0);
     for (int q = 0; q < Q; ++q) {
         h[q] = p->base_table[q];
@@ -183,6 +187,48 @@ int spectral_table(gpsig_ctx* c, const gpsig_params* p, const double** dev) {
         c->last_spec = h;
     }
     *dev = static_cast<const double*>(dp);
+    return GPSIG_OK;
+}
+
+// BASE_SPECTRAL beyond SPECTRAL_STRIDE columns with the kernel object's opt-in: the calls that take the kernels of lr_eval_spectral_wide_inst.hip
+bool spectral_wide(const gpsig_params* p) {
+    return p->base_kernel == GPSIG_BASE_SPECTRAL && p->base_params[2] != 0.0 && p->num_features > SPECTRAL_STRIDE;
+}
+
+// ... and their table: alpha[Q], omega[Q][d], gamma[Q][d] as the caller holds it, on the device in B_SPECW.  Compared in full and uploaded only
+// when changed, as spectral_table above; a change refuses the replays of recorded graphs in the same way.
+int spectral_table_wide(gpsig_ctx* c, const gpsig_params* p, const double** dev) {
+    const size_t n = size_t(p->base_table_len);
+    void* dp;
+    CHK(ensure(c, B_SPECW, sizeof(double) * n, &dp));
+    if (!(c->spec_wide_base == dp && c->last_spec_wide.size() == n && memcmp(c->last_spec_wide.data(), p->base_table, sizeof(double) * n) == 0)) {
+        CHK(no_capture(c, "the spectral kernel's table changed"));
+        ++c->alloc_gen;                  // a recorded graph read the old contents of this buffer: its replays are refused from here on
+        c->spec_wide_base = nullptr;
+        c->last_spec_wide.assign(p->base_table, p->base_table + n);
+        HIPCHK(c, hipMemcpyAsync(dp, c->last_spec_wide.data(), sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+        CHK(host_sync(c));
+        c->spec_wide_base = dp;
+    }
+    *dev = static_cast<const double*>(dp);
+    return GPSIG_OK;
+}
+
+// kappa(A, B) (na, nb) of rows of d columns for a landmark Gram (gpsig_lr_whitening, gpsig_lr_draw, gpsig_base_kernel_matrix): the thread-per-pair
+// kernel of every family on the packed table, or -- spectral_wide -- its twin with row stride d
+int landmark_gram(gpsig_ctx* c, const gpsig_params* p, const double* A, const double* B, int64_t na, int64_t nb, int d, double* out) {
+    if (spectral_wide(p)) {
+        const double* tab;
+        CHK(spectral_table_wide(c, p, &tab));
+        const int rc = lr_spx_gram_launch(c->stream, A, B, na, nb, d, int(p->base_params[0]), int(p->base_params[1]), tab, out);
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral landmark Gram: %s", hipGetErrorString(hipError_t(rc)));
+        return GPSIG_OK;
+    }
+    const double* spec;
+    CHK(spectral_table(c, p, &spec));
+    hipLaunchKernelGGL(base_kernel_matrix_kernel<double>, dim3(grid_for(na * nb)), dim3(256), 0, c->stream, A, B, na, nb, d, int(p->base_kernel),
+                       p->base_params[0], p->base_params[1], spec, out);
+    HIPCHK(c, hipGetLastError());
     return GPSIG_OK;
 }
 
@@ -213,8 +259,11 @@ int upload_weights(gpsig_ctx* c, const gpsig_params* p, const double** w) {
 #define ENTER(c, p)                         \
     CHK(check_params((c), (p)));            \
     HIPCHK((c), hipSetDevice((c)->device));
-#define ENTER_LR(c, p)                      \
-    CHK(check_params((c), (p), true));      \
+#define ENTER_LR(c, p)                       \
+    CHK(check_params((c), (p), true, true)); \
+    HIPCHK((c), hipSetDevice((c)->device));
+#define ENTER_GRAM(c, p)                      \
+    CHK(check_params((c), (p), false, true)); \
     HIPCHK((c), hipSetDevice((c)->device));
 
 
@@ -707,9 +756,10 @@ size_t lr_wide_chunk_bytes(const gpsig_ctx* c) {     // (as lr_cross_inst.hip: c
 
 // what both wide routes set up: the feature kernels' view of the state (lr_state_args: float32 narrowed once per call), |S_i|^2 in B_LR3, the
 // chunk (objects of `per` bytes of kxs each) and its buffer
+// (`norms` false: SignatureSpectral's wide route, which has norms of its own per component -- A then only carries the kxs buffer)
 template <typename T, typename Entry>
 int lr_wide_open(gpsig_ctx* c, const gpsig_params* p, const LrDev& D, int d_eff, int64_t count, size_t per, LrEvalWideFeat<T, Entry>* W,
-                 LrCrossEvalArgs<T>* A, int64_t* chunk) {
+                 LrCrossEvalArgs<T>* A, int64_t* chunk, bool norms = true) {
     std::conditional_t<std::is_same<T, float>::value, LrEvalTiledArgsF32, LrEvalTiledArgs> st{};
     CHK(lr_state_args(c, p, D, d_eff, nullptr, &st));
     W->Wh = st.Wh;
@@ -726,7 +776,7 @@ int lr_wide_open(gpsig_ctx* c, const gpsig_params* p, const LrDev& D, int d_eff,
     A->sn = static_cast<const double*>(sn);
     A->K = static_cast<T*>(kxs);
     W->kxs = static_cast<const T*>(kxs);
-    if (count > 0) {
+    if (count > 0 && norms) {
         const int rc = lr_cross_norms_launch(c->stream, D.S, D.c, d_eff, static_cast<double*>(sn));
         if (rc != 0) return fail(c, GPSIG_ERR_HIP, "Nystrom cross kernel (landmark norms): %s", hipGetErrorString(hipError_t(rc)));
     }
@@ -784,6 +834,98 @@ int lr_tens_features_wide(gpsig_ctx* c, const gpsig_params* p, const ScaleParams
     return finish(c);
 }
 
+// ---- The same two routes for SignatureSpectral beyond the 32 columns of its packed table (spectral_wide: the kernel object opts in; which calls:
+// lr_spectral_eval_wide / lr_spectral_eval_tens_wide, lr_tile_plan.hpp).  The cross matrix comes from the evaluation form of the spectral cross
+// kernel (lr_eval_spectral_wide_inst.hip), which computes the points' phases in its own walk; gamma^2 and the landmarks' norms and phases are
+// the training op's kernels on S, once per call, in B_LR4.  Buffer, chunks and feature kernels are those of the routes above.
+int lr_spectral_wide_refused(gpsig_ctx* c, LrSpectralWide w, bool tensors, size_t lds) {
+    const int lo = int(SPECTRAL_STRIDE), hi = LR_EVAL_WIDE_MAX_D;
+    switch (w) {
+    case LR_SPX_F32: return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank SignatureSpectral features beyond %d columns are built for float64 only", lo);
+    case LR_SPX_COMPONENTS:
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank SignatureSpectral features beyond %d columns are built for num_components <= %d", lo, LR_EVAL_WIDE_MAX_C);
+    case LR_SPX_LEVELS:
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank SignatureSpectral features beyond %d columns are built for num_levels <= %d", lo, LR_FUSED_MAX_SKETCHES + 1);
+    case LR_SPX_COLUMNS: return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank SignatureSpectral features are built for at most %d columns", hi);
+    case LR_SPX_TENSORS: return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank SignatureSpectral tensor features beyond %d columns take at most 2^31 - 1 tensors", lo);
+    default: break;
+    }
+    if (tensors)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank SignatureSpectral tensor features beyond %d columns need a tensor's kzs arrays (%zu bytes) within %zu "
+                    "bytes of LDS", lo, lds, LR_TENS_FUSED_MAX_LDS);
+    return fail(c, GPSIG_ERR_UNSUPPORTED, "low-rank SignatureSpectral features beyond %d columns need one 64-step tile of max(num_components, rank_bound) "
+                "rows in the LDS (%zu bytes of %zu)", lo, lds, LR_FUSED_MAX_LDS);
+}
+
+// what both set up behind lr_wide_open: the table, gamma^2 and the landmarks' norms and phases
+int lr_spectral_wide_open(gpsig_ctx* c, const gpsig_params* p, const LrDev& D, int64_t count, LrSpxEvalArgs* A) {
+    const int Q = int(p->base_params[0]), d = p->num_features;
+    const double* tab;
+    CHK(spectral_table_wide(c, p, &tab));
+    void* head;
+    CHK(ensure(c, B_LR4, sizeof(double) * (size_t(Q) * d + 2 * size_t(Q) * D.c) + 64, &head));
+    double* const g2 = static_cast<double*>(head);
+    A->d = d; A->S = D.S; A->c = D.c; A->Q = Q; A->family = int(p->base_params[1]);
+    A->alpha = tab; A->omega = tab + Q;
+    A->g2 = g2; A->ss = g2 + size_t(Q) * d; A->phS = A->ss + size_t(Q) * D.c;
+    if (count > 0) {
+        const int rc = spectral_cross_prepare_launch(c->stream, D.S, D.c, d, Q, A->omega, tab + Q + size_t(Q) * d, g2);
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral cross kernel (landmark norms and phases): %s", hipGetErrorString(hipError_t(rc)));
+    }
+    return GPSIG_OK;
+}
+
+int lr_seq_features_spectral_wide(gpsig_ctx* c, const gpsig_params* p, const LrDev& D, const double* dX, int64_t N, int32_t L, const int32_t* dlen,
+                                  void* Phi, void* dPhi) {
+    const int F = 1 + D.c + (p->num_levels - 1) * D.r, d = p->num_features;
+    LrEvalWideFeat<double, LrEntry> W{};
+    LrCrossEvalArgs<double> B{};
+    int64_t chunk;
+    CHK(lr_wide_open(c, p, D, d, N, sizeof(double) * size_t(L) * D.c, &W, &B, &chunk, false));
+    LrSpxEvalArgs A{};
+    CHK(lr_spectral_wide_open(c, p, D, N, &A));
+    A.L = L; A.K = B.K;
+    W.L = L;
+    for (int64_t n0 = 0; n0 < N; n0 += chunk) {
+        const int64_t nn = std::min<int64_t>(chunk, N - n0);
+        A.X = dX + n0 * int64_t(L) * d; A.n = nn * L;
+        A.lengths = dlen ? dlen + n0 : nullptr;
+        int rc = lr_spx_eval_seq_launch(c->stream, A);
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral cross kernel (evaluation form): %s", hipGetErrorString(hipError_t(rc)));
+        W.N = nn; W.lengths = A.lengths;
+        W.Phi = static_cast<double*>(dPhi) + n0 * int64_t(F);
+        rc = lr_eval_wide_seq_launch(c->stream, W, c->lr_fused_pad);
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "tiled low-rank feature kernel (kxs from memory): %s", hipGetErrorString(hipError_t(rc)));
+    }
+    CHK(out_done(c, Phi, dPhi, sizeof(double) * size_t(N) * F));
+    return finish(c);
+}
+
+int lr_tens_features_spectral_wide(gpsig_ctx* c, const gpsig_params* p, const LrDev& D, const double* dZ, int64_t T_, int lt, int E, void* Phi,
+                                   void* dPhi) {
+    const int F = 1 + D.c + (p->num_levels - 1) * D.r, d = p->num_features;
+    LrEvalWideFeat<double, LrEntry> W{};
+    LrCrossEvalArgs<double> B{};
+    int64_t chunk;
+    CHK(lr_wide_open(c, p, D, d, T_, sizeof(double) * size_t(lt) * E * D.c, &W, &B, &chunk, false));
+    LrSpxEvalArgs A{};
+    CHK(lr_spectral_wide_open(c, p, D, T_, &A));
+    A.X = dZ; A.T = T_; A.E = E; A.K = B.K;
+    W.L = lt; W.E = E;
+    for (int64_t t0 = 0; t0 < T_; t0 += chunk) {
+        const int64_t nt = std::min<int64_t>(chunk, T_ - t0);
+        A.t0 = t0; A.nt = nt; A.n = int64_t(lt) * nt * E;
+        int rc = lr_spx_eval_tens_launch(c->stream, A);
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral cross kernel (evaluation form, tensors): %s", hipGetErrorString(hipError_t(rc)));
+        W.N = nt;
+        W.Phi = static_cast<double*>(dPhi) + t0 * int64_t(F);
+        rc = lr_eval_wide_tens_launch(c->stream, W);
+        if (rc != 0) return fail(c, GPSIG_ERR_HIP, "fused low-rank tensor feature kernel (kzs from memory): %s", hipGetErrorString(hipError_t(rc)));
+    }
+    CHK(out_done(c, Phi, dPhi, sizeof(double) * size_t(T_) * F));
+    return finish(c);
+}
+
 // gpsig_lr_seq_features / gpsig_lr_seq_features_ragged in T.  Whole sequences (`ragged` false): the fused kernels (lr_fused_kernel.hpp: one
 // workgroup per sequence, intermediates in LDS) where a sequence's arrays fit; beyond them, with lr_fused != 0, the time-tiled kernels of
 // lr_eval_tiled.hpp where at least one 64-step tile fits (float32: the families of base_eval only); beyond those the wide route above (the
@@ -801,6 +943,21 @@ int lr_seq_features_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* 
     ScaleParams s;
     CHK(scale_params(c, p, true, &s));
     const int d_eff = s.d_eff();
+    if (spectral_wide(p)) {                  // one route, dense or ragged, at any lr_fused
+        const LrSpectralWide w = lr_spectral_eval_wide(f32, cc, r, d_eff, L, M, p->difference, c->lr_fused_pad);
+        if (w != LR_SPX_WIDE) return lr_spectral_wide_refused(c, w, false, lr_eval_tiled_lds_bytes(false, cc, r, 0, LR_TILE_STEP, c->lr_fused_pad));
+        if constexpr (!f32) {
+            LrDev D;
+            CHK(lr_upload(c, lr, d_eff, &D));
+            const void* dX;
+            CHK(in_dev(c, B_IN0, X, sizeof(T) * size_t(N) * L * d_eff, &dX));
+            const void* dlen = nullptr;
+            if (ragged) CHK(in_dev(c, B_IN1, lengths, sizeof(int32_t) * size_t(N), &dlen));
+            void* dPhi;
+            CHK(out_dev(c, B_OUT0, Phi, sizeof(T) * size_t(N) * (1 + cc + (M - 1) * r), &dPhi));
+            return lr_seq_features_spectral_wide(c, p, D, static_cast<const double*>(dX), N, L, static_cast<const int32_t*>(dlen), Phi, dPhi);
+        }
+    }
     // two arrays in LDS instead of three where a wavefront can hold its output columns in registers (lr_fused2): a third workgroup per CU
     const bool two = c->lr_fused == 1 && lr_fused2_ok(cc, r, L);
     const size_t lds = !f32 ? lr_fused_lds_bytes(cc, r, d_eff, L, c->lr_fused_pad)
@@ -863,6 +1020,20 @@ int lr_tens_features_t(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank*
     ScaleParams s;
     CHK(scale_params(c, p, true, &s));
     const int d_eff = s.d_eff();
+    if (spectral_wide(p)) {
+        const LrSpectralWide w = lr_spectral_eval_tens_wide(f32, cc, r, d_eff, M, E, T_);
+        if (w != LR_SPX_WIDE) return lr_spectral_wide_refused(c, w, true, lr_tens_fused_lds_bytes(cc, r, 0, lt, E));
+        if constexpr (!f32) {
+            LrDev D;
+            CHK(lr_upload(c, lr, d_eff, &D));
+            const void* dZ;
+            CHK(in_dev(c, B_IN0, Z, sizeof(T) * size_t(lt) * T_ * E * d_eff, &dZ));
+            void* dPhi;
+            CHK(out_dev(c, B_OUT0, Phi, sizeof(T) * size_t(T_) * (1 + cc + (M - 1) * r), &dPhi));
+            if (T_ <= 0) return finish(c);
+            return lr_tens_features_spectral_wide(c, p, D, static_cast<const double*>(dZ), T_, lt, E, Phi, dPhi);
+        }
+    }
     const size_t lds = f32 ? lr_tens_fused_lds_bytes_f32(cc, r, d_eff, lt, E) : lr_tens_fused_lds_bytes(cc, r, d_eff, lt, E);
     const LrEvalRoute route = lr_eval_tens_route(f32, cc, r, d_eff, M, E, c->lr_fused, p->base_kernel == GPSIG_BASE_SPECTRAL, T_);
     const bool fused = route == LR_EVAL_FUSED;
@@ -2242,7 +2413,9 @@ static int e_symmetrize_compact_rows(gpsig_ctx* c, int32_t dtype, const void* ha
 }
 
 static int e_kernel_Kdiag(gpsig_ctx* c, const gpsig_params* p, const void* X, int64_t N, int32_t L, int32_t return_levels, void* out) {
-    ENTER(c, p);
+    // (normalised, the diagonal is sigma * variances and no base kernel runs: low-rank mode's normalised Kdiag comes here too, so a spectral
+    // kernel object that opted in beyond 32 columns passes -- its unnormalised diagonal is refused as every exact evaluation is)
+    if (p && p->normalization) { ENTER_GRAM(c, p); } else { ENTER(c, p); }
     const int M1 = p->num_levels + 1;
     const size_t ob = sizeof(TT) * size_t(N) * (return_levels ? M1 : 1);
     void* dout;
@@ -2897,7 +3070,7 @@ int gpsig_lr_gather_points(gpsig_ctx* c, const gpsig_params* p, const void* X, i
 
 int gpsig_base_kernel_matrix(gpsig_ctx* c, const gpsig_params* p, const double* A_host, const double* B_host, int64_t na, int64_t nb,
                              int32_t d, double* out_host) {
-    ENTER(c, p);
+    ENTER_GRAM(c, p);
     if (!A_host || !B_host || !out_host || na < 0 || nb < 0 || d < 1) return fail(c, GPSIG_ERR_INVALID, "bad base-kernel-matrix request");
     void *da, *db, *dout;
     CHK(ensure(c, B_LR2, sizeof(double) * size_t(na) * d + 8, &da));
@@ -2906,14 +3079,7 @@ int gpsig_base_kernel_matrix(gpsig_ctx* c, const gpsig_params* p, const double* 
     if (na > 0 && nb > 0) {
         HIPCHK(c, hipMemcpyAsync(da, A_host, sizeof(double) * size_t(na) * d, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(db, B_host, sizeof(double) * size_t(nb) * d, hipMemcpyHostToDevice, c->stream));
-        double p0, p1;
-        base_p(p, &p0, &p1);
-        const double* spec;
-        CHK(spectral_table(c, p, &spec));
-        hipLaunchKernelGGL(base_kernel_matrix_kernel<double>, dim3(grid_for(na * nb)), dim3(256), 0, c->stream,
-                           static_cast<const double*>(da), static_cast<const double*>(db), na, nb, int(d), int(p->base_kernel), p0, p1, spec,
-                           static_cast<double*>(dout));
-        HIPCHK(c, hipGetLastError());
+        CHK(landmark_gram(c, p, static_cast<const double*>(da), static_cast<const double*>(db), na, nb, int(d), static_cast<double*>(dout)));
         HIPCHK(c, hipMemcpyAsync(out_host, dout, sizeof(double) * size_t(na) * nb, hipMemcpyDeviceToHost, c->stream));
     }
     CHK(host_sync(c));
@@ -2922,7 +3088,7 @@ int gpsig_base_kernel_matrix(gpsig_ctx* c, const gpsig_params* p, const double* 
 
 int gpsig_lr_whitening(gpsig_ctx* c, const gpsig_params* p, const double* S_host, int32_t nc, int32_t d, const double* jitter_diag_host,
                        double* Wh_host, double* ev_host) {
-    ENTER(c, p);
+    ENTER_GRAM(c, p);
     if (!S_host || !jitter_diag_host || !Wh_host || nc < 1 || d < 1) return fail(c, GPSIG_ERR_INVALID, "bad whitening request");
     CHK(no_capture(c, "the Nystrom whitening copies to and from the host"));
     void *dS, *dW, *dJ, *dWh;
@@ -2935,15 +3101,9 @@ int gpsig_lr_whitening(gpsig_ctx* c, const gpsig_params* p, const double* S_host
     int* const dInfo = reinterpret_cast<int*>(static_cast<double*>(dJ) + 3 * size_t(nc));
     HIPCHK(c, hipMemcpyAsync(dS, S_host, sizeof(double) * size_t(nc) * d, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(dJ, jitter_diag_host, sizeof(double) * size_t(nc), hipMemcpyHostToDevice, c->stream));
-    double p0, p1;
-    base_p(p, &p0, &p1);
-    const double* spec;
-    CHK(spectral_table(c, p, &spec));
     const int64_t total = int64_t(nc) * nc;
-    hipLaunchKernelGGL(base_kernel_matrix_kernel<double>, dim3(grid_for(total)), dim3(256), 0, c->stream, static_cast<const double*>(dS),
-                       static_cast<const double*>(dS), int64_t(nc), int64_t(nc), int(d), int(p->base_kernel), p0, p1, spec,
-                       static_cast<double*>(dW));                                                         // low_rank_calculations.py:51
-    HIPCHK(c, hipGetLastError());
+    CHK(landmark_gram(c, p, static_cast<const double*>(dS), static_cast<const double*>(dS), int64_t(nc), int64_t(nc), int(d),
+                      static_cast<double*>(dW)));                                                          // low_rank_calculations.py:51
     hipLaunchKernelGGL(add_diag_kernel, dim3((nc + 255) / 256), dim3(256), 0, c->stream, static_cast<double*>(dW),
                        static_cast<const double*>(dJ), int(nc));
     HIPCHK(c, hipGetLastError());
@@ -3067,13 +3227,7 @@ int gpsig_lr_draw(gpsig_ctx* c, const gpsig_params* p, int32_t num_components, i
     HIPCHK(c, hipStreamWaitEvent(c->side_stream, c->side_fork, 0));
     hipStream_t const ss = c->side_stream;
     // W = kappa(S, S) + diag(jd)                                                          low_rank_calculations.py:51-52
-    double p0, p1;
-    base_p(p, &p0, &p1);
-    const double* spec;
-    CHK(spectral_table(c, p, &spec));
-    hipLaunchKernelGGL(base_kernel_matrix_kernel<double>, dim3(grid_for(int64_t(cc) * cc)), dim3(256), 0, c->stream, static_cast<const double*>(st->S),
-                       static_cast<const double*>(st->S), int64_t(cc), int64_t(cc), d_eff, int(p->base_kernel), p0, p1, spec, st->W);
-    HIPCHK(c, hipGetLastError());
+    CHK(landmark_gram(c, p, static_cast<const double*>(st->S), static_cast<const double*>(st->S), int64_t(cc), int64_t(cc), d_eff, st->W));
     hipLaunchKernelGGL(add_diag_kernel, dim3((cc + 255) / 256), dim3(256), 0, c->stream, st->W, static_cast<const double*>(st->jd), cc);
     HIPCHK(c, hipGetLastError());
     // eigendecomposition (:55), sign convention, U / sqrt(S + jitter) (:56-57, :60)

@@ -41,6 +41,7 @@ enum BufId {
     B_SF0, B_SF1, B_SF2, B_SF3, B_SF4, B_SF5,                               // explicit level features (sig_feat_kernel.hpp): both sides, partial products, level diagonals                              // weighted tensor-vs-sequence sums: partial factor gradients; level arrays of the fallback
     B_SPEC,                                                    // spectral base-kernel table
     B_SPECD, B_LRDK,                                           // low-rank spectral training path (lr_grad_api.hip): the table packed on the device, dkxs
+    B_SPECW,                                                   // ... in its own (Q, d) layout, for the low-rank evaluation side beyond 32 columns (api.hip: spectral_table_wide)
     B_LRF32,                                                   // low-rank mode, float32 calls: the state and the spectral table narrowed to float32
     B_TQ,                                                      // item counters of the Kzx tile kernel's persistent launch
     B_STASH,                                                   // what the fused reverse kernel needs of the forward recursion (gpsig_seq_gram_levels_stash)
@@ -139,6 +140,8 @@ struct gpsig_ctx {
     void* ls_base = nullptr;
     std::vector<double> last_spec;         // what B_SPEC currently holds (SignatureSpectral's parameter table)
     void* spec_base = nullptr;
+    std::vector<double> last_spec_wide;    // what B_SPECW currently holds
+    void* spec_wide_base = nullptr;
     // low-rank mode: what B_LR0 / B_LR1 currently hold (keyed by content: the random objects of an evaluation are handed to several
     // calls -- tensor features, sequence features, products -- and every upload was a host synchronisation)
     UploadCache lr_cache;                  // B_LR0: landmarks, whitening and projections (lr_upload, api.hip)

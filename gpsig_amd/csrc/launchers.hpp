@@ -199,6 +199,9 @@ int spectral_cross_wide(gpsig_ctx* c, int Q, int family, int d, const double* P,
 int spectral_cross_wide_grad(gpsig_ctx* c, int Q, int family, int d, const double* P, int64_t n, const double* S, int cc, const double* alpha,
                              const double* omega, const double* gamma, const double* G, double* dP, double* dS, double* dalpha, double* domega,
                              double* dgamma);
+// what both, and the evaluation side's wide spectral route (lr_eval_spectral_wide_inst.hip), compute once per call, at `head` (Q d + 2 Q c doubles):
+// gamma^2 (Q, d), the landmarks' norms sum_f g2_qf s_if^2 (Q, c) and their phases phi_q(S_i) (Q, c).  Returns the hipError_t of the launches.
+int spectral_cross_prepare_launch(hipStream_t stream, const double* S, int cc, int d, int Q, const double* omega, const double* gamma, double* head);
 
 // ---- lowrank_solver.hip: rocSOLVER / rocBLAS, opened at first use --------------------------------------------------------------------
 bool solver_dsyevd(void** handle_slot, hipStream_t stream, int n, double* A, double* ev, double* work, int* info, std::string* err);

@@ -46,22 +46,27 @@ unsigned points_grid(int64_t n) {
 // what a call computes once: gamma^2, the landmarks' norms and phases, at `head` (Q d + 2 Q c doubles)
 int prepare(gpsig_ctx* c, LrSpxArgs* A, const double* gamma, double* head) {
     const int Q = A->Q, d = A->d, cc = A->c;
-    double* const g2 = head;
-    double* const ss = g2 + size_t(Q) * d;
-    double* const phS = ss + size_t(Q) * cc;
-    hipLaunchKernelGGL(lr_spx_prep_kernel, dim3(unsigned((int64_t(Q) * d + 255) / 256)), dim3(256), 0, c->stream, gamma, int64_t(Q) * d, g2);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(lr_spx_norms_kernel, dim3(unsigned((cc + 15) / 16), unsigned(Q)), dim3(64), 0, c->stream, A->S, cc, d, g2, ss);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(lr_spx_phase_kernel, dim3(points_grid(cc)), dim3(LR_CROSS_THREADS), 0, c->stream, A->S, int64_t(cc), d, A->omega, Q, phS);
-    HIPCHK(c, hipGetLastError());
-    A->g2 = g2; A->ss = ss; A->phS = phS;
+    const int rc = spectral_cross_prepare_launch(c->stream, A->S, cc, d, Q, A->omega, gamma, head);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "%s", hipGetErrorString(hipError_t(rc)));
+    A->g2 = head; A->ss = head + size_t(Q) * d; A->phS = A->ss + size_t(Q) * cc;
     return GPSIG_OK;
 }
 
 }  // namespace
 
 namespace gpsig {
+
+int spectral_cross_prepare_launch(hipStream_t stream, const double* S, int cc, int d, int Q, const double* omega, const double* gamma, double* head) {
+    double* const g2 = head;
+    double* const ss = g2 + size_t(Q) * d;
+    double* const phS = ss + size_t(Q) * cc;
+    hipLaunchKernelGGL(lr_spx_prep_kernel, dim3(unsigned((int64_t(Q) * d + 255) / 256)), dim3(256), 0, stream, gamma, int64_t(Q) * d, g2);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return int(e);
+    hipLaunchKernelGGL(lr_spx_norms_kernel, dim3(unsigned((cc + 15) / 16), unsigned(Q)), dim3(64), 0, stream, S, cc, d, static_cast<const double*>(g2), ss);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return int(e);
+    hipLaunchKernelGGL(lr_spx_phase_kernel, dim3(points_grid(cc)), dim3(LR_CROSS_THREADS), 0, stream, S, int64_t(cc), d, omega, Q, phS);
+    return int(hipGetLastError());
+}
 
 int spectral_cross_wide(gpsig_ctx* c, int Q, int family, int d, const double* P, int64_t n, const double* S, int cc, const double* alpha,
                         const double* omega, const double* gamma, double* K) {

@@ -1,5 +1,6 @@
 // lr_tile_plan.hpp -- LDS footprints of the low-rank sequence feature kernels and the time-tile plan of their tiled forms.
-// Also: the footprints of the other evaluation kernels and the predicates that pick an evaluation call's route (lr_eval_route, lr_eval_tens_route).
+// Also: the footprints of the other evaluation kernels and the predicates that pick an evaluation call's route (lr_eval_route, lr_eval_tens_route;
+// SignatureSpectral beyond 32 columns: lr_spectral_eval_wide, lr_spectral_eval_tens_wide, tests/emu/test_lr_spectral_eval_route.cpp).
 // HIP-free (constexpr helpers are usable on the device): read by lr_fused_args.hpp / lr_grad_kernel.hpp (the whole-sequence kernels),
 // lr_tiled_kernel.hpp, lr_eval_tiled_inst.hip, the host paths of lr_grad_api.hip and api.hip, tests/emu/test_lr_tile_plan.cpp and
 // tests/emu/test_lr_eval_route.cpp.
@@ -163,6 +164,39 @@ inline LrEvalRoute lr_eval_tens_route(bool f32, int c, int r, int d, int M, int 
         (f32 ? lr_tens_fused_lds_bytes_f32(c, r, 0, lt, E) : lr_tens_fused_lds_bytes(c, r, 0, lt, E)) <= LR_TENS_FUSED_MAX_LDS)
         return LR_EVAL_WIDE;
     return f32 ? LR_EVAL_REFUSE : LR_EVAL_PASSES;
+}
+
+// ---- SignatureSpectral beyond the 32 columns of its packed table, for a kernel object that opts in (gpsig_params.base_params[2] != 0).  api.hip
+// asks these two only for GPSIG_BASE_SPECTRAL with the flag set and d > 32; every other call is lr_eval_route's / lr_eval_tens_route's, which
+// answer as they did.  There is one route at these widths -- the evaluation form of the spectral cross kernel (lr_eval_spectral_wide_inst.hip),
+// then the feature kernels that take kxs / kzs from memory, as WIDE above -- for dense and ragged calls and at any lr_fused, 0 included: the
+// multi-pass route has no form here.  LR_SPX_WIDE: the call takes it; any other value names the bound that refuses it (GPSIG_ERR_UNSUPPORTED).
+enum LrSpectralWide {
+    LR_SPX_WIDE = 0,
+    LR_SPX_F32,          // float64 only (the Python layer computes a float32 call in float64 and rounds)
+    LR_SPX_COMPONENTS,   // c <= 64: the cross kernel's four accumulator tiles
+    LR_SPX_LEVELS,       // M <= 8
+    LR_SPX_COLUMNS,      // d <= 4096
+    LR_SPX_TILE,         // sequences: a 64-step tile of max(c, r) rows in the LDS; tensors: the kx footprint within 64 KB
+    LR_SPX_TENSORS       // T <= 2^31 - 1
+};
+inline LrSpectralWide lr_spectral_eval_common(bool f32, int c, int d, int M) {
+    if (f32) return LR_SPX_F32;
+    if (c > LR_EVAL_WIDE_MAX_C) return LR_SPX_COMPONENTS;
+    if (M - 1 > LR_FUSED_MAX_SKETCHES) return LR_SPX_LEVELS;
+    if (d > LR_EVAL_WIDE_MAX_D) return LR_SPX_COLUMNS;
+    return LR_SPX_WIDE;
+}
+inline LrSpectralWide lr_spectral_eval_wide(bool f32, int c, int r, int d, int L, int M, int difference, int pad) {
+    const LrSpectralWide w = lr_spectral_eval_common(f32, c, d, M);
+    if (w != LR_SPX_WIDE) return w;
+    return lr_eval_tile_dir(false, c, r, 0, L - (difference ? 1 : 0), pad).TL > 0 ? LR_SPX_WIDE : LR_SPX_TILE;
+}
+inline LrSpectralWide lr_spectral_eval_tens_wide(bool f32, int c, int r, int d, int M, int E, int64_t T) {
+    const LrSpectralWide w = lr_spectral_eval_common(f32, c, d, M);
+    if (w != LR_SPX_WIDE) return w;
+    if (lr_tens_fused_lds_bytes(c, r, 0, M * (M + 1) / 2, E) > LR_TENS_FUSED_MAX_LDS) return LR_SPX_TILE;
+    return T <= 0x7fffffff ? LR_SPX_WIDE : LR_SPX_TENSORS;
 }
 
 // the reverse pass's E_i scratch per workgroup, in doubles (what the whole-sequence kernel takes as well)

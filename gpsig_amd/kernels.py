@@ -1012,9 +1012,13 @@ class SignatureSpectral(SignatureKernel):
         self.alpha = np.exp(np.random.randn(self.Q))                                                         # :919
         self.omega = np.exp(np.random.randn(self.Q, self.num_features))                                      # :920
         self.gamma = np.exp(np.random.randn(self.Q, self.num_features))                                      # :921
+        # low-rank mode beyond 32 columns on the library's own surface (K, Kdiag, K_tens*, K_seq_n_seq_covs, draw_low_rank, SVGP.predict_f): opt-in,
+        # float64, num_components <= 64; it travels to the library in base_params[2].  Exact mode keeps its 32 columns whatever this says.
+        self.lr_spectral_wide = False
 
     def _current_base_params(self):
-        return (float(self.Q), float(self._FAMILIES[self.family]))
+        bp = (float(self.Q), float(self._FAMILIES[self.family]))
+        return bp + (1.0,) if self.lr_spectral_wide else bp
 
     def _params(self, keep, dtype_id=_lib.F64):
         p = SignatureKernel._params(self, keep, dtype_id)

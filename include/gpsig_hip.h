@@ -50,7 +50,15 @@ enum gpsig_base_kernel {
     GPSIG_BASE_MATERN52 = 7,  /* SignatureMatern52  :991-993 */
     GPSIG_BASE_SPECTRAL = 8   /* SignatureSpectral  _spectral  :921-942  base_params = {Q, family (0 rbf, 1 exp, 2 mixed)};
                                  base_table = alpha[Q], omega[Q][d], gamma[Q][d]; needs lengthscales == NULL, num_lags == 0
-                                 (as the reference: :907, and its gamma clashes with the lag weights of :82) */
+                                 (as the reference: :907, and its gamma clashes with the lag weights of :82).
+                                 At most 32 features.  base_params[2] is the kernel object's OPT-IN to low-rank evaluation beyond
+                                 them: 0 (the default) refuses more than 32 features everywhere, as before; non-zero lets the low-rank
+                                 entry points -- gpsig_lr_seq_features, _ragged, gpsig_lr_tens_features, gpsig_lr_draw,
+                                 gpsig_lr_whitening, gpsig_lr_gather_points, gpsig_base_kernel_matrix, gpsig_lr_kernel / _diag and
+                                 the normalised gpsig_kernel_Kdiag (which runs no base kernel) -- take 33 .. 4096 features: float64,
+                                 num_components <= 64, num_levels <= 8 (see gpsig_lr_seq_features).  Up to 32 features the slot
+                                 changes nothing, and every exact (non-low-rank) evaluation keeps refusing more whatever it holds.
+                                 The opt-in is off until a follow-up flips the default. */
 };
 
 enum gpsig_dtype { GPSIG_F64 = 0, GPSIG_F32 = 1 };
@@ -329,7 +337,10 @@ typedef struct gpsig_lowrank {
  * projection per level 2..M; sparsity 0 'sqrt', 1 'log', 2 'lin'.  A counter-based generator (Philox-4x32-10) keyed by `seed`: the same
  * seed gives the same objects.  Device pointers; everything is queued on the ctx stream, nothing waits for the host.  *state: NULL to
  * create, or a state of this context to draw into again.  gpsig_lr_state_sizes / _export copy what was drawn to the host (for the
- * CPU restatement of the same evaluation); they wait for the stream. */
+ * CPU restatement of the same evaluation); they wait for the stream.
+ * SignatureSpectral beyond 32 features with the opt-in p->base_params[2] != 0: the landmark Gram here, in gpsig_lr_whitening and in
+ * gpsig_base_kernel_matrix comes from a thread-per-pair kernel on the table in its (Q, d) layout, in the difference form (symmetric; at most
+ * 64 landmarks are ever whitened for a state the feature entry points accept).  Without the opt-in refused, as before. */
 int gpsig_lr_draw(gpsig_ctx* ctx, const gpsig_params* p, int32_t num_components, int32_t rank_bound, int32_t sparsity, uint64_t seed,
                   const void* X, int64_t N, int32_t L, const void* X2, int64_t N2, int32_t L2, const void* Z, int64_t T,
                   int32_t increments, gpsig_lr_state** state);
@@ -504,7 +515,14 @@ int gpsig_lr_tens_features_kx_grad(gpsig_ctx* ctx, const gpsig_params* p, int32_
  * grad_scratch_mb), and the result does not depend on the chunk count.  It serves the families of base_eval at num_components <= 64,
  * num_levels <= 8 and d' <= 4096 wherever max(c, r) rows fit a tile.  lr_fused = 0, SignatureSpectral or num_components > 64 beyond the
  * tiled kernels: the multi-pass route (float64 only; float32: GPSIG_ERR_UNSUPPORTED), which streams five (N, L, max(c, r)) arrays of
- * context-owned scratch.  The rule is csrc/lr_tile_plan.hpp: lr_eval_route. */
+ * context-owned scratch.  The rule is csrc/lr_tile_plan.hpp: lr_eval_route.
+ * SignatureSpectral beyond 32 features: refused (GPSIG_ERR_UNSUPPORTED, "at most 32 features") unless p->base_params[2] != 0, the kernel
+ * object's opt-in (off by default).  With it, 33 .. 4096 features take ONE route, dense or ragged and at any lr_fused, 0 included: the
+ * evaluation form of the spectral cross kernel (csrc/lr_eval_spectral_wide_inst.hip: the d-deep contractions on the float64 matrix cores from
+ * the caller's raw points, the points' phases in the same walk, so that a landmark that is one of the points is at distance and phase exactly
+ * 0), then the feature kernels above that take the cross matrix from memory, in the same chunks.  Float64, num_components <= 64,
+ * num_levels <= 8, max(c, r) rows within a tile; outside that GPSIG_ERR_UNSUPPORTED with a message that names the bound -- float32 included
+ * (the Python layer computes such a call in float64 and rounds).  The rule is csrc/lr_tile_plan.hpp: lr_spectral_eval_wide. */
 int gpsig_lr_seq_features(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L, void* Phi);
 /* ... for a RAGGED batch: lengths (N int32, in the context's pointer mode like X; host pointers are copied in), sequence n is
  * X[n, :lengths[n]] and Phi[n] its features evaluated alone.  The rows beyond a sequence's length are never read (they may hold NaN);
@@ -513,13 +531,18 @@ int gpsig_lr_seq_features(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_low
  * in the cross kernel's operand and their rows of the cross matrix are never written), whatever lr_fused says; float64 and float32,
  * SignatureSpectral in float64 only.
  * GPSIG_ERR_UNSUPPORTED: p->num_lags > 0 (the lag interpolation runs on the table's own time axis), float32 SignatureSpectral, and shapes
- * whose 64-step tile exceeds the LDS where the wide route does not apply (SignatureSpectral, num_components > 64, max(c, r) rows beyond a tile). */
+ * whose 64-step tile exceeds the LDS where the wide route does not apply (SignatureSpectral, num_components > 64, max(c, r) rows beyond a tile).
+ * SignatureSpectral beyond 32 features with the opt-in p->base_params[2] != 0: the route of gpsig_lr_seq_features above -- the padded rows are
+ * zeros in the spectral cross kernel's operand, are never read or written, and a wavefront whose 16 rows are all padding skips its arithmetic. */
 int gpsig_lr_seq_features_ragged(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L,
                                  const int32_t* lengths, void* Phi);
 /* SignatureKernel._K_tens_lr_feat (kernels.py:285-311): Nystrom_map + tensor_kern_lr_feature.  Phi: (T, F).  With lr_fused != 0 one fused kernel
  * where a tensor's arrays -- 8 (lt E (d' + 2 c) + lt c + 2 max(c, r)) bytes, half in float32 -- fit 64 KB of LDS; where they do without the
  * points (d' = 0) the wide route as for sequences (the cross matrix of Z's points in their flat order, then the kx instance of the fused
- * kernel; tensors in chunks), for the families of base_eval at num_components <= 64; else the multi-pass route (float64 only). */
+ * kernel; tensors in chunks), for the families of base_eval at num_components <= 64; else the multi-pass route (float64 only).
+ * SignatureSpectral beyond 32 features with the opt-in p->base_params[2] != 0: the spectral cross kernel's evaluation form on Z's points in their
+ * flat order, then the kx instance of the fused kernel, under the bounds of gpsig_lr_seq_features with the kzs footprint (d' = 0) within 64 KB
+ * and T <= 2^31 - 1 (csrc/lr_tile_plan.hpp: lr_spectral_eval_tens_wide); without the opt-in refused, as before. */
 int gpsig_lr_tens_features(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_lowrank* lr, const void* Z, int64_t T,
                            int32_t increments, void* Phi);
 /* Kernel matrix from factors: level Grams PhiA_m PhiB_m^T (fp64 MFMA; float32 factors: v_mfma_f32_16x16x4_f32), optional per-side level normalisation
