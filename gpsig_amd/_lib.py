@@ -74,6 +74,7 @@ _KERNEL_FUNCS = {
     "gpsig_lr_whitening": [C.POINTER(C.c_double), _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "gpsig_lr_seq_features": [_LR, _vp, _i64, _i32, _vp],
     "gpsig_lr_seq_features_ragged": [_LR, _vp, _i64, _i32, _vp, _vp],
+    "gpsig_lr_seq_features_ragged_lagged": [_LR, _vp, _i64, _i32, _vp, _vp],
     "gpsig_lr_tens_features": [_LR, _vp, _i64, _i32, _vp],
     "gpsig_lr_seq_features_dev": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp],
     "gpsig_lr_seq_features_grad": [_i32, _i32, _i32, C.POINTER(SketchC), _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)],
@@ -110,6 +111,8 @@ _PLAIN = {
     "gpsig_abi_version": ([], C.c_int),
     "gpsig_spectral_cross": ([_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp], C.c_int),
     "gpsig_spectral_cross_grad": ([_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "gpsig_seq_lags_ragged_dev": ([_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp], C.c_int),
+    "gpsig_seq_lags_ragged_grad": ([_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp], C.c_int),
     "gpsig_lr_state_destroy": ([_vp], None),
     "gpsig_lr_state_sizes": ([_vp, _vp, C.POINTER(_i32), C.POINTER(_i32)], C.c_int),
     "gpsig_lr_state_export": ([_vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -690,6 +690,70 @@ def _add_lags(X, lags):
     return torch.cat((X[:, :, None, :], _lin_interp(time, X, time_lags)), dim=2)                    # :59-61
 
 
+def _add_lags_ragged(X, lags, lens):
+    """_add_lags for a ragged batch, each sequence on ITS OWN time axis: X (N, L, d), lags (p,), lens (N,) integers in [1, L] ->
+    (N, L, p+1, d).  Sequence n is X[n, :len_n] and nothing else: its axis is i / (len_n - 1), the query of lag j at observation t is
+    max(t / (len_n - 1) - lag_j, 0) (gpsig/lags.py:56-57), bracket and value are lags.py:20-33 -- row block n is _add_lags(X[n:n+1, :len_n]).
+    The output rows at or beyond len_n repeat output row len_n - 1 (the pool the landmarks are gathered from holds real points only); the
+    input rows there are never read (a gather of valid rows: nothing, NaN included, flows from or to them).  A sequence of ONE point has no
+    axis (0 / 0 in the reference's formula): its lagged copies are the point itself, and it adds exactly zero to the gradient of the lags.
+    Gather-based torch ops: the restatement and checker of _SeqLagsRagged, and the route of CPU tensors and of ``lr_hip = False``."""
+    N, L, d = X.shape
+    dev = X.device
+    lens = lens.to(device=dev, dtype=torch.long)
+    last = (lens - 1)[:, None]                                                                      # (N, 1)
+    te = torch.minimum(torch.arange(L, device=dev)[None, :], last)                                  # (N, L): rows >= len repeat row len - 1
+    rows = torch.arange(N, device=dev)[:, None]
+    one = last == 0                                                                                 # sequences of one point
+    denom = torch.where(one, torch.ones_like(last), last).to(X.dtype)                               # (N, 1); (their axis is never used)
+    tq = torch.clamp(te.to(X.dtype)[:, :, None] / denom[:, :, None] - lags[None, None, :], min=0.)  # :57 (N, L, p)
+    # left = the last i < len_n with not (i / (len_n - 1) - tq > jitter) (:20-22), found without the (N, L, L, p) table of _lin_interp: the
+    # floor of (tq + jitter) (len_n - 1), moved by one where the reference's own predicate says so (the product's rounding moves it no further)
+    dn, l3, q = denom[:, :, None], last[:, :, None], tq.detach()
+    late = lambda i: i.to(X.dtype) / dn - q > JITTER                                                # noqa: E731
+    i0 = torch.minimum(torch.clamp(torch.floor((q + JITTER) * dn).long(), min=0), l3)
+    left = torch.where(late(i0), i0 - 1, torch.where((i0 + 1 <= l3) & ~late(i0 + 1), i0 + 1, i0))   # (N, L, p)
+    right = torch.minimum(left + 1, l3)                                                             # :23
+    r3 = rows[:, :, None]
+    Xl, Xr = X[r3, left], X[r3, right]                                                              # :25-26 (N, L, p, d)
+    tl, tr = (left.to(X.dtype) / denom[:, :, None])[..., None], (right.to(X.dtype) / denom[:, :, None])[..., None]      # :28-29
+    one4 = one[:, :, None, None]
+    span = torch.where(one4, torch.ones_like(tr), tr - tl)
+    lagged = Xl + (tq[..., None] - tl) * (Xr - Xl) / span                                           # :33
+    lagged = torch.where(one4, X[rows, te][:, :, None, :].expand(-1, -1, lags.shape[0], -1), lagged)
+    return torch.cat((X[rows, te][:, :, None, :], lagged), dim=2)                                   # :59-61
+
+
+class _SeqLagsRagged(torch.autograd.Function):
+    """_add_lags_ragged by the library's lag op (csrc/seq_lags_kernel.hpp): X (N, L, d), lags (p,), lens (N,) int32 on X's device ->
+    (N, L, p+1, d) by gpsig_seq_lags_ragged_dev, the bracket found arithmetically; the reverse pass by gpsig_seq_lags_ragged_grad: d X (rows
+    at or beyond a sequence's length exact zeros) and d lags, no atomics, bit-for-bit repeatable.  float64, CUDA tensors."""
+
+    @staticmethod
+    def forward(ctx, X, lags, lens):
+        Xd, ld = _c(X), _c(lags)
+        lens = _lr_lengths(lens, Xd)
+        N, L, d = Xd.shape
+        p = int(ld.shape[0])
+        out = torch.empty((N, L, p + 1, d), dtype=torch.float64, device=Xd.device)
+        c = _ctx_for(Xd)
+        c.check(c._lib.gpsig_seq_lags_ragged_dev(c._h, _ptr(Xd), _ptr(lens), _ptr(ld), N, L, d, p, _ptr(out)))
+        ctx.dt = (X.dtype, lags.dtype)
+        ctx.save_for_backward(Xd, ld, lens)
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        Xd, ld, lens = ctx.saved_tensors
+        G = _c(G)
+        N, L, d = Xd.shape
+        p = int(ld.shape[0])
+        gX, gl = torch.empty_like(Xd), torch.empty_like(ld)
+        c = _ctx_for(Xd)
+        c.check(c._lib.gpsig_seq_lags_ragged_grad(c._h, _ptr(Xd), _ptr(lens), _ptr(ld), _ptr(G), N, L, d, p, _ptr(gX), _ptr(gl)))
+        return gX.to(ctx.dt[0]), gl.to(ctx.dt[1]), None
+
+
 class _DenseSelection:
     """One projection as a dense (entries, r) matrix holding each entry's value in its output column: summing an entry's product into its
     column is then a GEMM (index_add does it with atomics on r addresses per row: 6-14 ms for the inducing tensors' six chained
@@ -1371,7 +1435,7 @@ class SignatureKernelModule(torch.nn.Module):
         if not self.kern.low_rank:
             raise NotImplementedError("lengths= is built for low-rank mode only: in exact mode pad each sequence by repeating its last "
                                       "observation, which is exact there with difference=True (zero increments add nothing)")
-        if self.kern.num_lags > 0:
+        if self.kern.num_lags > 0 and self.kern._lag_axis() == "table":
             raise NotImplementedError("lengths= is not built for num_lags > 0: the lag interpolation runs on the table's own time axis")
         N, L = int(X3.shape[0]), int(X3.shape[1])
         host = lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else np.asarray(lengths)
@@ -1386,14 +1450,15 @@ class SignatureKernelModule(torch.nn.Module):
     def _scaled(self, X, presliced=False, lengths=None):
         """The scaled sequences of a public evaluation.  With ``lengths`` the table is cleaned first -- the rows beyond a sequence's length are
         replaced by its last valid row (a gather of valid rows: nothing, NaN included, flows from or to the padded rows) -- so that the pool the
-        landmarks are gathered from holds real points only, and the lengths are kept for the evaluation's feature maps."""
+        landmarks are gathered from holds real points only, and the lengths are kept for the evaluation's feature maps.  With lags
+        (``kern.lag_axis = "sequence"``) the lagged copies are interpolated on each sequence's own time axis (scale_sequences)."""
         X3 = self._seq3(X, presliced)
         if lengths is None:
             return self.scale_sequences(X3)
         lens = self._ragged_lengths(lengths, X3)
         N, L = X3.shape[0], X3.shape[1]
         idx = torch.minimum(torch.arange(L, device=X3.device)[None, :], (lens.long() - 1)[:, None])
-        Xs = self.scale_sequences(X3[torch.arange(N, device=X3.device)[:, None], idx])
+        Xs = self.scale_sequences(X3[torch.arange(N, device=X3.device)[:, None], idx], lens)
         self._ragged = (self._ragged or ()) + ((Xs, lens),)
         return Xs
 
@@ -1404,11 +1469,16 @@ class SignatureKernelModule(torch.nn.Module):
                 return self._lr.seq(Xs, lens)
         return self._lr.seq(Xs)
 
-    def scale_sequences(self, X):
-        """kernels.py:343-364.  (N, L, d) -> (N, L, d * (num_lags + 1))."""
+    def scale_sequences(self, X, lens=None):
+        """kernels.py:343-364.  (N, L, d) -> (N, L, d * (num_lags + 1)).  lens ((N,) int32 on X's device, from _scaled): the lags of a ragged
+        batch run on each sequence's own time axis -- the library's lag op (_SeqLagsRagged) for float64 CUDA tensors, its torch restatement
+        (_add_lags_ragged) for CPU tensors and under ``lr_hip = False``.  Dense calls keep _add_lags."""
         k = self.kern
         N, L, _ = X.shape
-        if k.num_lags > 0:
+        if k.num_lags > 0 and lens is not None:
+            hip = X.is_cuda and getattr(self, "lr_hip", True) and X.dtype == torch.float64 and N > 0
+            X = _SeqLagsRagged.apply(X, self.lags, lens) if hip else _add_lags_ragged(X, self.lags, lens)
+        elif k.num_lags > 0:
             X = _add_lags(X, self.lags)                                                             # :353
         X = X.reshape(N, L, k.num_lags + 1, k.num_features)                                         # :355
         if self.raw_lengthscales is not None:

@@ -3142,6 +3142,17 @@ int gpsig_lr_seq_features_ragged(gpsig_ctx* c, const gpsig_params* p, const gpsi
     return lr_seq_features_t<double>(c, p, lr, X, N, L, true, lengths, Phi);
 }
 
+// ... with lags on each sequence's own time axis: the kernels of lr_seq_features_t's ragged routes take a sequence's length as the axis of its lag
+// interpolation (scaled_point's seq_len; lr_cross_eval_kernel's brackets) wherever a call has lengths -- only this entry point sends them lags
+int gpsig_lr_seq_features_ragged_lagged(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L,
+                                        const int32_t* lengths, void* Phi) {
+    ENTER_LR(c, p);
+    CHK(lr_check(c, p, lr));
+    if (!lengths && N > 0) return fail(c, GPSIG_ERR_INVALID, "null lengths pointer");
+    if (p->dtype == GPSIG_F32) return lr_seq_features_t<float>(c, p, lr, X, N, L, true, lengths, Phi);
+    return lr_seq_features_t<double>(c, p, lr, X, N, L, true, lengths, Phi);
+}
+
 int gpsig_lr_tens_features(gpsig_ctx* c, const gpsig_params* p, const gpsig_lowrank* lr, const void* Z, int64_t T, int32_t increments,
                            void* Phi) {
     ENTER_LR(c, p);

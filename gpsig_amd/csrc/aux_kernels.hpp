@@ -33,13 +33,19 @@ struct ScaleParams {
 // x~[n][t][fe]: observation t of sequence n after add_lags_to_sequences (gpsig/lags.py:41-63), division by
 // the lengthscales (kernels.py:357-358) and the lag weights gamma (kernels.py:360-361).  fe = lag * d_in + f.
 // In: the stored type of the points (float32 points are widened value by value when T is double: the result is that of the widened array)
+// seq_len > 0 (ragged calls with lags, gpsig_lr_seq_features_ragged_lagged): the sequence is its first seq_len rows and the lag interpolation
+// runs on ITS axis i / (seq_len - 1) -- the value the truncated sequence has on its own; rows at or beyond seq_len are not read.  A sequence of
+// one point has no axis (0 / 0 in the reference's formula): its lagged copies are the point itself.  seq_len = 0: the table's axis, L rows.
 template <typename T, typename In = T>
-__device__ __forceinline__ T scaled_point(const In* __restrict__ Xn, int L, int t, int fe, const ScaleParams& P) {
+__device__ __forceinline__ T scaled_point(const In* __restrict__ Xn, int L, int t, int fe, const ScaleParams& P, int seq_len = 0) {
     const int lag = fe / P.d_in, f = fe - lag * P.d_in;
     T v;
     if (lag == 0) {
         v = T(Xn[int64_t(t) * P.d_in + f]);
+    } else if (seq_len == 1) {
+        v = T(Xn[f]);
     } else {
+        if (seq_len > 0) L = seq_len;
         // lin_interp (gpsig/lags.py:7-38): left = the last grid time not later than the query (+jitter)
         const T denom = T(L - 1);
         const T tq = fmax(T(t) / denom - T(P.lags[lag - 1]), T(0));     // lags.py:56-57

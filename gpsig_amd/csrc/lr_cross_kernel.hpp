@@ -132,7 +132,7 @@ __device__ __forceinline__ void lr_cross_diag_put(const lr_cross_f64x4& xx, doub
 // the kernels that hold the points in LDS (lr_eval_wide_inst.hip; the feature kernels that take kxs from memory follow it).  The walk and the
 // wavefront layout are lr_cross_kernel's; loader and store differ:
 //   loader   the table as the caller gives it, double or float, widened value by value and scaled in float64 as scaled_point<double, In> does
-//            (sequences: lengthscales, lags and lag weights on the sequence's own time axis, the interpolation bracket found once per (row, lag)
+//            (sequences: lengthscales, lags and lag weights on the table's time axis -- with `lengths`, on that of the sequence's own points --, the interpolation bracket found once per (row, lag)
 //            into the wavefront's LDS, not once per element) or as lr_tens_cross_kernel does (tensors: Z (lt, T, E, d) in its flat order,
 //            lengthscales and lag weights).  The landmarks of a state are float64 values gathered from widened, scaled points: the loader
 //            reproduces those bits, so a landmark that is one of the points is at distance exactly 0 in float32 calls too.
@@ -142,19 +142,24 @@ __device__ __forceinline__ void lr_cross_diag_put(const lr_cross_f64x4& xx, doub
 //   store    in the call's element type: double, or float rounded once.  Arithmetic is float64 for both.
 // (LrCrossEvalArgs<In>: lr_eval_wide.hpp)
 
-// the lag interpolation of scaled_point (aux_kernels.hpp; gpsig/lags.py:7-57) in two steps: the bracket of (point t, lag) ...
-__device__ __forceinline__ int lr_cross_lag_bracket(int L, int t, double lag, double jitter, double* tq_out) {
-    const double denom = double(L - 1);
+// the lag interpolation of scaled_point (aux_kernels.hpp; gpsig/lags.py:7-57) in two steps: the bracket of (point t, lag) on an axis of La
+// points -- the table's L, or with lengths and lags the sequence's own (scaled_point's seq_len; La == 1: no axis, the point itself) ...
+__device__ __forceinline__ int lr_cross_lag_bracket(int La, int t, double lag, double jitter, double* tq_out) {
+    if (La == 1) { *tq_out = 0.0; return 0; }                               // (a table of L = 1 too: what the search below gave there, tq = fmax(NaN, 0))
+    const double denom = double(La - 1);
     const double tq = fmax(double(t) / denom - lag, 0.0);
     int left = 0;
-    for (int i = L - 1; i >= 0; --i)
+    for (int i = La - 1; i >= 0; --i)
         if (!(double(i) / denom - tq > jitter)) { left = i; break; }
     *tq_out = tq;
     return left;
 }
-// ... and the value of column f between its two rows: the same operations on the same values as scaled_point<double, In>
+// ... and the value of column f between its two rows: the same operations on the same values as scaled_point<double, In>.  seq_len as there:
+// 0 is the table's axis of L points, 1 returns the sequence's one point.
 template <typename In>
-__device__ __forceinline__ double lr_cross_lag_value(const In* __restrict__ Xn, int L, int d_in, int f, int left, double tq) {
+__device__ __forceinline__ double lr_cross_lag_value(const In* __restrict__ Xn, int L, int d_in, int f, int left, double tq, int seq_len = 0) {
+    if (seq_len == 1) return double(Xn[f]);
+    if (seq_len > 0) L = seq_len;
     const double denom = double(L - 1);
     const int right = left + 1 < L ? left + 1 : L - 1;
     const double xl = double(Xn[int64_t(left) * d_in + f]), xr = double(Xn[int64_t(right) * d_in + f]);
@@ -167,6 +172,7 @@ __global__ __launch_bounds__(LR_CROSS_THREADS) void lr_cross_eval_kernel(LrCross
     __shared__ double tiles[LR_CROSS_WAVES][16 * LR_CROSS_LD];
     __shared__ int64_t roff[LR_CROSS_WAVES][16];                            // a row's sequence (tensors: the row itself) in X, in elements
     __shared__ int rtime[LR_CROSS_WAVES][16];                               // its point in the sequence; -1: the row is not read
+    __shared__ int rlen[LR_CROSS_WAVES][16];                                // with lengths: the points of its sequence (the lags' axis); else 0
     __shared__ int bleft[LR_CROSS_WAVES][16 * MAX_LAGS];                    // the lag brackets of the wavefront's rows
     __shared__ double btq[LR_CROSS_WAVES][16 * MAX_LAGS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 15, kq = lane >> 4;
@@ -182,7 +188,7 @@ __global__ __launch_bounds__(LR_CROSS_THREADS) void lr_cross_eval_kernel(LrCross
         if (lane < 16) {
             const int64_t row = row0 + lane;
             int64_t off = 0;
-            int t = -1;
+            int t = -1, sl = 0;
             if (row < A.n) {
                 if constexpr (TENS) {
                     const int64_t per = A.nt * A.E, k = row / per;
@@ -195,19 +201,21 @@ __global__ __launch_bounds__(LR_CROSS_THREADS) void lr_cross_eval_kernel(LrCross
                     if (A.lengths) {
                         len = A.lengths[nq];
                         len = len < 1 ? 1 : (len > L ? L : len);
+                        sl = len;
                     }
                     if (tt < len) { off = nq * int64_t(L) * d_in; t = tt; }
                 }
             }
             roff[wave][lane] = off;
             rtime[wave][lane] = t;
+            rlen[wave][lane] = sl;
         }
         __syncthreads();
         if constexpr (!TENS) {
             for (int q = lane; q < 16 * nlags; q += 64) {                   // once per (row, lag)
-                const int rr = q / nlags, lg = q - rr * nlags, t = rtime[wave][rr];
+                const int rr = q / nlags, lg = q - rr * nlags, t = rtime[wave][rr], sl = rlen[wave][rr];
                 double tq = 0.0;
-                bleft[wave][q] = t >= 0 ? lr_cross_lag_bracket(L, t, A.P.lags[lg], A.P.jitter, &tq) : 0;
+                bleft[wave][q] = t >= 0 ? lr_cross_lag_bracket(sl > 0 ? sl : L, t, A.P.lags[lg], A.P.jitter, &tq) : 0;
                 btq[wave][q] = tq;
             }
         }
@@ -232,7 +240,7 @@ __global__ __launch_bounds__(LR_CROSS_THREADS) void lr_cross_eval_kernel(LrCross
                             }
                         } else {
                             v = lag == 0 ? double(Xn[int64_t(t) * d_in + f])
-                                         : lr_cross_lag_value(Xn, L, d_in, f, bleft[wave][rr * nlags + lag - 1], btq[wave][rr * nlags + lag - 1]);
+                                         : lr_cross_lag_value(Xn, L, d_in, f, bleft[wave][rr * nlags + lag - 1], btq[wave][rr * nlags + lag - 1], rlen[wave][rr]);
                             if (A.P.has_ls) v = v / ls;
                             if (A.P.num_lags > 0) v = v * gm;
                         }

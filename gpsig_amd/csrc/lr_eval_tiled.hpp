@@ -7,7 +7,9 @@
 // point comes from global memory), in float64 and in float32 (arrays and carries in float: lr_eval_tiled_lds_bytes_f32, lr_tile_plan.hpp).
 // `lengths` (N int32 on the device) may be NULL: every sequence then has L points (lr_ragged_nullable, one wave-uniform branch).  Otherwise
 // sequence n has lengths[n] points, clamped to [1, L] in the kernel: that bounds its points, steps, 64-lane chunks and tiles, and the rows
-// beyond are never read.  Lags and lengths together are refused by the caller (the lag interpolation runs on the table's own time axis).
+// beyond are never read.  Lags with lengths (gpsig_lr_seq_features_ragged_lagged; gpsig_lr_seq_features_ragged refuses them) are interpolated
+// on the sequence's own axis i / (lengths[n] - 1), halo point included: the features of the truncated sequence evaluated on its own.  A
+// sequence of one point has no axis; its lagged copies are the point itself (scaled_point, aux_kernels.hpp).
 // Families: every family of base_eval at run-time kind, in both element types; SignatureSpectral in float64 only.
 #pragma once
 

@@ -8,7 +8,8 @@
 //   carries    cf[i][j] = sum of P_i[j] (P_1 = U) over the earlier tiles: what E_{i+1} = excumsum_t(P_i) starts from in this tile, and
 //              Phi_i after the last tile.  A running sum continues from its carry, so the additions happen in the whole-sequence kernel's order.
 //   ragged     Ln = lengths[n] clamped to [1, L] through the scalar unit; ln = Ln - halo steps in lr_tile_count(ln, TL) tiles (one tile of no
-//              steps for ln = 0: Phi = [1, 0, ..]).  A tile reads the points [t0, t0 + tl + halo) -- all below Ln.
+//              steps for ln = 0: Phi = [1, 0, ..]).  A tile reads the points [t0, t0 + tl + halo) -- all below Ln.  With lags the interpolation
+//              runs on the axis of Ln points (scaled_point's seq_len): its brackets lie below Ln too.
 #define GPSIG_LR_BODIES_ONLY         // the headers' kernels that are no templates belong to lr_fused_inst.hip
 #include "lr_fused_kernel.hpp"
 #include "lr_eval_tiled.hpp"
@@ -39,8 +40,9 @@ __device__ __forceinline__ double lr_eval_spectral_pair(lr_const_ptr<double> tab
 }
 
 // a tile's U from the raw points: `np` points from point t0 of the sequence at Xn, `tl` steps.  xb / ft may be one array.  Ends with a barrier.
+// la: scaled_point's seq_len -- the sequence's own points where the call has lengths (its lags then run on the sequence's own axis), else 0.
 template <int THREADS, bool SPEC, typename Args, typename T = typename Args::value_type>
-__device__ __forceinline__ void lr_tile_u(const Args& A, const T* Xn, int t0, int tl, int np, T* xb, T* kx, T* ft, T* u, int lane, int wave) {
+__device__ __forceinline__ void lr_tile_u(const Args& A, const T* Xn, int t0, int tl, int np, int la, T* xb, T* kx, T* ft, T* u, int lane, int wave) {
     constexpr int NW = THREADS / 64;
     const int lp = A.lp, c = A.c, L = A.L, d_eff = A.P.d_eff();
     const int pchunk = (np + 63) / 64, nchunk = (tl + 63) / 64;
@@ -54,7 +56,7 @@ __device__ __forceinline__ void lr_tile_u(const Args& A, const T* Xn, int t0, in
         // ---- phase 0: scaled observations, xb[fe][t]
         for (int q = threadIdx.x; q < np * d_eff; q += THREADS) {
             const int t = q / d_eff, fe = q - t * d_eff;
-            xb[fe * lp + t] = scaled_point<T>(Xn, L, t0 + t, fe, A.P);
+            xb[fe * lp + t] = scaled_point<T>(Xn, L, t0 + t, fe, A.P, la);
         }
         __syncthreads();
         // ---- phase 1: kxs, kx[i][t]
@@ -145,14 +147,16 @@ __device__ __forceinline__ void lr_seq_features_eval_tiled_body(const Args& A) {
     for (int64_t n = blockIdx.x; n < A.N; n += gridDim.x) {
         const T* Xn = A.X + n * int64_t(L) * A.P.d_in;
         T* phi = A.Phi + n * int64_t(A.F);
-        const int ln = lr_seq_points(A, n, L) - halo;       // the sequence's own steps (wave-uniform), >= 0
+        const int Ln = lr_seq_points(A, n, L);
+        const int ln = Ln - halo;                           // the sequence's own steps (wave-uniform), >= 0
+        const int la = A.lengths ? Ln : 0;                  // ragged: lags on the sequence's own axis (dense: the table's, as ever)
         const int ntiles = lr_tile_count(ln, TL);
         __syncthreads();                                    // (the previous sequence's features were read from the carries)
         for (int q = threadIdx.x; q < M * rows; q += THREADS) cf[q] = T(0);
         for (int k = 0; k < ntiles; ++k) {
             const int t0 = lr_tile_first(k, TL), tl = lr_tile_steps(ln, k, TL), np = tl + halo;
             const int nchunk = (tl + 63) / 64;
-            lr_tile_u<THREADS, SPEC>(A, Xn, t0, tl, np, bufB, bufA, bufB, U, lane, wave);
+            lr_tile_u<THREADS, SPEC>(A, Xn, t0, tl, np, la, bufB, bufA, bufB, U, lane, wave);
             lr_eval_excumsum<THREADS>(U, bufA, c, lp, tl, cf, M >= 2);                               // level 1; E_2 of the tile
             __syncthreads();
             T* cur = bufA;

@@ -337,6 +337,9 @@ class SignatureKernel:
         self.rng = np.random.default_rng()   # low-rank mode: source of landmarks and projections (the reference uses TF's global RNG)
         self.device_draw = True              # ... drawn on the device for CUDA tensors (gpsig_lr_draw), on the host for host arrays
         self.lr_native_f32 = False           # low-rank mode, all-float32 arguments: float32 feature / Gram kernels (default: float64, rounded)
+        # ``lengths=`` with num_lags > 0: "table" refuses (the reference pads, and its lag interpolation runs on the table's own time axis);
+        # "sequence" evaluates X[n, :len_n] as that truncated sequence would be on its own -- its axis is i / (len_n - 1) (_ragged_lengths)
+        self.lag_axis = "table"
 
     # ---- validators (kernels.py:94-133) ------------------------------------------------------
     @staticmethod
@@ -647,7 +650,11 @@ class SignatureKernel:
         per level (low_rank_calculations.py:76-193).  Returns a LowRankState that can be passed to K(..., lr_state=).
         A state returned to the caller is the caller's: later draws never write into it, for host arrays and CUDA tensors alike
         (only the per-evaluation draws of K / Kdiag / K_tens / ... with lr_state=None reuse one device block of the kernel object).
-        lengths: per-sequence lengths of a ragged X (as in K): the pool the landmarks are drawn from holds real points only."""
+        lengths: per-sequence lengths of a ragged X (as in K): the pool the landmarks are drawn from holds real points only.
+        With lags and ``lag_axis = "sequence"`` the pool is left as it is, deliberately: the rows beyond a sequence's length repeat its last
+        valid row, and the lagged blocks of a landmark are interpolated on the TABLE's axis from those real rows (gpsig_lr_gather_points /
+        gpsig_lr_draw know no lengths).  Any point of the state space is a valid Nystrom landmark; only the features of the sequences
+        themselves follow the per-sequence axis."""
         if lengths is not None:
             X = self._real_points(X, self._ragged_lengths(lengths, X))
         L_ = _launch_lr(self, X, X2, Z)
@@ -735,7 +742,7 @@ class SignatureKernel:
         if not self.low_rank:
             raise NotImplementedError("lengths= is built for low-rank mode only: in exact mode pad each sequence by repeating its last "
                                       "observation, which is exact there with difference=True (zero increments add nothing)")
-        if self.num_lags > 0:
+        if self.num_lags > 0 and self._lag_axis() == "table":
             raise NotImplementedError("lengths= is not built for num_lags > 0: the lag interpolation runs on the table's own time axis")
         if X is None:
             raise ValueError("lengths given without their sequences")
@@ -748,6 +755,18 @@ class SignatureKernel:
         if N and (int(host.min()) < 1 or int(host.max()) > L):
             raise ValueError("lengths must lie in [1, %d], got [%d, %d]" % (L, int(host.min()), int(host.max())))
         return np.ascontiguousarray(host, dtype=np.int32)
+
+    def _lag_axis(self):
+        """``lag_axis``, checked: "table" (the default) or "sequence".  With "sequence" a ragged evaluation of a kernel with lags takes
+        sequence n as X[n, :len_n] and NOTHING else: the time axis of gpsig/lags.py:56-57 is i / (len_n - 1), the query of lag j at observation
+        t is max(t / (len_n - 1) - lag_j, 0), bracket and value are lags.py:20-32 -- what the truncated sequence gives on its own.  The
+        reference has no such meaning (it pads, and padding is not neutral with lags: the lagged channels keep moving after the sequence
+        has ended), hence the explicit switch.  A deliberate deviation: a sequence of ONE point has no axis (0 / 0 in the reference's formula;
+        NaN from the dense kernels at L = 1) -- its lagged copies are the point itself."""
+        axis = getattr(self, "lag_axis", "table")
+        if axis not in ("table", "sequence"):
+            raise ValueError('lag_axis must be "table" or "sequence", got %r' % (axis,))
+        return axis
 
     def _real_points(self, X, lengths):
         """The table the landmarks are drawn from: each row beyond a sequence's length replaced by the sequence's last valid row (a gather of
@@ -776,7 +795,8 @@ class SignatureKernel:
             lens = torch.as_tensor(lengths, device=L_.dev) if L_.device_mode else lengths
             L_.keep.append(lens)
             lp = C.c_void_p(lens.data_ptr() if L_.device_mode else lens.ctypes.data)
-            L_.ctx.call("gpsig_lr_seq_features_ragged", p, lr, L_.inp(A), n, l, lp, pp)
+            # with lags (lag_axis = "sequence": _ragged_lengths let them through) the entry point that interpolates on each sequence's own axis
+            L_.ctx.call("gpsig_lr_seq_features_ragged_lagged" if self.num_lags > 0 else "gpsig_lr_seq_features_ragged", p, lr, L_.inp(A), n, l, lp, pp)
             return Phi, pp, n
         L_.ctx.call("gpsig_lr_seq_features", p, lr, L_.inp(A), n, l, pp)
         return Phi, pp, n

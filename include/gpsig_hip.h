@@ -536,6 +536,27 @@ int gpsig_lr_seq_features(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_low
  * zeros in the spectral cross kernel's operand, are never read or written, and a wavefront whose 16 rows are all padding skips its arithmetic. */
 int gpsig_lr_seq_features_ragged(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L,
                                  const int32_t* lengths, void* Phi);
+/* ... for a ragged batch WITH LAGS, each sequence on its own time axis (no reference analogue: the reference pads and interpolates on the
+ * table's axis).  The contract, routes and refusals of gpsig_lr_seq_features_ragged, except that p->num_lags > 0 is served: sequence n is
+ * X[n, :len] (len = lengths[n]) and Phi[n] the features of that truncated sequence evaluated on its own -- its axis is i / (len - 1), the query
+ * of lag j at observation t is max(t / (len - 1) - lag_j, 0), bracket and value as gpsig/lags.py:20-32 with jitter 1e-6 -- equal to
+ * gpsig_lr_seq_features on X[n:n+1, :len] with the same lr.  Rows at or beyond len are never read.  A sequence of ONE point has no axis (the
+ * reference's formula is 0 / 0 there and the dense entry points return NaN at L = 1): its lagged copies are the point itself.  With full
+ * lengths the bits are gpsig_lr_seq_features', with p->num_lags == 0 those of gpsig_lr_seq_features_ragged. */
+int gpsig_lr_seq_features_ragged_lagged(gpsig_ctx* ctx, const gpsig_params* p, const gpsig_lowrank* lr, const void* X, int64_t N, int32_t L,
+                                        const int32_t* lengths, void* Phi);
+/* The TRAINING path's lag op for ragged batches (gpsig/lags.py:41-63 on per-sequence axes, the semantics above): X (N, L, d), lengths (N int32,
+ * clamped to [1, L]), lags (p doubles, 1 <= p <= 8) -> out (N, L, p + 1, d): copy 0 is X, copy j the interpolation at lag j; the output rows at
+ * or beyond a sequence's length repeat its row len - 1 (so that landmarks gathered from it are real points), the input rows there are never
+ * read.  Device pointers, device-pointer mode, float64, asynchronous on the context's stream, d <= 4096.
+ * _grad: G = dL/dout -> dX (N, L, d), every element written, rows at or beyond len exact zeros (the gradients of the repeated output rows go
+ * to the sources of row len - 1), and dlags (p) = - sum G (x_r - x_l) / (t_r - t_l) over the queries that the clamp at 0 did not catch; a
+ * sequence of one point contributes exactly zero to dlags.  No floating-point atomics: two calls return the same bits.  N = 0: dlags is
+ * zeroed.  Scratch: N p doubles of the context's. */
+int gpsig_seq_lags_ragged_dev(gpsig_ctx* ctx, const double* X, const int32_t* lengths, const double* lags, int64_t N, int32_t L, int32_t d,
+                              int32_t p, double* out);
+int gpsig_seq_lags_ragged_grad(gpsig_ctx* ctx, const double* X, const int32_t* lengths, const double* lags, const double* G, int64_t N,
+                               int32_t L, int32_t d, int32_t p, double* dX, double* dlags);
 /* SignatureKernel._K_tens_lr_feat (kernels.py:285-311): Nystrom_map + tensor_kern_lr_feature.  Phi: (T, F).  With lr_fused != 0 one fused kernel
  * where a tensor's arrays -- 8 (lt E (d' + 2 c) + lt c + 2 max(c, r)) bytes, half in float32 -- fit 64 KB of LDS; where they do without the
  * points (d' = 0) the wide route as for sequences (the cross matrix of Z's points in their flat order, then the kx instance of the fused
