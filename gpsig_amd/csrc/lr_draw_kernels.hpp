@@ -304,7 +304,7 @@ static __global__ void __launch_bounds__(LR_JACOBI_THREADS) lr_jacobi_eig_kernel
             perm[k] = pj;
         }
         *info = sweep >= 30 ? 1 : 0;
-        info[2] = sweep;                               // sweeps taken (diagnostics)
+        info[2] = sweep < 30 ? sweep + 1 : 30;         // sweeps taken, the one that found nothing left to rotate included (diagnostics; 0: rocSOLVER)
     }
     __syncthreads();
     for (int j = tid; j < n; j += nt) ev[j] = A[perm[j] * ld + perm[j]];

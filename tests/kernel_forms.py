@@ -32,7 +32,7 @@ OPTIONS = {
     "tvs_zreg": {"default": -1, "values": [-1, 0, 1], "tests": [_F + "test_tvs_zreg_in_the_tensor_lane_gradient"]},
     "tvs_grad_tile": {"default": 1, "values": [0, 1], "tests": [_G + "test_tensor_vs_sequence_tile_gradient_kernel", _F + "test_tvs_zreg_in_the_tensor_lane_gradient"]},
     "pinned_staging": {"default": 1, "values": [0, 1], "tests": [_F + "test_pinned_staging_in_host_pointer_mode"]},
-    "lr_jacobi": {"default": 1, "values": [0, 1], "tests": [_P + "test_low_rank_objects_drawn_on_the_device"]},
+    "lr_jacobi": {"default": 1, "values": [0, 1], "tests": [_P + "test_low_rank_objects_drawn_on_the_device", "test_gpu_draw_edges.py::test_eigendecomposition_backward_error"]},
     "sig_features": {"default": -1, "values": [-1, 0, 1], "tests": [_P + "test_linear_gram_as_feature_contraction", _F + "test_keep_reset_in_the_float64_pair_kernel"]},
     "sig_gemm_dma": {"default": 1, "values": [0, 1], "tests": [_P + "test_linear_gram_as_feature_contraction"]},
     "sig_graded": {"default": 1, "values": [0, 1], "tests": [_F + "test_sig_graded_pieces"]},
