@@ -1,5 +1,5 @@
 // ctx.hpp -- the gpsig_ctx object and the host-side helpers shared by the translation units that implement
-// the C ABI (api.hip: evaluation, grad_api.hip: gradients).
+// the C ABI (api.hip: evaluation, lr_api.hip: low-rank evaluation, grad_api.hip: gradients, ...).
 #pragma once
 #include <atomic>
 
@@ -41,7 +41,7 @@ enum BufId {
     B_SF0, B_SF1, B_SF2, B_SF3, B_SF4, B_SF5,                               // explicit level features (sig_feat_kernel.hpp): both sides, partial products, level diagonals                              // weighted tensor-vs-sequence sums: partial factor gradients; level arrays of the fallback
     B_SPEC,                                                    // spectral base-kernel table
     B_SPECD, B_LRDK,                                           // low-rank spectral training path (lr_grad_api.hip): the table packed on the device, dkxs
-    B_SPECW,                                                   // ... in its own (Q, d) layout, for the low-rank evaluation side beyond 32 columns (api.hip: spectral_table_wide)
+    B_SPECW,                                                   // ... in its own (Q, d) layout, for the low-rank evaluation side beyond 32 columns (lr_api.hip: spectral_table_wide)
     B_LRF32,                                                   // low-rank mode, float32 calls: the state and the spectral table narrowed to float32
     B_TQ,                                                      // item counters of the Kzx tile kernel's persistent launch
     B_STASH,                                                   // what the fused reverse kernel needs of the forward recursion (gpsig_seq_gram_levels_stash)
@@ -144,7 +144,7 @@ struct gpsig_ctx {
     void* spec_wide_base = nullptr;
     // low-rank mode: what B_LR0 / B_LR1 currently hold (keyed by content: the random objects of an evaluation are handed to several
     // calls -- tensor features, sequence features, products -- and every upload was a host synchronisation)
-    UploadCache lr_cache;                  // B_LR0: landmarks, whitening and projections (lr_upload, api.hip)
+    UploadCache lr_cache;                  // B_LR0: landmarks, whitening and projections (lr_upload, lr_api.hip)
     int64_t lr_off_key[3] = {-1, -1, -1};  // (M, c, r) of the level offsets in B_LR1
     void* lr_off_base = nullptr;
     UploadCache lr_sketch_cache;           // B_LR8: the projections of the training path's entry points (upload_sketches, lr_grad_api.hip)
@@ -285,6 +285,15 @@ inline uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
     }
     for (; i < n; ++i) h = (h ^ b[i]) * 0x100000001b3ull;
     return h;
+}
+// ... over a projection: its sizes, then colptr, i1, i2, val (the content keys of lr_upload, lr_api.hip, and upload_sketches, lr_grad_api.hip)
+inline uint64_t fnv1a_sketch(uint64_t h, const gpsig_sketch& sk) {
+    const int64_t sd[4] = {sk.k1, sk.k2, sk.r, sk.nnz};
+    h = fnv1a(h, sd, sizeof(sd));
+    h = fnv1a(h, sk.colptr, sizeof(int32_t) * (size_t(sk.r) + 1));
+    h = fnv1a(h, sk.i1, sizeof(int32_t) * size_t(sk.nnz));
+    h = fnv1a(h, sk.i2, sizeof(int32_t) * size_t(sk.nnz));
+    return fnv1a(h, sk.val, sizeof(double) * size_t(sk.nnz));
 }
 
 // One upload of host arrays into a scratch buffer kept by content: open() takes the buffer and tells (`cached`) whether it already

@@ -1,4 +1,4 @@
-// lowrank_solver.hip -- the eigendecomposition behind gpsig_lr_whitening (api.hip), on rocSOLVER.
+// lowrank_solver.hip -- the eigendecomposition behind gpsig_lr_whitening (lr_api.hip), on rocSOLVER.
 //
 // Reference: gpsig/low_rank_calculations.py:55 (tf.self_adjoint_eig of the landmark Gram inside Nystrom_map).  rocSOLVER / rocBLAS are opened at first use (dlopen by
 // SONAME: a process that has PyTorch-ROCm loaded gets the copies PyTorch loaded, everything else the ROCm installation's),

@@ -1,5 +1,5 @@
 // lr_draw_kernels.hpp -- the random objects of a low-rank evaluation drawn ON THE DEVICE: kernels and the state object (the host side
-// is gpsig_lr_draw / gpsig_lr_state_* in api.hip).
+// is gpsig_lr_draw / gpsig_lr_state_* in lr_api.hip).
 //
 // The reference draws them inside the TensorFlow graph, afresh at every evaluation: the landmarks of Nystrom_map (uniformly,
 // without replacement, gpsig/low_rank_calculations.py:12-20, :47-48), the jitter diagonal of :52, and one random projection per

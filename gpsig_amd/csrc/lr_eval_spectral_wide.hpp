@@ -1,4 +1,4 @@
-// lr_eval_spectral_wide.hpp -- the evaluation side's wide route for SignatureSpectral (api.hip: lr_seq_features_t, lr_tens_features_t; which calls
+// lr_eval_spectral_wide.hpp -- the evaluation side's wide route for SignatureSpectral (lr_api.hip: lr_seq_features_t, lr_tens_features_t; which calls
 // take it: lr_spectral_eval_wide / lr_spectral_eval_tens_wide, lr_tile_plan.hpp): argument block and launchers of the evaluation form of the
 // spectral cross kernel and of the landmark Gram at more than 32 columns (kernels and instances: lr_eval_spectral_wide_inst.hip).  The feature
 // kernels that follow the cross matrix take kxs / kzs from memory (lr_eval_wide.hpp: lr_eval_wide_seq_launch / _tens_launch).

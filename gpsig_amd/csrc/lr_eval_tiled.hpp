@@ -1,5 +1,5 @@
 // lr_eval_tiled.hpp -- the evaluation side's time-tiled, lengths-aware low-rank sequence feature kernels (lr_eval_tiled_inst.hip): argument
-// blocks and launchers, for api.hip (gpsig_lr_seq_features beyond the whole-sequence kernels, gpsig_lr_seq_features_ragged).
+// blocks and launchers, for lr_api.hip (gpsig_lr_seq_features beyond the whole-sequence kernels, gpsig_lr_seq_features_ragged).
 //
 // The forward walk of lr_tiled_kernel.hpp -- tiles of TL time steps in increasing time, one carried column vector per level, the additions in
 // the whole-sequence kernel's order -- on the evaluation side's block: the caller's RAW points, scaled in the kernel as
@@ -29,7 +29,7 @@ template <> struct lr_ragged<LrEvalTiledArgsF32> { static constexpr bool value =
 template <> struct lr_ragged_nullable<LrEvalTiledArgs> { static constexpr bool value = true; };
 template <> struct lr_ragged_nullable<LrEvalTiledArgsF32> { static constexpr bool value = true; };
 
-// The float32 kernel BEHIND the Nystrom cross matrix (the wide route of api.hip; float64 takes lr_seq_features_tiled_kx_kernel, lr_kx.hpp): X is
+// The float32 kernel BEHIND the Nystrom cross matrix (the wide route of lr_api.hip; float64 takes lr_seq_features_tiled_kx_kernel, lr_kx.hpp): X is
 // kxs (N, L, c) in float, from lr_cross_eval_kernel; phases 0 and 1 are a load, the rest is the kernel above.  S and kind are not read.
 struct LrEvalTiledKxArgsF32 : LrEvalTiledArgsF32 {};
 template <typename Args> struct lr_eval_kx { static constexpr bool value = false; };

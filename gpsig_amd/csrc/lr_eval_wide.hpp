@@ -1,4 +1,4 @@
-// lr_eval_wide.hpp -- the evaluation side's wide route (api.hip: lr_seq_features_t, lr_tens_features_t; which calls take it: lr_eval_route,
+// lr_eval_wide.hpp -- the evaluation side's wide route (lr_api.hip: lr_seq_features_t, lr_tens_features_t; which calls take it: lr_eval_route,
 // lr_tile_plan.hpp): argument block and launchers of the evaluation form of the Nystrom cross kernel (lr_cross_kernel.hpp, instances in
 // lr_eval_wide_inst.hip).  The feature kernels that follow it take kxs / kzs from memory: float64 lr_kx.hpp, float32 lr_eval_tiled.hpp
 // (sequences) and lr_kx.hpp (tensors).

@@ -2,7 +2,7 @@
 // launchers (own translation unit: the training kernels of lr_cross_inst.hip stay the code they were).  Element type of the caller's table x
 // sequences / inducing tensors; what they compute and the argument block: lr_cross_kernel.hpp, lr_eval_wide.hpp.
 // Also here, host code alone: the launches of the feature kernels that follow the cross matrix (lr_eval_wide_*_launch), from the plain fields of
-// lr_eval_wide.hpp -- so that api.hip sees neither the training path's argument blocks nor its kernels' headers.
+// lr_eval_wide.hpp -- so that lr_api.hip sees neither the training path's argument blocks nor its kernels' headers.
 #define GPSIG_LR_CROSS_TEMPLATES_ONLY     // the header's kernels that are no templates belong to lr_cross_inst.hip
 #define GPSIG_LR_BODIES_ONLY              // ... and those of the training path's headers to lr_grad_api.hip
 #include "lr_cross_kernel.hpp"

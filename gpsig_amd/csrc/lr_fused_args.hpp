@@ -1,5 +1,5 @@
 // lr_fused_args.hpp -- argument blocks and launchers of the fused low-rank feature kernels (lr_fused_kernel.hpp), float64 and float32.
-// lr_fused_inst.hip instantiates the kernels and exports one launcher per form; api.hip (evaluation) and lr_grad_api.hip (training
+// lr_fused_inst.hip instantiates the kernels and exports one launcher per form; lr_api.hip (evaluation) and lr_grad_api.hip (training
 // path) fill only what their callers decide: points, scaling, landmarks, whitening, base parameters, spectral table and projections.
 #pragma once
 

@@ -1,5 +1,5 @@
 // lr_fused_inst.hip -- the fused low-rank feature kernels, float64 and float32, plain and spectral, and their launchers (own translation
-// unit: api.hip and lr_grad_api.hip only see the arguments, lr_fused_args.hpp).
+// unit: lr_api.hip and lr_grad_api.hip only see the arguments, lr_fused_args.hpp).
 #include "lr_fused_kernel.hpp"
 
 namespace gpsig {

@@ -3,7 +3,7 @@
 //
 // When the reference trains in low-rank mode, the Nystrom landmarks are gathered from the scaled inputs and their Gram is decomposed
 // inside the differentiated graph (gpsig/low_rank_calculations.py:47-60): landmarks and whitening are functions of the trainable
-// parameters, new at every step, and live where the step runs.  gpsig_lr_seq_features (api.hip) takes them from the host (or from a
+// parameters, new at every step, and live where the step runs.  gpsig_lr_seq_features (lr_api.hip) takes them from the host (or from a
 // gpsig_lr_draw state) because the evaluation path's caller owns them; the entry points here take device pointers.  Each map has a forward
 // entry (`_dev`: Phi) and a reverse one (`_grad`: dPhi -> d points, dS, dWh and the base kernel's parameters):
 //     gpsig_lr_seq_features_dev / _grad                   sequences (N, L, d): lr_fused_kernel.hpp / lr_grad_kernel.hpp; where a sequence's arrays
@@ -26,7 +26,7 @@
 //     LrCall, open()      the call's sizes, landmarks, whitening and projections; check() and the entry's own size / NULL test.  An entry's
 //                         plan and LDS refusals follow, then upload_sketches: the projections are value-independent random objects that come from
 //                         the host once per draw, are kept on the device by content (with the two transposed copies the reverse pass gathers over:
-//                         ContentUpload, ctx.hpp, as api.hip's lr_upload) and reused by every call that passes the same ones
+//                         ContentUpload, ctx.hpp, as lr_api.hip's lr_upload) and reused by every call that passes the same ones
 //     forward_fields, reverse_fields     the fields the argument blocks of one direction have in common
 //     spectral_table      alpha, omega, gamma packed into the table of the spectral forward instances, on the device (no host round trip)
 //     zero_outputs        an empty batch
@@ -67,12 +67,7 @@ int upload_sketches(gpsig_ctx* c, int cc, int r, int nsk, const gpsig_sketch* sk
         const gpsig_sketch& s = sk[i];
         if (s.k1 != cc || s.k2 != k2 || s.r != r || s.nnz < 0 || !s.colptr || (s.nnz > 0 && (!s.i1 || !s.i2 || !s.val)))
             return fail(c, GPSIG_ERR_INVALID, "sketch %d has shape (%d, %d) -> %d, expected (%d, %d) -> %d", i, s.k1, s.k2, s.r, cc, k2, r);
-        const int64_t sd[4] = {s.k1, s.k2, s.r, s.nnz};
-        h = fnv1a(h, sd, sizeof(sd));
-        h = fnv1a(h, s.colptr, sizeof(int32_t) * (size_t(s.r) + 1));
-        h = fnv1a(h, s.i1, sizeof(int32_t) * size_t(s.nnz));
-        h = fnv1a(h, s.i2, sizeof(int32_t) * size_t(s.nnz));
-        h = fnv1a(h, s.val, sizeof(double) * size_t(s.nnz));
+        h = fnv1a_sketch(h, s);
         bytes += 3 * (sizeof(LrEntry) * (size_t(s.nnz) + 1) + 16) + sizeof(int32_t) * (size_t(s.r) + size_t(s.k1) + size_t(s.k2) + 3) + 48;
         k2 = r;
     }

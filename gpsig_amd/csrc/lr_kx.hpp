@@ -4,7 +4,7 @@
 // The feature map sees the state-space width d only in kxs = kappa(x, S) and its adjoint.  With kxs computed by the cross op on the matrix cores
 // (lr_cross_kernel.hpp) the instances here begin behind it: no points, no landmarks, d in neither the LDS plan nor a per-thread table.  Float64,
 // order 1, every family of base_eval (the kernels never see which).  Two callers: the training path (lr_grad_api.hip: gpsig_lr_*_kx_dev / _kx_grad
-// behind gpsig_lr_cross) and the evaluation side's wide route (api.hip through lr_eval_wide.hpp: the forward instances behind the evaluation
+// behind gpsig_lr_cross) and the evaluation side's wide route (lr_api.hip through lr_eval_wide.hpp: the forward instances behind the evaluation
 // form of the cross kernel; its float32 calls take LrTensKxArgsF32 here and the kx instance of lr_eval_tiled.hpp for sequences).
 //   sequences   the time-tiled bodies (lr_tiled_fwd_body.inc, lr_tiled_rev_body.inc) on a lengths-aware block (`lengths` may be NULL: L points
 //               each); a sequence that fits the LDS is one tile.  The bodies step through A.X in rows of A.d values per point: here X is
@@ -27,7 +27,7 @@ template <> struct lr_ragged_nullable<LrTiledKxArgs> { static constexpr bool val
 
 struct LrTensKxArgs : LrTensFusedArgs { const double* kzs; };      // Z unused, P.d_in = 0
 struct LrTensGradKxArgs : LrTensGradSpectralArgs { const double* kzs; };   // Z, alpha, omega, gamma unused, d = 0; dkx: dkzs
-struct LrTensKxArgsF32 : LrTensFusedArgsF32 { const float* kzs; };  // the evaluation side's float32 calls (api.hip, the wide route)
+struct LrTensKxArgsF32 : LrTensFusedArgsF32 { const float* kzs; };  // the evaluation side's float32 calls (lr_api.hip, the wide route)
 template <> struct lr_tens_kx<LrTensKxArgs> { static constexpr bool value = true; };
 template <> struct lr_tens_kx<LrTensKxArgsF32> { static constexpr bool value = true; };
 template <> struct lr_tens_kx<LrTensGradKxArgs> { static constexpr bool value = true; };

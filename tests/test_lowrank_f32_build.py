@@ -58,7 +58,7 @@ def test_float32_feature_kernels_exist_without_scratch_at_their_occupancy(tmp_pa
 
 
 def test_float32_gram_gemm_exists_without_scratch(tmp_path):
-    text = _compile(tmp_path, "api.hip")
+    text = _compile(tmp_path, "lr_api.hip")
     vgprs, scratch, occ = _report(text, GEMM_F32)
     _, _, occ64 = _report(text, GEMM_F64)
     assert scratch == 0 and occ >= occ64 and occ >= 2, (vgprs, scratch, occ, occ64)

@@ -22,7 +22,7 @@ def test_route_predicates_on_the_host(tmp_path):
 
 
 def test_api_calls_the_predicates():
-    """both host paths of api.hip ask the predicate, and no option name was added for the route (tests/kernel_forms.py pins the set)"""
-    with open(os.path.join(CSRC, "api.hip")) as f:
+    """both host paths of lr_api.hip ask the predicate, and no option name was added for the route (tests/kernel_forms.py pins the set)"""
+    with open(os.path.join(CSRC, "lr_api.hip")) as f:
         api = f.read()
     assert "lr_eval_route(" in api and "lr_eval_tens_route(" in api

@@ -22,12 +22,17 @@ def test_spectral_route_predicates_on_the_host(tmp_path):
 
 
 def test_api_asks_the_predicates_behind_the_opt_in():
-    """both host paths of api.hip ask the new predicates, only for a kernel object that opts in (base_params[2]); the opt-in is no option name
-    (tests/kernel_forms.py pins that set), and the exact entry points' parameter check does not read it"""
+    """both host paths of lr_api.hip ask the new predicates, only for a kernel object that opts in (base_params[2]); the opt-in is no option name
+    (tests/kernel_forms.py pins that set: neither lr_api.hip nor api.hip, which holds the option setter, names one), and the exact entry points'
+    parameter check (the ENTER macro, api_common.hpp) does not read it"""
+    with open(os.path.join(CSRC, "lr_api.hip")) as f:
+        lr_api = f.read()
     with open(os.path.join(CSRC, "api.hip")) as f:
         api = f.read()
-    assert "lr_spectral_eval_wide(" in api and "lr_spectral_eval_tens_wide(" in api and "base_params[2]" in api
-    assert "lr_eval_route(" in api and "lr_eval_tens_route(" in api
-    assert '"lr_spectral_wide"' not in api
-    enter = api[api.index("#define ENTER(c, p)"):api.index("#define ENTER_LR(c, p)")]
+    with open(os.path.join(CSRC, "api_common.hpp")) as f:
+        common = f.read()
+    assert "lr_spectral_eval_wide(" in lr_api and "lr_spectral_eval_tens_wide(" in lr_api and "base_params[2]" in lr_api
+    assert "lr_eval_route(" in lr_api and "lr_eval_tens_route(" in lr_api
+    assert '"lr_spectral_wide"' not in lr_api and '"lr_spectral_wide"' not in api
+    enter = common[common.index("#define ENTER(c, p)"):common.index("#define ENTER_LR(c, p)")]
     assert "check_params((c), (p))" in enter
