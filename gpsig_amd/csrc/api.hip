@@ -108,7 +108,9 @@ int check_params(gpsig_ctx* c, const gpsig_params* p, bool low_rank, bool lr_wid
     if (p->base_kernel == GPSIG_BASE_SPECTRAL) {
         const int Q = int(p->base_params[0]), fam = int(p->base_params[1]);
         if (Q < 1 || Q > 64 || fam < 0 || fam > 2) return fail(c, GPSIG_ERR_INVALID, "spectral kernel: bad number of components / family");
-        if (p->num_features > SPECTRAL_STRIDE && !(lr_wide && p->base_params[2] != 0.0))
+        // (beyond the packed table's columns: low-rank mode's wide evaluation for a kernel object with lr_spectral_wide, base_params[2]; exact calls --
+        // the wide route, wide_api.hip: wide_spectral -- for one with spectral_wide, base_params[3])
+        if (p->num_features > SPECTRAL_STRIDE && !(lr_wide && p->base_params[2] != 0.0) && !(!low_rank && p->base_params[3] != 0.0))
             return fail(c, GPSIG_ERR_UNSUPPORTED, "the spectral base kernel is built for at most %d features", int(SPECTRAL_STRIDE));
         if (!p->base_table || p->base_table_len != int64_t(Q) * (1 + 2 * p->num_features))
             return fail(c, GPSIG_ERR_INVALID, "spectral kernel: base_table must hold alpha[Q], omega[Q][d], gamma[Q][d]");
@@ -811,8 +813,20 @@ static int generic_levels(gpsig_ctx* c, const gpsig_params* p, bool apply_scalin
     // wide route (wide_api.hip): the argument lattices by dgemm, one wavefront per lattice -- the distance kernels at order 1, up to 512 lattice columns
     // (the dot-product families: beyond 32 columns, or by option -- up to there this fallback stays what it was for them)
     // (SignaturePoly, SignatureMix: beyond 64 columns, or by option)
-    if (wide_lat_available(c, p, L1, L2) && (!(wide_dot_kind(p->base_kernel) || wide_base_param_kind(p->base_kernel)) || c->wide == 1 || d_eff > wide_auto_cols(p, 32)) && sm == (diag ? N1 : N1 * N2) && si == (diag ? 1 : N2) &&
-        sj == (diag ? 0 : 1)) {
+    // (exact-mode SignatureSpectral beyond 32 columns: this route or none -- a diagonal asked for in another layout is computed in this one and copied)
+    const bool spx = wide_spectral(p);
+    if (spx && !wide_lat_fwd_available(c, p, L1, L2)) return wide_spectral_refusal(c, p, true, L2);
+    const bool wide_layout = sm == (diag ? N1 : N1 * N2) && si == (diag ? 1 : N2) && sj == (diag ? 0 : 1);
+    if (spx && !wide_layout) {
+        if (!diag) return fail(c, GPSIG_ERR_UNSUPPORTED, "exact-mode SignatureSpectral beyond 32 columns (spectral_wide): no route for this output layout");
+        void* tmp;
+        CHK(ensure(c, B_WS3, sizeof(double) * size_t(M + 1) * N1 + 8, &tmp));
+        CHK(generic_levels(c, p, apply_scaling, X, Y, N1, N2, L1, L2, true, static_cast<double*>(tmp), N1, 1, 0));
+        hipLaunchKernelGGL(levels_relayout_kernel, dim3(grid_for(N1 * int64_t(M + 1))), dim3(256), 0, c->stream, static_cast<const double*>(tmp), N1, M + 1, sm, si, out);
+        HIPCHK(c, hipGetLastError());
+        return GPSIG_OK;
+    }
+    if (wide_lat_fwd_available(c, p, L1, L2) && (!(wide_dot_kind(p->base_kernel) || wide_base_param_kind(p->base_kernel)) || c->wide == 1 || d_eff > wide_auto_cols(p, 32)) && wide_layout) {
         const bool same_ = diag || Y == nullptr || Y == X;
         void *xs, *ys = nullptr;
         CHK(ensure(c, B_GR0, sizeof(double) * size_t(N1) * L1 * d_eff + 8, &xs));
@@ -933,7 +947,7 @@ static int diag_levels_mn(gpsig_ctx* c, const gpsig_params* p, bool apply_scalin
     SeqPlanned pl;
     const int rc = plan_seq(c, p, d_eff, L, &pl);
     // (option wide = 1: the wide route wherever built -- generic_levels takes it)
-    if ((rc == GPSIG_ERR_UNSUPPORTED || (rc == GPSIG_OK && c->wide == 1 && wide_lat_available(c, p, L, L))) && generic_ok(p))
+    if ((rc == GPSIG_ERR_UNSUPPORTED || (rc == GPSIG_OK && c->wide == 1 && wide_lat_fwd_available(c, p, L, L))) && generic_ok(p))
         return generic_levels(c, p, apply_scaling, X, X, N, N, L, L, true, static_cast<double*>(out), N, 1, 0);
     CHK(rc);
     const void* rec;
@@ -970,12 +984,12 @@ static int seq_K_device(gpsig_ctx* c, const gpsig_params* p, bool raw, const voi
         swap = !swap;
         rc = plan_seq(c, p, d_eff, swap ? L1 : L2, &pl, pairs_hint);
     }
-    if (rc == GPSIG_OK && c->wide == 1 && generic_ok(p) && row_end == 0 && wide_lat_available(c, p, L1, L2)) rc = GPSIG_ERR_UNSUPPORTED;   // (option wide = 1)
+    if (rc == GPSIG_OK && c->wide == 1 && generic_ok(p) && row_end == 0 && wide_lat_fwd_available(c, p, L1, L2)) rc = GPSIG_ERR_UNSUPPORTED;   // (option wide = 1)
     // 17 .. 32 columns, first order: the exact-shape kernels' 32-column instances hold four lattice columns x 32 features per lane at one wavefront per
     // SIMD -- a Gram of 384 sequences of 50 x 17 takes 10.8 ms there, 4.5 through the wide route's dgemm + lattice sweeps (tools/probe_shapes_rbf.py)
     // (the dot-product families have no instance there to be pulled off: their rule reads "beyond 32 columns", where plan_seq has already said no)
     if (rc == GPSIG_OK && c->wide < 0 && sizeof(TT) == 8 && d_eff > wide_auto_cols(p, 16) && pairs_hint >= 4096 && generic_ok(p) && row_end == 0 && !(p->order > 1 && p->num_levels > 1) &&
-        wide_lat_available(c, p, L1, L2))
+        wide_lat_fwd_available(c, p, L1, L2))
         rc = GPSIG_ERR_UNSUPPORTED;
     if (rc == GPSIG_ERR_UNSUPPORTED && generic_ok(p) && row_end == 0) {     // any-shape fallback (wide route where built; else orders of magnitude slower per pair)
         if (timed) { c->t_launches += 0; }
@@ -1058,7 +1072,8 @@ static int tens_gram_device(gpsig_ctx* c, const gpsig_params* p, bool raw, const
     if (sizeof(TT) == 8 && Tn > 0) {        // wide state spaces (wide_api.hip): beyond 12 columns, or wherever built when the option says so
         ScaleParams s;
         CHK(scale_params(c, p, !raw, &s));
-        if (wide_tens_available(c, p, Tn) && (c->wide == 1 || s.d_eff() > wide_auto_cols(p, 12))) {
+        if (wide_spectral(p) && !wide_tens_fwd_available(c, p, Tn)) return wide_spectral_refusal(c, p, false, 0);
+        if (wide_tens_fwd_available(c, p, Tn) && (c->wide == 1 || s.d_eff() > wide_auto_cols(p, 12))) {
             const double* w = nullptr;
             if (!raw) CHK(upload_weights(c, p, &w));
             return wide_tens_forward(c, p, s, s.d_eff(), static_cast<const double*>(Z), Tn, increments, w, (raw || return_levels) ? 0 : 1, static_cast<double*>(out));
@@ -1296,7 +1311,8 @@ static int tens_vs_seq_device(gpsig_ctx* c, const gpsig_params* p, bool raw, con
         // older mappings take -- 0.83 against 0.68 ms at UWave's shape --, the reverse pass saves its own forward sweep: 2.05 -> 1.59; option
         // wide_few_cols: the widest state space of this rule, A/B runs)
         const bool few = increments && d_eff > 4 && d_eff <= (c->wide_few_cols > 0 ? c->wide_few_cols : 8) && N <= 256 && p->base_kernel == GPSIG_BASE_RBF;
-        if (!wide_tvs_available(c, p, d_eff, Tn, N, L) || !(c->wide == 1 || d_eff > wide_auto_cols(p, 8) || (few && c->wide != 0 && c->tvs_tile != 1))) return GPSIG_OK;
+        if (wide_spectral(p) && !wide_tvs_fwd_available(c, p, d_eff, Tn, N, L)) return wide_spectral_refusal(c, p, false, 0);
+        if (!wide_tvs_fwd_available(c, p, d_eff, Tn, N, L) || !(c->wide == 1 || d_eff > wide_auto_cols(p, 8) || (few && c->wide != 0 && c->tvs_tile != 1))) return GPSIG_OK;
         void* xs;
         CHK(ensure(c, B_XT, sizeof(double) * size_t(N) * L * d_eff + 8, &xs));
         hipLaunchKernelGGL(prep_seq_scaled_kernel<double>, dim3(grid_for(N * int64_t(L) * d_eff)), dim3(256), 0, c->stream,
@@ -1374,7 +1390,7 @@ static int e_seq_gram_levels(gpsig_ctx* c, const gpsig_params* p, const void* X,
     const int d = p->num_features * (p->num_lags + 1);
     gpsig_params q = *p;
     q.num_features = d; q.num_lags = 0;      // raw entry point: columns are taken as they come
-    if (d > MAX_FEATURES && !(sizeof(TT) == 8 && d <= MAX_FEATURES_WIDE && wide_lat_available(c, p, L1, X2 ? L2 : L1)))
+    if (d > MAX_FEATURES && !(sizeof(TT) == 8 && d <= MAX_FEATURES_WIDE && (wide_spectral(p) || wide_lat_fwd_available(c, p, L1, X2 ? L2 : L1))))
         return fail(c, GPSIG_ERR_UNSUPPORTED, "d=%d too large", d);
     const void *dX, *dX2 = nullptr;
     CHK(in_dev(c, B_IN0, X, sizeof(TT) * size_t(N1) * L1 * d, &dX));
@@ -1393,7 +1409,7 @@ static int e_seq_diag_levels(gpsig_ctx* c, const gpsig_params* p, const void* X,
     const int d = p->num_features * (p->num_lags + 1);
     gpsig_params q = *p;
     q.num_features = d; q.num_lags = 0;
-    if (d > MAX_FEATURES && !(sizeof(TT) == 8 && d <= MAX_FEATURES_WIDE && wide_lat_available(c, p, L, L)))
+    if (d > MAX_FEATURES && !(sizeof(TT) == 8 && d <= MAX_FEATURES_WIDE && (wide_spectral(p) || wide_lat_fwd_available(c, p, L, L))))
         return fail(c, GPSIG_ERR_UNSUPPORTED, "d=%d too large", d);
     const int M1 = p->num_levels + 1;
     const void* dX;
@@ -1408,7 +1424,7 @@ static int e_seq_diag_levels(gpsig_ctx* c, const gpsig_params* p, const void* X,
 static int e_tens_gram_levels(gpsig_ctx* c, const gpsig_params* p, const void* Z, int64_t T, int32_t increments, void* out) {
     ENTER(c, p);
     const int d = p->num_features * (p->num_lags + 1), lt = p->num_levels * (p->num_levels + 1) / 2, E = increments ? 2 : 1;
-    if (d > MAX_FEATURES && !(sizeof(TT) == 8 && d <= MAX_FEATURES_WIDE && wide_tens_available(c, p, T)))
+    if (d > MAX_FEATURES && !(sizeof(TT) == 8 && d <= MAX_FEATURES_WIDE && (wide_spectral(p) || wide_tens_fwd_available(c, p, T))))
         return fail(c, GPSIG_ERR_UNSUPPORTED, "d=%d too large", d);
     const void* dZ;
     CHK(in_dev(c, B_IN0, Z, sizeof(TT) * size_t(lt) * T * E * d, &dZ));
@@ -1427,7 +1443,7 @@ static int e_tens_vs_seq_levels(gpsig_ctx* c, const gpsig_params* p, const void*
     ENTER(c, p);
     const int d = p->num_features * (p->num_lags + 1), lt = p->num_levels * (p->num_levels + 1) / 2, E = increments ? 2 : 1;
     // (beyond MAX_FEATURES columns only the wide route -- wide_api.hip -- takes the call)
-    if (d > MAX_FEATURES && !(sizeof(TT) == 8 && d <= MAX_FEATURES_WIDE && wide_tvs_available(c, p, d, T, N, L)))
+    if (d > MAX_FEATURES && !(sizeof(TT) == 8 && d <= MAX_FEATURES_WIDE && (wide_spectral(p) || wide_tvs_fwd_available(c, p, d, T, N, L))))
         return fail(c, GPSIG_ERR_UNSUPPORTED, "d=%d too large", d);
     const void *dZ, *dX;
     CHK(in_dev(c, B_IN0, Z, sizeof(TT) * size_t(lt) * T * E * d, &dZ));
@@ -1449,7 +1465,7 @@ static int e_tens_vs_seq_weighted(gpsig_ctx* c, const gpsig_params* p, const voi
                                int32_t increments, const void* fac, void* out, void* aux, int32_t* aux_written) {
     ENTER(c, p);
     const int d = p->num_features * (p->num_lags + 1), lt = p->num_levels * (p->num_levels + 1) / 2, E = increments ? 2 : 1;
-    if (d > MAX_FEATURES && !(sizeof(TT) == 8 && d <= MAX_FEATURES_WIDE && wide_tvs_available(c, p, d, T, N, L)))
+    if (d > MAX_FEATURES && !(sizeof(TT) == 8 && d <= MAX_FEATURES_WIDE && (wide_spectral(p) || wide_tvs_fwd_available(c, p, d, T, N, L))))
         return fail(c, GPSIG_ERR_UNSUPPORTED, "d=%d too large", d);
     if (!fac && N > 0) return fail(c, GPSIG_ERR_INVALID, "null factor array");
     const void *dZ, *dX, *dF;

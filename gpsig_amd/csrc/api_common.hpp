@@ -13,6 +13,9 @@ int check_params(gpsig_ctx* c, const gpsig_params* p, bool low_rank = false, boo
 int scale_params(gpsig_ctx* c, const gpsig_params* p, bool apply_scaling, ScaleParams* out);
 // BASE_SPECTRAL: alpha[Q], omega[Q][SPECTRAL_STRIDE], gamma[Q][SPECTRAL_STRIDE] on the device (zero padded); NULL otherwise
 int spectral_table(gpsig_ctx* c, const gpsig_params* p, const double** dev);
+// ... beyond SPECTRAL_STRIDE columns (low-rank evaluation with lr_spectral_wide, exact evaluation with spectral_wide): alpha[Q], omega[Q][d], gamma[Q][d]
+// as the caller holds them, on the device in B_SPECW (lr_api.hip)
+int spectral_table_wide(gpsig_ctx* c, const gpsig_params* p, const double** dev);
 void base_p(const gpsig_params* p, double* p0, double* p1);
 // weights sigma * variances[m] on the device
 int upload_weights(gpsig_ctx* c, const gpsig_params* p, const double** w);

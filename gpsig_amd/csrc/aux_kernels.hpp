@@ -918,4 +918,17 @@ __global__ void levels_epilogue_kernel(const double* __restrict__ lev, int64_t N
                                        const double* __restrict__ by, double jitter_diag, int sum_levels, double* __restrict__ out);
 #endif
 
+// level diagonals (M1, N) -> out[m * sm + i * si]
+#ifdef GPSIG_KERNEL_DEFS
+__global__ void levels_relayout_kernel(const double* __restrict__ lev, int64_t N, int M1, int64_t sm, int64_t si, double* __restrict__ out) {
+    const int64_t total = N * M1;
+    for (int64_t idx = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; idx < total; idx += int64_t(gridDim.x) * blockDim.x) {
+        const int64_t m = idx / N, i = idx - m * N;
+        out[m * sm + i * si] = lev[idx];
+    }
+}
+#else
+__global__ void levels_relayout_kernel(const double* __restrict__ lev, int64_t N, int M1, int64_t sm, int64_t si, double* __restrict__ out);
+#endif
+
 }  // namespace gpsig

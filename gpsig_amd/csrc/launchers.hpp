@@ -193,6 +193,23 @@ int wide_lat_forward(gpsig_ctx* c, const gpsig_params* p, int d, const double* X
 int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* Xs, const double* Ys, int64_t N1, int64_t N2, int L1, int L2, bool diag,
                       const double* G, double* gX, double* gY, double* g_base);
 
+// the forward side's own predicates (api.hip's evaluation entry points and level primitives): the three above, or exact-mode SignatureSpectral beyond 32
+// columns (wide_spectral: the kernel object has opted in -- check_params --; forward only, the reverse entry points keep asking the three above).
+// wide_spectral_refusal: why such a call is not served, as the context's error (GPSIG_ERR_UNSUPPORTED)
+bool wide_spectral(const gpsig_params* p);
+bool wide_tvs_fwd_available(const gpsig_ctx* c, const gpsig_params* p, int d, int64_t Tn, int64_t N, int L);
+bool wide_tens_fwd_available(const gpsig_ctx* c, const gpsig_params* p, int64_t Tn);
+bool wide_lat_fwd_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L2);
+int wide_spectral_refusal(gpsig_ctx* c, const gpsig_params* p, bool lattice, int L2);
+
+// ---- wide_spectral_inst.hip: SignatureSpectral's kernel-argument array of the wide route (wide_spectral_kernel.hpp).  They return the hipError_t of the launch.
+struct WideSpxArgs;
+int wide_spx_prep_launch(hipStream_t stream, const double* gamma, int64_t count, double* g2);          // g2 = gamma^2
+// nrm, ph (Q, rows): the norms sum_f g2_qf x_f^2 and the phases <omega_q, x> of the rows X (rows, ld)
+int wide_spx_side_launch(hipStream_t stream, const double* X, int64_t rows, int64_t ld, int d, int Q, const double* omega, const double* g2, double* nrm,
+                         double* ph);
+int wide_spx_launch(hipStream_t stream, const WideSpxArgs& A);
+
 // ---- lr_cross_spectral_inst.hip: gpsig_spectral_cross / gpsig_spectral_cross_grad beyond 32 columns (the entry points: spectral_cross_api.hip)
 int spectral_cross_wide(gpsig_ctx* c, int Q, int family, int d, const double* P, int64_t n, const double* S, int cc, const double* alpha,
                         const double* omega, const double* gamma, double* K);

@@ -58,9 +58,12 @@ bool spectral_wide(const gpsig_params* p) {
     return p->base_kernel == GPSIG_BASE_SPECTRAL && p->base_params[2] != 0.0 && p->num_features > SPECTRAL_STRIDE;
 }
 
+}  // namespace
+
 // ... and their table: alpha[Q], omega[Q][d], gamma[Q][d] as the caller holds it, on the device in B_SPECW.  Compared in full and uploaded only
-// when changed, as api.hip's spectral_table; a change refuses the replays of recorded graphs in the same way.
-int spectral_table_wide(gpsig_ctx* c, const gpsig_params* p, const double** dev) {
+// when changed, as api.hip's spectral_table; a change refuses the replays of recorded graphs in the same way.  (Exact mode's wide route takes the
+// same table: wide_api.hip.)
+int gpsig::spectral_table_wide(gpsig_ctx* c, const gpsig_params* p, const double** dev) {
     const size_t n = size_t(p->base_table_len);
     void* dp;
     CHK(ensure(c, B_SPECW, sizeof(double) * n, &dp));
@@ -76,6 +79,8 @@ int spectral_table_wide(gpsig_ctx* c, const gpsig_params* p, const double** dev)
     *dev = static_cast<const double*>(dp);
     return GPSIG_OK;
 }
+
+namespace {
 
 // kappa(A, B) (na, nb) of rows of d columns for a landmark Gram (gpsig_lr_whitening, gpsig_lr_draw, gpsig_base_kernel_matrix): the thread-per-pair
 // kernel of every family on the packed table, or -- spectral_wide -- its twin with row stride d

@@ -5,10 +5,15 @@
 // dot-product families, whose kappa IS that number: SignatureLinear on plain rows -- increments where the kernel takes differences, so that the kernels run in
 // their difference = 0 form on one row less and half the tensor columns --, SignatureCosine on unit rows.
 // SignaturePoly (whole degrees) on plain rows; SignatureMix on the distance kernels' rows, psi of the dgemm's number plus the one-sided norm terms (mix_sides).
+// SignatureSpectral in exact mode beyond 32 columns, forward only (wide_spectral): kappa is no function of one inner product, so the argument array is
+// filled by wide_spectral_kernel.hpp's kernel on plain rows instead of the dgemm, and holds kappa itself -- the kernels run in their identity kind with
+// SignatureCosine's difference handling.  Every entry depends on its row and column alone: the same bits under any chunking.
 #include "ctx.hpp"
+#include "api_common.hpp"
 #include "launchers.hpp"
 #include "aux_kernels.hpp"
 #include "wide_kernels.hpp"
+#include "wide_spectral_kernel.hpp"
 
 #include <string>
 
@@ -28,10 +33,11 @@ bool wide_kind(const gpsig_params* p) {
 int kind_of(int base_kernel) {
     if (base_kernel == GPSIG_BASE_POLY) return WIDE_KD_POLY;
     if (base_kernel == GPSIG_BASE_MIX) return WIDE_KD_MIX;          // (the distance kernels' augmented rows: rows_mode falls through to WIDE_ROWS_DIST)
+    if (base_kernel == GPSIG_BASE_SPECTRAL) return WIDE_KD_ID;      // (the argument array holds kappa: wide_spectral_kernel.hpp)
     return base_kernel == GPSIG_BASE_RBF ? WIDE_KD_RBF : (wide_dot_kind(base_kernel) ? WIDE_KD_ID : WIDE_KD_MATERN);
 }
 int rows_mode(int base_kernel) {
-    if (base_kernel == GPSIG_BASE_POLY) return WIDE_ROWS_PLAIN;
+    if (base_kernel == GPSIG_BASE_POLY || base_kernel == GPSIG_BASE_SPECTRAL) return WIDE_ROWS_PLAIN;
     return base_kernel == GPSIG_BASE_LINEAR ? WIDE_ROWS_PLAIN : (base_kernel == GPSIG_BASE_COSINE ? WIDE_ROWS_UNIT : WIDE_ROWS_DIST);
 }
 // SignatureLinear: <.,.> is bilinear, so the differences along the sequences (signature_algs.py:26 / :114) and between a tensor's two points
@@ -94,6 +100,53 @@ int dgemm_batched(gpsig_ctx* c, bool ta, bool tb, int64_t m, int64_t n, int64_t 
     if (!solver_dgemm_batched(&c->blas_handle, c->stream, ta, tb, int(m), int(n), int(k), 1.0, A, int(lda), sa, B, int(ldb), sb, 0.0, C, int(ldc), sc, int(batch), &err))
         return fail(c, GPSIG_ERR_HIP, "%s", err.c_str());
     return GPSIG_OK;
+}
+
+// ---- SignatureSpectral (exact mode beyond 32 columns): what a call computes once -- the table on the device, gamma^2 -- and per side
+struct SpxSetup {
+    const double *alpha, *omega, *g2;
+    int Q, family, d;
+};
+int spx_setup(gpsig_ctx* c, const gpsig_params* p, int d, SpxSetup* s) {
+    const double* tab;
+    CHK(spectral_table_wide(c, p, &tab));
+    s->Q = int(p->base_params[0]); s->family = int(p->base_params[1]); s->d = d;
+    s->alpha = tab; s->omega = tab + s->Q;
+    void* g2;
+    CHK(ensure(c, B_WS0, sizeof(double) * size_t(s->Q) * d + 64, &g2));
+    const int rc = wide_spx_prep_launch(c->stream, s->omega + size_t(s->Q) * d, int64_t(s->Q) * d, static_cast<double*>(g2));
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral wide route: %s", hipGetErrorString(hipError_t(rc)));
+    s->g2 = static_cast<const double*>(g2);
+    return GPSIG_OK;
+}
+// the norms and phases (Q, rows) each of the plain rows X (rows, d + 2), in buffer `id`: *nrm, then the phases `Q * rows` doubles on
+int spx_side(gpsig_ctx* c, const SpxSetup& s, const double* X, int64_t rows, int id, const double** nrm) {
+    void* b;
+    CHK(ensure(c, id, sizeof(double) * 2 * size_t(s.Q) * size_t(rows) + 64, &b));
+    double* n = static_cast<double*>(b);
+    const int rc = wide_spx_side_launch(c->stream, X, rows, s.d + 2, s.d, s.Q, s.omega, s.g2, n, n + int64_t(s.Q) * rows);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral wide route: %s", hipGetErrorString(hipError_t(rc)));
+    *nrm = n;
+    return GPSIG_OK;
+}
+// C_b (m, ldc) = kappa(A_b (m, d + 2), B_b (n, d + 2)) for `batch` matrices `sa`, `sb`, `sc` doubles apart; nA / nB: spx_side's arrays of ALL `planeA` /
+// `planeB` rows of the two sides, the first row of A_0 / B_0 at row a0 / b0 of them
+int spx_arguments(gpsig_ctx* c, const SpxSetup& s, const double* A, const double* B, double* C, int64_t m, int64_t n, int64_t ldc, int64_t sa, int64_t sb,
+                  int64_t sc, int64_t batch, const double* nA, int64_t planeA, int64_t a0, const double* nB, int64_t planeB, int64_t b0) {
+    if (m > 0x7fffffff || n > 0x7fffffff || ldc > 0x7fffffff) return fail(c, GPSIG_ERR_UNSUPPORTED, "wide route: a matrix dimension beyond 2^31");
+    const int DA = s.d + 2;
+    WideSpxArgs K;
+    memset(&K, 0, sizeof(K));
+    K.A = A; K.B = B; K.C = C; K.m = m; K.n = n; K.lda = DA; K.ldb = DA; K.ldc = ldc; K.sa = sa; K.sb = sb; K.sc = sc; K.batch = batch;
+    K.d = s.d; K.Q = s.Q; K.family = s.family; K.alpha = s.alpha; K.g2 = s.g2;
+    K.nrmA = nA + a0; K.phA = nA + int64_t(s.Q) * planeA + a0; K.planeA = planeA; K.rowsA = sa / DA;
+    K.nrmB = nB + b0; K.phB = nB + int64_t(s.Q) * planeB + b0; K.planeB = planeB; K.rowsB = sb / DA;
+    const int rc = wide_spx_launch(c->stream, K);
+    if (rc != 0) return fail(c, GPSIG_ERR_HIP, "spectral wide route: %s", hipGetErrorString(hipError_t(rc)));
+    return GPSIG_OK;
+}
+bool spx_context_ok(const gpsig_ctx* c, const gpsig_params* p) {
+    return c->wide != 0 && !c->capturing && p->num_levels >= 1 && p->num_levels <= WIDE_MAX_LEVELS;
 }
 
 int aug_rows(gpsig_ctx* c, const double* src, int64_t rows, int d, int right, int mode, int diff, double* dst) {
@@ -238,6 +291,38 @@ bool wide_tvs_available(const gpsig_ctx* c, const gpsig_params* p, int d, int64_
     return true;
 }
 
+// ---- the forward side's own predicates: exact-mode SignatureSpectral beyond 32 columns is served by the forward functions only
+bool wide_spectral(const gpsig_params* p) { return p->base_kernel == GPSIG_BASE_SPECTRAL && p->num_features * (p->num_lags + 1) > SPECTRAL_STRIDE; }
+
+bool wide_tvs_fwd_available(const gpsig_ctx* c, const gpsig_params* p, int d, int64_t Tn, int64_t N, int L) {
+    if (!wide_spectral(p)) return wide_tvs_available(c, p, d, Tn, N, L);
+    return spx_context_ok(c, p) && !(p->order > WIDE_MAX_ORDER && p->num_levels > WIDE_MAX_ORDER) && Tn >= 1 && N >= 1 && L >= 1;
+}
+static bool tens_fits(const gpsig_params* p, int64_t Tn) {
+    const int64_t Tpad = (Tn + 63) / 64 * 64;
+    return Tn >= 1 && size_t(p->num_levels * (p->num_levels + 1) / 2) * size_t(4 * Tpad * Tpad) * sizeof(double) <= (size_t(2) << 30);
+}
+bool wide_tens_fwd_available(const gpsig_ctx* c, const gpsig_params* p, int64_t Tn) {
+    if (!wide_spectral(p)) return wide_tens_available(c, p, Tn);
+    return spx_context_ok(c, p) && tens_fits(p, Tn);
+}
+bool wide_lat_fwd_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L2) {
+    if (!wide_spectral(p)) return wide_lat_available(c, p, L1, L2);
+    return spx_context_ok(c, p) && !(p->order > 1 && p->num_levels > 1) && L1 >= 1 && L2 >= 1 && L2 - (p->difference ? 1 : 0) <= 512;
+}
+// why a call of exact-mode SignatureSpectral beyond 32 columns is not served (lattice: a sequence lattice of L2 columns; else Kzx / Kzz)
+int wide_spectral_refusal(gpsig_ctx* c, const gpsig_params* p, bool lattice, int L2) {
+    const char* const who = "exact-mode SignatureSpectral beyond 32 columns (spectral_wide)";
+    if (c->wide == 0) return fail(c, GPSIG_ERR_UNSUPPORTED, "%s runs on the wide route only: context option wide = 0 refuses it", who);
+    if (c->capturing) return fail(c, GPSIG_ERR_UNSUPPORTED, "%s is not served during library graph capture", who);
+    if (p->num_levels > WIDE_MAX_LEVELS) return fail(c, GPSIG_ERR_UNSUPPORTED, "%s is built for num_levels <= %d (got %d)", who, WIDE_MAX_LEVELS, p->num_levels);
+    if (lattice && p->order > 1 && p->num_levels > 1)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "%s serves first-order sequence lattices only (order = %d; Kzx: orders <= %d)", who, p->order, WIDE_MAX_ORDER);
+    if (lattice) return fail(c, GPSIG_ERR_UNSUPPORTED, "%s serves sequence lattices of at most 512 columns (got %d)", who, L2 - (p->difference ? 1 : 0));
+    if (p->order > WIDE_MAX_ORDER && p->num_levels > WIDE_MAX_ORDER) return fail(c, GPSIG_ERR_UNSUPPORTED, "%s serves Kzx at orders <= %d (got %d)", who, WIDE_MAX_ORDER, p->order);
+    return fail(c, GPSIG_ERR_UNSUPPORTED, "%s: the argument blocks of the inducing tensors must fit 2 GB, and every size must be positive", who);
+}
+
 // Kzx (kernels.py:313-340 + signature_algs.py:101-127 + the epilogue of kernels.py:572-588).  Z: the caller's (lt, T, E, d) array, scaled here when
 // sz.has_ls; Xs: (N, L, d) scaled sequences.  fx (N, M+1), w (M+1): factors or NULL.  out: (T, N) level sum or (M+1, T, N).  aux: chain totals or NULL.
 int wide_tvs_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz, int d, const double* Z, const double* Xs, int64_t Tn, int64_t N, int L,
@@ -263,10 +348,19 @@ int wide_tvs_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz,
     hipEvent_t e0, e1;
     bool timed;
     CHK(wide_timing_begin(c, &e0, &e1, &timed));
+    const bool spx = wide_spectral(p);
+    SpxSetup ss;
+    const double *nz = nullptr, *nx = nullptr;
+    if (spx) {
+        CHK(spx_setup(c, p, d, &ss));
+        CHK(spx_side(c, ss, ZA, CW, B_WS1, &nz));
+        CHK(spx_side(c, ss, XA, N * int64_t(L), B_WS2, &nx));
+    }
     for (int64_t n0 = 0; n0 < N; n0 += chunk) {
         const int64_t nc = N - n0 < chunk ? N - n0 : chunk;
         // row-major arg (nc L, CW) = XA_chunk (nc L, DA) ZA^T  ==  column-major arg^T (CW x nc L) = ZA_cm^T (CW x DA) XA_cm (DA x nc L)
-        CHK(dgemm(c, true, false, CW, nc * L, DA, ZA, DA, XA + n0 * L * DA, DA, 0.0, static_cast<double*>(arg), CW));
+        if (spx) CHK(spx_arguments(c, ss, XA + n0 * L * DA, ZA, static_cast<double*>(arg), nc * L, CW, CW, 0, 0, 0, 1, nx, N * int64_t(L), n0 * L, nz, CW, 0));
+        else CHK(dgemm(c, true, false, CW, nc * L, DA, ZA, DA, XA + n0 * L * DA, DA, 0.0, static_cast<double*>(arg), CW));
         WideTvsArgs A;
         memset(&A, 0, sizeof(A));
         A.arg = static_cast<const double*>(arg); A.CW = CW; A.Tpad = Tpad; A.Tn = Tn; A.n0 = n0; A.Nc = nc; A.N = N;
@@ -286,7 +380,7 @@ int wide_tvs_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz,
         HIPCHK(c, hipEventRecord(e1, c->stream));
         c->t_launches += 1;
         c->t_pairs += Tn * N;
-        c->t_kernel = "wide_tvs (dgemm + wide_tvs_fwd_kernel)";
+        c->t_kernel = spx ? "wide_tvs (wide_spx_kernel + wide_tvs_fwd_kernel)" : "wide_tvs (dgemm + wide_tvs_fwd_kernel)";
         c->t_flops += 2.0 * double(CW) * double(N) * L * DA;
     }
     return GPSIG_OK;
@@ -481,8 +575,17 @@ int lat_plan(gpsig_ctx* c, const gpsig_params* p, int d, const double* Xs, const
 
 // the argument lattices of the left sequences i0 .. i0 + ni - 1 into `arg`
 // (j0 > 0: the right sequences j0 .. N2 - 1 only -- the symmetric Gram's reverse pass, pairs i <= j)
-int lat_arguments(gpsig_ctx* c, const LatPlan& pl, int64_t i0, int64_t ni, int64_t N2, int L1, int L2, bool diag, double* arg, int64_t j0 = 0) {
+// (spx: SignatureSpectral -- the entries are kappa, from wide_spectral_kernel.hpp's kernel with the sides' norms and phases nl, nr of all N1 L1 / N2 L2 rows)
+struct LatSpx { SpxSetup s; const double *nl = nullptr, *nr = nullptr; int64_t N1 = 0; };
+int lat_arguments(gpsig_ctx* c, const LatPlan& pl, int64_t i0, int64_t ni, int64_t N2, int L1, int L2, bool diag, double* arg, int64_t j0 = 0,
+                  const LatSpx* spx = nullptr) {
     const int DA = pl.DA;
+    if (spx && diag)
+        return spx_arguments(c, spx->s, pl.XL + i0 * L1 * DA, pl.XR + i0 * L2 * DA, arg, L1, L2, L2, int64_t(L1) * DA, int64_t(L2) * DA, int64_t(L1) * L2, ni,
+                             spx->nl, spx->N1 * L1, i0 * L1, spx->nr, N2 * L2, i0 * L2);
+    if (spx)
+        return spx_arguments(c, spx->s, pl.XL + i0 * L1 * DA, pl.XR + j0 * L2 * DA, arg, ni * L1, (N2 - j0) * L2, (N2 - j0) * L2, 0, 0, 0, 1, spx->nl,
+                             spx->N1 * L1, i0 * L1, spx->nr, N2 * L2, j0 * L2);
     if (diag)      // per sequence: row-major arg (L1, L2) = XL_n XR_n^T  ==  column-major (L2 x L1) = XR_n,cm^T (L2 x DA) XL_n,cm (DA x L1)
         return dgemm_batched(c, true, false, L2, L1, DA, pl.XR + i0 * L2 * DA, DA, int64_t(L2) * DA, pl.XL + i0 * L1 * DA, DA, int64_t(L1) * DA, arg, L2,
                              int64_t(L1) * L2, ni);
@@ -512,9 +615,18 @@ int wide_lat_forward(gpsig_ctx* c, const gpsig_params* p, int d, const double* X
     hipEvent_t e0, e1;
     bool timed;
     CHK(wide_timing_begin(c, &e0, &e1, &timed));
+    LatSpx spx;
+    const bool is_spx = wide_spectral(p);
+    if (is_spx) {
+        if (ho) return wide_spectral_refusal(c, p, true, L2);
+        spx.N1 = N1;
+        CHK(spx_setup(c, p, d, &spx.s));
+        CHK(spx_side(c, spx.s, pl.XL, N1 * int64_t(L1), B_WS1, &spx.nl));
+        CHK(spx_side(c, spx.s, pl.XR, N2 * int64_t(L2), B_WS2, &spx.nr));
+    }
     for (int64_t i0 = 0; i0 < N1; i0 += pl.chunk_i) {
         const int64_t ni = N1 - i0 < pl.chunk_i ? N1 - i0 : pl.chunk_i;
-        CHK(lat_arguments(c, pl, i0, ni, N2, L1, L2, diag, static_cast<double*>(arg)));
+        CHK(lat_arguments(c, pl, i0, ni, N2, L1, L2, diag, static_cast<double*>(arg), 0, is_spx ? &spx : nullptr));
         WideLatArgs A;
         memset(&A, 0, sizeof(A));
         A.arg = static_cast<const double*>(arg); A.ld = pl.ld; A.si = pl.si; A.sj = pl.sj; A.N2 = pl.N2;
@@ -541,7 +653,7 @@ int wide_lat_forward(gpsig_ctx* c, const gpsig_params* p, int d, const double* X
         HIPCHK(c, hipEventRecord(e1, c->stream));
         c->t_launches += 1;
         c->t_pairs += pl.Ptot;
-        c->t_kernel = "wide_lattice (dgemm + wide_lattice_fwd_kernel)";
+        c->t_kernel = is_spx ? "wide_lattice (wide_spx_kernel + wide_lattice_fwd_kernel)" : "wide_lattice (dgemm + wide_lattice_fwd_kernel)";
     }
     return GPSIG_OK;
 }
@@ -732,8 +844,17 @@ int tens_arguments(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz, i
         HIPCHK(c, hipGetLastError());
     }
     // block k, row-major (R, R) = ZL_k ZR_k^T  ==  column-major (R x R) = ZR_k,cm^T (R x DA) ZL_k,cm (DA x R)
-    CHK(dgemm_batched(c, true, false, R, R, DA, static_cast<const double*>(zrr), DA, R * DA, static_cast<const double*>(zl), DA, R * DA, static_cast<double*>(ar), R,
-                      R * R, lt));
+    if (wide_spectral(p)) {          // (forward only; plain rows: both forms hold the same rows, one pre-pass serves both sides)
+        SpxSetup ss;
+        const double* nz;
+        CHK(spx_setup(c, p, d, &ss));
+        CHK(spx_side(c, ss, static_cast<const double*>(zl), zr, B_WS1, &nz));
+        CHK(spx_arguments(c, ss, static_cast<const double*>(zl), static_cast<const double*>(zrr), static_cast<double*>(ar), R, R, R, R * DA, R * DA, R * R, lt, nz,
+                          zr, 0, nz, zr, 0));
+    } else {
+        CHK(dgemm_batched(c, true, false, R, R, DA, static_cast<const double*>(zrr), DA, R * DA, static_cast<const double*>(zl), DA, R * DA,
+                          static_cast<double*>(ar), R, R * R, lt));
+    }
     *ZL = static_cast<double*>(zl); *ZR = static_cast<double*>(zrr); *arg = static_cast<double*>(ar);
     return GPSIG_OK;
 }
@@ -760,7 +881,7 @@ int wide_tens_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz
         HIPCHK(c, hipEventRecord(e1, c->stream));
         c->t_launches += 1;
         c->t_pairs += Tn * Tn;
-        c->t_kernel = "wide_tens (dgemm + wide_tens_fwd_kernel)";
+        c->t_kernel = wide_spectral(p) ? "wide_tens (wide_spx_kernel + wide_tens_fwd_kernel)" : "wide_tens (dgemm + wide_tens_fwd_kernel)";
     }
     return GPSIG_OK;
 }

@@ -1035,9 +1035,15 @@ class SignatureSpectral(SignatureKernel):
         # low-rank mode beyond 32 columns on the library's own surface (K, Kdiag, K_tens*, K_seq_n_seq_covs, draw_low_rank, SVGP.predict_f): opt-in,
         # float64, num_components <= 64; it travels to the library in base_params[2].  Exact mode keeps its 32 columns whatever this says.
         self.lr_spectral_wide = False
+        # exact (non-low-rank) mode beyond 32 columns, evaluation only (K, Kdiag, K_tens*, K_seq_n_seq_covs, the compute_* wrappers, Kuu / Kuf,
+        # SVGP.predict_f): opt-in, float64 inside the library (float32 inputs are computed in float64 and rounded), 33 .. 4096 columns, Q <= 64,
+        # num_levels <= 8, first-order sequence Grams, Kzx orders <= 4, dense batches; it travels in base_params[3].  Up to 32 columns it changes nothing.
+        self.spectral_wide = False
 
     def _current_base_params(self):
         bp = (float(self.Q), float(self._FAMILIES[self.family]))
+        if self.spectral_wide:
+            return bp + (1.0 if self.lr_spectral_wide else 0.0, 1.0)
         return bp + (1.0,) if self.lr_spectral_wide else bp
 
     def _params(self, keep, dtype_id=_lib.F64):

@@ -58,7 +58,22 @@ enum gpsig_base_kernel {
                                  the normalised gpsig_kernel_Kdiag (which runs no base kernel) -- take 33 .. 4096 features: float64,
                                  num_components <= 64, num_levels <= 8 (see gpsig_lr_seq_features).  Up to 32 features the slot
                                  changes nothing, and every exact (non-low-rank) evaluation keeps refusing more whatever it holds.
-                                 The opt-in is off until a follow-up flips the default. */
+                                 The opt-in is off until a follow-up flips the default.
+                                 base_params[3] is the kernel object's OPT-IN to EXACT (non-low-rank) evaluation beyond 32 features
+                                 (kernels.SignatureSpectral.spectral_wide), independent of [2]: 0 (the default) refuses as before, with
+                                 the same messages and codes; non-zero lets the evaluation entry points and forward level primitives --
+                                 gpsig_kernel_K, _Kdiag, _K_tens, _K_tens_vs_seq, _K_tens_n_seq_covs, _K_seq_n_seq_covs,
+                                 gpsig_seq_gram_levels, gpsig_seq_diag_levels, gpsig_tens_gram_levels, gpsig_tens_vs_seq_levels,
+                                 gpsig_tens_vs_seq_weighted -- take 33 .. 4096 features on the wide route (the argument array by
+                                 wide_spx_kernel on the float64 matrix cores; two bitwise-equal points are at distance and phase
+                                 exactly 0): float64, Q <= 64, num_levels <= 8, first-order sequence lattices of at most 512 columns,
+                                 Kzx at orders <= 4, Kzz within 2 GB of argument blocks, dense batches, host and device pointers; the
+                                 result does not depend on wide_chunk_mb bit for bit.  GPSIG_ERR_UNSUPPORTED with a message naming the
+                                 bound: "... serves first-order sequence lattices only", "... sequence lattices of at most 512 columns",
+                                 "... serves Kzx at orders <= 4", "... is built for num_levels <= 8", "... context option wide = 0
+                                 refuses it", "... is not served during library graph capture", "the spectral base kernel is built
+                                 for float64 only", "num_features=... outside [1, 4096]".  No gradient entry point takes the family;
+                                 up to 32 features the slot changes no bit. */
 };
 
 enum gpsig_dtype { GPSIG_F64 = 0, GPSIG_F32 = 1 };
