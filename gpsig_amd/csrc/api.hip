@@ -3,13 +3,14 @@
 // Host-side orchestration only: input preparation, kernel-shape selection, task lists, scratch
 // memory, HIP-event timing.  All arithmetic happens in kernels: the pair recursions of seq_gram_kernel.hpp
 // and seq_pk2_kernel.hpp, the tensor kernels and elementwise passes of aux_kernels.hpp and tvs_tile_kernel.hpp,
-// the level features and their contraction of sig_feat_kernel.hpp, and the wide route's wide_kernels.hpp (wide_api.hip).  The kernels
+// the level features and their contraction of sig_feat_kernel.hpp (sig_feat_api.hip), and the wide route's wide_kernels.hpp (wide_api.hip).  The kernels
 // are instantiated in the instance units; launchers.hpp declares their lookups, and the sequence-Gram units are
 // found through the table of descriptors below.  There is deliberately no CPU fallback: without a HIP device
 // every entry point fails with GPSIG_ERR_HIP.
 // Here: contexts, options, graphs, timing, the clock probe and the entry points of the exact kernels.  Low-rank evaluation is lr_api.hip, low-rank
-// training lr_grad_api.hip, the gradients grad_api.hip, sig_feat_grad_api.hip and tvs_grad_api.hip, the spectral cross op spectral_cross_api.hip.
-// What this unit and lr_api.hip both open a call with is defined here and declared in api_common.hpp.
+// training lr_grad_api.hip, the gradients grad_api.hip, sig_feat_grad_api.hip and tvs_grad_api.hip, the spectral cross op spectral_cross_api.hip; the
+// feature route of the linear / cosine kernel (sig_features_K, tvs_features_plan, tens_vs_seq_features_device) is sig_feat_api.hip.
+// What this unit and lr_api.hip both open a call with, and the timed-launch helper, are defined here and declared in api_common.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -27,7 +28,6 @@
 #include "seq_configs.hpp"
 #include "tvs_tile_kernel.hpp"
 #include "seq_pk2_kernel.hpp"
-#include "sig_feat_kernel.hpp"
 
 using namespace gpsig;
 
@@ -207,12 +207,7 @@ int upload_weights(gpsig_ctx* c, const gpsig_params* p, const double** w) {
     return GPSIG_OK;
 }
 
-}  // namespace gpsig
-
-namespace {
-
-constexpr size_t TIMING_MAX_EVENTS = 8192;
-int timing_begin_any(gpsig_ctx* c, hipEvent_t* e0, hipEvent_t* e1, bool* on) {
+int timing_begin(gpsig_ctx* c, hipEvent_t* e0, hipEvent_t* e1, bool* on) {
     *on = false;
     if (c->capturing || c->ev_used + 2 > TIMING_MAX_EVENTS) return GPSIG_OK;
     if (c->ev_used + 2 > c->ev.size()) {
@@ -230,273 +225,9 @@ int timing_begin_any(gpsig_ctx* c, hipEvent_t* e0, hipEvent_t* e1, bool* on) {
     return GPSIG_OK;
 }
 
+}  // namespace gpsig
 
-// ---- the linear / cosine kernel's Kzx as a product of level features (round 4) ------------------------------------------------------
-// An inducing tensor's level m is the rank-one tensor z_1 (x) .. (x) z_m (first factor <-> earliest time, signature_algs.py:118-125), and
-// K_m(z, x) = <z_1 (x) .. (x) z_m, Phi_m(x)> with the level features of sig_feat_kernel.hpp (every order: :129-160 too).
-// Zf[t][k]: the tensors' features in the layout of the sequences' (natural order, level-0 column = 1, zero padding).  ZT / ZS as
-// prep_tensors_kernel leaves them: ZT[((t * d + f) * lt + c) * E + e], ZS[(t * lt + c) * E + e] = |z|^2.
-static __global__ void tens_level_features_kernel(const double* __restrict__ ZT, const double* __restrict__ ZS, int lt, int E, int d, int64_t Tn,
-                                                  int M, int unit, int64_t ld, double* __restrict__ Zf) {
-    const int64_t total = Tn * ld;
-    for (int64_t e = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; e < total; e += int64_t(gridDim.x) * blockDim.x) {
-        const int64_t t = e / ld;
-        int k = int(e - t * ld), m = 1, w = d, off = 0;
-        while (m <= M && k >= off + w) { off += w; ++m; w *= d; }
-        double v;
-        if (m > M) {
-            v = k == off ? 1.0 : 0.0;                                 // level 0, then the padding
-        } else {
-            int idx = k - off;
-            const int c0 = m * (m - 1) / 2;
-            v = 1.0;
-            for (int j = m - 1; j >= 0; --j) {                        // last index fastest = the component paired with the latest time
-                const int f = idx % d;
-                idx /= d;
-                const int c = c0 + j;
-                double z = ZT[((t * d + f) * lt + c) * E + (E - 1)];
-                if (unit) z *= rsqrt(ZS[(t * lt + c) * E + (E - 1)]);  // SignatureCosine: unit vectors (kernels.py:820-828)
-                if (E == 2) {                                         // increments: k(z1, x) - k(z0, x) is linear in z (kernels.py:329-330)
-                    double z0 = ZT[((t * d + f) * lt + c) * E];
-                    if (unit) z0 *= rsqrt(ZS[(t * lt + c) * E]);
-                    z -= z0;
-                }
-                v *= z;
-            }
-        }
-        Zf[e] = v;
-    }
-}
-
-static __global__ void square_small_kernel(const double* __restrict__ a, int n, double* __restrict__ b) {
-    if (int(threadIdx.x) < n) b[threadIdx.x] = a[threadIdx.x] * a[threadIdx.x];
-}
-
-// ---- SignatureLinear, first order: the Gram as a contraction of explicit level features (sig_feat_kernel.hpp) --------------------
-// Taken where it is the cheaper evaluation -- 2 sum_m d^m flops per entry on the matrix cores against the lattice sweep's
-// L1 L2 (2d + 3M - 1) on the vector unit at about 0.6 of the GEMM's efficiency -- and the feature matrices fit.  *done = false
-// leaves the call to the lattice kernels.  row_end > 0: the owned entries of rows [row_begin, row_end) (multi-GPU row blocks).
-int sig_features_K(gpsig_ctx* c, const gpsig_params* p, bool raw, const void* X, const void* X2, int64_t N1, int64_t N2, int L1, int L2,
-                   int return_levels, void* out, bool timed, int x_squared, int64_t row_begin, int64_t row_end, int compact, bool* done,
-                   bool row_block_call = false) {
-    *done = false;
-    // the linear kernel, and the cosine kernel as the linear kernel of the unit vectors x / |x| (kernels.py:820-828)
-    const bool cosine = p->base_kernel == GPSIG_BASE_COSINE;
-    // float32 calls too: computed in float64 (the matrix cores' own precision), inputs widened and the result rounded -- 29 -> 1.4 ms at
-    // d = 16, num_levels = 3, and closer to the reference than a float32 recursion; not for row blocks (float64 only)
-    const bool f32 = p->dtype == GPSIG_F32;
-    if (c->sig_features == 0 || !(p->dtype == GPSIG_F64 || f32) || !(p->base_kernel == GPSIG_BASE_LINEAR || cosine)) return GPSIG_OK;
-    if (x_squared && (X2 == nullptr || raw || !p->normalization)) return GPSIG_OK;       // (the quirk is a cross Gram's: its X side only)
-    if (f32 && (row_end > 0 || row_block_call)) return GPSIG_OK;
-    if (c->shard_n > 1) return GPSIG_OK;          // gpsig_set_shard: "entries outside the shard are left untouched" is the pair kernels' contract
-    const int M = p->num_levels;
-    if (M < 2 || p->order < 1 || p->order > M) return GPSIG_OK;
-    const int d = p->num_features * ((raw ? 0 : p->num_lags) + 1);
-    SigFeatLaunchFn ffn = sig_feat_lookup(d, M);
-    if (!ffn) return GPSIG_OK;
-    const bool sym = X2 == nullptr;
-    void* out32 = nullptr;                    // float32 calls: where the rounded result goes
-    const void* const X_given = X;            // (the caller's pointer: what "sig_features_keep" recognises)
-    const int64_t F = sig_feature_count(d, M), ld = (F + 1 + 15) / 16 * 16;
-    const int r1 = p->difference ? L1 - 1 : L1, r2 = p->difference ? L2 - 1 : L2;
-    if (r1 < 1 || r2 < 1) return GPSIG_OK;
-    // One-column state spaces take this route whatever the time model says (round 5): the pair recursion's sums over index tuples cancel by
-    // orders of magnitude for scalar increments -- the float64 pair kernels AND the float64 CPU restatement are 2e-3 .. 5e-3 from an 80-bit evaluation on
-    // case 779 of the round-5 sweep (tests/golden/fuzz_cases_r5.npz) -- while the per-sequence feature sums do not (8.7e-7 there, float32 rounding).
-    if (c->sig_features < 0 && d != 1) {
-        // (the higher-order pair kernels carry order^2 grids per level: 34 to 150 times the first order's time at configs[1]'s size)
-        const double lattice = double(r1) * r2 * (2.0 * d + 3.0 * M - 1.0) * (p->order > 1 ? 8.0 : 1.0) * (cosine ? 1.5 : 1.0) * (f32 ? 0.5 : 1.0), feat = 2.0 * double(F);      // (the float32 pair kernels run at twice the float64 ones' rate)
-        const double pairs = sym ? double(N1) * N1 / 2 : double(N1) * N2;
-        if (!(feat * 0.6 < lattice)) return GPSIG_OK;
-        // small problems: the contraction is three or four launches with a floor of ~60 us plus its feature kernel (60 us per sequence
-        // and CU at 32,768 top-level features), the pair kernels one launch with a floor of ~100 us; rates as measured
-        // (tools/bench_crossover.py, profiles/r03_crossover.txt)
-        const double seqs = double(N1) + (sym ? 0.0 : double(N2)), t_seq = 60e-6 * double(sig_ipow(d, M)) / 32768.0;
-        const double t_feat_kernel = ceil(seqs / 256.0) * t_seq > 15e-6 ? ceil(seqs / 256.0) * t_seq : 15e-6;
-        const double t_lattice = 100e-6 + pairs * lattice / (d > 8 ? 12.5e12 : 25e12), t_features = 60e-6 + t_feat_kernel + pairs * feat / 60e12;
-        if (pairs < 1024.0 || !(t_features < t_lattice)) return GPSIG_OK;
-    }
-    const size_t lds = sig_features_lds_bytes(d, M, L1 > L2 ? L1 : L2);
-    if (lds > 150 * 1024) return GPSIG_OK;
-    // (row_block_call: an EMPTY row block -- a rank that owns no rows -- takes the decisions of a non-empty one and returns before launching)
-    const bool rows = row_end > 0 || row_block_call;
-    const int64_t NA = rows ? row_end - row_begin : N1, H = N1 / 2;
-    int64_t NB = sym ? N1 : N2;
-    if (rows) NB = (NA + H < N1) ? NA + H : N1;
-    const int nti = int((NA + SG_BM - 1) / SG_BM), ntj = int((NB + SG_BN - 1) / SG_BN);
-    const bool symtiles = sym && !rows;
-    const int ntiles = symtiles ? nti * (nti + 1) / 2 : nti * ntj;
-    const int nslab_all = int((ld + SG_BK - 1) / SG_BK);
-    // Workgroups per tile along the depth.  One piece per tile leaves a launch of a few hundred tiles with a nearly empty last round
-    // (528 tiles on the chip's 512 workgroup slots: two rounds) and a launch of a few tiles with most of the chip idle; many pieces cost
-    // a partial sum each to write and add (the whole result once per piece).  The count minimises a small model of the launch --
-    // rounds of 512 workgroups x (slabs per piece x 3.6 us + 10 us; 1.8 us per slab while no CU holds two workgroups) + 2 x pieces x result bytes at 3 TB/s --
-    // evaluated for the FULL problem (the Gram's total size and the depth), not for the tiles of this call: the order in which an
-    // entry's products are added is then the same whichever tile, row block or rank computes it, and row blocks
-    // (gpsig_kernel_K_symm_rows*) reassemble the one-call Gram bit for bit.  16 pieces at N = 4,096 (configs[1]); large Grams keep
-    // at least 4 (a rank's chunk of one is a launch of ~1,000 tiles); pieces of at least 8 slabs.
-    int nsplit = 1, graded = 1;         // equal depth pieces; the last of them cut into `graded` finer ones
-    {
-        const int64_t nt_full = (N1 + SG_BM - 1) / SG_BM;
-        const int64_t tiles_full = sym ? nt_full * (nt_full + 1) / 2 : nt_full * ((N2 + SG_BN - 1) / SG_BN);
-        const double result_bytes = 8.0 * double(N1) * double(sym ? N1 : N2) * (sym ? 0.5 : 1.0);
-        double best = 1e300;
-        for (int ns = 1; ns <= 128 && ns * 8 <= nslab_all + 7; ++ns) {
-            const double wgs = double(tiles_full) * ns, per_piece = double(nslab_all) / ns;
-            const double t = (wgs <= 256.0 ? per_piece * 1.8e-6 + 10e-6 : ceil(wgs / 512.0) * (per_piece * 3.6e-6 + 10e-6)) +
-                             (ns > 1 ? 2.0 * ns * result_bytes / 3e12 : 0.0);          // (a piece's sum is written, then read)
-            if (t < best * 0.999) { best = t; nsplit = ns; }
-        }
-        if (tiles_full > 1024 && nsplit < 4 && nslab_all >= 32) nsplit = 4;
-        // Equal pieces end in a last round of workgroups that takes as long as the others but is only partly full (configs[1]: 528 tiles
-        // x 11 pieces = 11.34 rounds of 512, paid as 12).  Cutting the LAST piece into finer ones of halving size (sig_piece_bounds) lets
-        // the launch end within one small piece of (total work / slots): the waste of the equal pieces' last round against the finest
-        // piece plus a partial sum per extra piece (round 4; option "sig_graded" 0 keeps the equal pieces).
-        const double wgs = double(tiles_full) * nsplit, piece_t = double(nslab_all) / nsplit * 3.6e-6;
-        if (c->sig_graded != 0 && wgs > 512.0 && nslab_all / nsplit >= 32) {
-            const double rounds = wgs / 512.0, waste_equal = (ceil(rounds) - rounds) * piece_t;
-            double best_t = waste_equal;
-            for (int g = 2; g <= 5; ++g) {
-                const double t = piece_t / double(1 << (g - 1)) + (g - 1) * 2.0 * result_bytes / 3e12;
-                if (t < best_t * 0.95 && (nslab_all / nsplit) >> (g - 1) >= 8) { best_t = t; graded = g; }
-            }
-        }
-    }
-    const size_t part_one = sizeof(double) * size_t(NA) * NB;
-    while (nsplit > 1 && part_one * size_t(nsplit - 1 + graded) > (size_t(40) << 30)) { --nsplit; graded = 1; }       // (the exception to the rule above: 40 GiB of partial sums)
-    const int npieces = nsplit - 1 + graded;
-    const size_t feat_bytes = sizeof(double) * size_t(ld) * (size_t(N1) + (sym ? 0 : size_t(N2)));
-    if (feat_bytes + part_one * size_t(npieces) > (size_t(96) << 30)) return GPSIG_OK;
-    {
-        // what the scratch buffers would have to grow by, against what the device has left: the pair recursion needs no such memory
-        // and is the better answer to a full device than an allocation error
-        auto grow = [&](int id, size_t bytes) { return bytes > c->buf[id].cap ? bytes + bytes / 8 + 256 : size_t(0); };
-        const size_t extra = grow(B_SF0, sizeof(double) * size_t(ld) * N1 + 64) + (sym ? 0 : grow(B_SF1, sizeof(double) * size_t(ld) * N2 + 64)) +
-                             grow(B_SF2, part_one * size_t(npieces) + 64);
-        // (not for row blocks: the ranks of a sharded evaluation must all take the same route whatever each device has left -- there a
-        // full device is an allocation error of that rank, not a silent change of route that the other ranks do not follow)
-        if (extra > (size_t(1) << 30) && !c->capturing && !rows) {
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                size_t held = 0;                // (a buffer that grows is freed first)
-                for (int id : {int(B_SF0), int(B_SF1), int(B_SF2)}) held += grow(id, id == B_SF0 ? sizeof(double) * size_t(ld) * N1 + 64 : id == B_SF1 ? (sym ? 0 : sizeof(double) * size_t(ld) * N2 + 64) : part_one * size_t(npieces) + 64) ? c->buf[id].cap : 0;
-                if (extra > free_b + held - (free_b + held) / 16) return GPSIG_OK;
-            }
-        }
-    }
-    if (rows && NA <= 0) { *done = true; return GPSIG_OK; }        // an empty row block: the route is decided, there is nothing to compute
-    const double* w = nullptr;
-    if (!raw) CHK(upload_weights(c, p, &w));
-    ScaleParams s;
-    CHK(scale_params(c, p, !raw, &s));
-    void *phi1, *phi2 = nullptr, *part;
-    CHK(ensure(c, B_SF0, sizeof(double) * size_t(ld) * N1 + 64, &phi1));
-    if (!sym) CHK(ensure(c, B_SF1, sizeof(double) * size_t(ld) * N2 + 64, &phi2));
-    CHK(ensure(c, B_SF2, part_one * size_t(npieces) + 64, &part));
-    if (f32) {
-        void *x64, *y64 = nullptr, *o64;
-        const int64_t per1 = int64_t(L1) * p->num_features, per2 = int64_t(L2) * p->num_features;
-        CHK(ensure(c, B_SF3, sizeof(double) * size_t(N1 * per1) + 64, &x64));
-        HIPCHK(c, sig_convert_launch(X, x64, N1 * per1, true, c->stream));
-        if (!sym) {
-            CHK(ensure(c, B_SF4, sizeof(double) * size_t(N2 * per2) + 64, &y64));
-            HIPCHK(c, sig_convert_launch(X2, y64, N2 * per2, true, c->stream));
-        }
-        CHK(ensure(c, B_SF5, sizeof(double) * size_t(return_levels ? M + 1 : 1) * size_t(N1) * size_t(sym ? N1 : N2) + 64, &o64));
-        out32 = out; X = x64; X2 = sym ? nullptr : y64; out = o64;
-    }
-    const int normalize = (!raw && p->normalization) ? 1 : 0;
-    auto features = [&](const void* Xs, int64_t N, int L, void* phi, bool squared) -> int {
-        SigFeatArgs A;
-        memset(&A, 0, sizeof(A));
-        A.X = static_cast<const double*>(Xs); A.N = N; A.L = L; A.difference = p->difference ? 1 : 0; A.P = s;
-        A.w = w; A.normalize = normalize; A.jitter = p->jitter; A.Phi = static_cast<double*>(phi); A.ld = ld; A.dlev = nullptr;
-        A.order = p->order;
-        A.unit_points = cosine ? 1 : 0;
-        A.norm_squared = squared ? 1 : 0;
-        const int64_t cap = sig_threads(d, M) <= 128 ? 16384 : 4096;      // (one- or two-wavefront workgroups are latency-bound at 16 per CU)
-        const unsigned grid = unsigned(N < cap ? N : cap);
-        hipError_t e = ffn(A, grid, sig_features_lds_bytes(d, M, L), c->stream);
-        if (e != hipSuccess) return fail(c, GPSIG_ERR_HIP, "sig_features_kernel: %s", hipGetErrorString(e));
-        return GPSIG_OK;
-    };
-    // "sig_features_keep": between the calls of ONE decomposed evaluation (the chunks of a rank's row block: parallel.ShardedGram) the
-    // features of the same sequences under the same parameters are built once.  The caller promises not to write X in between.
-    uint64_t key = 1469598103934665603ull;
-    auto mix = [&](const void* ptr, size_t bytes) {
-        const unsigned char* b = static_cast<const unsigned char*>(ptr);
-        for (size_t i = 0; i < bytes; ++i) { key ^= b[i]; key *= 1099511628211ull; }
-    };
-    {
-        const int32_t head[8] = {p->base_kernel, p->dtype, p->num_features, p->num_levels, p->order, p->difference, p->normalization, p->num_lags};
-        mix(head, sizeof(head));
-        mix(&p->sigma, sizeof(double)); mix(&p->jitter, sizeof(double));
-        mix(p->variances, sizeof(double) * (M + 1));
-        if (p->lengthscales) mix(p->lengthscales, sizeof(double) * p->num_features);
-        if (p->num_lags > 0) { mix(p->lags, sizeof(double) * p->num_lags); mix(p->gamma, sizeof(double) * (p->num_lags + 1)); }
-        const int64_t tail[4] = {N1, L1, (raw ? 1 : 0) + (x_squared ? 2 : 0), ld};
-        mix(tail, sizeof(tail));
-    }
-    const bool reuse = c->sf_keep && c->sf_valid && c->sf_X == X_given && c->sf_phi == phi1 && c->sf_key == key;
-    if (N1 > 0 && !reuse) CHK(features(X, N1, L1, phi1, x_squared != 0));
-    c->sf_valid = c->sf_keep != 0 && N1 > 0;
-    c->sf_X = X_given; c->sf_phi = phi1; c->sf_key = key;
-    if (!sym && N2 > 0) CHK(features(X2, N2, L2, phi2, false));
-    if (NA <= 0 || NB <= 0) { *done = true; return GPSIG_OK; }
-    // level sums of the weights: the exact diagonal of the normalised symmetric Gram (kernels.py:430-433: (K_ii + jitter) / (K_ii + jitter))
-    const int nlev = return_levels ? M + 1 : 1;
-    const int64_t Ncols = sym ? N1 : N2;
-    for (int lv = 0; lv < nlev; ++lv) {
-        int kb = 0, ke = int(F) + 1;                         // all levels and the level-0 column: the level sum is inside the contraction
-        double dval = 0.0;
-        if (return_levels) {
-            if (lv == 0) { kb = int(F); ke = int(F) + 1; }
-            else { kb = sig_feature_count(d, lv - 1); ke = sig_feature_count(d, lv); }
-            dval = raw ? 0.0 : p->sigma * p->variances[lv];
-        } else {
-            for (int m = 0; m <= M; ++m) dval += p->sigma * p->variances[m];
-        }
-        SigGramArgs G;
-        memset(&G, 0, sizeof(G));
-        G.A = static_cast<const double*>(phi1) + (rows ? row_begin * ld : 0);
-        G.B = static_cast<const double*>(sym ? phi1 : phi2);
-        G.NA = NA; G.NB = NB; G.lda = ld; G.ldb = ld;
-        G.b_off = rows ? ((row_begin - H) % N1 + N1) % N1 : 0; G.b_mod = sym ? N1 : N2;
-        G.k_begin = kb; G.k_end = ke;
-        G.band = (rows && NA + H <= N1) ? H : 0;      // column c of the block is sequence row_begin - H + c (no wrap inside the block): row i owns c in [i, i + H]
-        const int nslab = (ke - kb + SG_BK - 1) / SG_BK;
-        // (the per-level products of return_levels: equal pieces of their own, shorter depth)
-        const int ns = sig_piece_bounds(nslab, nsplit, return_levels ? 1 : graded, G.bound);
-        G.nsplit = ns; G.symmetric = symtiles ? 1 : 0; G.ntj = ntj; G.part = static_cast<double*>(part);
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        bool on = false;
-        if (timed) CHK(timing_begin_any(c, &e0, &e1, &on));
-        // the LDS-DMA form reads whole slabs: only where the columns behind k_end are the zero padding of the feature rows
-        int used_dma = 0;
-        HIPCHK(c, sig_gram_launch(G, ntiles, c->stream, (c->sig_gemm_dma && !return_levels) ? 1 : 0, &used_dma));
-        if (on) {
-            HIPCHK(c, hipEventRecord(e1, c->stream));
-            c->t_launches += 1;
-            c->t_pairs += NA * NB;
-            c->t_kernel = used_dma ? "sig_gram_dma_kernel" : "sig_gram_kernel";
-            // what is executed: the LDS-DMA form computes 36 of the 64 16 x 16 blocks of a symmetric product's diagonal tiles
-            const double tiles_done = double(ntiles) - ((used_dma && symtiles) ? double(nti) * 28.0 / 64.0 : 0.0);
-            c->t_flops += 2.0 * tiles_done * SG_BM * SG_BN * double(nslab) * SG_BK;
-        }
-        SigReduceArgs R;
-        memset(&R, 0, sizeof(R));
-        R.part = static_cast<const double*>(part); R.nsplit = ns; R.NA = NA; R.NB = NB;
-        R.out = static_cast<double*>(out) + (return_levels ? int64_t(lv) * N1 * Ncols : 0);
-        R.so_i = Ncols; R.so_j = 1;
-        R.mode = rows ? 2 : (symtiles ? 1 : 0);
-        R.diag_set = (sym && normalize) ? 1 : 0; R.diag_value = dval;
-        R.N = N1; R.r0 = row_begin; R.c0 = G.b_off; R.compact = compact;
-        HIPCHK(c, sig_reduce_launch(R, c->stream));
-    }
-    if (out32) HIPCHK(c, sig_convert_launch(out, out32, int64_t(return_levels ? M + 1 : 1) * N1 * (sym ? N1 : N2), false, c->stream));
-    *done = true;
-    return GPSIG_OK;
-}
+namespace {
 
 template <typename TT>
 struct Impl {
@@ -644,10 +375,6 @@ static int make_records(gpsig_ctx* c, const gpsig_params* p, bool apply_scaling,
     *rec = d;
     return GPSIG_OK;
 }
-
-// Timing covers the launches since gpsig_timing_reset, up to TIMING_MAX_EVENTS of them (a long-running caller that never
-// reads the timing must not accumulate events); *on says whether this launch is timed.  Never inside a graph capture.
-static int timing_begin(gpsig_ctx* c, hipEvent_t* e0, hipEvent_t* e1, bool* on) { return timing_begin_any(c, e0, e1, on); }
 
 struct SeqRun {
     const void* xrec; const void* yrec;
@@ -967,7 +694,7 @@ static int seq_K_device(gpsig_ctx* c, const gpsig_params* p, bool raw, const voi
                  int64_t row_end = 0, int compact = 0) {
     if (L1 < 1 || L2 < 1) return fail(c, GPSIG_ERR_INVALID, "sequence length must be >= 1");
     {       // the linear / cosine kernel's Gram as one contraction of explicit level features, where that is the cheaper evaluation (float32 calls: computed in float64)
-        bool done = false;
+        bool done = false;       // (sig_features_K: sig_feat_api.hip)
         CHK(sig_features_K(c, p, raw, X, X2, N1, N2, L1, L2, return_levels, out, timed, x_squared, row_begin, row_end, compact, &done));
         if (done) return GPSIG_OK;
     }
@@ -1214,88 +941,13 @@ static int tens_vs_seq_tile_device(gpsig_ctx* c, const gpsig_params* p, bool raw
 }
 
 // Kzx on device pointers.  Zdev: the caller's (lt, T, E, d') tensor array; ZT/ZS: its sequence-lane preparation.
-static bool tvs_features_plan(gpsig_ctx* c, const gpsig_params* p, int64_t Tn, int64_t N, int L) {
-    const bool cosine = p->base_kernel == GPSIG_BASE_COSINE;
-    const int M = p->num_levels;
-    if (sizeof(TT) != 8 || c->tvs_features == 0 || c->capturing || !(p->base_kernel == GPSIG_BASE_LINEAR || cosine)) return false;
-    if (M < 2 || M > 8 || p->order < 1 || p->order > M || Tn <= 0 || N <= 0 || Tn > 0x3fffffff || N > 0x3fffffff) return false;
-    const int d = p->num_features * (p->num_lags + 1);
-    SigFeatLaunchFn ffn = sig_feat_lookup(d, M);
-    if (!ffn || (p->difference ? L - 1 : L) < 1) return false;
-    if (sig_features_lds_bytes(d, M, L) > 150 * 1024) return false;
-    for (int m = 0; m <= M; ++m)
-        if (!(p->sigma * p->variances[m] >= 0.0)) return false;             // (the weights go in squared: sqrt(w^2 / (diag + jitter)))
-    const int64_t F = sig_feature_count(d, M), ld = (F + 1 + 15) / 16 * 16;
-    if (sizeof(double) * size_t(ld) * (size_t(N) + size_t(Tn)) > (size_t(16) << 30)) return false;
-    if (c->tvs_features < 0) {
-        // rates as measured at BASELINE configs[2] (512 x 16,384, L = 50, d = 6, M = 4): the tile kernel 1.05 ms, here 0.18 + 0.42 ms
-        const int lt = M * (M + 1) / 2;
-        const double t_tile = 40e-6 + double(Tn) * double(N) * L * lt / 4.0e12;
-        const double t_seq = 60e-6 * double(sig_ipow(d, M)) / 32768.0, rounds = ceil(double(N) / 256.0);
-        const double t_feat = 80e-6 + (rounds * t_seq > 15e-6 ? rounds * t_seq : 15e-6) + 2.0 * double(Tn) * double(N) * double(ld) / 50e12;
-        if (!(t_feat < t_tile)) return false;
-    }
-    return true;
-}
-// Kzx = sum_m w_m / sqrt(K_m(x, x) + jitter) K_m(z, x) (kernels.py:572-588) of the linear / cosine kernel as ONE product of the tensors' and the
-// sequences' level features (rocBLAS dgemm): the weights and the normalisation ride on the sequences' features.  *done = false: the tile kernel.
-static int tens_vs_seq_features_device(gpsig_ctx* c, const gpsig_params* p, const void* ZT, const void* ZS, const void* X, int64_t Tn, int64_t N,
-                                       int L, int increments, const double* w, void* out, bool* done) {
-    *done = false;
-    if (!tvs_features_plan(c, p, Tn, N, L)) return GPSIG_OK;
-    const bool cosine = p->base_kernel == GPSIG_BASE_COSINE;
-    const int M = p->num_levels, d = p->num_features * (p->num_lags + 1);
-    SigFeatLaunchFn ffn = sig_feat_lookup(d, M);
-    const int64_t F = sig_feature_count(d, M), ld = (F + 1 + 15) / 16 * 16;
-    void *phi, *zf, *w2;
-    CHK(ensure(c, B_SF0, sizeof(double) * size_t(ld) * N + 64, &phi));
-    CHK(ensure(c, B_SF1, sizeof(double) * size_t(ld) * Tn + 64, &zf));
-    CHK(ensure(c, B_TW2, sizeof(double) * 16, &w2));
-    c->sf_valid = false;                          // (B_SF0 no longer holds what "sig_features_keep" remembers)
-    hipLaunchKernelGGL(square_small_kernel, dim3(1), dim3(64), 0, c->stream, w, M + 1, static_cast<double*>(w2));
-    HIPCHK(c, hipGetLastError());
-    ScaleParams s;
-    CHK(scale_params(c, p, true, &s));
-    SigFeatArgs A;
-    memset(&A, 0, sizeof(A));
-    A.X = static_cast<const double*>(X); A.N = N; A.L = L; A.difference = p->difference ? 1 : 0; A.P = s;
-    A.w = static_cast<const double*>(w2); A.normalize = p->normalization ? 1 : 0; A.jitter = p->jitter; A.Phi = static_cast<double*>(phi); A.ld = ld;
-    A.dlev = nullptr; A.order = p->order; A.unit_points = cosine ? 1 : 0; A.norm_squared = 0; A.natural_order = 1;
-    {
-        // (workgroups of one or two wavefronts -- small d^M -- are latency-bound at 16 per CU: up to 16,384 of them; 0.667 -> 0.647 ms at configs[2])
-        const int64_t cap = sig_threads(d, M) <= 128 ? 16384 : 4096;
-        hipError_t e = ffn(A, unsigned(N < cap ? N : cap), sig_features_lds_bytes(d, M, L), c->stream);
-        if (e != hipSuccess) return fail(c, GPSIG_ERR_HIP, "sig_features_kernel: %s", hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(tens_level_features_kernel, dim3(grid_for(Tn * ld)), dim3(256), 0, c->stream, static_cast<const double*>(ZT),
-                       static_cast<const double*>(ZS), M * (M + 1) / 2, increments ? 2 : 1, d, Tn, M, cosine ? 1 : 0, ld, static_cast<double*>(zf));
-    HIPCHK(c, hipGetLastError());
-    hipEvent_t e0, e1;
-    bool timed;
-    CHK(timing_begin(c, &e0, &e1, &timed));
-    // row-major out (T, N) = Zf (T, ld) Phi (N, ld)^T  ==  column-major out^T (N x T) = Phi_cm^T (N x ld) Zf_cm (ld x T)
-    std::string err;
-    if (!solver_dgemm(&c->blas_handle, c->stream, true, false, int(N), int(Tn), int(ld), 1.0, static_cast<const double*>(phi), int(ld),
-                      static_cast<const double*>(zf), int(ld), 0.0, static_cast<double*>(out), int(N), &err))
-        return fail(c, GPSIG_ERR_HIP, "%s", err.c_str());
-    if (timed) {
-        HIPCHK(c, hipEventRecord(e1, c->stream));
-        c->t_launches += 1;
-        c->t_pairs += Tn * N;
-        c->t_kernel = "tvs_features_dgemm";
-        c->t_flops += 2.0 * double(Tn) * double(N) * double(ld);
-    }
-    *done = true;
-    return GPSIG_OK;
-}
-
 static int tens_vs_seq_device(gpsig_ctx* c, const gpsig_params* p, bool raw, const void* Zdev, const void* ZT, const void* ZS,
                        const void* X, int64_t Tn, int64_t N, int L, int increments, const void* fx, const double* w,
                        int return_levels, void* out) {
     const int M = p->num_levels;
     if (!raw && !return_levels && w) {      // the linear / cosine kernel's weighted level sum: one product of level features
         bool done = false;
-        CHK(tens_vs_seq_features_device(c, p, ZT, ZS, X, Tn, N, L, increments, w, out, &done));
+        CHK(tens_vs_seq_features_device(c, p, sizeof(TT) == 8, ZT, ZS, X, Tn, N, L, increments, w, out, &done));
         if (done) return GPSIG_OK;
     }
     // wide state spaces (wide_api.hip): beyond the tile kernel's 8 columns, or wherever built when the option says so
@@ -1628,7 +1280,7 @@ static int e_kernel_K_tens_vs_seq(gpsig_ctx* c, const gpsig_params* p, const voi
     void* dout;
     CHK(out_dev(c, B_OUT0, out, ob, &dout));
     const void* fx = nullptr;
-    if (p->normalization && !(!return_levels && tvs_features_plan(c, p, T, N, L))) CHK(seq_diag_factors(c, p, dX, N, L, &fx));     // kernels.py:572-581
+    if (p->normalization && !(!return_levels && tvs_features_plan(c, p, sizeof(TT) == 8, T, N, L))) CHK(seq_diag_factors(c, p, dX, N, L, &fx));     // kernels.py:572-581
     const double* w;
     CHK(upload_weights(c, p, &w));
     const void *ZT, *ZS;
@@ -1661,7 +1313,7 @@ static int e_kernel_K_tens_n_seq_covs(gpsig_ctx* c, const gpsig_params* p, const
     // Kzx: divided by sqrt(diag_x + jitter) when normalising (kernels.py:638 / :660) -- with full_X_cov the
     // diagonal of (Kxx + jitter*I) is the same number
     const void* fx = nullptr;
-    if (p->normalization && !(!return_levels && tvs_features_plan(c, p, T, N, L))) CHK(seq_diag_factors(c, p, dX, N, L, &fx));
+    if (p->normalization && !(!return_levels && tvs_features_plan(c, p, sizeof(TT) == 8, T, N, L))) CHK(seq_diag_factors(c, p, dX, N, L, &fx));
     const void *ZT, *ZS;
     CHK(prep_tensors(c, p, true, dZ, T, E, &ZT, &ZS));
     CHK(tens_vs_seq_device(c, p, false, dZ, ZT, ZS, dX, T, N, L, increments, fx, w, return_levels, dzx));

@@ -1,5 +1,6 @@
 // api_common.hpp -- what the evaluation entry points of api.hip (the exact kernels) and of lr_api.hip (low-rank mode) both open with: the
-// parameter check and the device copies of what a gpsig_params carries.  Defined in api.hip; host code only.
+// parameter check and the device copies of what a gpsig_params carries; and the timed-launch helper of every host unit that times.
+// Defined in api.hip; host code only.
 #pragma once
 #include "ctx.hpp"
 
@@ -19,6 +20,11 @@ int spectral_table_wide(gpsig_ctx* c, const gpsig_params* p, const double** dev)
 void base_p(const gpsig_params* p, double* p0, double* p1);
 // weights sigma * variances[m] on the device
 int upload_weights(gpsig_ctx* c, const gpsig_params* p, const double** w);
+// A pair of events from the context's pool around the launches a call times (gpsig_timing_*); *e0 is recorded here, *e1 by the caller.  Timing covers
+// the launches since gpsig_timing_reset, up to TIMING_MAX_EVENTS events (a long-running caller that never reads the timing must not accumulate
+// them); *on says whether this launch is timed.  Never inside a graph capture.  Used by api.hip, sig_feat_api.hip and wide_api.hip.
+constexpr size_t TIMING_MAX_EVENTS = 8192;
+int timing_begin(gpsig_ctx* c, hipEvent_t* e0, hipEvent_t* e1, bool* on);
 // lr_api.hip: the context is going away -- its low-rank states outlive it as plain memory blocks (gpsig_ctx_destroy)
 void lr_detach_states(gpsig_ctx* c);
 

@@ -138,6 +138,22 @@ SigFeatGradLaunchFn sig_feat_grad_pick_f(int d, int M);
 hipError_t sig_gram_launch(const SigGramArgs& G, int ntiles, hipStream_t stream, int dma, int* used_dma);
 hipError_t sig_reduce_launch(const SigReduceArgs& R, hipStream_t stream);
 hipError_t sig_convert_launch(const void* in, void* out, int64_t n, bool widen, hipStream_t stream);
+// sig_feat_api.hip: the forward side of the feature route, and what it shares with the reverse side (sig_feat_grad_api.hip).
+// What every site of the route asks first: the linear or cosine family and a feature kernel built for (d, M) -- sig_feat_lookup is null outside
+// 1 <= d <= 32 and (sig_feat_pick.hpp: the switch's default) outside 2 <= M <= 8, so no site tests those ranges itself --, then the width
+// F = sum_m d^m and the row stride ld of the feature matrix.  The order is each site's own business.
+struct SigShape { int d, M; bool cosine; int64_t F, ld; SigFeatLaunchFn ffn; };
+bool sig_shape(const gpsig_params* p, int d, SigShape* s);
+constexpr size_t SIG_FEAT_LDS_MAX = 150 * 1024, SIG_FEAT_GRAD_LDS_MAX = 158 * 1024;       // the feature kernel's / the reverse kernel's arrays of one sequence
+bool sig_shape_fits(const SigShape& s, const gpsig_params* p, int L);          // at least one step, and the feature kernel's arrays within SIG_FEAT_LDS_MAX
+// the one launch of sig_features_kernel: N sequences X into Phi (N, s.ld); every SigFeatArgs field that the sites set differently is an argument
+int sig_launch_features(gpsig_ctx* c, const SigShape& s, const gpsig_params* p, const ScaleParams& P, int order, const double* X, int64_t N, int L,
+                        const double* w, int normalize, double jitter, int norm_squared, int natural_order, double* Phi, double* dlev);
+int sig_features_K(gpsig_ctx* c, const gpsig_params* p, bool raw, const void* X, const void* X2, int64_t N1, int64_t N2, int L1, int L2, int return_levels,
+                   void* out, bool timed, int x_squared, int64_t row_begin, int64_t row_end, int compact, bool* done, bool row_block_call = false);
+bool tvs_features_plan(gpsig_ctx* c, const gpsig_params* p, bool f64, int64_t Tn, int64_t N, int L);
+int tens_vs_seq_features_device(gpsig_ctx* c, const gpsig_params* p, bool f64, const void* ZT, const void* ZS, const void* X, int64_t Tn, int64_t N, int L,
+                                int increments, const double* w, void* out, bool* done);
 // sig_feat_grad_api.hip: SignatureLinear's levels differentiated through the feature contraction
 int sig_features_grad(gpsig_ctx* c, const gpsig_params* p, int d, const double* X, const double* Y, int64_t N1, int64_t N2, int L1, int L2, bool diag,
                       bool sym, const double* G, double* gX, double* gY, bool* done);

@@ -2,7 +2,7 @@
 // Also: the footprints of the other evaluation kernels and the predicates that pick an evaluation call's route (lr_eval_route, lr_eval_tens_route;
 // SignatureSpectral beyond 32 columns: lr_spectral_eval_wide, lr_spectral_eval_tens_wide, tests/emu/test_lr_spectral_eval_route.cpp).
 // HIP-free (constexpr helpers are usable on the device): read by lr_fused_args.hpp / lr_grad_kernel.hpp (the whole-sequence kernels),
-// lr_tiled_kernel.hpp, lr_eval_tiled_inst.hip, the host paths of lr_grad_api.hip and api.hip, tests/emu/test_lr_tile_plan.cpp and
+// lr_tiled_kernel.hpp, lr_eval_tiled_inst.hip, the host paths of lr_grad_api.hip and lr_api.hip, tests/emu/test_lr_tile_plan.cpp and
 // tests/emu/test_lr_eval_route.cpp.
 //
 // The whole-sequence kernels keep (width, L) arrays of a sequence in LDS: three in the forward direction (lr_fused_lds_bytes), four in the
@@ -125,7 +125,7 @@ inline size_t lr_fused2_lds_bytes_f32(int c, int r, int d_eff, int L, int pad = 
 inline size_t lr_tens_fused_lds_bytes_f32(int c, int r, int d_eff, int lt, int E) { return lr_tens_fused_lds_bytes(c, r, d_eff, lt, E) / 2; }
 constexpr size_t LR_TENS_FUSED_MAX_LDS = 64 * 1024; // what the evaluation side gives the fused tensor kernel (several workgroups per CU)
 
-// ---- which route serves an evaluation call (api.hip: lr_seq_features_t, lr_tens_features_t; tests/emu/test_lr_eval_route.cpp)
+// ---- which route serves an evaluation call (lr_api.hip: lr_seq_features_t, lr_tens_features_t; tests/emu/test_lr_eval_route.cpp)
 //   FUSED    the whole-sequence kernels (lr_fused_kernel.hpp) / the fused tensor kernel: the object's arrays, points included, in LDS
 //   TILED    the time-tiled kernels on raw points (lr_eval_tiled.hpp): a 64-step tile of max(c, r, d) rows fits
 //   WIDE     beyond those: the Nystrom cross matrix on the float64 matrix cores from the raw points (lr_cross_kernel.hpp, evaluation form), then
@@ -166,7 +166,7 @@ inline LrEvalRoute lr_eval_tens_route(bool f32, int c, int r, int d, int M, int 
     return f32 ? LR_EVAL_REFUSE : LR_EVAL_PASSES;
 }
 
-// ---- SignatureSpectral beyond the 32 columns of its packed table, for a kernel object that opts in (gpsig_params.base_params[2] != 0).  api.hip
+// ---- SignatureSpectral beyond the 32 columns of its packed table, for a kernel object that opts in (gpsig_params.base_params[2] != 0).  lr_api.hip
 // asks these two only for GPSIG_BASE_SPECTRAL with the flag set and d > 32; every other call is lr_eval_route's / lr_eval_tens_route's, which
 // answer as they did.  There is one route at these widths -- the evaluation form of the spectral cross kernel (lr_eval_spectral_wide_inst.hip),
 // then the feature kernels that take kxs / kzs from memory, as WIDE above -- for dense and ragged calls and at any lr_fused, 0 included: the

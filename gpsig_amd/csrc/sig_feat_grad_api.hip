@@ -8,17 +8,32 @@
 //     gX, gY                  sig_feat_reverse_kernel / sig_feat_reverse_ho_kernel (sig_feat_grad_kernel.hpp): dPhi back through the feature sweep
 //                             (first order / the higher orders' truncated-exponential steps; SignatureCosine: on the unit vectors)
 // The pair kernels' reverse pass costs about three lattice sweeps per pair, L1 L2 (2d + 3M - 1) flops each; this costs 4 sum_m d^m per
-// pair on the matrix cores plus a sweep per SEQUENCE.  Reference: TensorFlow's autodiff of signature_algs.py:8-35 behind
+// pair on the matrix cores plus a sweep per SEQUENCE.  The forward side of the route is sig_feat_api.hip, which also defines what both sides
+// share (launchers.hpp: sig_shape, sig_shape_fits, sig_launch_features); every function here that writes B_SF0 clears sf_valid.  Reference: TensorFlow's autodiff of signature_algs.py:8-35 behind
 // kernels.py:208-237 (no gradient code of its own to cite).
 #include "ctx.hpp"
 #include "launchers.hpp"
 #include "sig_feat_grad_kernel.hpp"
 
 namespace gpsig {
+// (the same ranges as sig_feat_lookup, sig_feat_inst.hip: null outside 1 <= d <= 32, and -- the pick switches' default -- outside 2 <= M <= 8)
 static SigFeatGradLaunchFn sig_feat_grad_lookup(int d, int M) {
     if (d < 1 || d > 32) return nullptr;
     return d <= 4 ? sig_feat_grad_pick_a(d, M) : d <= 8 ? sig_feat_grad_pick_b(d, M) : d <= 12 ? sig_feat_grad_pick_c(d, M)
          : d <= 16 ? sig_feat_grad_pick_d(d, M) : d <= 24 ? sig_feat_grad_pick_e(d, M) : sig_feat_grad_pick_f(d, M);
+}
+
+// What the three sites of this unit ask of a shape: the feature route's own question (sig_shape: family, a feature kernel for (d, M), hence
+// 1 <= d <= 32 and 2 <= M <= 8), a reverse kernel too, at least one step on either side, and both kernels' arrays of the longer sequence within the LDS.
+// The order is clamped into [1, num_levels] here, where the forward side (sig_feat_api.hip) refuses it outside.
+struct SigRevShape { SigShape s; SigFeatGradLaunchFn rfn; int order; };
+static bool sig_reverse_shape(const gpsig_params* p, int d, int L1, int L2, SigRevShape* r) {
+    const int M = p->num_levels, Lmax = L1 > L2 ? L1 : L2;
+    r->order = p->order < 1 ? 1 : (p->order > M ? M : p->order);
+    if (!sig_shape(p, d, &r->s)) return false;
+    r->rfn = sig_feat_grad_lookup(d, M);
+    if (!r->rfn || !sig_shape_fits(r->s, p, L1) || !sig_shape_fits(r->s, p, L2)) return false;
+    return (r->order > 1 ? sig_feat_grad_ho_lds_bytes(d, M, Lmax) : sig_feat_grad_lds_bytes(d, M, Lmax)) <= SIG_FEAT_GRAD_LDS_MAX;
 }
 
 // E(dx) = sum_{k <= order} dx^(x)k / k!: its inverse series, and the weights of the Horner sub-steps' intermediates
@@ -37,35 +52,25 @@ static void sig_ho_tables(int order, SigFeatGradArgs& A) {
 }
 
 // raw level features of N sequences (no weights, no normalisation), natural order, into Phi (N, ld); dlev: (N, M+1) level diagonals or NULL
-static int sig_launch_features(gpsig_ctx* c, SigFeatLaunchFn ffn, const gpsig_params* p, int d, int order, bool cosine, int64_t ld, const double* Xs,
-                               int64_t N, int L, double* phi, double* dlev) {
-    const int M = p->num_levels;
+static int sig_raw_features(gpsig_ctx* c, const SigRevShape& r, const gpsig_params* p, const double* Xs, int64_t N, int L, double* phi, double* dlev) {
     ScaleParams sp;
     memset(&sp, 0, sizeof(sp));
-    sp.d_in = d;                                  // the level primitives take their inputs as they come: no lengthscales, no lags
-    SigFeatArgs A;
-    memset(&A, 0, sizeof(A));
-    A.X = Xs; A.N = N; A.L = L; A.difference = p->difference ? 1 : 0; A.P = sp;
-    A.w = nullptr; A.normalize = 0; A.jitter = 0.0; A.Phi = phi; A.ld = ld; A.dlev = dlev;
-    A.order = order; A.natural_order = 1; A.unit_points = cosine ? 1 : 0;
-    const int64_t cap = sig_threads(d, M) <= 128 ? 16384 : 4096;      // (one- or two-wavefront workgroups are latency-bound at 16 per CU)
-    hipError_t e = ffn(A, unsigned(N < cap ? N : cap), sig_features_lds_bytes(d, M, L), c->stream);
-    if (e != hipSuccess) return fail(c, GPSIG_ERR_HIP, "sig_features_kernel: %s", hipGetErrorString(e));
-    return GPSIG_OK;
+    sp.d_in = r.s.d;                              // the level primitives take their inputs as they come: no lengthscales, no lags
+    return sig_launch_features(c, r.s, p, sp, r.order, Xs, N, L, nullptr, 0, 0.0, 0, 1, phi, dlev);
 }
 
 // dPhi (N, ld) back through the feature sweep of N sequences: gx (N, L, d)
-static int sig_launch_reverse(gpsig_ctx* c, SigFeatGradLaunchFn rfn, const gpsig_params* p, int d, int order, bool cosine, int64_t ld, const double* Xs,
-                              int64_t N, int L, const double* Ph, const double* dP, double* gx) {
-    const int M = p->num_levels;
+static int sig_launch_reverse(gpsig_ctx* c, const SigRevShape& r, const gpsig_params* p, const double* Xs, int64_t N, int L, const double* Ph,
+                              const double* dP, double* gx) {
+    const int M = r.s.M, d = r.s.d, order = r.order;
     SigFeatGradArgs A;
     memset(&A, 0, sizeof(A));
-    A.X = Xs; A.N = N; A.L = L; A.difference = p->difference ? 1 : 0; A.Phi = Ph; A.dPhi = dP; A.ld = ld; A.gX = gx;
-    A.unit_points = cosine ? 1 : 0;
+    A.X = Xs; A.N = N; A.L = L; A.difference = p->difference ? 1 : 0; A.Phi = Ph; A.dPhi = dP; A.ld = r.s.ld; A.gX = gx;
+    A.unit_points = r.s.cosine ? 1 : 0;
     A.order = order;
     if (order > 1) sig_ho_tables(order, A);
     const size_t lds_rev = order > 1 ? sig_feat_grad_ho_lds_bytes(d, M, L) : sig_feat_grad_lds_bytes(d, M, L);
-    hipError_t e = rfn(A, unsigned(N < 8192 ? N : 8192), lds_rev, c->stream);
+    hipError_t e = r.rfn(A, unsigned(N < 8192 ? N : 8192), lds_rev, c->stream);
     if (e != hipSuccess) return fail(c, GPSIG_ERR_HIP, "sig_feat_reverse_kernel: %s", hipGetErrorString(e));
     return GPSIG_OK;
 }
@@ -186,22 +191,13 @@ static __global__ void sig_weight_grad_kernel(const double* __restrict__ cdot, i
 int sig_features_grad(gpsig_ctx* c, const gpsig_params* p, int d, const double* X, const double* Y, int64_t N1, int64_t N2, int L1, int L2, bool diag,
                       bool sym, const double* G, double* gX, double* gY, bool* done) {
     *done = false;
-    const int M = p->num_levels;
-    // the linear kernel, and the cosine kernel as the linear kernel of the unit vectors x / |x| (kernels.py:820-828)
-    const bool cosine = p->base_kernel == GPSIG_BASE_COSINE;
-    const int order = p->order < 1 ? 1 : (p->order > M ? M : p->order);
-    if (c->sig_features_grad == 0 || !(p->base_kernel == GPSIG_BASE_LINEAR || cosine) || M < 2 || M > 8 || c->capturing) return GPSIG_OK;
+    if (c->sig_features_grad == 0 || c->capturing) return GPSIG_OK;         // (inside a capture the route is refused outright, as tvs_features_plan does and sig_features_K does not)
     if (N1 <= 0 || N2 <= 0 || N1 > 0x3fffffff || N2 > 0x3fffffff) return GPSIG_OK;
-    SigFeatLaunchFn ffn = sig_feat_lookup(d, M);
-    SigFeatGradLaunchFn rfn = sig_feat_grad_lookup(d, M);
-    if (!ffn || !rfn) return GPSIG_OK;
-    const int r1 = p->difference ? L1 - 1 : L1, r2 = p->difference ? L2 - 1 : L2;
-    if (r1 < 1 || r2 < 1) return GPSIG_OK;
-    const int64_t F = sig_feature_count(d, M), ld = (F + 1 + 15) / 16 * 16;
-    const int Lmax = L1 > L2 ? L1 : L2;
-    const size_t lds_f = sig_features_lds_bytes(d, M, Lmax);
-    const size_t lds_r = order > 1 ? sig_feat_grad_ho_lds_bytes(d, M, Lmax) : sig_feat_grad_lds_bytes(d, M, Lmax);
-    if (lds_f > 150 * 1024 || lds_r > 158 * 1024) return GPSIG_OK;
+    SigRevShape r;
+    if (!sig_reverse_shape(p, d, L1, L2, &r)) return GPSIG_OK;
+    const int M = r.s.M, order = r.order, r1 = p->difference ? L1 - 1 : L1, r2 = p->difference ? L2 - 1 : L2, Lmax = L1 > L2 ? L1 : L2;
+    const bool cosine = r.s.cosine;
+    const int64_t F = r.s.F, ld = r.s.ld;
     const bool two = !diag && !sym;
     const size_t bytes = sizeof(double) * size_t(ld) * (size_t(N1) + (two ? size_t(N2) : 0)) * 2 + (sym ? sizeof(double) * size_t(N1) * N1 : 0);
     if (bytes > (size_t(48) << 30)) return GPSIG_OK;
@@ -226,8 +222,8 @@ int sig_features_grad(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
     void* gsym = nullptr;
     if (sym) CHK(ensure(c, B_SF5, sizeof(double) * size_t(N1) * N1 + 64, &gsym));
     c->sf_valid = false;                          // (B_SF0 no longer holds what "sig_features_keep" remembers)
-    CHK(sig_launch_features(c, ffn, p, d, order, cosine, ld, X, N1, L1, static_cast<double*>(phi1), nullptr));
-    if (two) CHK(sig_launch_features(c, ffn, p, d, order, cosine, ld, Y, N2, L2, static_cast<double*>(phi2), nullptr));
+    CHK(sig_raw_features(c, r, p, X, N1, L1, static_cast<double*>(phi1), nullptr));
+    if (two) CHK(sig_raw_features(c, r, p, Y, N2, L2, static_cast<double*>(phi2), nullptr));
     const double* P1 = static_cast<const double*>(phi1);
     const double* P2 = two ? static_cast<const double*>(phi2) : P1;
     double* D1 = static_cast<double*>(dphi1);
@@ -259,8 +255,8 @@ int sig_features_grad(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
             w *= d;
         }
     }
-    CHK(sig_launch_reverse(c, rfn, p, d, order, cosine, ld, X, N1, L1, P1, D1, gX));
-    if (two) CHK(sig_launch_reverse(c, rfn, p, d, order, cosine, ld, Y, N2, L2, P2, D2, gY));
+    CHK(sig_launch_reverse(c, r, p, X, N1, L1, P1, D1, gX));
+    if (two) CHK(sig_launch_reverse(c, r, p, Y, N2, L2, P2, D2, gY));
     *done = true;
     return GPSIG_OK;
 }
@@ -271,22 +267,14 @@ int sig_features_grad(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
 int sig_features_sum_grad(gpsig_ctx* c, const gpsig_params* p, int d, const double* X, const double* Y, int64_t N1, int64_t N2, int L1, int L2,
                           const double* g, double* gX, double* gY, double* gw, bool probe, bool* done) {
     *done = false;
-    const int M = p->num_levels;
-    const bool cosine = p->base_kernel == GPSIG_BASE_COSINE;
     const bool sym = Y == nullptr;
-    const int order = p->order < 1 ? 1 : (p->order > M ? M : p->order);
-    if (c->sig_features_grad == 0 || !(p->base_kernel == GPSIG_BASE_LINEAR || cosine) || M < 2 || M > 8 || c->capturing) return GPSIG_OK;
+    if (c->sig_features_grad == 0 || c->capturing) return GPSIG_OK;         // (as sig_features_grad)
     if (N1 <= 0 || N2 <= 0 || N1 > 0x3fffffff || N2 > 0x3fffffff) return GPSIG_OK;
-    SigFeatLaunchFn ffn = sig_feat_lookup(d, M);
-    SigFeatGradLaunchFn rfn = sig_feat_grad_lookup(d, M);
-    if (!ffn || !rfn) return GPSIG_OK;
-    const int r1 = p->difference ? L1 - 1 : L1, r2 = p->difference ? L2 - 1 : L2;
-    if (r1 < 1 || r2 < 1) return GPSIG_OK;
-    const int64_t F = sig_feature_count(d, M), ld = (F + 1 + 15) / 16 * 16;
-    const int Lmax = L1 > L2 ? L1 : L2;
-    const size_t lds_f = sig_features_lds_bytes(d, M, Lmax);
-    const size_t lds_r = order > 1 ? sig_feat_grad_ho_lds_bytes(d, M, Lmax) : sig_feat_grad_lds_bytes(d, M, Lmax);
-    if (lds_f > 150 * 1024 || lds_r > 158 * 1024) return GPSIG_OK;
+    SigRevShape r;
+    if (!sig_reverse_shape(p, d, L1, L2, &r)) return GPSIG_OK;
+    const int M = r.s.M, order = r.order, r1 = p->difference ? L1 - 1 : L1, r2 = p->difference ? L2 - 1 : L2, Lmax = L1 > L2 ? L1 : L2;
+    const bool cosine = r.s.cosine;
+    const int64_t F = r.s.F, ld = r.s.ld;
     const bool norm = p->normalization != 0;
     const size_t rows = size_t(N1) + (sym ? 0 : size_t(N2));
     const size_t bytes = sizeof(double) * size_t(ld) * rows * (norm ? 3 : 2) + (sym ? sizeof(double) * size_t(N1) * N1 : 0);
@@ -315,8 +303,8 @@ int sig_features_sum_grad(gpsig_ctx* c, const gpsig_params* p, int d, const doub
     void* gsym = nullptr;
     if (sym) CHK(ensure(c, B_SF5, sizeof(double) * size_t(N1) * N1 + 64, &gsym));
     c->sf_valid = false;
-    CHK(sig_launch_features(c, ffn, p, d, order, cosine, ld, X, N1, L1, static_cast<double*>(phi1), dl1));
-    if (!sym) CHK(sig_launch_features(c, ffn, p, d, order, cosine, ld, Y, N2, L2, static_cast<double*>(phi2), dl2));
+    CHK(sig_raw_features(c, r, p, X, N1, L1, static_cast<double*>(phi1), dl1));
+    if (!sym) CHK(sig_raw_features(c, r, p, Y, N2, L2, static_cast<double*>(phi2), dl2));
     const double* P1 = static_cast<const double*>(phi1);
     const double* P2 = sym ? P1 : static_cast<const double*>(phi2);
     const double *U1 = P1, *U2 = P2;
@@ -362,8 +350,8 @@ int sig_features_sum_grad(gpsig_ctx* c, const gpsig_params* p, int d, const doub
         hipLaunchKernelGGL(sig_weight_grad_kernel, dim3(1), dim3(256), 0, c->stream, cdot, N1, M, sym ? 0.5 : 1.0, gw);
         HIPCHK(c, hipGetLastError());
     }
-    CHK(sig_launch_reverse(c, rfn, p, d, order, cosine, ld, X, N1, L1, P1, D1, gX));
-    if (!sym) CHK(sig_launch_reverse(c, rfn, p, d, order, cosine, ld, Y, N2, L2, P2, D2, gY));
+    CHK(sig_launch_reverse(c, r, p, X, N1, L1, P1, D1, gX));
+    if (!sym) CHK(sig_launch_reverse(c, r, p, Y, N2, L2, P2, D2, gY));
     *done = true;
     return GPSIG_OK;
 }
@@ -396,45 +384,35 @@ extern "C" int gpsig_kernel_K_grad(gpsig_ctx* c, const gpsig_params* p, const vo
 // the reference's notebook checks against esig).  With them <z_1 (x) .. (x) z_m, Phi_m(x)> is the tensor-vs-sequence kernel of a rank-one
 // inducing tensor (signature_algs.py:101-127), so the linear kernel's Kzx is a plain product of (T, F) and (N, F) matrices.
 namespace gpsig {
-static bool sig_features_plan(const gpsig_params* p, int L, SigFeatLaunchFn* ffn, SigFeatGradLaunchFn* rfn, int64_t* ld, int* order, bool* cosine) {
-    const int M = p->num_levels, d = p->num_features;
-    *cosine = p->base_kernel == GPSIG_BASE_COSINE;
-    *order = p->order < 1 ? 1 : (p->order > M ? M : p->order);
-    if (!(p->base_kernel == GPSIG_BASE_LINEAR || *cosine) || M < 2 || M > 8 || d < 1 || d > 32) return false;
+// (the op's own conditions: float64 inputs as they come -- no lengthscales, no lags, so d = num_features, which the lookup holds to 1 .. 32)
+static bool sig_features_plan(const gpsig_params* p, int L, SigRevShape* r) {
     if (p->lengthscales || p->num_lags != 0 || p->dtype != GPSIG_F64) return false;
-    *ffn = sig_feat_lookup(d, M);
-    *rfn = sig_feat_grad_lookup(d, M);
-    if (!*ffn || !*rfn) return false;
-    if ((p->difference ? L - 1 : L) < 1) return false;
-    const size_t lds_f = sig_features_lds_bytes(d, M, L);
-    const size_t lds_r = *order > 1 ? sig_feat_grad_ho_lds_bytes(d, M, L) : sig_feat_grad_lds_bytes(d, M, L);
-    if (lds_f > 150 * 1024 || lds_r > 158 * 1024) return false;
-    *ld = (int64_t(sig_feature_count(d, M)) + 1 + 15) / 16 * 16;
-    return true;
+    return sig_reverse_shape(p, p->num_features, L, L, r);
 }
 }  // namespace gpsig
 
 extern "C" int64_t gpsig_seq_features_ld(const gpsig_params* p, int32_t L) {
     using namespace gpsig;
-    SigFeatLaunchFn ffn; SigFeatGradLaunchFn rfn; int64_t ld = 0; int order; bool cosine;
-    if (!p || !sig_features_plan(p, L, &ffn, &rfn, &ld, &order, &cosine)) return 0;
-    return ld;
+    SigRevShape r;
+    if (!p || !sig_features_plan(p, L, &r)) return 0;
+    return r.s.ld;
 }
 
 extern "C" int gpsig_seq_features(gpsig_ctx* c, const gpsig_params* p, const void* X, int64_t N, int32_t L, void* out) {
     using namespace gpsig;
     if (!c || !p) return GPSIG_ERR_INVALID;
-    SigFeatLaunchFn ffn; SigFeatGradLaunchFn rfn; int64_t ld = 0; int order; bool cosine;
-    if (!sig_features_plan(p, L, &ffn, &rfn, &ld, &order, &cosine))
+    SigRevShape r;
+    if (!sig_features_plan(p, L, &r))
         return fail(c, GPSIG_ERR_UNSUPPORTED, "gpsig_seq_features: linear / cosine kernel, float64, 2 <= num_levels <= 8, d <= 32, inputs as they come, a sequence's arrays within the LDS (gpsig_seq_features_ld says 0 otherwise)");
     if (N <= 0 || !X || !out) return fail(c, GPSIG_ERR_INVALID, "gpsig_seq_features: null or empty argument");
     HIPCHK(c, hipSetDevice(c->device));
     const int d = p->num_features;
+    const int64_t ld = r.s.ld;
     const void* dx;
     void* dout;
     CHK(in_dev(c, B_IN0, X, sizeof(double) * size_t(N) * L * d, &dx));
     CHK(out_dev(c, B_OUT0, out, sizeof(double) * size_t(N) * ld, &dout));
-    CHK(sig_launch_features(c, ffn, p, d, order, cosine, ld, static_cast<const double*>(dx), N, L, static_cast<double*>(dout), nullptr));
+    CHK(sig_raw_features(c, r, p, static_cast<const double*>(dx), N, L, static_cast<double*>(dout), nullptr));
     CHK(out_done(c, out, dout, sizeof(double) * size_t(N) * ld));
     return finish(c);
 }
@@ -443,11 +421,11 @@ extern "C" int gpsig_seq_features_grad(gpsig_ctx* c, const gpsig_params* p, cons
                                        void* gX) {
     using namespace gpsig;
     if (!c || !p) return GPSIG_ERR_INVALID;
-    SigFeatLaunchFn ffn; SigFeatGradLaunchFn rfn; int64_t ld = 0; int order; bool cosine;
-    if (!sig_features_plan(p, L, &ffn, &rfn, &ld, &order, &cosine)) return fail(c, GPSIG_ERR_UNSUPPORTED, "gpsig_seq_features_grad: see gpsig_seq_features");
+    SigRevShape r;
+    if (!sig_features_plan(p, L, &r)) return fail(c, GPSIG_ERR_UNSUPPORTED, "gpsig_seq_features_grad: see gpsig_seq_features");
     if (c->ptr_mode != GPSIG_PTR_DEVICE) return fail(c, GPSIG_ERR_INVALID, "gpsig_seq_features_grad takes device pointers");
     if (N <= 0 || !X || !Phi || !dPhi || !gX) return fail(c, GPSIG_ERR_INVALID, "gpsig_seq_features_grad: null or empty argument");
     HIPCHK(c, hipSetDevice(c->device));
-    return sig_launch_reverse(c, rfn, p, p->num_features, order, cosine, ld, static_cast<const double*>(X), N, L, static_cast<const double*>(Phi),
-                              static_cast<const double*>(dPhi), static_cast<double*>(gX));
+    return sig_launch_reverse(c, r, p, static_cast<const double*>(X), N, L, static_cast<const double*>(Phi), static_cast<const double*>(dPhi),
+                              static_cast<double*>(gX));
 }

@@ -8,7 +8,7 @@
 // A Gram entry then costs 2 sum_m d^m flops instead of the lattice sweep's L1 L2 (2d + 3M - 1): at BASELINE configs[1] (L = 64, d = 8,
 // M = 5) 74.9 k against 119 k -- and the N x N batch of them is ONE contraction of depth 37,448, which is what the matrix cores are
 // for (north_star: "MFMA only where it is a true contraction"; the float64 matrix rate of this chip equals its vector rate, but a GEMM
-// runs near it while the lattice sweep, with its hand-overs and latencies, reaches half).  The planner (sig_features_plan in api.hip)
+// runs near it while the lattice sweep, with its hand-overs and latencies, reaches half).  The planner (sig_features_K in sig_feat_api.hip)
 // takes this route where it is the cheaper one and the feature matrix fits; everything else -- every other base kernel, long state
 // spaces, many levels -- stays on the lattice kernels.  Results agree with them to rounding (different summation order).
 //
@@ -475,7 +475,7 @@ __global__ void sig_narrow_kernel(const double* __restrict__ in, float* __restri
 // ---- C = A B^T, float64 matrix cores, depth split over workgroups ----------------------------------------------------------------
 typedef double sig_f64x4 __attribute__((ext_vector_type(4)));
 constexpr int SG_BM = 128, SG_BN = 128, SG_BK = 16, SG_LDK = SG_BK + 1;
-constexpr int SG_MAX_PIECES = 144;        // depth pieces per tile (api.hip's planner: at most 128 equal ones, or a few more of graded sizes)
+constexpr int SG_MAX_PIECES = 144;        // depth pieces per tile (sig_pieces.hpp's sig_piece_counts: at most 128 equal ones, or a few more of graded sizes)
 
 struct SigGramArgs {
     const double* A; const double* B;     // (NA, lda), (NB, ldb) row-major; B row of output column c is (b_off + c) mod b_mod

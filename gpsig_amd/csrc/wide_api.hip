@@ -213,7 +213,6 @@ int wide_tvs_rows(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz, co
     return GPSIG_OK;
 }
 
-// a pair of events from the context's pool around the timed launches (gpsig_timing_*; as api.hip: timing_begin_any)
 // The two contractions of a reverse pass with the adjoint array W (R, CW) of an argument array  arg = XA (R, DA) ZA^T (CW, DA):
 //     gXA (R, DA) = W ZA   (overwritten),      gZA (CW, DA) (+)= W^T XA   (accumulated over the chunks of R).
 int contract_both(gpsig_ctx* c, const double* W, const double* XA, const double* ZA, int64_t R, int64_t CW, int DA, bool accumulate, double* gXA, double* gZA) {
@@ -259,24 +258,6 @@ int gbase_reduce(gpsig_ctx* c, double* part, int64_t n, double* g_base) {
     hipLaunchKernelGGL(wide_sum_kernel, dim3(blocks), dim3(256), 0, c->stream, static_cast<const double*>(part), n, 0, part + n);
     hipLaunchKernelGGL(wide_sum_kernel, dim3(1), dim3(256), 0, c->stream, static_cast<const double*>(part + n), int64_t(blocks), 1, g_base);
     HIPCHK(c, hipGetLastError());
-    return GPSIG_OK;
-}
-
-int wide_timing_begin(gpsig_ctx* c, hipEvent_t* e0, hipEvent_t* e1, bool* on) {
-    *on = false;
-    if (c->capturing || c->ev_used + 2 > 8192) return GPSIG_OK;
-    if (c->ev_used + 2 > c->ev.size()) {
-        hipEvent_t a, b;
-        HIPCHK(c, hipEventCreate(&a));
-        HIPCHK(c, hipEventCreate(&b));
-        c->ev.push_back(a);
-        c->ev.push_back(b);
-    }
-    *e0 = c->ev[c->ev_used];
-    *e1 = c->ev[c->ev_used + 1];
-    c->ev_used += 2;
-    HIPCHK(c, hipEventRecord(*e0, c->stream));
-    *on = true;
     return GPSIG_OK;
 }
 
@@ -347,7 +328,7 @@ int wide_tvs_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz,
     }
     hipEvent_t e0, e1;
     bool timed;
-    CHK(wide_timing_begin(c, &e0, &e1, &timed));
+    CHK(timing_begin(c, &e0, &e1, &timed));
     const bool spx = wide_spectral(p);
     SpxSetup ss;
     const double *nz = nullptr, *nx = nullptr;
@@ -614,7 +595,7 @@ int wide_lat_forward(gpsig_ctx* c, const gpsig_params* p, int d, const double* X
     WideLatKernel fn = ho ? nullptr : lat_kernel(M, pl.C, false, p->base_kernel, NW);
     hipEvent_t e0, e1;
     bool timed;
-    CHK(wide_timing_begin(c, &e0, &e1, &timed));
+    CHK(timing_begin(c, &e0, &e1, &timed));
     LatSpx spx;
     const bool is_spx = wide_spectral(p);
     if (is_spx) {
@@ -869,7 +850,7 @@ int wide_tens_forward(gpsig_ctx* c, const gpsig_params* p, const ScaleParams& sz
     double *ZL, *ZR, *arg;
     hipEvent_t e0, e1;
     bool timed;
-    CHK(wide_timing_begin(c, &e0, &e1, &timed));          // (around the rows, the batched dgemm and the kernel: what the record's name says)
+    CHK(timing_begin(c, &e0, &e1, &timed));          // (around the rows, the batched dgemm and the kernel: what the record's name says)
     CHK(tens_arguments(c, p, sz, d, Z, lt, E, zinc ? 1 : 0, Tn, Tpad, &ZL, &ZR, &arg));
     WideTensArgs A;
     memset(&A, 0, sizeof(A));

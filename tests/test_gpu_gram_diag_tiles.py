@@ -29,7 +29,7 @@ def wave_blocks(w):
 
 
 def planned_pieces(N, d, M):
-    """api.hip, sig_features_K: the depth pieces of a symmetric N x N Gram below the sizes where the graded tail applies (> 512 workgroups)"""
+    """sig_feat_api.hip, sig_features_K (the model: sig_piece_counts of sig_pieces.hpp): the depth pieces of a symmetric N x N Gram below the sizes where the graded tail applies (> 512 workgroups)"""
     F = sum(d ** m for m in range(1, M + 1))
     nslab = ((F + 1 + 15) // 16 * 16 + BK - 1) // BK
     nt = (N + BM - 1) // BM

@@ -1879,7 +1879,7 @@ def test_round5_sweep_one_column_float32_case_and_the_oracle_it_was_judged_by(K,
     it) says the float64 ORACLE is the one 2.3e-3 off (the index-tuple sums of a one-column sequence cancel, as in case 187 above) -- and so are
     the product's float64 PAIR kernels (5e-3, the same cancellation in another order), which the planner would have picked for 19 x 12 sequences:
     the sweep had drawn `sig_features = 1`.  Since then one-column state spaces take the per-sequence feature route whatever their size
-    (api.hip, sig_features_K), float32 requests on them are evaluated in float64, and the product is held to the 80-bit values."""
+    (sig_feat_api.hip, sig_features_K), float32 requests on them are evaluated in float64, and the product is held to the 80-bit values."""
     fz, key = fuzz_cases_r5, "s71c779"
     kern, _ = _fuzz_kernel(K, fz, key)
     X, X2 = fz[key + "_X"], fz[key + "_X2"]
