@@ -68,6 +68,11 @@ _KERNEL_FUNCS = {
     "gpsig_kernel_K_tens_vs_seq": [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
     "gpsig_kernel_K_tens_n_seq_covs": [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "gpsig_kernel_K_seq_n_seq_covs": [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    # ragged batches in exact mode: the dense twin's arguments plus `lengths` directly after each L
+    "gpsig_kernel_Kdiag_ragged": [_vp, _i64, _i32, _vp, _i32, _vp],
+    "gpsig_kernel_K_tens_vs_seq_ragged": [_vp, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp],
+    "gpsig_kernel_K_tens_n_seq_covs_ragged": [_vp, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    "gpsig_kernel_K_ragged": [_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _vp],
     "gpsig_lr_draw": [_i32, _i32, _i32, C.c_uint64, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _i32, C.POINTER(_vp)],
     "gpsig_lr_gather_points": [_vp, _i64, _i32, C.POINTER(_i64), _i64, C.POINTER(C.c_double)],
     "gpsig_base_kernel_matrix": [C.POINTER(C.c_double), C.POINTER(C.c_double), _i64, _i64, _i32, C.POINTER(C.c_double)],

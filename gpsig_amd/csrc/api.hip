@@ -1394,6 +1394,13 @@ static int e_kernel_K_seq_n_seq_covs(gpsig_ctx* c, const gpsig_params* p, const 
 
 }  // namespace
 
+namespace gpsig {
+// Kzz of a ragged covariance call (wide_ragged_api.hip) is the dense call's: the same function on the same device pointers
+int tens_gram_f64(gpsig_ctx* c, const gpsig_params* p, const void* Z, int64_t Tn, int increments, int return_levels, void* out) {
+    return Impl<double>::tens_gram_device(c, p, false, Z, Tn, increments, return_levels, out);
+}
+}  // namespace gpsig
+
 // =====================================================================================================
 extern "C" {
 

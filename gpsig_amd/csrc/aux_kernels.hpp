@@ -554,6 +554,25 @@ __global__ void prep_seq_scaled_kernel(const T* __restrict__ X, int64_t N, int L
     }
 }
 
+// The lengths-aware form (ragged batches on the wide route, wide_ragged_api.hip): sequence n is its first len[n] rows, written PACKED --
+// out[(off[n] + t) * d_eff + fe], t < len[n], off the prefix sums of len -- and, where the call has lags, interpolated on its own axis
+// i / (len[n] - 1) (scaled_point's seq_len).  No row at or beyond len[n] is read.  One workgroup per sequence (grid-stride).
+template <typename T>
+__global__ void prep_seq_scaled_kernel(const T* __restrict__ X, int64_t N, int L, ScaleParams P, const int32_t* __restrict__ len,
+                                       const int64_t* __restrict__ off, T* __restrict__ out) {
+    const int d_eff = P.d_eff();
+    for (int64_t n = blockIdx.x; n < N; n += gridDim.x) {
+        const int ln = len[n];
+        const int total = ln * d_eff;
+        const T* Xn = X + n * int64_t(L) * P.d_in;
+        T* o = out + off[n] * d_eff;
+        for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+            const int t = idx / d_eff, fe = idx - t * d_eff;
+            o[idx] = scaled_point<T>(Xn, L, t, fe, P, P.num_lags > 0 ? ln : 0);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Inducing tensors vs inducing tensors: SignatureKernel._K_tens + tensor_kern (kernels.py:263-283,
 // signature_algs.py:76-99) + sigma*variances weighting (kernels.py:531-536).  One thread per (t, t').

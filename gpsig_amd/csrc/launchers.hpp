@@ -218,6 +218,16 @@ bool wide_tens_fwd_available(const gpsig_ctx* c, const gpsig_params* p, int64_t 
 bool wide_lat_fwd_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L2);
 int wide_spectral_refusal(gpsig_ctx* c, const gpsig_params* p, bool lattice, int L2);
 
+// what the ragged form of the route (wide_ragged_api.hip) shares with it: the argument budget of one chunk (option wide_chunk_mb), the columns per lane
+// of a lattice of R2 columns and the wavefronts per lattice of a launch (option wide_lat_waves)
+size_t wide_chunk_bytes(const gpsig_ctx* c);
+int wide_lat_columns(int R2);
+int wide_lat_waves(const gpsig_ctx* c, int C, int64_t lattices);
+
+// ---- wide_ragged_api.hip: ragged batches in exact mode -- the entry points gpsig_kernel_*_ragged (include/gpsig_hip.h).  Kzz of the covariances is
+// the dense call's: api.hip's evaluation of K_tens on device pointers, float64
+int tens_gram_f64(gpsig_ctx* c, const gpsig_params* p, const void* Z, int64_t Tn, int increments, int return_levels, void* out);
+
 // ---- wide_spectral_inst.hip: SignatureSpectral's kernel-argument array of the wide route (wide_spectral_kernel.hpp).  They return the hipError_t of the launch.
 struct WideSpxArgs;
 int wide_spx_prep_launch(hipStream_t stream, const double* gamma, int64_t count, double* g2);          // g2 = gamma^2

@@ -18,6 +18,25 @@
 #include <string>
 
 namespace gpsig {
+
+// (shared with the ragged form of the route, wide_ragged_api.hip: launchers.hpp)
+size_t wide_chunk_bytes(const gpsig_ctx* c) {
+    if (c->wide_chunk_mb > 0) return size_t(c->wide_chunk_mb) << 20;
+    // 4 GB by default (the forward pass holds one such array, the reverse pass two and the partial sums of the narrow contraction: a launch of a
+    // minibatch is bound by the serial sweep of one chain, so halving it doubles that time -- NetFlow's shape is 2 GB); grad_scratch_mb scales it
+    return size_t(c->grad_scratch_mb > 0 ? c->grad_scratch_mb : 4096) << 20;
+}
+// wavefronts per lattice: a launch of few lattices of more than 256 columns spreads each lattice's columns over eight wavefronts of one column per
+// lane instead of eight columns per lane of one (NetFlow's / CMUsubject16's level diagonals, 50 / 23 lattices of 499 x 499: reverse pass 3.5 -> 3.2 / 2.9 ms;
+// at four and two columns per lane the barrier per step costs more than the shorter steps save: AUSLAN 0.74 -> 0.79).  Option wide_lat_waves: 0 never,
+// 1 wherever there are two or more columns per lane (the tests), -1 this rule
+int wide_lat_waves(const gpsig_ctx* c, int C, int64_t lattices) {
+    if (C < 2 || c->wide_lat_waves == 0) return 1;
+    if (c->wide_lat_waves > 0) return C;
+    return (C == 8 && lattices <= 128) ? C : 1;
+}
+int wide_lat_columns(int R2) { return R2 <= 64 ? 1 : (R2 <= 128 ? 2 : (R2 <= 256 ? 4 : 8)); }
+
 namespace {
 
 // (SignaturePoly: the whole degrees 1 .. 8 of the kernels' repeated squaring -- any other degree is left to the routes that call the library's pow)
@@ -71,13 +90,6 @@ MixSides mix_sides(const gpsig_params* p, MixPrim prim, int increments) {
     else if (prim == MIX_LAT) s.rows = s.cols = !p->difference;
     else s.rows = s.cols = !increments;
     return s;
-}
-
-size_t wide_chunk_bytes(const gpsig_ctx* c) {
-    if (c->wide_chunk_mb > 0) return size_t(c->wide_chunk_mb) << 20;
-    // 4 GB by default (the forward pass holds one such array, the reverse pass two and the partial sums of the narrow contraction: a launch of a
-    // minibatch is bound by the serial sweep of one chain, so halving it doubles that time -- NetFlow's shape is 2 GB); grad_scratch_mb scales it
-    return size_t(c->grad_scratch_mb > 0 ? c->grad_scratch_mb : 4096) << 20;
 }
 
 int dgemm(gpsig_ctx* c, bool ta, bool tb, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* B, int64_t ldb, double beta,
@@ -179,16 +191,6 @@ WideLatKernel lat_kernel(int M, int C, bool bwd, int base_kernel, int NW = 1) {
     GPSIG_WIDE_KIND(base_kernel, return M <= 4 ? lat_kernel_of<3, KD>(C, bwd, NW) : lat_kernel_of<7, KD>(C, bwd, NW))
     return nullptr;
 }
-// wavefronts per lattice: a launch of few lattices of more than 256 columns spreads each lattice's columns over eight wavefronts of one column per
-// lane instead of eight columns per lane of one (NetFlow's / CMUsubject16's level diagonals, 50 / 23 lattices of 499 x 499: reverse pass 3.5 -> 3.2 / 2.9 ms;
-// at four and two columns per lane the barrier per step costs more than the shorter steps save: AUSLAN 0.74 -> 0.79).  Option wide_lat_waves: 0 never,
-// 1 wherever there are two or more columns per lane (the tests), -1 this rule
-int lat_waves(const gpsig_ctx* c, int C, int64_t lattices) {
-    if (C < 2 || c->wide_lat_waves == 0) return 1;
-    if (c->wide_lat_waves > 0) return C;
-    return (C == 8 && lattices <= 128) ? C : 1;
-}
-int lat_columns(int R2) { return R2 <= 64 ? 1 : (R2 <= 128 ? 2 : (R2 <= 256 ? 4 : 8)); }
 
 // the augmented rows of both sides: ZA (lt * E * Tpad, DA) left form, XA (NL, DA) right form.  E, NL: as the KERNELS see them -- SignatureLinear: E = 1 from
 // the caller's two points per tensor (zdiff), NL = N (L - 1) increment rows of sequences of xdiff = L observations
@@ -536,7 +538,7 @@ struct LatPlan {
 // (xd1, xd2 > 0: the rows are the increments of sequences of xd1 / xd2 observations, L1 / L2 of them per sequence -- LatInc)
 int lat_plan(gpsig_ctx* c, const gpsig_params* p, int d, const double* Xs, const double* Ys, int64_t N1, int64_t N2, int L1, int L2, bool diag, int bufs,
              int xd1, int xd2, LatPlan* pl) {
-    pl->DA = d + 2; pl->dr = p->difference ? 1 : 0; pl->R1 = L1 - pl->dr; pl->R2 = L2 - pl->dr; pl->C = lat_columns(pl->R2);
+    pl->DA = d + 2; pl->dr = p->difference ? 1 : 0; pl->R1 = L1 - pl->dr; pl->R2 = L2 - pl->dr; pl->C = wide_lat_columns(pl->R2);
     void *xl, *xr;
     CHK(ensure(c, B_WD0, sizeof(double) * size_t(N1) * L1 * pl->DA + 64, &xl));
     CHK(ensure(c, B_WD1, sizeof(double) * size_t(N2) * L2 * pl->DA + 64, &xr));
@@ -591,7 +593,7 @@ int wide_lat_forward(gpsig_ctx* c, const gpsig_params* p, int d, const double* X
     void *arg, *dmat = nullptr;
     CHK(ensure(c, B_WD2, sizeof(double) * size_t(pl.chunk_i) * L1 * L2 * size_t(diag ? 1 : N2) + 64, &arg));
     if (ho) CHK(ensure(c, B_WD6, sizeof(double) * size_t(pl.chunk_i) * L1 * L2 * size_t(diag ? 1 : N2) + 64, &dmat));
-    const int NW = ho ? 1 : lat_waves(c, pl.C, diag ? (N1 < pl.chunk_i ? N1 : pl.chunk_i) : (N1 < pl.chunk_i ? N1 : pl.chunk_i) * N2);
+    const int NW = ho ? 1 : wide_lat_waves(c, pl.C, diag ? (N1 < pl.chunk_i ? N1 : pl.chunk_i) : (N1 < pl.chunk_i ? N1 : pl.chunk_i) * N2);
     WideLatKernel fn = ho ? nullptr : lat_kernel(M, pl.C, false, p->base_kernel, NW);
     hipEvent_t e0, e1;
     bool timed;
@@ -677,7 +679,7 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
     CHK(ensure(c, B_WD4, sizeof(double) * size_t(N1) * L1 * DA + 64, &gxl));
     CHK(ensure(c, B_WD5, sizeof(double) * size_t(N2) * L2 * DA + 64, &gxr));
     const int64_t Pmax = diag ? pl.chunk_i : pl.chunk_i * N2;
-    const int NW = (ho || short_lat) ? 1 : lat_waves(c, pl.C, Pmax);
+    const int NW = (ho || short_lat) ? 1 : wide_lat_waves(c, pl.C, Pmax);
     const int TF = pl.R1 + 64 * NW - 1;
     const size_t per_group = sizeof(double) * size_t(M > 1 ? M - 1 : 1) * TF * 64 * (NW > 1 ? NW : pl.C);
     int64_t groups = int64_t(wide_chunk_bytes(c) / per_group);

@@ -25,6 +25,13 @@
 #include "grad_wave_core.hpp"
 #include "fast_exp.hpp"
 
+// The kernels that are no templates have ONE definition with external linkage, in wide_api.hip.  A second unit that includes this file for the kernel
+// templates (wide_ragged_api.hip: their ragged forms) defines GPSIG_WIDE_GLOBAL as `template <int UNIT = 0> __global__` before it does: there they are
+// templates too -- the two it launches (as `name<>`) are instantiated as copies of its own, the others are never emitted.
+#ifndef GPSIG_WIDE_GLOBAL
+#define GPSIG_WIDE_GLOBAL __global__
+#endif
+
 namespace gpsig {
 
 constexpr int WIDE_MAX_LEVELS = 8;
@@ -288,13 +295,14 @@ __device__ __forceinline__ void wide_chain_fwd(const double* __restrict__ col, i
     }
 }
 
+// (L: the rows of this sequence -- A.L, or its own length in a ragged launch)
 template <int E, int KD>
-__device__ __forceinline__ void wide_level_fwd(int i, const double* col, const WideTvsArgs& A, const WideKap& K, double* u /* [i] */, const WideMixCtx& X) {
+__device__ __forceinline__ void wide_level_fwd(int i, const double* col, const WideTvsArgs& A, int L, const WideKap& K, double* u /* [i] */, const WideMixCtx& X) {
     const int k0 = i * (i - 1) / 2;
 #define GPSIG_WIDE_CASE(I_)                                                                          \
     case I_: {                                                                                       \
         double v[I_];                                                                                \
-        wide_chain_fwd<I_, E, KD>(col, A.CW, A.Tpad, k0, A.L, A.difference, A.order, K, v, X);               \
+        wide_chain_fwd<I_, E, KD>(col, A.CW, A.Tpad, k0, L, A.difference, A.order, K, v, X);                 \
         _Pragma("unroll") for (int j = 0; j < I_; ++j) u[j] = v[j];                                 \
     } break;
     switch (i) {
@@ -324,25 +332,30 @@ __device__ __forceinline__ WideMixCtx wide_mix_ctx(const WideTvsArgs& A, int64_t
 // grid: (Tpad / 64, sequences of the chunk (grid-stride), levels); block: one wavefront, lane = tensor.  A launch of few sequences is bound by the
 // serial sweep of one chain: the levels of a (tensor, sequence) pair go to different workgroups (blockIdx.z + 1 = level), each leaving its chain totals
 // in aux (N, lt, Tpad) -- tensors fastest --, and wide_tvs_epilogue_kernel forms the outputs from them.
+// RG (ragged batches, wide_ragged_api.hip: wide_tvs_fwd_ragged_kernel): the argument array holds the sequences' own rows back to back -- sequence n has
+// len[n] of them from row off[n] - off[n0] of the chunk --, and its chains take len[n] steps.  The totals land in aux as in the dense form: the epilogue is
+// the same kernel.  The two kernels are one body; the dense one compiles to what it was.
+struct WideTvsRaggedArgs : WideTvsArgs {
+    const int32_t* len;     // (N) rows per sequence, >= 1
+    const int64_t* off;     // (N + 1) their prefix sums
+};
+
 template <int E, int KD>
 __global__ void __launch_bounds__(64) wide_tvs_fwd_kernel(const WideTvsArgs A) {
-    __shared__ double etab[EXP_TAB_N];
-    const WideKap K = wide_kap(A.kind, wide_tab<KD>(etab, threadIdx.x, 64), A.kp0, A.kp1);
-    const int64_t t = int64_t(blockIdx.x) * 64 + threadIdx.x;
-    const int M = A.M, lt = M * (M + 1) / 2;
-    const int i = blockIdx.z + 1, k0 = i * (i - 1) / 2;
-    for (int64_t nl = blockIdx.y; nl < A.Nc; nl += gridDim.y) {
-        const int64_t n = A.n0 + nl;
-        const double* col = A.arg + nl * int64_t(A.L) * A.CW + t;
-        double u[WIDE_MAX_LEVELS];
-        wide_level_fwd<E, KD>(i, col, A, K, u, wide_mix_ctx<KD>(A, n, t));
-        for (int j = 0; j < i; ++j) A.aux[(n * lt + k0 + j) * A.Tpad + t] = u[j];
-    }
+#define GPSIG_WIDE_RG 0
+#include "wide_tvs_fwd_body.inc"
+#undef GPSIG_WIDE_RG
+}
+template <int E, int KD>
+__global__ void __launch_bounds__(64) wide_tvs_fwd_ragged_kernel(const WideTvsRaggedArgs A) {
+#define GPSIG_WIDE_RG 1
+#include "wide_tvs_fwd_body.inc"
+#undef GPSIG_WIDE_RG
 }
 
 // out[t][n] = fac_0 + sum_i fac_i K_i  or  out[i][t][n] = fac_i K_i  (fac = fx[n][i] * w[i]: kernels.py:572-588), K_i = the total of level i's last chain
 // (signature_algs.py:125).  One thread per (t, n) of the chunk, tensors fastest.
-__global__ void wide_tvs_epilogue_kernel(const WideTvsArgs A) {
+GPSIG_WIDE_GLOBAL void wide_tvs_epilogue_kernel(const WideTvsArgs A) {
     const int M = A.M, lt = M * (M + 1) / 2;
     const int64_t total = A.Nc * A.Tn;
     for (int64_t idx = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; idx < total; idx += int64_t(gridDim.x) * blockDim.x) {
@@ -597,7 +610,7 @@ __global__ void __launch_bounds__(64) wide_tvs_bwd_kernel(const WideTvsArgs A) {
         if (A.aux) {
             for (int j = 0; j < i; ++j) u[j] = A.aux[(n * lt + k0 + j) * A.Tpad + t];
         } else {
-            wide_level_fwd<E, KD>(i, col, A, K, u, X);
+            wide_level_fwd<E, KD>(i, col, A, A.L, K, u, X);
         }
         if (A.gfac_part) {
             double ui = 0.0;
@@ -632,7 +645,7 @@ __global__ void __launch_bounds__(64) wide_tvs_bwd_kernel(const WideTvsArgs A) {
 // out[b] (+)= the sum of part[0 .. n) taken by block b of gridDim.x blocks of 256 threads: a thread adds its entries in ascending order, the block's 256
 // sums meet in a fixed tree.  Two launches -- (blocks, part -> tmp), (1, tmp -> g_base[0], add = 1) -- sum the offset's partials in an order that
 // depends on n alone (SignaturePoly's reverse passes).
-__global__ void __launch_bounds__(256) wide_sum_kernel(const double* __restrict__ part, int64_t n, int add, double* __restrict__ out) {
+GPSIG_WIDE_GLOBAL void __launch_bounds__(256) wide_sum_kernel(const double* __restrict__ part, int64_t n, int add, double* __restrict__ out) {
     __shared__ double sh[256];
     double s = 0.0;
     for (int64_t idx = blockIdx.x * int64_t(256) + threadIdx.x; idx < n; idx += int64_t(gridDim.x) * 256) s += part[idx];
@@ -646,7 +659,7 @@ __global__ void __launch_bounds__(256) wide_sum_kernel(const double* __restrict_
 }
 
 // gfac[n][m] = sum over the tensor blocks of the partial sums (a fixed order: the result does not depend on the schedule)
-__global__ void wide_gfac_reduce_kernel(const double* __restrict__ part, int TB, int64_t NM, double* __restrict__ gfac) {
+GPSIG_WIDE_GLOBAL void wide_gfac_reduce_kernel(const double* __restrict__ part, int TB, int64_t NM, double* __restrict__ gfac) {
     for (int64_t idx = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; idx < NM; idx += int64_t(gridDim.x) * blockDim.x) {
         double s = 0.0;
         for (int b = 0; b < TB; ++b) s += part[int64_t(b) * NM + idx];
@@ -668,7 +681,7 @@ __global__ void wide_gfac_reduce_kernel(const double* __restrict__ part, int TB,
 // One wavefront per row.
 constexpr int WIDE_ROWS_DIST = 0, WIDE_ROWS_PLAIN = 1, WIDE_ROWS_UNIT = 2;
 
-__global__ void __launch_bounds__(64) wide_aug_rows_kernel(const double* __restrict__ src, int64_t rows, int d, int right, int lt, int64_t Tn, int64_t Tpad,
+GPSIG_WIDE_GLOBAL void __launch_bounds__(64) wide_aug_rows_kernel(const double* __restrict__ src, int64_t rows, int d, int right, int lt, int64_t Tn, int64_t Tpad,
                                                            int E, ScaleParams P, int mode, int diff, double* __restrict__ dst) {
     const int DA = d + 2;
     for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
@@ -720,7 +733,7 @@ __global__ void __launch_bounds__(64) wide_aug_rows_kernel(const double* __restr
 // Tensor rows go back to the caller's (lt, T, E, d) order; sequences as they come.  One thread per output element.
 // adj (SignatureMix where this side's term q |v|^2 / 2 survives; else NULL, and the arithmetic is what it was): the sums of the values' adjoints over the
 // other side, per augmented row -- the norm column's adjoint becomes ga[norm column] - q adj[row].
-__global__ void wide_unaug_rows_kernel(const double* __restrict__ ga, const double* __restrict__ va, int64_t rows_out, int d, int right, int lt, int64_t Tn,
+GPSIG_WIDE_GLOBAL void wide_unaug_rows_kernel(const double* __restrict__ ga, const double* __restrict__ va, int64_t rows_out, int d, int right, int lt, int64_t Tn,
                                        int64_t Tpad, int E, double* __restrict__ g, const double* __restrict__ adj = nullptr, double q = 0.0) {
     const int DA = d + 2, nc = right ? d + 1 : d;
     const int64_t total = rows_out * d;
@@ -743,7 +756,7 @@ __global__ void wide_unaug_rows_kernel(const double* __restrict__ ga, const doub
 // The adjoints of the dot-product families' rows.  Sources: the adjoint gl of left-form rows vl and / or gr of right-form rows vr (both: one array on both
 // sides of the lattices, the two forms of the tensors in Kzz -- the sum of the two); row mapping as wide_aug_rows_kernel.
 // WIDE_ROWS_UNIT:  g_v = (g_u - <g_u, u> u) / |v|   (u = v / |v|; 1 / |v| from the form's own column).  One wavefront per output row.
-__global__ void __launch_bounds__(64) wide_unaug_unit_kernel(const double* __restrict__ gl, const double* __restrict__ vl, const double* __restrict__ gr,
+GPSIG_WIDE_GLOBAL void __launch_bounds__(64) wide_unaug_unit_kernel(const double* __restrict__ gl, const double* __restrict__ vl, const double* __restrict__ gr,
                                                              const double* __restrict__ vr, int64_t rows_out, int d, int lt, int64_t Tn, int64_t Tpad, int E,
                                                              double* __restrict__ g) {
     const int DA = d + 2;
@@ -776,7 +789,7 @@ __global__ void __launch_bounds__(64) wide_unaug_unit_kernel(const double* __res
 //   sequences (lt == 0, diff = observations per sequence, rows_out = N diff):  gX[t] = gD[t - 1] - gD[t]   (zero outside 0 .. diff - 2),
 //   tensors (lt > 0, the caller's (lt, T, 2, d) array, rows_out = lt T 2):     gz^1 = gD,  gz^0 = -gD.
 // One thread per output element.
-__global__ void wide_unaug_inc_kernel(const double* __restrict__ gl, const double* __restrict__ gr, int64_t rows_out, int d, int lt, int64_t Tn, int64_t Tpad,
+GPSIG_WIDE_GLOBAL void wide_unaug_inc_kernel(const double* __restrict__ gl, const double* __restrict__ gr, int64_t rows_out, int d, int lt, int64_t Tn, int64_t Tpad,
                                       int diff, double* __restrict__ g) {
     const int DA = d + 2;
     const int64_t total = rows_out * d;
@@ -920,82 +933,30 @@ __device__ __forceinline__ double wide_from_right(double v) {      // lane l <- 
 // NW > 1: NW wavefronts per lattice (a workgroup), lane lam = threadIdx.x of 64 NW; the hand-over across a wavefront boundary goes through LDS (two buffers
 // alternating by the step's parity, one barrier per step).  For a FEW long lattices (the level diagonals of a minibatch: 50 lattices of 499 x 499 keep
 // 50 of 1,024 SIMDs busy with eight columns per lane) -- more steps (R1 + 64 NW - 1), an eighth of the work per step, NW times the wavefronts.
+// RG (ragged batches, wide_ragged_api.hip: wide_lattice_fwd_ragged_kernel, the same body -- the dense kernel compiles to what it was): every lattice has its
+// own extent, base and row stride.  Pair pg = (i, j) = divmod(pg, N2) is len1[i] x len2[j].
+// A full Gram (ld = all packed right rows): first row rbase[i] - rbase[0] of the chunk's argument array, first column cbase[j] -- the sides' packed row
+// offsets.  The block diagonal (ld == 0, N2 = 1, len2 = len1, cbase = NULL): the lattice starts rbase[i] - rbase[0] CELLS into the array and its row stride
+// is its own len2[j].  C and NW are the launch's, from the longest sequence: a shorter lattice leaves its last lanes without columns, and they pass the
+// row prefixes on unchanged.
+struct WideLatRaggedArgs : WideLatArgs {
+    const int32_t* len1;    // the launch's left sequences
+    const int32_t* len2;    // the right sequences (the diagonal: == len1)
+    const int64_t* rbase;   // per left sequence of the launch: packed rows (full Gram) or lattice cells (diagonal) before it
+    const int64_t* cbase;   // per right sequence: packed rows before it, or NULL
+};
+
 template <int C, int LQ, int KD, int NW = 1>
 __global__ void __launch_bounds__(64 * NW) wide_lattice_fwd_kernel(const WideLatArgs A) {
-    __shared__ double etab[EXP_TAB_N];
-    __shared__ double xw[2][NW][LQ + 2];
-    const double* const ktab = wide_tab<KD>(etab, threadIdx.x, 64 * NW);
-    constexpr int GL = 64 * NW, PF = wide_lat_pf(C);
-    const int lam = threadIdx.x, M = A.M, wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
-    const int dr = A.difference ? 1 : 0, R1 = A.L1 - dr, R2 = A.L2 - dr, TF = R1 + GL - 1;
-    for (int64_t pp = blockIdx.x; pp < A.P; pp += gridDim.x) {
-        if constexpr (NW > 1) {
-            __syncthreads();
-            if (ln == 63) {
-#pragma unroll
-                for (int m = 0; m < LQ + 2; ++m) xw[0][wv][m] = xw[1][wv][m] = 0.0;
-            }
-            __syncthreads();
-        }
-        const int64_t pg = A.p0 + pp;
-        WideLatDm<C, KD> dmg;
-        dmg.lat = A.arg + (pg / A.N2) * A.si + (pg % A.N2) * A.sj;
-        dmg.ld = A.ld; dmg.b0 = C * lam; dmg.L2 = A.L2; dmg.K = wide_kap(A.kind, ktab, A.kp0, A.kp1); dmg.diff = dr;
-        { const int nv = R2 - C * lam; dmg.nvalid = nv < 0 ? 0 : (nv > C ? C : nv); }
-        dmg.mix_terms(A, pg);
-        WaveFwd<C, LQ> fw;
-        fw.reset();
-        // the argument rows of the coming PF steps are in flight while a step computes (a launch of a few lattices is one wavefront per
-        // SIMD: nothing else hides the latency of these strided loads)
-        double raw[PF][C + 1];
-        if (dr) { dmg.load(0, true, raw[0]); dmg.prime(raw[0]); }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) { const int r = u - lam + dr; dmg.load(r, r >= 0 && r < A.L1, raw[u]); }
-        double kM = 0.0;
-        for (int t0 = 0; t0 < TF; t0 += PF) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                const int t = t0 + u;
-                if (t >= TF) break;
-                double cin[LQ + 2], cur[C + 1];
-                cin[0] = 0.0;
-#pragma unroll
-                for (int m = 1; m < LQ + 2; ++m) {
-                    cin[m] = wide_from_left(fw.sout[m]);
-                    if constexpr (NW > 1) {
-                        const double x = xw[t & 1][wv > 0 ? wv - 1 : 0][m];
-                        cin[m] = (ln == 0 && wv > 0) ? x : cin[m];
-                    }
-                }
-#pragma unroll
-                for (int c = 0; c <= C; ++c) cur[c] = raw[u][c];
-                const int a = t - lam;
-                { const int r = a + PF + dr; dmg.load(r, r >= 0 && r < A.L1, raw[u]); }
-                if (a >= 0 && a < R1) {
-                    double dm[C];
-                    dmg.row(cur, true, dm);
-                    fw.step(dm, cin, M);
-#pragma unroll
-                    for (int m = 1; m <= LQ + 1; ++m)
-                        if (m == M) kM += fw.sout[m];
-                }
-                if constexpr (NW > 1) {
-                    if (ln == 63) {
-#pragma unroll
-                        for (int m = 1; m < LQ + 2; ++m) xw[(t + 1) & 1][wv][m] = fw.sout[m];
-                    }
-                    __syncthreads();
-                }
-            }
-        }
-        if (lam == GL - 1) {
-            A.out[pg] = 1.0;                                                       // signature_algs.py:20
-#pragma unroll
-            for (int m = 1; m <= LQ; ++m)
-                if (m < M) A.out[int64_t(m) * A.Ptot + pg] = fw.q[m - 1][C - 1];
-            A.out[int64_t(M) * A.Ptot + pg] = kM;
-        }
-    }
+#define GPSIG_WIDE_RG 0
+#include "wide_lattice_fwd_body.inc"
+#undef GPSIG_WIDE_RG
+}
+template <int C, int LQ, int KD, int NW = 1>
+__global__ void __launch_bounds__(64 * NW) wide_lattice_fwd_ragged_kernel(const WideLatRaggedArgs A) {
+#define GPSIG_WIDE_RG 1
+#include "wide_lattice_fwd_body.inc"
+#undef GPSIG_WIDE_RG
 }
 
 // Both sweeps (grad_wave_kernel.hpp: seq_grad_wave_kernel with the argument lattice in place of the point rows): Lam[a][b] = dL/ddM[a][b] out.
@@ -1178,7 +1139,7 @@ __global__ void wide_lattice_adjoint_kernel(const WideLatArgs A, double* __restr
 // The same for SignaturePoly, with the sum of what it stores (the offset's gradient): workgroups of ONE wavefront, each taking a slice of WIDE_GB_SLICE
 // cells of one lattice, so that a slice's sum of W is formed in an order that depends on the lattice's shape alone, and lands in the slice's own slot
 // (three 64-bit divisions: held to eight wavefronts per SIMD, which its scalar registers would otherwise miss by a few)
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) wide_lattice_adjoint_poly_kernel(const WideLatArgs A, double* __restrict__ W) {
+GPSIG_WIDE_GLOBAL void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) wide_lattice_adjoint_poly_kernel(const WideLatArgs A, double* __restrict__ W) {
     const WideKap K = wide_kap(A.kind, nullptr, A.kp0, A.kp1);
     const int dr = A.difference ? 1 : 0, R1 = A.L1 - dr, R2 = A.L2 - dr;
     const int64_t cells = int64_t(A.L1) * A.L2;
@@ -1207,7 +1168,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) wi
 
 // The same for SignatureMix, with the slice's sum of Gam d kappa / d p0 (the mixing's gradient): d kappa / d p0 = exp(a) - a, less the two half norms where
 // the one-sided terms survive (no differences).  Slices, slots and order of summation as above.
-__global__ void __launch_bounds__(64) wide_lattice_adjoint_mix_kernel(const WideLatArgs A, double* __restrict__ W) {
+GPSIG_WIDE_GLOBAL void __launch_bounds__(64) wide_lattice_adjoint_mix_kernel(const WideLatArgs A, double* __restrict__ W) {
     __shared__ double etab[EXP_TAB_N];
     const WideKap K = wide_kap(A.kind, wide_tab<WIDE_KD_MIX>(etab, threadIdx.x, 64), A.kp0, A.kp1);
     const int dr = A.difference ? 1 : 0, R1 = A.L1 - dr, R2 = A.L2 - dr;
@@ -1241,7 +1202,7 @@ __global__ void __launch_bounds__(64) wide_lattice_adjoint_mix_kernel(const Wide
 // launch's Lam lattices.  One wavefront per unit, in an order fixed by the launch's shape: unit u < NI L1 is row r of left sequence il (sums over its lattices'
 // columns), the others column c of right sequence jl (over its lattices' rows).  NI x NJ lattices, pair il NJ + jl (the diagonal: NJ = 1 and jl = il).
 // radj (NI L1) is written; cadj (NJ L2; the diagonal: NI L2) is written or, acc, added to (the chunks of left sequences one after the other).
-__global__ void __launch_bounds__(64) wide_lattice_sides_kernel(const double* __restrict__ lam, int64_t NI, int64_t NJ, int L1, int L2, int diag, int acc,
+GPSIG_WIDE_GLOBAL void __launch_bounds__(64) wide_lattice_sides_kernel(const double* __restrict__ lam, int64_t NI, int64_t NJ, int L1, int L2, int diag, int acc,
                                                                  double* __restrict__ radj, double* __restrict__ cadj) {
     const int64_t rows = NI * L1, cols = (diag ? NI : NJ) * L2, cells = int64_t(L1) * L2;
     for (int64_t un = blockIdx.x; un < rows + cols; un += gridDim.x) {
@@ -1270,7 +1231,7 @@ __global__ void __launch_bounds__(64) wide_lattice_sides_kernel(const double* __
 
 // The symmetric Gram's upstream gradient folded onto the pairs i <= j (the levels are symmetric functions of the two sequences):
 // Gs[m][i][j] = G[m][i][j] + G[m][j][i] (j > i),  G[m][i][i] (j == i),  0 (j < i).
-__global__ void wide_sym_upstream_kernel(const double* __restrict__ G, int64_t N, int M1, double* __restrict__ Gs) {
+GPSIG_WIDE_GLOBAL void wide_sym_upstream_kernel(const double* __restrict__ G, int64_t N, int M1, double* __restrict__ Gs) {
     const int64_t total = int64_t(M1) * N * N;
     for (int64_t idx = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; idx < total; idx += int64_t(gridDim.x) * blockDim.x) {
         const int64_t j = idx % N, i = (idx / N) % N, m = idx / (N * N);
@@ -1301,7 +1262,7 @@ __global__ void wide_lattice_dm_kernel(const WideLatArgs A, double* __restrict__
 
 // g[r][f] = left-form chain rule of (gl, vl) [+ right-form chain rule of (gr, vr) where given: one array on both sides of the lattices]
 // (adjl / adjr, q: as wide_unaug_rows_kernel)
-__global__ void wide_unaug_pair_kernel(const double* __restrict__ gl, const double* __restrict__ vl, const double* __restrict__ gr, const double* __restrict__ vr,
+GPSIG_WIDE_GLOBAL void wide_unaug_pair_kernel(const double* __restrict__ gl, const double* __restrict__ vl, const double* __restrict__ gr, const double* __restrict__ vr,
                                        int64_t rows, int d, double* __restrict__ g, const double* __restrict__ adjl = nullptr,
                                        const double* __restrict__ adjr = nullptr, double q = 0.0) {
     const int DA = d + 2;
@@ -1462,7 +1423,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KD == W
 }
 
 // gZ in the caller's (lt, T, E, d) order from the adjoints of the left-form and the right-form augmented rows (rows (k * E + e) * Tpad + t)
-__global__ void wide_unaug_tens_kernel(const double* __restrict__ gl, const double* __restrict__ vl, const double* __restrict__ gr, const double* __restrict__ vr,
+GPSIG_WIDE_GLOBAL void wide_unaug_tens_kernel(const double* __restrict__ gl, const double* __restrict__ vl, const double* __restrict__ gr, const double* __restrict__ vr,
                                        int64_t rows_out, int d, int64_t Tn, int64_t Tpad, int E, double* __restrict__ g,
                                        const double* __restrict__ adjl = nullptr, const double* __restrict__ adjr = nullptr, double q = 0.0) {
     const int DA = d + 2;
@@ -1691,7 +1652,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 }
 
 // dst[e][f] = (acc ? dst : 0) + sum over k of part[k][e][f], f < DA of DAP (a fixed order: deterministic)
-__global__ void wide_contract_reduce_kernel(const double* __restrict__ part, int64_t nparts, int64_t rows, int DA, int DAP, int acc, double* __restrict__ dst) {
+GPSIG_WIDE_GLOBAL void wide_contract_reduce_kernel(const double* __restrict__ part, int64_t nparts, int64_t rows, int DA, int DAP, int acc, double* __restrict__ dst) {
     const int64_t n = rows * DA;
     for (int64_t idx = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; idx < n; idx += int64_t(gridDim.x) * blockDim.x) {
         const int64_t e = idx / DA;

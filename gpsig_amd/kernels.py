@@ -340,6 +340,11 @@ class SignatureKernel:
         # ``lengths=`` with num_lags > 0: "table" refuses (the reference pads, and its lag interpolation runs on the table's own time axis);
         # "sequence" evaluates X[n, :len_n] as that truncated sequence would be on its own -- its axis is i / (len_n - 1) (_ragged_lengths)
         self.lag_axis = "table"
+        # ``lengths=`` in exact (non-low-rank) mode: refused unless the kernel object opts in.  True: K, Kdiag, K_tens_vs_seq, K_tens_n_seq_covs and
+        # K_seq_n_seq_covs (lengths2=) evaluate X[n, :len_n] as that truncated sequence would be on its own, on the library's ragged wide route
+        # (gpsig_kernel_*_ragged: SignatureRBF and the Matern families, first order, forward only; lags with lag_axis = "sequence" only).  It
+        # changes nothing about a call without lengths.
+        self.exact_ragged = False
 
     # ---- validators (kernels.py:94-133) ------------------------------------------------------
     @staticmethod
@@ -481,8 +486,8 @@ class SignatureKernel:
           lengths2=None):
         """Reference: kernels.py:401-476.  (N1, N2) or (M+1, N1, N2).  lr_state: low-rank mode only, the random
         objects to use (default: drawn afresh, as the reference does).
-        lengths / lengths2 (low-rank mode): per-sequence lengths of a ragged X / X2 -- ints, a NumPy array or a torch tensor, 1 <= l <= L.
-        Sequence n is X[n, :lengths[n]]; what the rows beyond hold does not matter (NaN included)."""
+        lengths / lengths2 (low-rank mode; exact mode with ``exact_ragged``): per-sequence lengths of a ragged X / X2 -- ints, a NumPy array or a
+        torch tensor, 1 <= l <= L.  Sequence n is X[n, :lengths[n]]; what the rows beyond hold does not matter (NaN included)."""
         if presliced:
             presliced_X = presliced_X2 = True
         if not presliced_X:
@@ -498,6 +503,10 @@ class SignatureKernel:
         n2, l2 = self._seq_dims(X2) if X2 is not None else (n1, l1)
         p = self._params(L_.keep, L_.dtype_id)
         out, optr = L_.out((self.num_levels + 1, n1, n2) if return_levels else (n1, n2))
+        if lengths is not None or lengths2 is not None:          # exact_ragged (_ragged_lengths let them through): a side without lengths is dense
+            L_.ctx.call("gpsig_kernel_K_ragged", p, L_.inp(X), L_.inp(X2), n1, n2, l1, self._lens_ptr(L_, lengths), l2, self._lens_ptr(L_, lengths2),
+                        int(bool(return_levels)), optr)
+            return out
         L_.ctx.call("gpsig_kernel_K", p, L_.inp(X), L_.inp(X2), n1, n2, l1, l2, int(bool(return_levels)), optr)
         return out
 
@@ -521,6 +530,9 @@ class SignatureKernel:
         n, l = self._seq_dims(X)
         p = self._params(L_.keep, L_.dtype_id)
         out, optr = L_.out((self.num_levels + 1, n) if return_levels else (n,))
+        if lengths is not None and not self.low_rank:            # exact_ragged
+            L_.ctx.call("gpsig_kernel_Kdiag_ragged", p, L_.inp(X), n, l, self._lens_ptr(L_, lengths), int(bool(return_levels)), optr)
+            return out
         L_.ctx.call("gpsig_kernel_Kdiag", p, L_.inp(X), n, l, int(bool(return_levels)), optr)
         return out
 
@@ -564,6 +576,10 @@ class SignatureKernel:
         n, l = self._seq_dims(X)
         p = self._params(L_.keep, L_.dtype_id)
         out, optr = L_.out((self.num_levels + 1, t, n) if return_levels else (t, n))
+        if lengths is not None:                                  # exact_ragged
+            L_.ctx.call("gpsig_kernel_K_tens_vs_seq_ragged", p, L_.inp(Z), L_.inp(X), t, n, l, self._lens_ptr(L_, lengths), int(bool(increments)),
+                        int(bool(return_levels)), optr)
+            return out
         L_.ctx.call("gpsig_kernel_K_tens_vs_seq", p, L_.inp(Z), L_.inp(X), t, n, l, int(bool(increments)),
                     int(bool(return_levels)), optr)
         return out
@@ -606,6 +622,10 @@ class SignatureKernel:
         Kzz, pzz = L_.out(lv + (t, t))
         Kzx, pzx = L_.out(lv + (t, n))
         Kxx, pxx = L_.out(lv + ((n, n) if full_X_cov else (n,)))
+        if lengths is not None:                                  # exact_ragged
+            L_.ctx.call("gpsig_kernel_K_tens_n_seq_covs_ragged", p, L_.inp(Z), L_.inp(X), t, n, l, self._lens_ptr(L_, lengths), int(bool(increments)),
+                        int(bool(full_X_cov)), int(bool(return_levels)), pzz, pzx, pxx)
+            return Kzz, Kzx, Kxx
         L_.ctx.call("gpsig_kernel_K_tens_n_seq_covs", p, L_.inp(Z), L_.inp(X), t, n, l, int(bool(increments)),
                     int(bool(full_X_cov)), int(bool(return_levels)), pzz, pzx, pxx)
         return Kzz, Kzx, Kxx
@@ -620,6 +640,8 @@ class SignatureKernel:
         lengths2 = self._ragged_lengths(lengths2, X2)
         if self.low_rank:
             return self._K_seq_n_seq_covs_lr(X, X2, full_X2_cov, return_levels, lr_state, lengths2)
+        if lengths2 is not None:                                 # exact_ragged
+            return self._K_seq_n_seq_covs_ragged(X, X2, full_X2_cov, return_levels, lengths2)
         L_ = _Launch(X, X2)
         n1, l1 = self._seq_dims(X)
         n2, l2 = self._seq_dims(X2)
@@ -630,6 +652,26 @@ class SignatureKernel:
         Kx2x2, p22 = L_.out(lv + ((n2, n2) if full_X2_cov else (n2,)))
         L_.ctx.call("gpsig_kernel_K_seq_n_seq_covs", p, L_.inp(X), L_.inp(X2), n1, n2, l1, l2, int(bool(full_X2_cov)),
                     int(bool(return_levels)), p11, p12, p22)
+        return Kxx, Kxx2, Kx2x2
+
+    def _K_seq_n_seq_covs_ragged(self, X, X2, full_X2_cov, return_levels, lengths2):
+        """K_seq_n_seq_covs with a ragged X2 (exact_ragged), composed from the evaluations that take lengths: the inducing sequences X are dense,
+        so Kxx is the dense K(X); Kxx2 and Kx2x2 take the ragged entry points.  The reference's double division of Kxx2 by the X-side diagonal in
+        the diagonal-only branch (:713 + :750) is reproduced level by level, as the dense entry point does."""
+        Kxx = self.K(X, presliced=True, return_levels=return_levels)
+        lev = self.K(X, X2, presliced=True, return_levels=True, lengths2=lengths2)          # (M+1, N1, N2): sigma variances_m K_m / (norms)
+        if self.normalization and not full_X2_cov:
+            import copy
+            raw = copy.copy(self)                                # the raw level diagonals of X: unnormalised, unit weights
+            raw.normalization, raw.sigma, raw.variances = False, 1.0, np.ones(self.num_levels + 1)
+            dx = raw.Kdiag(X, presliced=True, return_levels=True)                           # (M+1, N1)
+            s = (torch.sqrt(torch.clamp(dx, min=0.0) + JITTER) if _is_torch(dx) else np.sqrt(np.maximum(dx, 0.0) + JITTER))
+            lev = lev / s[:, :, None]
+        Kxx2 = lev if return_levels else lev.sum(0)
+        if full_X2_cov:
+            Kx2x2 = self.K(X2, presliced=True, return_levels=return_levels, lengths=lengths2)
+        else:
+            Kx2x2 = self.Kdiag(X2, presliced=True, return_levels=return_levels, lengths=lengths2)
         return Kxx, Kxx2, Kx2x2
 
     # ---- low-rank mode (kernels.py:239-311 and the low_rank branches of K / Kdiag / K_tens / K_tens_vs_seq) -----
@@ -739,7 +781,7 @@ class SignatureKernel:
         a torch tensor on any device; integers, shape (N,), 1 <= l <= L (ValueError otherwise).  X: the sliced table."""
         if lengths is None:
             return None
-        if not self.low_rank:
+        if not self.low_rank and not getattr(self, "exact_ragged", False):
             raise NotImplementedError("lengths= is built for low-rank mode only: in exact mode pad each sequence by repeating its last "
                                       "observation, which is exact there with difference=True (zero increments add nothing)")
         if self.num_lags > 0 and self._lag_axis() == "table":
@@ -755,6 +797,15 @@ class SignatureKernel:
         if N and (int(host.min()) < 1 or int(host.max()) > L):
             raise ValueError("lengths must lie in [1, %d], got [%d, %d]" % (L, int(host.min()), int(host.max())))
         return np.ascontiguousarray(host, dtype=np.int32)
+
+    @staticmethod
+    def _lens_ptr(L_, lengths):
+        """Checked host int32 lengths (_ragged_lengths), or None -> what a ragged entry point reads in the call's pointer mode."""
+        if lengths is None:
+            return None
+        lens = torch.as_tensor(lengths, device=L_.dev) if L_.device_mode else lengths
+        L_.keep.append(lens)
+        return C.c_void_p(lens.data_ptr() if L_.device_mode else lens.ctypes.data)
 
     def _lag_axis(self):
         """``lag_axis``, checked: "table" (the default) or "sequence".  With "sequence" a ragged evaluation of a kernel with lags takes

@@ -309,6 +309,31 @@ int gpsig_kernel_K_seq_n_seq_covs(gpsig_ctx* ctx, const gpsig_params* p, const v
                                   int64_t N1, int64_t N2, int32_t L1, int32_t L2, int32_t full_X2_cov,
                                   int32_t return_levels, void* Kxx, void* Kxx2, void* Kx2x2);
 
+/* ---- ragged batches in exact mode (no reference analogue: the reference pads).  Each entry point takes its dense twin's arguments plus
+ * `lengths`, directly after each L: N int32 in the context's pointer mode, 1 <= lengths[n] <= L (GPSIG_ERR_INVALID otherwise, and for a NULL
+ * `lengths` where one is required).  Sequence n is X[n, :lengths[n]], evaluated as that truncated sequence would be on its own: rows at or
+ * beyond lengths[n] are never read (NaN there changes no bit), difference = 1 gives lengths[n] - 1 increments, normalisation uses the
+ * sequence's own diagonal, and with num_lags > 0 the lag interpolation runs on the sequence's OWN axis i / (lengths[n] - 1) -- the query of lag
+ * j at observation t is max(t / (lengths[n] - 1) - lag_j, 0); the lagged copies of a one-point sequence are the point itself.  Outputs,
+ * factors, sigma * variances, the level sum and the return_levels layouts are the dense entry points'; Kzz is the dense call's.
+ * Forward evaluation on the wide route (kernel arguments by a contraction over packed rows, then chain / lattice kernels), taken at any width.
+ * The plan needs the lengths on the host: in device-pointer mode one copy of N int32 and a stream synchronisation.
+ * Served: SignatureRBF and the Matern families, float64, num_levels <= 8, first order, sequence lattices of at most 512 columns (the longest
+ * sequence of the right-hand / diagonal side, minus one with differences).  GPSIG_ERR_UNSUPPORTED, with the bound in the message: the other
+ * base kernels, order > 1 with num_levels > 1, context option wide = 0, graph capture, p->dtype = GPSIG_F32, longer lattices.  The argument
+ * chunks follow option wide_chunk_mb, in whole sequences; a result does not depend on it bit for bit (Kdiag) or beyond rounding (the dgemms). */
+int gpsig_kernel_Kdiag_ragged(gpsig_ctx* ctx, const gpsig_params* p, const void* X, int64_t N, int32_t L, const int32_t* lengths,
+                              int32_t return_levels, void* out);
+int gpsig_kernel_K_tens_vs_seq_ragged(gpsig_ctx* ctx, const gpsig_params* p, const void* Z, const void* X,
+                                      int64_t T, int64_t N, int32_t L, const int32_t* lengths, int32_t increments, int32_t return_levels, void* out);
+int gpsig_kernel_K_tens_n_seq_covs_ragged(gpsig_ctx* ctx, const gpsig_params* p, const void* Z, const void* X,
+                                          int64_t T, int64_t N, int32_t L, const int32_t* lengths, int32_t increments, int32_t full_X_cov,
+                                          int32_t return_levels, void* Kzz, void* Kzx, void* Kxx);
+/* lengths / lengths2: either may be NULL -- that side is dense, every sequence has its L1 / L2 rows.  X2 == NULL: symmetric (lengths2 unused). */
+int gpsig_kernel_K_ragged(gpsig_ctx* ctx, const gpsig_params* p, const void* X, const void* X2,
+                          int64_t N1, int64_t N2, int32_t L1, const int32_t* lengths, int32_t L2, const int32_t* lengths2,
+                          int32_t return_levels, void* out);
+
 /* ---- low-rank mode (low_rank=True): gpsig/low_rank_calculations.py, gpsig/signature_algs.py:162-222,
  * gpsig/kernels.py:239-311, :424-426, :442-458, :499-501, :525-527, :560-574.
  * Float types: the state (landmarks, whitening, projections) is float64 always.  p->dtype = GPSIG_F32 (float32 points, features and
