@@ -121,6 +121,11 @@ int check_params(gpsig_ctx* c, const gpsig_params* p, bool low_rank, bool lr_wid
     if (p->order < 1 || p->order > p->num_levels) return fail(c, GPSIG_ERR_INVALID, "order=%d outside [1, num_levels]", p->order);
     if (!p->variances) return fail(c, GPSIG_ERR_INVALID, "variances is NULL");
     if (p->num_lags > 0 && (!p->lags || !p->gamma)) return fail(c, GPSIG_ERR_INVALID, "num_lags > 0 needs lags and gamma");
+    // beyond MAX_FEATURES columns an exact evaluation has the wide route or none, and that route does not record: the warm-up of a recording (option
+    // capture_routes) and the recording itself are told so here, before any kernel of another route is asked for a width it was not built for
+    if (!low_rank && !lr_wide && routes_as_captured(c) && p->num_features * (p->num_lags + 1) > MAX_FEATURES)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "graph recording: a state space of %d columns is served by the wide route only, which does not record (the kernels that record reach %d columns)",
+                    p->num_features * (p->num_lags + 1), int(MAX_FEATURES));
     return GPSIG_OK;
 }
 
@@ -1518,6 +1523,7 @@ int gpsig_set_option(gpsig_ctx* c, const char* name, int value) {
     else if (!strcmp(name, "wide_o1_sweeps")) c->wide_o1_sweeps = value;
     else if (!strcmp(name, "tvs_features")) c->tvs_features = value;
     else if (!strcmp(name, "tvs_tile_nw")) c->tvs_tile_nw = value;
+    else if (!strcmp(name, "capture_routes")) c->capture_routes = value != 0 ? 1 : 0;
     else if (!strcmp(name, "diag_own")) c->diag_own = value;
     else if (!strcmp(name, "spectral_wave")) c->spectral_wave = value;
     else if (!strcmp(name, "tens_tile")) c->tens_tile = value;

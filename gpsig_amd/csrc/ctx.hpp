@@ -158,7 +158,9 @@ struct gpsig_ctx {
     double t_flops = 0.0;                // multiply-adds x 2 those launches executed on the matrix cores
     // HIP-graph capture (gpsig_graph_begin .. gpsig_graph_end): launches only -- nothing may allocate, upload or synchronise
     bool capturing = false, capture_failed = false;
-    uint64_t alloc_gen = 0;         // bumped whenever a scratch buffer moves; a graph replays only against the generation it saw
+    int capture_routes = 0;         // option "capture_routes": eager calls choose the routes a library capture chooses (routes_as_captured), so that the
+                                    // warm-up before gpsig_graph_begin sizes the buffers, task lists and weights of the route the recording takes
+    uint64_t alloc_gen = 0;        // bumped whenever a scratch buffer moves; a graph replays only against the generation it saw
     // effective shader clock (gpsig_clock_probe_*): one sleeping wavefront on a stream of its own samples s_memtime / s_memrealtime
     hipStream_t probe_stream = nullptr;
     unsigned long long* probe_buf = nullptr;   // device, 2 * probe_cap counters
@@ -209,6 +211,12 @@ inline int fail(gpsig_ctx* c, int code, const char* fmt, ...) {
         int rc__ = (expr);           \
         if (rc__ != GPSIG_OK) return rc__; \
     } while (0)
+
+// Does a ROUTE predicate answer as inside a library graph capture?  Inside one, and in eager calls on a context with the option "capture_routes" set (the
+// warm-up of a recording).  The routes that do not record -- the wide route (rocBLAS may allocate), Kzx as a product of level features and the feature
+// contraction's reverse pass -- ask this, every one of them, so that a warm-up under the option and the recording after it take the same path.
+// (sig_gram_headroom, pinned staging and the timing events read `capturing` for what they may not DO inside a capture: they stay on the flag itself.)
+inline bool routes_as_captured(const gpsig_ctx* c) { return c->capturing || c->capture_routes != 0; }
 
 // what a call needs the host for; inside a graph capture that is an error (the call was not run with these shapes and
 // hyper-parameters before the capture began)

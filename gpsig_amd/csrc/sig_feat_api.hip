@@ -321,7 +321,7 @@ int sig_features_K(gpsig_ctx* c, const gpsig_params* p, bool raw, const void* X,
 
 // f64: the call's element type (Kzx of a float32 call stays on the pair kernels)
 bool tvs_features_plan(gpsig_ctx* c, const gpsig_params* p, bool f64, int64_t Tn, int64_t N, int L) {
-    if (!f64 || c->tvs_features == 0 || c->capturing) return false;         // (inside a capture the route is refused outright, as on the reverse side)
+    if (!f64 || c->tvs_features == 0 || routes_as_captured(c)) return false;         // (inside a capture the route is refused outright, as on the reverse side)
     const int M = p->num_levels;
     if (p->order < 1 || p->order > M || Tn <= 0 || N <= 0 || Tn > 0x3fffffff || N > 0x3fffffff) return false;       // (the order: refused, as sig_features_K does)
     SigShape s;

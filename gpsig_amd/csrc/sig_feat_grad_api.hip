@@ -191,7 +191,7 @@ static __global__ void sig_weight_grad_kernel(const double* __restrict__ cdot, i
 int sig_features_grad(gpsig_ctx* c, const gpsig_params* p, int d, const double* X, const double* Y, int64_t N1, int64_t N2, int L1, int L2, bool diag,
                       bool sym, const double* G, double* gX, double* gY, bool* done) {
     *done = false;
-    if (c->sig_features_grad == 0 || c->capturing) return GPSIG_OK;         // (inside a capture the route is refused outright, as tvs_features_plan does and sig_features_K does not)
+    if (c->sig_features_grad == 0 || routes_as_captured(c)) return GPSIG_OK;         // (inside a capture the route is refused outright, as tvs_features_plan does and sig_features_K does not)
     if (N1 <= 0 || N2 <= 0 || N1 > 0x3fffffff || N2 > 0x3fffffff) return GPSIG_OK;
     SigRevShape r;
     if (!sig_reverse_shape(p, d, L1, L2, &r)) return GPSIG_OK;
@@ -268,7 +268,7 @@ int sig_features_sum_grad(gpsig_ctx* c, const gpsig_params* p, int d, const doub
                           const double* g, double* gX, double* gY, double* gw, bool probe, bool* done) {
     *done = false;
     const bool sym = Y == nullptr;
-    if (c->sig_features_grad == 0 || c->capturing) return GPSIG_OK;         // (as sig_features_grad)
+    if (c->sig_features_grad == 0 || routes_as_captured(c)) return GPSIG_OK;         // (as sig_features_grad)
     if (N1 <= 0 || N2 <= 0 || N1 > 0x3fffffff || N2 > 0x3fffffff) return GPSIG_OK;
     SigRevShape r;
     if (!sig_reverse_shape(p, d, L1, L2, &r)) return GPSIG_OK;

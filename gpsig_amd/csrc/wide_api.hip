@@ -158,7 +158,7 @@ int spx_arguments(gpsig_ctx* c, const SpxSetup& s, const double* A, const double
     return GPSIG_OK;
 }
 bool spx_context_ok(const gpsig_ctx* c, const gpsig_params* p) {
-    return c->wide != 0 && !c->capturing && p->num_levels >= 1 && p->num_levels <= WIDE_MAX_LEVELS;
+    return c->wide != 0 && !routes_as_captured(c) && p->num_levels >= 1 && p->num_levels <= WIDE_MAX_LEVELS;
 }
 
 int aug_rows(gpsig_ctx* c, const double* src, int64_t rows, int d, int right, int mode, int diff, double* dst) {
@@ -267,7 +267,7 @@ int gbase_reduce(gpsig_ctx* c, double* part, int64_t n, double* g_base) {
 
 // Is the route built for this call?  (float64 is the caller's business.)
 bool wide_tvs_available(const gpsig_ctx* c, const gpsig_params* p, int d, int64_t Tn, int64_t N, int L) {
-    if (c->wide == 0 || c->capturing) return false;
+    if (c->wide == 0 || routes_as_captured(c)) return false;
     if (!wide_kind(p) || (p->order > WIDE_MAX_ORDER && p->num_levels > WIDE_MAX_ORDER) || p->num_levels > WIDE_MAX_LEVELS || p->num_levels < 1) return false;
     if (Tn < 1 || N < 1 || L < 1 || d < 1) return false;
     if (rows_are_increments(p) && L < 2) return false;        // (no increment rows)
@@ -297,7 +297,9 @@ bool wide_lat_fwd_available(const gpsig_ctx* c, const gpsig_params* p, int L1, i
 int wide_spectral_refusal(gpsig_ctx* c, const gpsig_params* p, bool lattice, int L2) {
     const char* const who = "exact-mode SignatureSpectral beyond 32 columns (spectral_wide)";
     if (c->wide == 0) return fail(c, GPSIG_ERR_UNSUPPORTED, "%s runs on the wide route only: context option wide = 0 refuses it", who);
-    if (c->capturing) return fail(c, GPSIG_ERR_UNSUPPORTED, "%s is not served during library graph capture", who);
+    if (routes_as_captured(c))
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "graph recording: %s is served by the wide route only, which does not record (the exact-shape kernels that record reach %d columns)", who,
+                    int(SPECTRAL_STRIDE));
     if (p->num_levels > WIDE_MAX_LEVELS) return fail(c, GPSIG_ERR_UNSUPPORTED, "%s is built for num_levels <= %d (got %d)", who, WIDE_MAX_LEVELS, p->num_levels);
     if (lattice && p->order > 1 && p->num_levels > 1)
         return fail(c, GPSIG_ERR_UNSUPPORTED, "%s serves first-order sequence lattices only (order = %d; Kzx: orders <= %d)", who, p->order, WIDE_MAX_ORDER);
@@ -493,7 +495,7 @@ int wide_tvs_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
 constexpr int WIDE_LAT_MAX_COLS = 512;            // 64 lanes x 8 columns
 
 bool wide_lat_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L2) {
-    if (c->wide == 0 || c->capturing) return false;
+    if (c->wide == 0 || routes_as_captured(c)) return false;
     if (!wide_kind(p) || p->num_levels > WIDE_MAX_LEVELS || p->num_levels < 1) return false;
     const int dr = p->difference ? 1 : 0;
     if (p->order > 1 && p->num_levels > 1) {      // higher orders: the forward and the reverse sweeps of grad_wave_ho_kernel.hpp (<= 5 levels, orders <= 4)
@@ -508,7 +510,7 @@ bool wide_lat_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L
 // the reverse pass of the HIGHER-ORDER recursion on this route: argument lattices by dgemm -> dM lattices (wide_lattice_dm_kernel) -> both sweeps of a
 // pair in one wavefront (grad_wave_ho_kernel.hpp) -> the adjoint contracted back by dgemms; any number of columns
 bool wide_lat_ho_available(const gpsig_ctx* c, const gpsig_params* p, int L1, int L2) {
-    if (c->wide == 0 || c->capturing || !wide_kind(p) || wide_dot_kind(p->base_kernel) || wide_base_param_kind(p->base_kernel) || !(p->order > 1 && p->num_levels > 1)) return false;
+    if (c->wide == 0 || routes_as_captured(c) || !wide_kind(p) || wide_dot_kind(p->base_kernel) || wide_base_param_kind(p->base_kernel) || !(p->order > 1 && p->num_levels > 1)) return false;
     const int dr = p->difference ? 1 : 0;
     HoSweeps hs;
     return L1 >= 1 && L2 >= 1 && ho_sweeps_plan(c, p, L1 - dr, L2 - dr, &hs);
@@ -803,7 +805,7 @@ int wide_lat_backward(gpsig_ctx* c, const gpsig_params* p, int d, const double* 
 
 // ---- inducing tensors vs inducing tensors ----------------------------------------------------------------------------------------------------
 bool wide_tens_available(const gpsig_ctx* c, const gpsig_params* p, int64_t Tn) {
-    if (c->wide == 0 || c->capturing) return false;
+    if (c->wide == 0 || routes_as_captured(c)) return false;
     if (!wide_kind(p) || p->num_levels > WIDE_MAX_LEVELS || p->num_levels < 1) return false;
     const int64_t Tpad = (Tn + 63) / 64 * 64;
     // the argument blocks of every component at once (10 components x 1,024^2 x 8 bytes = 84 MB at 500 tensors with increments)

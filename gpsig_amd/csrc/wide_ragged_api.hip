@@ -47,7 +47,8 @@ int rg_check(gpsig_ctx* c, const gpsig_params* p) {
     if (p->num_levels > WIDE_MAX_LEVELS) return fail(c, GPSIG_ERR_UNSUPPORTED, "%s is built for num_levels <= %d (got %d)", WHO, WIDE_MAX_LEVELS, p->num_levels);
     if (p->order > 1 && p->num_levels > 1) return fail(c, GPSIG_ERR_UNSUPPORTED, "%s serves first order only (order = %d)", WHO, p->order);
     if (c->wide == 0) return fail(c, GPSIG_ERR_UNSUPPORTED, "%s runs on the wide route only: context option wide = 0 refuses it", WHO);
-    if (c->capturing) return fail(c, GPSIG_ERR_UNSUPPORTED, "%s is not served during library graph capture: the plan needs the lengths on the host", WHO);
+    if (routes_as_captured(c))          // (under option capture_routes too: the warm-up of a recording is told, not the recording)
+        return fail(c, GPSIG_ERR_UNSUPPORTED, "graph recording: %s is not served during library graph capture: the plan needs the lengths on the host", WHO);
     return GPSIG_OK;
 }
 

@@ -184,6 +184,10 @@ def _f32_upcast(method):
         if getattr(self, "_graph_recording", False):
             # graphed(): the float64 copies, the float64 result and its rounding would be torch temporaries recorded inside the capture and
             # recycled after it -- a replay would write into whatever lives there then
+            if ho:
+                raise ValueError("graphed(): this float32 Gram of SignatureRBF at order 2..4 is computed in float64 and rounded, because the float64 evaluation "
+                                 "kernel has exact instances at these orders and the float32 one only run-time ones (the float32 kernels are built for the "
+                                 "shape; the float64 ones are preferred); record it with float64 tensors")
             raise ValueError("graphed(): this float32 evaluation is computed in float64 and rounded (one-column state space, SignatureCosine or "
                              "a shape the float32 kernels are not built for); record it with float64 tensors")
         up = lambda a: (a.double() if _is_torch(a) else np.asarray(a, dtype=np.float64)) if _is_f32(a) else a   # noqa: E731
@@ -446,7 +450,19 @@ class SignatureKernel:
             X.copy_(X_next); K = g.replay()     # same shapes, new contents; K is g.out, overwritten by every replay
 
         For the methods that are library calls end to end (K, Kdiag, K_tens, K_tens_vs_seq, exact mode); hyper-parameters are
-        baked in -- record again after changing them."""
+        baked in -- record again after changing them.
+
+        The contract (include/gpsig_hip.h, graph section).  Some routes do not record -- the wide route (rocBLAS may allocate), Kzx as a product of
+        level features -- and are the eager default at many shapes (Kzx beyond 8 columns, Kzz beyond 12, sequence Grams beyond 16 / 32).  The
+        warm-up runs on the side stream's context under option ``capture_routes``, so that it takes the route the recording takes, and the option
+        is set back before graphed() returns or raises.  For any call the library serves eagerly, graphed() does exactly one of two things:
+
+        * it records: every replay on new contents of the same tensors is bit-equal to an eager call on a context with ``capture_routes`` set
+          (the route the recording took), and agrees with the default eager call -- possibly another route -- to the routes' own tolerance;
+        * it refuses at the warm-up with NotImplementedError("graph recording: ... is served by the wide route only, which does not record
+          (... reach N columns)"): more than 64 columns, exact SignatureSpectral beyond 32, ragged batches.  Never "a scratch buffer has to
+          grow".  The kernel object and its contexts are usable afterwards: no capture open, ``_graph_recording`` false, the side stream's
+          context given back."""
         if torch is None or not tensors or not all(t is None or (_is_torch(t) and t.is_cuda and t.is_contiguous()) for t in tensors):
             raise ValueError("graphed() takes contiguous CUDA tensors")
         if self.low_rank:
@@ -464,20 +480,22 @@ class SignatureKernel:
         dev = next(t for t in tensors if t is not None).device
         side = torch.cuda.Stream(dev)            # the default stream cannot be captured
         side.wait_stream(torch.cuda.current_stream(dev))
+        ctx = _lib.context(dev.index or 0, side.cuda_stream)
+        _lib.hold(dev.index or 0, side.cuda_stream)      # from the warm-up on: a refusal there gives the context back too
         self._graph_recording = True             # _f32_upcast refuses instead of converting (its temporaries must not be recorded)
+        recorded = False
         try:
+            ctx.set_option("capture_routes", 1)  # the warm-up takes the routes the capture takes (ctx.hpp: routes_as_captured)
             with torch.cuda.stream(side):
                 fn(*tensors, **kwargs)           # scratch buffers, task lists and level weights in place
-                ctx = _lib.context(dev.index or 0, side.cuda_stream)
-                _lib.hold(dev.index or 0, side.cuda_stream)
-                try:
-                    with ctx.graph() as g:
-                        out = fn(*tensors, **kwargs)
-                except Exception:
-                    _lib.release(dev.index or 0, side.cuda_stream)
-                    raise
+                with ctx.graph() as g:
+                    out = fn(*tensors, **kwargs)
+            recorded = True
         finally:
             self._graph_recording = False
+            ctx.set_option("capture_routes", 0)  # (torch hands side streams out from a pool: the context may serve other recordings)
+            if not recorded:
+                _lib.release(dev.index or 0, side.cuda_stream)
         torch.cuda.current_stream(dev).wait_stream(side)
         return GraphedCall(g, tensors, out, side)
 

@@ -71,7 +71,7 @@ enum gpsig_base_kernel {
                                  result does not depend on wide_chunk_mb bit for bit.  GPSIG_ERR_UNSUPPORTED with a message naming the
                                  bound: "... serves first-order sequence lattices only", "... sequence lattices of at most 512 columns",
                                  "... serves Kzx at orders <= 4", "... is built for num_levels <= 8", "... context option wide = 0
-                                 refuses it", "... is not served during library graph capture", "the spectral base kernel is built
+                                 refuses it", "graph recording: ... is served by the wide route only, which does not record", "the spectral base kernel is built
                                  for float64 only", "num_features=... outside [1, 4096]".  No gradient entry point takes the family;
                                  up to 32 features the slot changes no bit. */
 };
@@ -184,7 +184,12 @@ int gpsig_set_shard(gpsig_ctx* ctx, int index, int count);
  *                 the reference's own run settings, benchmarks/run_gpsig_benchmarks.py:32; 0 never; 1 wherever built (float64,
  *                 RBF and the Matern families, at most 8 levels, lattices of at most 512 columns; order 1, and at order > 1 the
  *                 tensor-vs-sequence chains (orders <= 4) and the sequence lattices' reverse pass (<= 5 levels)).  Not taken inside
- *                 a graph capture.
+ *                 a graph capture, nor under "capture_routes".
+ *   "capture_routes"  0 (default); 1: eager calls choose the routes a library graph capture chooses -- every route that does not record (the wide route,
+ *                 "tvs_features", "sig_features_grad") answers "not built", as it does between gpsig_graph_begin and gpsig_graph_end.  Set it around the
+ *                 warm-up call of a recording and set it back afterwards (see the graph section below).  A call that has no route but the wide one -- more
+ *                 than 64 columns, exact-mode SignatureSpectral beyond 32 -- then returns GPSIG_ERR_UNSUPPORTED with "graph recording: ... is served by the
+ *                 wide route only, which does not record"; so does a ragged (lengths) call, whose plan needs the host
  *   "wide_chunk_mb"  its argument chunk in HBM (0: "grad_scratch_mb", 4 GB by default: a latency-bound launch split in two takes twice as long)
  *   "wide_contract"  the two contractions of a reverse pass with the adjoint array (rows of at most 32 augmented columns) as one hand-written MFMA pass:
  *                 1 (default) part tiles of 16 rows in LDS with the second operands in registers (rows of at most 16 columns; wider: the first form),
@@ -235,7 +240,22 @@ int gpsig_clock_probe_xcds(gpsig_ctx* ctx, double* ghz, int32_t* xcc, int32_t ca
  * every recorded call was made once before with the same shapes and
  * hyper-parameters on this ctx (so that scratch buffers, task lists and level weights are in place -- a call that would
  * allocate, upload or wait fails with GPSIG_ERR_INVALID and the capture ends); a graph is replayable until a later call
- * moves a scratch buffer (gpsig_graph_launch then returns GPSIG_ERR_INVALID: capture again). */
+ * moves a scratch buffer (gpsig_graph_launch then returns GPSIG_ERR_INVALID: capture again).
+ *
+ * The warm-up must take the route the recording takes.  Several routes do not record (the wide route: rocBLAS may allocate; Kzx as a product of
+ * level features; the feature contraction's reverse pass) and are the eager default at many shapes: beyond 8 columns for Kzx, 12 for Kzz, 16 / 32 for
+ * the sequence Grams.  A plain warm-up there sizes only that route's buffers.  So make the warm-up call under option "capture_routes":
+ *
+ *     gpsig_set_option(ctx, "capture_routes", 1);   the call, once;   gpsig_set_option(ctx, "capture_routes", 0);
+ *     gpsig_graph_begin(ctx);   the same call;   gpsig_graph_end(ctx, &g);
+ *
+ * The contract, for any call the library serves eagerly, after that warm-up on the same ctx -- a recording of the same call does exactly one of two things:
+ *   it SUCCEEDS: every replay on new contents of the same buffers is bit-equal to an eager call under "capture_routes" = 1 (the route the recording took),
+ *     and agrees with a float64 reference to the tolerance that route is held to; or
+ *   it is REFUSED at the warm-up (GPSIG_ERR_UNSUPPORTED): the message opens with "graph recording:" and names what the caller can act on -- the bound
+ *     (64 columns; 32 for exact-mode SignatureSpectral), "served by the wide route only, which does not record".  It never reads "a scratch buffer has to
+ *     grow -- run the same calls once".  The context is usable afterwards: no capture is open, and an eager call (option back at 0) works.
+ * The same holds for the reverse-side entry points (the *_grad functions): their route predicates ask the same question. */
 typedef struct gpsig_graph gpsig_graph;
 int gpsig_graph_begin(gpsig_ctx* ctx);
 int gpsig_graph_end(gpsig_ctx* ctx, gpsig_graph** out);

@@ -58,6 +58,9 @@ OPTIONS = {
     "wide_o1_sweeps": {"default": 1, "values": [0, 1, 2], "tests": [_W + "test_wide_sequence_lattices_and_gradient", _F + "test_threshold_wide_o1_sweeps_at_1024_lattices"]},
     "tvs_features": {"default": -1, "values": [-1, 0, 1], "tests": [_P + "test_tensor_vs_sequence_through_level_features"]},
     "tvs_tile_nw": {"default": 0, "values": [0, 1, 2, 4], "tests": [_P + "test_tile_kernel_for_many_tensors"]},
+    "capture_routes": {"default": 0, "values": [0, 1], "tests": ["test_gpu_graph_routes.py::test_option_skips_only_the_wide_route_at_nine_columns",
+                                                                 "test_gpu_graph_routes.py::test_fresh_context_warm_up_sizes_the_recorded_route",
+                                                                 "test_gpu_graph_routes.py::test_option_is_restored_when_graphed_raises"]},
     "diag_own": {"default": 1, "values": [0, 1], "tests": [_P + "test_diagonal_pass_with_one_sequence_per_pair_group"]},
     "spectral_wave": {"default": 1, "values": [0, 1], "tests": [_P + "test_spectral_wavefront_kernels"]},
     "tens_tile": {"default": 1, "values": [0, 1], "tests": [_P + "test_tensor_gram_tiles"]},

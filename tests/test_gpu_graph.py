@@ -127,7 +127,8 @@ def test_replay_of_the_feature_contraction(env):
 def test_float32_requests_computed_in_float64_are_refused_by_capture(env):
     """Round 6: float32 evaluations of SignatureCosine and of one-column state spaces are computed in float64 and rounded
     (kernels._f32_upcast); their conversions would be torch temporaries recorded inside the capture.  graphed() refuses them; float32
-    requests the float32 kernels take as they are, and the float64 form of the refused ones, record and replay."""
+    requests the float32 kernels take as they are, and the float64 form of the refused ones, record and replay.  So is a float32 Gram of
+    SignatureRBF at order 2..4, for another reason, which its refusal names: the float64 exact instances are preferred to the float32 run-time ones."""
     torch, K, dev = env
     rng = np.random.default_rng(8)
     N, L, M = 12, 16, 3
@@ -142,8 +143,23 @@ def test_float32_requests_computed_in_float64_are_refused_by_capture(env):
         g = kern.graphed("K", X64)
         assert torch.equal(g.replay(), kern.K(X64))
         assert float((g.out.float() - eager).abs().max()) < 1e-5
+    # SignatureRBF at order 2: the float32 kernels ARE built for the shape; the float64 exact instances are preferred (round 6), and the refusal says so
+    kern = K.SignatureRBF(L * 3, 3, M, order=2)
+    X32 = torch.tensor(rng.standard_normal((N, L * 3)) * 0.5, device=dev, dtype=torch.float32)
+    with pytest.raises(ValueError, match="computed in float64") as ei:
+        kern.graphed("K", X32)
+    assert "float64 evaluation kernel has exact instances" in str(ei.value) and "order 2..4" in str(ei.value)
+    assert "float32 kernels are not built for" not in str(ei.value)
+    assert not kern._graph_recording
+    eager = kern.K(X32)
+    assert eager.dtype == torch.float32
+    X64 = X32.double()
+    g = kern.graphed("K", X64)
+    X64.copy_(torch.tensor(rng.standard_normal((N, L * 3)) * 0.5, device=dev))
+    got = g.replay().clone()
+    assert torch.equal(got, kern.K(X64)) and not torch.equal(got, torch.zeros_like(got))
     kern = K.SignatureRBF(L * 3, 3, M)
     X32 = torch.tensor(rng.standard_normal((N, L * 3)) * 0.5, device=dev, dtype=torch.float32)
-    g = kern.graphed("K", X32)                                        # float32 kernels proper: recorded as they are
+    g = kern.graphed("K", X32)                                       # float32 kernels proper: recorded as they are
     X32.copy_(torch.tensor(rng.standard_normal((N, L * 3)) * 0.5, device=dev, dtype=torch.float32))
     assert torch.equal(g.replay().clone(), kern.K(X32))
