@@ -48,6 +48,7 @@ enum BufId {
     B_WD0, B_WD1, B_WD2, B_WD3, B_WD4, B_WD5, B_WD6, B_WD7, B_WD8, B_WD9, B_WD10, B_WD11, B_WD12, B_WD13, B_WD14, B_WD15,   // wide state spaces (wide_api.hip): augmented rows, kernel-argument chunks, their adjoints, lattice states
     B_WS0, B_WS1, B_WS2, B_WS3,                                // ... SignatureSpectral in exact mode (wide_spectral_kernel.hpp): gamma^2, the norms and phases of the two sides' rows; level diagonals on their way to another layout
     B_RG0, B_RG1, B_RG2, B_RG3, B_RG4,                         // ... ragged batches in exact mode (wide_ragged_api.hip): the two sides' lengths and offsets, their packed scaled rows; level diagonals
+    B_SFC,                                                     // feature contraction folding its pieces in-kernel (sig_gram_fold): one arrival counter per tile
     B_COUNT
 };
 

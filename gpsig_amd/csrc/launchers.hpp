@@ -135,7 +135,7 @@ SigFeatGradLaunchFn sig_feat_grad_pick_c(int d, int M);
 SigFeatGradLaunchFn sig_feat_grad_pick_d(int d, int M);
 SigFeatGradLaunchFn sig_feat_grad_pick_e(int d, int M);
 SigFeatGradLaunchFn sig_feat_grad_pick_f(int d, int M);
-hipError_t sig_gram_launch(const SigGramArgs& G, int ntiles, hipStream_t stream, int dma, int* used_dma);
+hipError_t sig_gram_launch(const SigGramArgs& G, int ntiles, hipStream_t stream, int dma, int* used_dma, int* folded);
 hipError_t sig_reduce_launch(const SigReduceArgs& R, hipStream_t stream);
 hipError_t sig_convert_launch(const void* in, void* out, int64_t n, bool widen, hipStream_t stream);
 // sig_feat_api.hip: the forward side of the feature route, and what it shares with the reverse side (sig_feat_grad_api.hip).

@@ -5,7 +5,7 @@
 // The reverse side and the feature op are sig_feat_grad_api.hip.  Entry points (declared in launchers.hpp, called from api.hip on device pointers):
 //     sig_features_K               seq_K_device's first question (K, K_seq_n_seq_covs, gpsig_seq_gram_levels, the row blocks of
 //                                  gpsig_kernel_K_symm_rows*): features of both sides (sig_features_kernel), the contraction in depth pieces
-//                                  (sig_gram_launch), the pieces added in a fixed order (sig_reduce_launch).  float32 calls are widened, computed in
+//                                  (sig_gram_launch), the pieces added in a fixed order (inside it: sig_gram_fold, or sig_reduce_launch).  float32 calls are widened, computed in
 //                                  float64 and rounded.  *done = false leaves the call to the lattice kernels.
 //     tvs_features_plan            whether Kzx of this shape is one product of the tensors' and the sequences' level features (a pure predicate:
 //                                  the entry points ask it too, to skip the diagonal factors that the features carry themselves)
@@ -17,6 +17,7 @@
 // whatever the model says.  Differences between the sites that are meant are marked where they are.
 // Scratch:  B_SF0  Phi(X) (N1, ld)                 B_SF1  Phi(X2) (N2, ld) / the tensors' features Zf (Tn, ld)
 //           B_SF2  partial sums (pieces, NA, NB)    B_SF3, B_SF4  float32 calls: X, X2 widened      B_SF5  float32 calls: the float64 result
+//           B_SFC  the tiles' arrival counters (sig_gram_fold)
 //           B_TW2  Kzx: the squared level weights
 // "sig_features_keep" remembers what B_SF0 holds (sf_valid, sf_X, sf_phi, sf_key).  Whoever else writes B_SF0 clears sf_valid:
 // tens_vs_seq_features_device below, sig_features_grad and sig_features_sum_grad (sig_feat_grad_api.hip); the option's setter does too.
@@ -233,12 +234,36 @@ int sig_gram_levels(gpsig_ctx* c, const gpsig_params* p, const SigShape& s, cons
         // (the per-level products of return_levels: equal pieces of their own, shorter depth)
         const int ns = sig_piece_bounds(nslab, g.nsplit, return_levels ? 1 : g.graded, G.bound);
         G.nsplit = ns; G.symmetric = g.symtiles ? 1 : 0; G.ntj = g.ntj; G.part = static_cast<double*>(part);
+        SigReduceArgs R;
+        memset(&R, 0, sizeof(R));
+        R.part = static_cast<const double*>(part); R.nsplit = ns; R.NA = NA; R.NB = NB;
+        R.out = static_cast<double*>(out) + (return_levels ? int64_t(lv) * N1 * Ncols : 0);
+        R.so_i = Ncols; R.so_j = 1;
+        R.mode = rows ? 2 : (g.symtiles ? 1 : 0);
+        R.diag_set = (g.sym && normalize) ? 1 : 0; R.diag_value = dval;
+        R.N = N1; R.r0 = row_begin; R.c0 = G.b_off; R.compact = compact;
+        // The one-call symmetric product adds its pieces inside the LDS-DMA kernel (sig_gram_fold): the workgroup that finishes a tile's
+        // last piece does what the reduce kernel would, under the multiplies of the others.  Row blocks, general products, the per-level
+        // products and the staging kernel keep the reduce kernels.  The tiles' arrival counters are zero when a launch begins: an eager
+        // call zeroes them on the stream, in whole 16 bytes from the start of their block (a fresh block, or counters that an
+        // abandoned launch left behind), and every tile's last arriver sets its counter back to zero.  A capture records NO memset: with
+        // a memset node ahead of the contraction a replayed graph left the result untouched at 10 tiles x 5 pieces (nobody drew a last
+        // ticket; tests/test_gpu_graph.py, test_replay_of_the_feature_contraction), without it the replays are the eager call's bits.
+        // The block cannot be new inside a capture (a buffer that has to grow refuses it), so the warm-up call has left it zero.
+        if (R.mode == 1 && !return_levels && c->sig_gemm_dma) {
+            void* cnt = nullptr;
+            const size_t cnt_bytes = (sizeof(int) * size_t(g.ntiles) + 15) / 16 * 16;
+            CHK(ensure(c, B_SFC, cnt_bytes, &cnt));
+            if (ns > 1 && !c->capturing) HIPCHK(c, hipMemsetAsync(cnt, 0, cnt_bytes, c->stream));
+            G.fold = 1; G.cnt = static_cast<int*>(cnt);
+            G.out = R.out; G.so_i = R.so_i; G.so_j = R.so_j; G.diag_set = R.diag_set; G.diag_value = R.diag_value;
+        }
         hipEvent_t e0 = nullptr, e1 = nullptr;
         bool on = false;
         if (timed) CHK(timing_begin(c, &e0, &e1, &on));
         // the LDS-DMA form reads whole slabs: only where the columns behind k_end are the zero padding of the feature rows
-        int used_dma = 0;
-        HIPCHK(c, sig_gram_launch(G, g.ntiles, c->stream, (c->sig_gemm_dma && !return_levels) ? 1 : 0, &used_dma));
+        int used_dma = 0, folded = 0;
+        HIPCHK(c, sig_gram_launch(G, g.ntiles, c->stream, (c->sig_gemm_dma && !return_levels) ? 1 : 0, &used_dma, &folded));
         if (on) {
             HIPCHK(c, hipEventRecord(e1, c->stream));
             c->t_launches += 1;
@@ -248,15 +273,7 @@ int sig_gram_levels(gpsig_ctx* c, const gpsig_params* p, const SigShape& s, cons
             const double tiles_done = double(g.ntiles) - ((used_dma && g.symtiles) ? double(g.nti) * 28.0 / 64.0 : 0.0);
             c->t_flops += 2.0 * tiles_done * SG_BM * SG_BN * double(nslab) * SG_BK;
         }
-        SigReduceArgs R;
-        memset(&R, 0, sizeof(R));
-        R.part = static_cast<const double*>(part); R.nsplit = ns; R.NA = NA; R.NB = NB;
-        R.out = static_cast<double*>(out) + (return_levels ? int64_t(lv) * N1 * Ncols : 0);
-        R.so_i = Ncols; R.so_j = 1;
-        R.mode = rows ? 2 : (g.symtiles ? 1 : 0);
-        R.diag_set = (g.sym && normalize) ? 1 : 0; R.diag_value = dval;
-        R.N = N1; R.r0 = row_begin; R.c0 = G.b_off; R.compact = compact;
-        HIPCHK(c, sig_reduce_launch(R, c->stream));
+        if (!folded) HIPCHK(c, sig_reduce_launch(R, c->stream));
     }
     return GPSIG_OK;
 }

@@ -10,16 +10,23 @@ SigFeatLaunchFn sig_feat_lookup(int d, int M) {
          : d <= 24 ? sig_feat_pick_e(d, M) : sig_feat_pick_f(d, M);
 }
 
-hipError_t sig_gram_launch(const SigGramArgs& G, int ntiles, hipStream_t stream, int dma, int* used_dma) {
+// *folded: the launch added the pieces itself (G.fold asked for it and the LDS-DMA form ran): no reduce launch follows.  The staging
+// kernel never folds.
+hipError_t sig_gram_launch(const SigGramArgs& G_in, int ntiles, hipStream_t stream, int dma, int* used_dma, int* folded) {
     if (used_dma) *used_dma = 0;
+    if (folded) *folded = 0;
+    SigGramArgs G = G_in;
     const bool aligned = (G.lda % 2) == 0 && (G.ldb % 2) == 0 && (reinterpret_cast<uintptr_t>(G.A) % 16) == 0 &&
                          (reinterpret_cast<uintptr_t>(G.B) % 16) == 0;
     const int ke_pad = (G.k_end + SG_BK - 1) / SG_BK * SG_BK;
     if (dma && aligned && G.k_begin % SG_BK == 0 && ke_pad <= G.lda && ke_pad <= G.ldb) {     // whole slabs, zeros behind k_end
+        G.groups = G.fold ? SG_FOLD_GROUPS : 1;
         hipLaunchKernelGGL(sig_gram_dma_kernel, dim3(unsigned(ntiles) * unsigned(G.nsplit)), dim3(256), 0, stream, G);
         if (used_dma) *used_dma = 1;
+        if (folded) *folded = G.fold ? 1 : 0;
         return hipGetLastError();
     }
+    G.fold = 0; G.groups = 1;
     const bool vec = (G.k_begin % 2) == 0 && (G.lda % 2) == 0 && (G.ldb % 2) == 0 && (reinterpret_cast<uintptr_t>(G.A) % 16) == 0 &&
                      (reinterpret_cast<uintptr_t>(G.B) % 16) == 0;
     if (vec) hipLaunchKernelGGL(sig_gram_kernel<true>, dim3(unsigned(ntiles) * unsigned(G.nsplit)), dim3(256), 0, stream, G);

@@ -488,25 +488,53 @@ struct SigGramArgs {
     int ntj;                              // tile columns
     double* part;                         // (nsplit, NA, NB) partial sums
     int64_t band;                         // > 0 (row blocks of a symmetric Gram): row i owns columns i .. i + band only -- tiles outside are skipped
+    // The one-call symmetric product in the LDS-DMA form adds a tile's pieces itself (sig_gram_fold below) instead of leaving them to
+    // sig_gram_reduce_sym_kernel: the workgroup that finishes the last piece of a tile does it.  fold == 0: none of these is read.
+    int fold;
+    int groups;                           // the tile sequence is issued in this many consecutive groups (sig_tile_of; < 2: one)
+    int* cnt;                             // one arrival counter per tile, zero at the launch and set back to zero by the tile's last arriver (nsplit > 1)
+    double* out; int64_t so_i, so_j;      // out[i * so_i + j * so_j] and its mirror image, as SigReduceArgs mode 1
+    int diag_set; double diag_value;
 };
 
-// Which depth piece and which tile this workgroup computes.
-__device__ inline void sig_tile_of(const SigGramArgs& G, int& split_out, int& bi, int& bj) {
+// The tile sequence of a folding launch is cut into this many groups (SigGramArgs::groups).  Measured at configs[1]:
+// 2, 4 and 8 groups all lengthen the product by 0.35-0.5 ms -- an XCD then works on several depth pieces of fewer tiles at a time and
+// its workgroups share fewer slabs in its L2 -- which is more than the whole reduce pass the fold replaces; with ONE group the folds
+// run at the end of the launch and the step is 0.08 ms shorter than with the reduce kernel.
+constexpr int SG_FOLD_GROUPS = 1;
+
+// Which depth piece and which tile this workgroup computes.  The tile sequence (below) is cut into G.groups runs of consecutive tiles
+// and the workgroups go through them group after group, piece-major inside a group: with several groups a tile's last piece is computed
+// long before the launch ends -- all but the last group's -- and whoever adds the tile's pieces (sig_gram_fold) does so under the
+// multiplies of the next group.  One group (what SG_FOLD_GROUPS asks for, see there) is the piece-major order of the whole launch.  A
+// choice of speed alone: every (piece, tile) is computed once whatever the order, and nothing downstream depends on who computes it or
+// when.  tile_out: the tile's place in the sequence.
+__device__ inline void sig_tile_of(const SigGramArgs& G, int& split_out, int& bi, int& bj, int& tile_out) {
     const int ntiles = gridDim.x / G.nsplit;
-    const int split = blockIdx.x / ntiles;
+    int t0 = 0, t1 = ntiles;
+    if (G.groups > 1) {
+        int g = 0;
+        for (int gg = 1; gg < G.groups; ++gg)
+            if (int(int64_t(ntiles) * gg / G.groups) * G.nsplit <= int(blockIdx.x)) g = gg;
+        t0 = int(int64_t(ntiles) * g / G.groups);
+        t1 = int(int64_t(ntiles) * (g + 1) / G.groups);
+    }
+    const int ng = t1 - t0, base = t0 * G.nsplit;             // this group's tiles [t0, t1); its workgroups start at base
+    const int split = (int(blockIdx.x) - base) / ng;
     int tile;
     {
         // Workgroups go to the 8 XCDs round robin by their index, and each XCD has an L2 of its own: give XCD x a CONTIGUOUS range of
-        // this split's tiles (in the block-major order below), so that the ~64 tiles it works on at a time share operand panels in its
-        // L2 -- an 8 x 8 block of tiles reads 16 panels, 64 tiles strided over the whole triangle read all of them.
-        const int j = blockIdx.x - split * ntiles, off = (split * ntiles) & 7, x = (off + j) & 7;
+        // this split's tiles of the group (in the block-major order below), so that the tiles it works on at a time share operand
+        // panels in its L2 -- an 8 x 8 block of tiles reads 16 panels, 64 tiles strided over the whole triangle read all of them.
+        const int j = int(blockIdx.x) - base - split * ng, off = (base + split * ng) & 7, x = (off + j) & 7;
         int start = 0;
         for (int xp = 0; xp < x; ++xp) {
             const int j0 = (xp - off + 8) & 7;
-            start += j0 < ntiles ? (ntiles - 1 - j0) / 8 + 1 : 0;
+            start += j0 < ng ? (ng - 1 - j0) / 8 + 1 : 0;
         }
-        tile = start + ((j - ((x - off + 8) & 7)) >> 3);
+        tile = t0 + start + ((j - ((x - off + 8) & 7)) >> 3);
     }
+    tile_out = tile;
     {
         // tile -> (bi, bj): 8 x 8 blocks of tiles, block rows first; symmetric products keep the blocks and tiles with bi <= bj
         constexpr int SB = 8;
@@ -561,8 +589,9 @@ static __global__ __launch_bounds__(256, 2) void sig_gram_kernel(const SigGramAr
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wr = wave >> 1, wc = wave & 1;
     const int li = lane & 15, lk = lane >> 4;
-    int split, bi, bj;
-    sig_tile_of(G, split, bi, bj);
+    int split, bi, bj, tile;
+    sig_tile_of(G, split, bi, bj, tile);
+    (void)tile;
     const int64_t tile_i = int64_t(bi) * SG_BM, tile_j = int64_t(bj) * SG_BN;
     if (G.band > 0 && (tile_j + SG_BN - 1 < tile_i || tile_j > tile_i + SG_BM - 1 + G.band)) return;      // nothing of this tile is owned
     // depth chunk of this workgroup, in whole slabs
@@ -673,6 +702,99 @@ static __global__ __launch_bounds__(256, 2) void sig_gram_kernel(const SigGramAr
 __host__ __device__ inline bool sig_gram_diag_owned(int r, int c) { return (r >> 4) <= (c >> 4); }       // (r, c) inside the tile
 
 #ifdef GPSIG_KERNEL_DEFS          // defined once, in kernel_defs.hip; every other unit sees the declaration
+// The fold (G.fold): what a workgroup of sig_gram_dma_kernel does behind its stores.  It publishes its partial tile -- every wave waits
+// for its stores, the workgroup meets, ONE lane releases at agent scope, waits, and draws a ticket on the tile's counter -- and the
+// workgroup that draws the last ticket acquires once and repeats sig_gram_reduce_sym_kernel for this tile: s = 0.0, s += part[k] for
+// k = 0 .. pieces - 1 (every piece read back, this workgroup's own too: its place in the sum does not move), the set diagonal, the
+// entry stored along rows, the mirror image stored along rows after a transpose through LDS, and on a diagonal tile only the entries
+// that sig_gram_diag_owned says were written (an entry not owned is never read: its lane reads the tile's first entry and drops it).
+// Nobody waits for anybody: a workgroup that is not last leaves.  Whoever is last, the sum is the same -- results do not depend on the
+// order of the launch.  One piece: the workgroup is the last by construction, no counter.
+// lds: the kernel's ONE shared array, free after the slab loop (a flag of its own would be a second object: the compiler then waits
+// vmcnt(0) in front of the fragment reads); [0] the flag, from [16] a strip of SG_FOLD_ROWS x SG_BN sums, rows padded by one.
+constexpr int SG_FOLD_ROWS = 32, SG_FOLD_LD = SG_BN + 1;
+__device__ __forceinline__ void sig_gram_fold(const SigGramArgs& G, int tile, int bi, int bj, double* lds, int tid) {
+    static_assert(SG_BN == 128 && SG_BM % SG_FOLD_ROWS == 0, "thread = (column, row parity) of a 128-column strip");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's partial sums are on their way out of the CU
+    __syncthreads();                                            // ... and every wave's; nobody reads a slab any more
+    if (G.nsplit > 1) {
+        int* const flag = reinterpret_cast<int*>(lds);
+        if (tid == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const int ticket = __hip_atomic_fetch_add((__attribute__((address_space(1))) int*)(G.cnt + tile), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int last = ticket == G.nsplit - 1 ? 1 : 0;
+            if (last) {
+                // every arrival of this launch is in: the counter goes back to zero, so a launch leaves the counters as it needs to find
+                // them -- a recorded graph replays without a memset node of its own (sig_gram_levels says why)
+                __hip_atomic_store((__attribute__((address_space(1))) int*)(G.cnt + tile), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            *flag = last;
+        }
+        __syncthreads();
+        if (*flag == 0) return;
+    }
+    double* const S = lds + 16;
+    const int c = tid & (SG_BN - 1), rh = tid >> 7;             // this thread: column c, rows rh, rh + 2, .. of a strip
+    const bool diag = bi == bj;
+    const int64_t tile_i = int64_t(bi) * SG_BM, tile_j = int64_t(bj) * SG_BN, j = tile_j + c;
+    const int64_t stride = G.NA * G.NB;
+    const char* const P0 = reinterpret_cast<const char*>(G.part + tile_i * G.NB + tile_j);
+    constexpr int NQ = SG_FOLD_ROWS / 2;
+    auto owned = [&](int r) { return tile_i + r < G.NA && j < G.NB && (!diag || sig_gram_diag_owned(r, c)); };       // (r, c) of the tile holds a sum
+    for (int r0 = 0; r0 < SG_BM && tile_i + r0 < G.NA; r0 += SG_FOLD_ROWS) {
+        unsigned off[NQ];                     // bytes from the tile's first entry; that entry itself where (r, c) holds no sum
+        double s[NQ], v0[NQ], v1[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int r = r0 + rh + 2 * q;
+            off[q] = owned(r) ? unsigned(r * G.NB + c) * unsigned(sizeof(double)) : 0u;
+            s[q] = 0.0;
+        }
+        // piece k + 1 is on its way while piece k is added: two batches of NQ loads per thread in flight
+        // (buffer loads: the piece's tile is the scalar base, the lane's 32-bit offset the only vector operand -- no 64-bit address per load)
+        auto load = [&](double (&v)[NQ], int k) {
+            const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P0 + int64_t(k) * stride * int64_t(sizeof(double))), 0, -1, 0x00020000);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) v[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rsrc, int(off[q]), 0, 0));
+        };
+        auto add = [&](const double (&v)[NQ]) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) s[q] += v[q];
+        };
+        int k = 0;
+        load(v0, 0);
+        for (; k + 1 < G.nsplit; k += 2) {
+            load(v1, k + 1);
+            add(v0);
+            if (k + 2 < G.nsplit) load(v0, k + 2);
+            add(v1);
+        }
+        if (k < G.nsplit) add(v0);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int r = r0 + rh + 2 * q;
+            const int64_t i = tile_i + r;
+            if (owned(r)) {
+                if (i == j && G.diag_set) s[q] = G.diag_value;
+                G.out[i * G.so_i + j * G.so_j] = s[q];
+            }
+            S[(r - r0) * SG_FOLD_LD + c] = s[q];
+        }
+        __syncthreads();
+        // the mirror image: row j of it holds this strip's SG_FOLD_ROWS values of column j
+        const int il = tid & (SG_FOLD_ROWS - 1);
+        const int64_t i = tile_i + r0 + il;
+        for (int jl = tid / SG_FOLD_ROWS; jl < SG_BN; jl += 256 / SG_FOLD_ROWS) {
+            const int64_t jj = tile_j + jl;
+            if (i < G.NA && jj < G.NB && (!diag || !sig_gram_diag_owned(jl, r0 + il))) G.out[jj * G.so_i + i * G.so_j] = S[il * SG_FOLD_LD + jl];
+        }
+        __syncthreads();
+    }
+}
+
 // As: the first of the two slab buffers of sig_gram_dma_kernel (the second one SG_BM * SG_BK doubles behind it).
 template <int W>
 __device__ __forceinline__ void sig_gram_diag_tile(const SigGramArgs& G, int split, int64_t tile_i, int s0, int nsl, double* As, int lane) {
@@ -762,6 +884,7 @@ __global__ __launch_bounds__(256, 2) void sig_gram_dma_kernel(const SigGramArgs 
     // destinations below are given minus that offset -- down to 1 KiB below the first buffer)
     constexpr int SG_GUARD = 8 * SG_BK;
     __shared__ __attribute__((aligned(16))) double lds_all[SG_GUARD + 2 * SG_BM * SG_BK + 2 * SG_BN * SG_BK];
+    static_assert(sizeof(lds_all) >= sizeof(double) * (16 + SG_FOLD_ROWS * SG_FOLD_LD), "sig_gram_fold's strip lives in this array after the loop");
     double (*const As)[SG_BM * SG_BK] = reinterpret_cast<double (*)[SG_BM * SG_BK]>(lds_all + SG_GUARD);
     double (*const Bs)[SG_BN * SG_BK] = reinterpret_cast<double (*)[SG_BN * SG_BK]>(lds_all + SG_GUARD + 2 * SG_BM * SG_BK);
     // the wavefront's index as a SCALAR: everything that depends on it and on the buffer alone (the LDS-DMA destinations) stays in
@@ -770,8 +893,8 @@ __global__ __launch_bounds__(256, 2) void sig_gram_dma_kernel(const SigGramArgs 
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = tid & 63;
     const int wr = wave >> 1, wc = wave & 1;
     const int li = lane & 15, lk = lane >> 4;
-    int split, bi, bj;
-    sig_tile_of(G, split, bi, bj);
+    int split, bi, bj, tile;
+    sig_tile_of(G, split, bi, bj, tile);
     const int64_t tile_i = int64_t(bi) * SG_BM, tile_j = int64_t(bj) * SG_BN;
     if (G.band > 0 && (tile_j + SG_BN - 1 < tile_i || tile_j > tile_i + SG_BM - 1 + G.band)) return;      // nothing of this tile is owned
     const int s0 = G.bound[split], s1 = G.bound[split + 1];
@@ -781,6 +904,7 @@ __global__ __launch_bounds__(256, 2) void sig_gram_dma_kernel(const SigGramArgs 
         else if (wave == 1) sig_gram_diag_tile<1>(G, split, tile_i, s0, nsl, As[0], lane);
         else if (wave == 2) sig_gram_diag_tile<2>(G, split, tile_i, s0, nsl, As[0], lane);
         else sig_gram_diag_tile<3>(G, split, tile_i, s0, nsl, As[0], lane);
+        if (G.fold) sig_gram_fold(G, tile, bi, bj, lds_all, tid);
         return;
     }
     const double* ga[4];          // this lane's 16 bytes of the CURRENT slab, piece q; the next slab is 128 bytes on
@@ -886,6 +1010,7 @@ __global__ __launch_bounds__(256, 2) void sig_gram_dma_kernel(const SigGramArgs 
                 const int64_t i = tile_i + wr * 64 + m * 16 + lk + 4 * r, j = tile_j + wc * 64 + n * 16 + li;
                 if (i < G.NA && j < G.NB) P[i * G.NB + j] = acc[m][n][r];
             }
+    if (G.fold) sig_gram_fold(G, tile, bi, bj, lds_all, tid);
 }
 #else
 __global__ __launch_bounds__(256, 2) void sig_gram_dma_kernel(const SigGramArgs G);
