@@ -116,6 +116,8 @@ _PLAIN = {
     "gpsig_abi_version": ([], C.c_int),
     "gpsig_spectral_cross": ([_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp], C.c_int),
     "gpsig_spectral_cross_grad": ([_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "gpsig_spectral_kappa": ([_vp, _i32, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp], C.c_int),
+    "gpsig_spectral_kappa_grad": ([_vp, _i32, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "gpsig_seq_lags_ragged_dev": ([_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp], C.c_int),
     "gpsig_seq_lags_ragged_grad": ([_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp], C.c_int),
     "gpsig_lr_state_destroy": ([_vp], None),

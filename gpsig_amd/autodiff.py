@@ -1086,6 +1086,77 @@ class _SpectralCross(torch.autograd.Function):
         return tuple(t.to(dt) for t, dt in zip((gP, gS, ga, go, gg), ctx.dt)) + (None,)
 
 
+class _SpectralKappa(torch.autograd.Function):
+    """SignatureSpectral's kappa(A, B) (kernels.py:921-942) of exact mode's matrix route, by gpsig_spectral_kappa: A (m, d), B (n, d) -> (m, n), or
+    A (batch, m, d), B (batch, n, d) -> (batch, m, n); the reverse pass by gpsig_spectral_kappa_grad: d A, d B, d alpha, d omega, d gamma, the
+    parameters read from device memory.  What base_kernel_matrix computes for this family without the (batch, m, n, d) difference tensor and its
+    scaled copy per component under autograd, with the same convention at zero distance (_SqrtZeroGrad): rows that are bitwise equal are at
+    distance and phase exactly 0 (csrc/wide_spectral_kernel.hpp), so K(X, X) and the level diagonals hold sum(alpha) exactly on their self-pairs.
+    A and B may be one tensor.  No floating-point atomics: the reverse pass repeats bit for bit.  float64 CUDA tensors, d <= 4096, Q <= 64
+    (spectral_kappa_route decides who gets here)."""
+
+    @staticmethod
+    def forward(ctx, A, B, alpha, omega, gamma, family):
+        if A.dim() != B.dim() or A.dim() not in (2, 3) or A.shape[-1] != B.shape[-1] or (A.dim() == 3 and A.shape[0] != B.shape[0]):
+            raise ValueError("_SpectralKappa: A (m, d) and B (n, d), or A (batch, m, d) and B (batch, n, d); got %s, %s" % (tuple(A.shape), tuple(B.shape)))
+        Ad, Bd, a, o, g = (_c(t) for t in (A, B, alpha, omega, gamma))
+        batch = Ad.shape[0] if Ad.dim() == 3 else 1
+        m, n, d, Q = Ad.shape[-2], Bd.shape[-2], Ad.shape[-1], a.shape[0]
+        out = torch.empty(Ad.shape[:-1] + (n,), dtype=torch.float64, device=Ad.device)
+        lc = _ctx_for(Ad)
+        lc.check(lc._lib.gpsig_spectral_kappa(lc._h, Q, _SPECTRAL_FAMILY[family], d, _ptr(Ad), _ptr(Bd), batch, m, n, _ptr(a), _ptr(o), _ptr(g),
+                                              _ptr(out)))
+        ctx.family = family
+        ctx.dt = tuple(t.dtype for t in (A, B, alpha, omega, gamma))
+        ctx.save_for_backward(Ad, Bd, a, o, g)
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        Ad, Bd, a, o, g = ctx.saved_tensors
+        batch = Ad.shape[0] if Ad.dim() == 3 else 1
+        m, n, d, Q = Ad.shape[-2], Bd.shape[-2], Ad.shape[-1], a.shape[0]
+        G = _c(G)
+        gA, gB, ga, go, gg = (torch.empty_like(t) for t in (Ad, Bd, a, o, g))
+        lc = _ctx_for(Ad)
+        lc.check(lc._lib.gpsig_spectral_kappa_grad(lc._h, Q, _SPECTRAL_FAMILY[ctx.family], d, _ptr(Ad), _ptr(Bd), batch, m, n, _ptr(a), _ptr(o),
+                                                   _ptr(g), _ptr(G), _ptr(gA), _ptr(gB), _ptr(ga), _ptr(go), _ptr(gg)))
+        return tuple(t.to(dt) for t, dt in zip((gA, gB, ga, go, gg), ctx.dt)) + (None,)
+
+
+# "auto" sends kappa to _SpectralKappa only where the difference tensor that the torch ops would build (batch * m * n * d float64) reaches this size: a
+# MEMORY condition -- that tensor, and one scaled copy of it per component kept for autograd, is what runs exact-mode training out of the device at
+# the reference's own shapes --, not a speed claim; every smaller call keeps the torch ops and their bits
+SPECTRAL_KAPPA_MIN_BYTES = 2 ** 30
+SPECTRAL_KAPPA_MAX_COLUMNS = 4096
+SPECTRAL_KAPPA_MAX_COMPONENTS = 64
+
+
+def spectral_kappa_route(mode, is_cuda, dtype, batch, m, n, d, Q):
+    """Who computes exact-mode SignatureSpectral's kappa of A (batch, m, d) and B (batch, n, d) with Q components -> "torch" (base_kernel_matrix, the
+    difference form) or "hip" (_SpectralKappa).  ``mode`` is SignatureKernelModule.spectral_kappa: "torch"; "hip" -- NotImplementedError naming the
+    bound where the op does not serve the call (CPU tensors, tensors other than float64, d > 4096, Q > 64) --; "auto": the op where it serves the call
+    AND batch * m * n * d * 8 >= SPECTRAL_KAPPA_MIN_BYTES, else torch.  A pure function of its arguments."""
+    if mode not in ("auto", "torch", "hip"):
+        raise ValueError("spectral_kappa must be 'auto', 'torch' or 'hip', got %r" % (mode,))
+    if mode == "torch":
+        return "torch"
+    why = None
+    if not is_cuda:
+        why = "CUDA (ROCm) tensors, got CPU tensors"
+    elif dtype != torch.float64:
+        why = "float64 tensors, got %s" % (dtype,)
+    elif d > SPECTRAL_KAPPA_MAX_COLUMNS:
+        why = "at most %d columns, got %d" % (SPECTRAL_KAPPA_MAX_COLUMNS, d)
+    elif Q > SPECTRAL_KAPPA_MAX_COMPONENTS:
+        why = "at most %d components, got %d" % (SPECTRAL_KAPPA_MAX_COMPONENTS, Q)
+    if mode == "hip":
+        if why is not None:
+            raise NotImplementedError("spectral_kappa = 'hip': the kappa op (gpsig_spectral_kappa) takes " + why)
+        return "hip"
+    return "hip" if why is None and batch * m * n * d * 8 >= SPECTRAL_KAPPA_MIN_BYTES else "torch"
+
+
 def _lr_limits(cc, r, d, M):
     """What csrc/lr_grad_api.hip takes of a low-rank feature map -> (the sizes its reverse kernels are built for: at most 64 components, 4096
     (component, column) pairs, 8 levels; whether one 64-step tile of a sequence's arrays fits the LDS with its carry rows (csrc/lr_tile_plan.hpp:
@@ -1370,6 +1441,10 @@ class SignatureKernelModule(torch.nn.Module):
         # low-rank SignatureSpectral: sequences beyond the whole-sequence kernels and ragged batches through the lengths-aware tiled instances
         # (_LrSeqFeaturesSpectralRagged) instead of torch ops.  A plain switch, off until the default is flipped
         self.lr_spectral_tiled = False
+        # exact-mode SignatureSpectral: who computes kappa of the matrix route's primitives (_mx_kappa, spectral_kappa_route; low-rank mode never asks) -- "torch": base_kernel_matrix's difference form;
+        # "hip": _SpectralKappa (NotImplementedError where it does not serve the call); "auto": the op where the difference tensor would reach
+        # SPECTRAL_KAPPA_MIN_BYTES, a memory condition
+        self.spectral_kappa = "auto"
         d_cols = kern.num_features * (kern.num_lags + 1)
         # beyond 64 columns and for the spectral kernel: base-kernel tensors here (GEMMs, autograd), recursions in the library
         # (round 6: beyond 64 columns the library's wide route takes the primitives it is built for -- _mx below)
@@ -1605,6 +1680,18 @@ class SignatureKernelModule(torch.nn.Module):
             spec = (self.kern.family, positive(self.raw_alpha), positive(self.raw_omega), positive(self.raw_sgamma))
         return base_kernel_matrix(self.kern._base, A, B, self.p0, self._spec.p1, spec)
 
+    def _mx_kappa(self, A, B):
+        """kappa of the exact matrix route's four primitives below: two matrices, or two batches of as many.  SignatureSpectral asks
+        spectral_kappa_route who computes it -- the batched HIP op (_SpectralKappa) or _kappa's torch ops --; every other family is _kappa.
+        Only these primitives ask: _kappa itself stays torch ops for its other callers (the low-rank scope's fallback and checker, _LowRankScope._cross)."""
+        if self.kern._base == "spectral":
+            batch = A.shape[0] if A.dim() == 3 else 1
+            dtype = A.dtype if A.dtype == B.dtype else None
+            if spectral_kappa_route(self.spectral_kappa, A.is_cuda and B.is_cuda, dtype, batch, A.shape[-2], B.shape[-2], A.shape[-1],
+                                    self.raw_alpha.shape[0]) == "hip":
+                return _SpectralKappa.apply(A, B, positive(self.raw_alpha), positive(self.raw_omega), positive(self.raw_sgamma), self.kern.family)
+        return self._kappa(A, B)
+
     def _mx_lattices(self, K4):
         """(P, L1, L2) base-kernel lattices -> levels (M+1, P): signature_algs.py:25-26 here, :28-74 in the library."""
         if self.kern.difference:
@@ -1615,19 +1702,19 @@ class SignatureKernelModule(torch.nn.Module):
         N1, L1, d = Xs.shape                                                                        # kernels.py:208-237
         Ys = Xs if X2s is None else X2s
         N2, L2 = Ys.shape[:2]
-        Kt = self._kappa(Xs.reshape(N1 * L1, d), Ys.reshape(N2 * L2, d)).reshape(N1, L1, N2, L2)
+        Kt = self._mx_kappa(Xs.reshape(N1 * L1, d), Ys.reshape(N2 * L2, d)).reshape(N1, L1, N2, L2)
         return self._mx_lattices(Kt.permute(0, 2, 1, 3).reshape(N1 * N2, L1, L2)).reshape(-1, N1, N2)
 
     def _mx_diag_levels(self, Xs):
-        return self._mx_lattices(self._kappa(Xs, Xs))                                               # kernels.py:188-205
+        return self._mx_lattices(self._mx_kappa(Xs, Xs))                                               # kernels.py:188-205
 
     def _mx_tens_levels(self, Zs, increments):
         lt, T, d = Zs.shape[0], Zs.shape[1], Zs.shape[-1]                                           # kernels.py:263-283
         if increments:
-            Mk = self._kappa(Zs.reshape(lt, 2 * T, d), Zs.reshape(lt, 2 * T, d)).reshape(lt, T, 2, T, 2)
+            Mk = self._mx_kappa(Zs.reshape(lt, 2 * T, d), Zs.reshape(lt, 2 * T, d)).reshape(lt, T, 2, T, 2)
             Mk = Mk[:, :, 1, :, 1] + Mk[:, :, 0, :, 0] - Mk[:, :, 1, :, 0] - Mk[:, :, 0, :, 1]      # :276-277
         else:
-            Mk = self._kappa(Zs, Zs)
+            Mk = self._mx_kappa(Zs, Zs)
         lev, k = [torch.ones_like(Mk[0])], 0                                                        # signature_algs.py:76-99
         for i in range(1, self._spec.num_levels + 1):
             R = Mk[k]
@@ -1642,10 +1729,10 @@ class SignatureKernelModule(torch.nn.Module):
         N, L = Xs.shape[:2]
         Xf = Xs.reshape(N * L, d)
         if increments:
-            Mk = self._kappa(Zs.reshape(lt * T * 2, d), Xf).reshape(lt, T, 2, N, L)
+            Mk = self._mx_kappa(Zs.reshape(lt * T * 2, d), Xf).reshape(lt, T, 2, N, L)
             Mk = Mk[:, :, 1] - Mk[:, :, 0]                                                          # :329-330
         else:
-            Mk = self._kappa(Zs.reshape(lt * T, d), Xf).reshape(lt, T, N, L)
+            Mk = self._mx_kappa(Zs.reshape(lt * T, d), Xf).reshape(lt, T, N, L)
         if self.kern.difference:
             Mk = Mk[..., 1:] - Mk[..., :-1]                                                         # signature_algs.py:114
         if self._spec.order > 1 and self._spec.num_levels > 1:

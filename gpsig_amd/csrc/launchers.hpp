@@ -236,6 +236,18 @@ int wide_spx_side_launch(hipStream_t stream, const double* X, int64_t rows, int6
                          double* ph);
 int wide_spx_launch(hipStream_t stream, const WideSpxArgs& A);
 
+// ---- spectral_kappa_inst.hip: the reverse pass of the batched kappa op gpsig_spectral_kappa / _grad (kernels: spectral_kappa_kernel.hpp; the entry
+// points and the chunking: spectral_kappa_api.hip; the forward pass is the three launchers above).  They return the hipError_t of the launch.
+struct SpecKappaArgs;
+int spk_weights_launch(hipStream_t stream, const SpecKappaArgs& A);                                   // U_q and the per-tile sums of a chunk
+// out[e] = (first ? 0 : out[e]) + part[0][e] + part[1][e] + ... + part[count - 1][e], e < width: every sum of the op, in this order
+int spk_reduce_launch(hipStream_t stream, const double* part, int64_t count, int64_t width, int first, double* out);
+int spk_scale_launch(hipStream_t stream, const SpecKappaArgs& A);                                     // AS_q = gamma_q^2 o A
+int spk_rows_launch(hipStream_t stream, const SpecKappaArgs& A);                                      // dA of the chunk's rows
+int spk_cols_launch(hipStream_t stream, const SpecKappaArgs& A);                                      // dB of the chunk's batch members
+int spk_param_launch(hipStream_t stream, const SpecKappaArgs& A, int side);                           // per-slice sums of domega, dgamma: side 0 rows of A, 1 rows of B
+int spk_finish_launch(hipStream_t stream, const SpecKappaArgs& A, double* dalpha, double* domega, double* dgamma);
+
 // ---- lr_cross_spectral_inst.hip: gpsig_spectral_cross / gpsig_spectral_cross_grad beyond 32 columns (the entry points: spectral_cross_api.hip)
 int spectral_cross_wide(gpsig_ctx* c, int Q, int family, int d, const double* P, int64_t n, const double* S, int cc, const double* alpha,
                         const double* omega, const double* gamma, double* K);

@@ -29,6 +29,7 @@ struct SolverApi {
                                rocblas_int, rocblas_stride, const double*, rocblas_int, rocblas_stride, const double*, double*, rocblas_int, rocblas_stride,
                                rocblas_int) = nullptr;
     rocblas_status (*set_pointer_mode)(rocblas_handle, rocblas_pointer_mode) = nullptr;
+    rocblas_status (*set_atomics_mode)(rocblas_handle, rocblas_atomics_mode) = nullptr;
     std::string err;
 };
 
@@ -53,6 +54,7 @@ void load_api() {
     g_api.dgemm = reinterpret_cast<decltype(g_api.dgemm)>(dlsym(g_api.blas, "rocblas_dgemm"));
     g_api.dgemm_sb = reinterpret_cast<decltype(g_api.dgemm_sb)>(dlsym(g_api.blas, "rocblas_dgemm_strided_batched"));
     g_api.set_pointer_mode = reinterpret_cast<decltype(g_api.set_pointer_mode)>(dlsym(g_api.blas, "rocblas_set_pointer_mode"));
+    g_api.set_atomics_mode = reinterpret_cast<decltype(g_api.set_atomics_mode)>(dlsym(g_api.blas, "rocblas_set_atomics_mode"));
     g_api.create_handle = reinterpret_cast<decltype(g_api.create_handle)>(dlsym(g_api.blas, "rocblas_create_handle"));
     g_api.destroy_handle = reinterpret_cast<decltype(g_api.destroy_handle)>(dlsym(g_api.blas, "rocblas_destroy_handle"));
     g_api.set_stream = reinterpret_cast<decltype(g_api.set_stream)>(dlsym(g_api.blas, "rocblas_set_stream"));
@@ -104,6 +106,8 @@ bool solver_dgemm(void** handle_slot, hipStream_t stream, bool transA, bool tran
     rocblas_handle h = static_cast<rocblas_handle>(*handle_slot);
     if (g_api.set_stream(h, stream) != rocblas_status_success) { *err = "rocblas_set_stream failed"; return false; }
     if (g_api.set_pointer_mode) (void)g_api.set_pointer_mode(h, rocblas_pointer_mode_host);
+    // no floating-point atomics inside a product, whatever the library's default is: callers promise the same bits from the same call
+    if (g_api.set_atomics_mode) (void)g_api.set_atomics_mode(h, rocblas_atomics_not_allowed);
     const rocblas_status st = g_api.dgemm(h, transA ? rocblas_operation_transpose : rocblas_operation_none,
                                           transB ? rocblas_operation_transpose : rocblas_operation_none, m, n, k, &alpha, A, lda, B, ldb, &beta, C, ldc);
     if (st != rocblas_status_success) { *err = "rocblas_dgemm failed (status " + std::to_string(int(st)) + ")"; return false; }
@@ -123,6 +127,8 @@ bool solver_dgemm_batched(void** handle_slot, hipStream_t stream, bool transA, b
     rocblas_handle h = static_cast<rocblas_handle>(*handle_slot);
     if (g_api.set_stream(h, stream) != rocblas_status_success) { *err = "rocblas_set_stream failed"; return false; }
     if (g_api.set_pointer_mode) (void)g_api.set_pointer_mode(h, rocblas_pointer_mode_host);
+    // no floating-point atomics inside a product, whatever the library's default is: callers promise the same bits from the same call
+    if (g_api.set_atomics_mode) (void)g_api.set_atomics_mode(h, rocblas_atomics_not_allowed);
     const rocblas_status st = g_api.dgemm_sb(h, transA ? rocblas_operation_transpose : rocblas_operation_none,
                                              transB ? rocblas_operation_transpose : rocblas_operation_none, m, n, k, &alpha, A, lda, sa, B, ldb, sb, &beta, C, ldc, sc,
                                              batch);

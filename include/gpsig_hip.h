@@ -529,6 +529,25 @@ int gpsig_spectral_cross(gpsig_ctx* ctx, int32_t Q, int32_t family, int32_t d, c
 int gpsig_spectral_cross_grad(gpsig_ctx* ctx, int32_t Q, int32_t family, int32_t d, const double* P, int64_t n, const double* S, int32_t c,
                               const double* alpha, const double* omega, const double* gamma, const double* G, double* dP, double* dS,
                               double* dalpha, double* domega, double* dgamma);
+/* SignatureSpectral's kappa as a BATCHED op for exact-mode training (kernels.py:921-942): K (batch, m, n) = kappa(A_b[i], B_b[j]) for A (batch, m, d),
+ * B (batch, n, d), contiguous float64; alpha (Q), omega (Q, d), gamma (Q, d) read from DEVICE memory; family as in gpsig_spectral_cross.  What the
+ * matrix route's torch ops compute from the (batch, m, n, d) difference tensor, without that tensor: the d-deep contractions run on the float64 matrix
+ * cores, a component's squared distance is nrm(a) + nrm(b) - 2 ip from three products accumulated in one order and its phase a difference of two, so
+ * where a row of A and a row of B are bitwise equal the entry is exactly sum_q alpha_q.  A and B may be the same array (the rows' norms and phases are
+ * then computed once).  Device pointers, device-pointer mode, asynchronous on the context's stream; not inside a graph capture.
+ * Limits: 1 <= Q <= 64, 1 <= d <= 4096, m, n < 2^31; outside them GPSIG_ERR_UNSUPPORTED with the bound in the message.  batch, m or n equal to 0 is
+ * served: nothing is launched.
+ * _grad: G = dL/dK (batch, m, n) -> dA (batch, m, d), dB (batch, n, d), dalpha (Q), domega (Q, d), dgamma (Q, d), overwritten (dA and dB are two
+ * arrays even where A and B are one: the caller adds them).  The exponential envelope's sqrt has derivative 0 at zero distance.  With batch, m or n
+ * equal to 0 all five are written as zeros.  Scratch stays inside the context's chunk budget (wide_chunk_mb, else grad_scratch_mb): whole batch
+ * members go in chunks, and rows of A in blocks of a multiple of 64 where one member exceeds it (a single 64-row block beyond the budget is still
+ * served).  Sums inside a chunk are added slot by slot, the column-side and parameter sums of the chunks in chunk order: no floating-point atomics,
+ * two identical calls return the same bits (a different budget may round the sums differently).  The two skinny products per chunk are rocBLAS GEMMs. */
+int gpsig_spectral_kappa(gpsig_ctx* ctx, int32_t Q, int32_t family, int32_t d, const double* A, const double* B, int64_t batch, int64_t m, int64_t n,
+                         const double* alpha, const double* omega, const double* gamma, double* K);
+int gpsig_spectral_kappa_grad(gpsig_ctx* ctx, int32_t Q, int32_t family, int32_t d, const double* A, const double* B, int64_t batch, int64_t m,
+                              int64_t n, const double* alpha, const double* omega, const double* gamma, const double* G, double* dA, double* dB,
+                              double* dalpha, double* domega, double* dgamma);
 /* The Nystrom cross matrix of the other families for the TRAINING path on WIDE state spaces (low_rank_calculations.py:59): K (n, c) =
  * kappa(P, S) for points P (n, d) and landmarks S (c, d), p->base_kernel in GPSIG_BASE_LINEAR .. GPSIG_BASE_MATERN52 with p->base_params as
  * the fused feature kernels read them, d = p->num_features; the d-deep contraction runs on the float64 matrix cores.  Device pointers,
