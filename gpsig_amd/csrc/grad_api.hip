@@ -29,23 +29,14 @@ using namespace gpsig;
 namespace gpsig {
 bool ho_sweeps_plan(const gpsig_ctx* c, const gpsig_params* p, int R1, int R2, HoSweeps* hs) {
     const int M = p->num_levels, order = p->order < M ? p->order : M;
-    if ((c->grad_impl != 0 && c->grad_impl != 3) || order < 2 || R1 < 1 || R2 < 1) return false;
-    static const int shapes[][2] = {{16, 2}, {16, 4}, {64, 2}, {64, 4}, {64, 8}};
+    // the decision (lane shape, the ho_g32 rule, scratch-free or HBM slots): ho_sweeps_plan_shape of grad_plan.hpp
+    const GradInstance g = ho_sweeps_plan_shape(c->grad_impl, c->ho_g32, M, p->order, R1, R2, &hs->lds);
     hs->fn = nullptr;
-    for (auto& sh : shapes) {
-        if (sh[0] * sh[1] < R2) continue;
-        hs->G = sh[0]; hs->C = sh[1];
-        // 33 .. 64 columns at order >= 3: two columns per lane and two pairs per wavefront instead of four and four -- the four-column instances of
-        // orders 3 / 4 spill (312 B .. 1.6 KB of scratch at one wavefront per SIMD): K(X) N = 512 order 4 64.7 -> 39.3 ms; at order 2 they do not (25.8 against 27.0).
-        // Option ho_g32: -1 this rule, 0 never, 1 always
-        if (hs->G == 16 && hs->C == 4 && c->grad_impl == 0 && (c->ho_g32 > 0 || (c->ho_g32 < 0 && order >= 3))) { hs->G = 32; hs->C = 2; }
-        hs->lds = wave_ho_undo_lds(hs->G, R1, order, M);
-        if (c->grad_impl == 0 && hs->lds <= 64 * 1024)
-            hs->fn = hs->G == 16 ? wave_ho_undo_lookup_g16(hs->C, order, M) : (hs->G == 32 ? wave_ho_undo_lookup_g32(hs->C, order, M) : wave_ho_undo_lookup_g64(hs->C, order, M));
-        if (!hs->fn && hs->G == 32) { hs->G = 16; hs->C = 4; }
-        if (!hs->fn) { hs->fn = wave_ho_lookup(hs->G, hs->C, order, M); hs->lds = 0; }
-        break;
-    }
+    hs->G = g.G; hs->C = g.C;
+    if (g.family == GRAD_HO_UNDO)
+        hs->fn = g.G == 16 ? wave_ho_undo_lookup_g16(g.C, order, M) : (g.G == 32 ? wave_ho_undo_lookup_g32(g.C, order, M) : wave_ho_undo_lookup_g64(g.C, order, M));
+    else if (g.family == GRAD_HO_SLOT)
+        hs->fn = wave_ho_lookup(g.G, g.C, order, M);
     if (!hs->fn) return false;
     hs->slot = hs->lds == 0 ? sizeof(double) * size_t(ho_stash_words(order, M)) * size_t(R1 + hs->G - 1) * hs->G * hs->C : 0;
     return true;
@@ -258,16 +249,13 @@ int gbase_end(gpsig_ctx* c, const double* dev, double* user) {
 
 // ---- wavefront-parallel path (grad_wave_kernel.hpp) ------------------------------------------------------------------------
 WaveLaunchFn wave_plan(int mode, int R2, int DP, int M, int* G, int* C) {
-    if (DP > 16 || M - 1 > 7) return nullptr;
-    static const int shapes[][2] = {{16, 2}, {16, 4}, {64, 2}, {64, 4}, {64, 8}};
-    for (auto& sh : shapes) {
-        if (sh[0] * sh[1] < R2) continue;
-        WaveLaunchFn f = mode == MODE_INC ? wave_lookup_inc(sh[0], sh[1], DP, M - 1)
-                                          : (mode == MODE_PT_DIFF ? wave_lookup_ptd(sh[0], sh[1], DP, M - 1) : wave_lookup_ptn(sh[0], sh[1], DP, M - 1));
-        if (f) { *G = sh[0]; *C = sh[1]; return f; }
-    }
-    return nullptr;
+    const GradInstance g = wave_plan_shape(mode, R2, DP, M);           // grad_plan.hpp
+    if (g.family != GRAD_WAVE) return nullptr;
+    *G = g.G; *C = g.C;
+    return mode == MODE_INC ? wave_lookup_inc(g.G, g.C, DP, M - 1) : (mode == MODE_PT_DIFF ? wave_lookup_ptd(g.G, g.C, DP, M - 1) : wave_lookup_ptn(g.G, g.C, DP, M - 1));
 }
+static_assert(int(MODE_INC) == int(GRAD_MODE_INC) && int(MODE_PT_DIFF) == int(GRAD_MODE_PT_DIFF) && int(MODE_PT_NODIFF) == int(GRAD_MODE_PT_NODIFF),
+              "grad_plan.hpp restates the lattice modes of seq_core.hpp");
 
 // workgroups of lam_contract_kernel: the partner loop waits on its Lam loads, so the launch is sized for several wavefronts per SIMD
 constexpr int64_t CONTRACT_BLOCKS = 16384;
@@ -356,23 +344,18 @@ int seq_grad_wave(gpsig_ctx* c, const gpsig_params* p, WaveLaunchFn fn, int G, i
 
 
 // ---- scratch-free wavefront path (seq_grad_wave2_kernel): one launch per register-resident side ------------------------------
-Wave2LaunchFn wave2_plan(int mode, int Rreg, int DP, int M, int* G, int* C) {
-    // The linear kernel on increments only: the point kernels would carry the derivative coefficients of a whole row on top
-    // of the recursion state; they run through seq_lam_undo_kernel + lam_contract_kernel.
-    if (mode != MODE_INC || DP > 16 || M - 1 > 7) return nullptr;
-    static const int shapes[][2] = {{16, 2}, {16, 4}, {64, 2}, {64, 8}};
-    for (auto& sh : shapes) {
-        if (sh[0] * sh[1] < Rreg) continue;
-        if (sh[1] * DP > 32) continue;                     // larger per-lane tiles spill
-        Wave2LaunchFn f = wave2_lookup_inc(sh[0], sh[1], DP, M - 1);
-        if (f) { *G = sh[0]; *C = sh[1]; return f; }
-    }
-    return nullptr;
+// The linear kernel on increments only; both sides of a call, or neither: wave2_plan_call of grad_plan.hpp (with wave2_lds, the dynamic LDS
+// of the scratch-free kernels, and WAVE2_LDS_MAX)
+bool wave2_plan(int mode, int R1, int R2, int DP, int M, bool one_side, Wave2LaunchFn* fx, int* Gx, Wave2LaunchFn* fy, int* Gy) {
+    GradInstance gx, gy;
+    *fx = *fy = nullptr;
+    if (!wave2_plan_call(mode, R1, R2, DP, M, one_side, &gx, &gy)) return false;
+    *Gx = gx.G; *Gy = gy.G;
+    *fx = wave2_lookup_inc(gx.G, gx.C, DP, M - 1);
+    *fy = one_side ? *fx : wave2_lookup_inc(gy.G, gy.C, DP, M - 1);
+    if (!*fx || !*fy) *fx = *fy = nullptr;
+    return *fx != nullptr;
 }
-
-// dynamic LDS of the scratch-free kernels: the row totals of 64 / G streamed sequences
-size_t wave2_lds(int G, int R1, int M) { return sizeof(double) * size_t(64 / G) * size_t(R1 > 0 ? R1 : 1) * size_t(M - 1 == 3 ? 3 : (M - 1 <= 4 ? 4 : 7)); }
-constexpr size_t WAVE2_LDS_MAX = 64 * 1024;
 
 // tasks of the scratch-free kernels: one register-side sequence (0 .. NR) x a run of streamed sequences (0 .. NS); diag: (r, r).
 int wave2_tasks(gpsig_ctx* c, int64_t NS, int64_t NR, bool diag, const SeqTask** tasks, size_t* ntasks_out) {
@@ -417,18 +400,12 @@ int wave2_side(gpsig_ctx* c, const gpsig_params* p, Wave2LaunchFn fn, int G, int
 
 // ---- point kernels: scratch-free sweeps that store Lam (seq_lam_undo_kernel) + lam_contract_kernel for both sides -------------
 Wave2LaunchFn lam_undo_plan(int mode, int kind, int R1, int R2, int DP, int M, int* G, int* C) {
-    // the linear kernel on increments runs faster through seq_grad_wave2_kernel (44 ms against 66 ms for a 1024 x 1024 Gram)
-    if (mode == MODE_INC || DP > 16 || M - 1 > 7) return nullptr;
-    static const int shapes[][2] = {{16, 2}, {16, 4}, {64, 2}, {64, 4}, {64, 8}};
-    for (auto& sh : shapes) {
-        if (sh[0] * sh[1] < R2) continue;
-        if (wave2_lds(sh[0], R1, M) > WAVE2_LDS_MAX) continue;
-        const bool rbf = kind == BASE_RBF;
-        Wave2LaunchFn f = mode == MODE_PT_DIFF ? (rbf ? lam_undo_lookup_ptd_rbf : lam_undo_lookup_ptd_gen)(sh[0], sh[1], DP, M - 1)
-                                               : (rbf ? lam_undo_lookup_ptn_rbf : lam_undo_lookup_ptn_gen)(sh[0], sh[1], DP, M - 1);
-        if (f) { *G = sh[0]; *C = sh[1]; return f; }
-    }
-    return nullptr;
+    const bool rbf = kind == BASE_RBF;
+    const GradInstance g = lam_undo_plan_shape(mode, rbf, R1, R2, DP, M);           // grad_plan.hpp
+    if (g.family != GRAD_LAM_UNDO) return nullptr;
+    *G = g.G; *C = g.C;
+    return mode == MODE_PT_DIFF ? (rbf ? lam_undo_lookup_ptd_rbf : lam_undo_lookup_ptd_gen)(g.G, g.C, DP, M - 1)
+                                : (rbf ? lam_undo_lookup_ptn_rbf : lam_undo_lookup_ptn_gen)(g.G, g.C, DP, M - 1);
 }
 
 // Blocks of pairs (i0 .. i0+ni) x (j0 .. j0+nj) sized to the scratch budget for Lam.  Symmetric Gram: block rows i0 .. i0+ni
@@ -831,15 +808,10 @@ int seq_grad(gpsig_ctx* c, const gpsig_params* p, const void* X, const void* Y, 
     double* const kgb = (p->base_kernel == GPSIG_BASE_POLY || p->base_kernel == GPSIG_BASE_MIX) ? dgb : nullptr;
     WaveLaunchFn wfn = nullptr;
     Wave2LaunchFn w2x = nullptr, w2y = nullptr;            // scratch-free kernels with x resp. y as the register-resident side
-    int wG = 0, wC = 0, w2xG = 0, w2xC = 0, w2yG = 0, w2yC = 0;
+    int wG = 0, wC = 0, w2xG = 0, w2yG = 0;
     const int drr = mode == MODE_PT_NODIFF ? 0 : 1;
     if ((c->grad_impl == 0 || c->grad_impl == 3 || c->grad_impl == 4) && N1 > 0 && N2 > 0) wfn = wave_plan(mode, L2 - drr, DP, M, &wG, &wC);
-    if ((c->grad_impl == 0 || c->grad_impl == 4) && N1 > 0 && N2 > 0 && L1 - drr > 0 && L2 - drr > 0) {
-        w2x = wave2_plan(mode, L1 - drr, DP, M, &w2xG, &w2xC);
-        w2y = (diag || sym) ? w2x : wave2_plan(mode, L2 - drr, DP, M, &w2yG, &w2yC);
-        if (!w2x || !w2y) w2x = w2y = nullptr;
-    }
-    if (w2x && (wave2_lds(w2xG, L2 - drr, M) > WAVE2_LDS_MAX || (!diag && !sym && wave2_lds(w2yG, L1 - drr, M) > WAVE2_LDS_MAX))) w2x = w2y = nullptr;
+    if ((c->grad_impl == 0 || c->grad_impl == 4) && N1 > 0 && N2 > 0) wave2_plan(mode, L1 - drr, L2 - drr, DP, M, diag || sym, &w2x, &w2xG, &w2y, &w2yG);
     Wave2LaunchFn lfn = nullptr;                           // point kernels: scratch-free sweeps with Lam out
     int lG = 0, lC = 0;
     if ((c->grad_impl == 0 || c->grad_impl == 4) && N1 > 0 && N2 > 0) lfn = lam_undo_plan(mode, p->base_kernel, L1 - drr, L2 - drr, DP, M, &lG, &lC);

@@ -241,8 +241,11 @@ struct WaveUndo {
     }
     // rowtot[m-1] = sum_b R_m[a][b]; sufin[m-1] / svin[p-1]: the right neighbour's sufout / svout of ITS previous step.
     // first_row: a == 0 (Q[-1][.] == 0 exactly); first_lane: b_0 == 0 (Q[.][-1] == 0 exactly).
+    // a, b0 (optional: the row and the lane's first column): a level-m chain needs m rows and m columns, so Q_m[a-1][b-1] == 0 exactly for
+    // a < m or b < m.  The undone Q there is what the subtractions left of the last row's Q (its rounding, ~1e-16 of a value that may be 1e9)
+    // and is multiplied by U_{m+1}: with fewer lattice rows than levels that was the largest term of Lam's error (1e-9 of the gradient).
     GPSIG_HD void step(const double (&dm)[C], const double (&clev)[LQ + 2], const double (&rowtot)[LQ], const double (&sufin)[LQ],
-                       const double (&svin)[LQ], int M, bool first_row, bool first_lane, double (&lam)[C]) {
+                       const double (&svin)[LQ], int M, bool first_row, bool first_lane, double (&lam)[C], int a = -1, int b0 = 0) {
         double D[LQ + 1][C];                    // D[m][c] = Q_m[a-1][b_c - 1];  D[0] == 1
 #pragma unroll
         for (int c = 0; c < C; ++c) D[0][c] = 1.0;
@@ -262,6 +265,7 @@ struct WaveUndo {
             for (int c = 0; c < C; ++c) {
                 double d = c == 0 ? qfg[m - 1] : qf[m - 1][c > 0 ? c - 1 : 0];
                 if (first_row || (first_lane && c == 0) || m >= M) d = 0.0;
+                if (a >= 0 && (a < m || b0 + c < m)) d = 0.0;
                 D[m][c] = d;
             }
         }

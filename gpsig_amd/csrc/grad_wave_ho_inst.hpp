@@ -13,19 +13,17 @@ static hipError_t wave_ho_launch(const WaveHoArgs& a, int nblocks, size_t, hipSt
 }
 template <int G, int C>
 static WaveHoLaunchFn pick(int order) {
-    if (order == 2) return &wave_ho_launch<G, C, 2>;
-    if (order == 3) return &wave_ho_launch<G, C, 3>;
-    if (order == 4) return &wave_ho_launch<G, C, 4>;
+#define X_HO(O_) if (order == O_) return &wave_ho_launch<G, C, O_>;
+    GPSIG_HO_SLOT_ORDERS(X_HO)
+#undef X_HO
     return nullptr;
 }
-// order: min(order, num_levels) >= 2
+// order: min(order, num_levels) >= 2.  Forms and orders: GPSIG_HO_SLOT_FORMS / GPSIG_HO_SLOT_ORDERS of grad_plan.hpp
 WaveHoLaunchFn wave_ho_lookup(int G, int C, int order, int M) {
-    if (M < 2 || M > 5) return nullptr;
-    if (G == 16 && C == 2) return pick<16, 2>(order);
-    if (G == 16 && C == 4) return pick<16, 4>(order);
-    if (G == 64 && C == 2) return pick<64, 2>(order);
-    if (G == 64 && C == 4) return pick<64, 4>(order);
-    if (G == 64 && C == 8) return pick<64, 8>(order);
+    if (M < HO_SLOT_MIN_LEVELS || M > HO_SLOT_MAX_LEVELS) return nullptr;
+#define X_HO(G_, C_) if (G == G_ && C == C_) return pick<G_, C_>(order);
+    GPSIG_HO_SLOT_FORMS(X_HO)
+#undef X_HO
     return nullptr;
 }
 #endif
@@ -56,17 +54,12 @@ static hipError_t wave_ho_undo_launch(const WaveHoArgs& a, int nblocks, size_t l
     hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64), lds, s, a);
     return hipGetLastError();
 }
+// (num_levels, order): GPSIG_HO_UNDO_LEVELS of grad_plan.hpp
 template <int G, int C>
 static WaveHoLaunchFn pick_undo(int order, int M) {
-    if (M == 2 && order == 2) return &wave_ho_undo_launch<G, C, 2, 2>;
-    if (M == 3 && order == 2) return &wave_ho_undo_launch<G, C, 3, 2>;
-    if (M == 3 && order == 3) return &wave_ho_undo_launch<G, C, 3, 3>;
-    if (M == 4 && order == 2) return &wave_ho_undo_launch<G, C, 4, 2>;
-    if (M == 4 && order == 3) return &wave_ho_undo_launch<G, C, 4, 3>;
-    if (M == 4 && order == 4) return &wave_ho_undo_launch<G, C, 4, 4>;
-    if (M == 5 && order == 2) return &wave_ho_undo_launch<G, C, 5, 2>;
-    if (M == 5 && order == 3) return &wave_ho_undo_launch<G, C, 5, 3>;
-    if (M == 5 && order == 4) return &wave_ho_undo_launch<G, C, 5, 4>;
+#define X_HO(M_, O_) if (M == M_ && order == O_) return &wave_ho_undo_launch<G, C, M_, O_>;
+    GPSIG_HO_UNDO_LEVELS(X_HO)
+#undef X_HO
     return nullptr;
 }
 template <int G, int C, int MM, int O>
@@ -76,44 +69,29 @@ static hipError_t wave_ho_levels_launch(const WaveHoArgs& a, int nblocks, size_t
 }
 template <int G, int C>
 static WaveHoLaunchFn pick_levels(int order, int M) {
-    if (M == 2 && order == 2) return &wave_ho_levels_launch<G, C, 2, 2>;
-    if (M == 3 && order == 2) return &wave_ho_levels_launch<G, C, 3, 2>;
-    if (M == 3 && order == 3) return &wave_ho_levels_launch<G, C, 3, 3>;
-    if (M == 4 && order == 2) return &wave_ho_levels_launch<G, C, 4, 2>;
-    if (M == 4 && order == 3) return &wave_ho_levels_launch<G, C, 4, 3>;
-    if (M == 4 && order == 4) return &wave_ho_levels_launch<G, C, 4, 4>;
-    if (M == 5 && order == 2) return &wave_ho_levels_launch<G, C, 5, 2>;
-    if (M == 5 && order == 3) return &wave_ho_levels_launch<G, C, 5, 3>;
-    if (M == 5 && order == 4) return &wave_ho_levels_launch<G, C, 5, 4>;
+#define X_HO(M_, O_) if (M == M_ && order == O_) return &wave_ho_levels_launch<G, C, M_, O_>;
+    GPSIG_HO_UNDO_LEVELS(X_HO)
+#undef X_HO
+    return nullptr;
+}
+// this unit's share (lanes per pair GG) of GPSIG_HO_UNDO_FORMS: the other forms are discarded statements, not instantiated
+template <int GG>
+static WaveHoLaunchFn undo_lookup_of(int C, int order, int M) {
+#define X_HO(G_, C_) if constexpr (GG == G_) { if (C == C_) return pick_undo<G_, C_>(order, M); }
+    GPSIG_HO_UNDO_FORMS(X_HO)
+#undef X_HO
+    return nullptr;
+}
+template <int GG>
+static WaveHoLaunchFn levels_lookup_of(int C, int order, int M) {
+#define X_HO(G_, C_) if constexpr (GG == G_) { if (C == C_) return pick_levels<G_, C_>(order, M); }
+    GPSIG_HO_UNDO_FORMS(X_HO)
+#undef X_HO
     return nullptr;
 }
 #define HO_CAT2(a, b) a##b
 #define HO_CAT(a, b) HO_CAT2(a, b)
-WaveHoLaunchFn HO_CAT(wave_ho_undo_lookup_g, GPSIG_HO_UNDO_G)(int C, int order, int M) {
-#if GPSIG_HO_UNDO_G == 16
-    if (C == 2) return pick_undo<16, 2>(order, M);
-    if (C == 4) return pick_undo<16, 4>(order, M);
-#elif GPSIG_HO_UNDO_G == 32
-    if (C == 2) return pick_undo<32, 2>(order, M);
-#else
-    if (C == 2) return pick_undo<64, 2>(order, M);
-    if (C == 4) return pick_undo<64, 4>(order, M);
-    if (C == 8) return pick_undo<64, 8>(order, M);
-#endif
-    return nullptr;
-}
-WaveHoLaunchFn HO_CAT(wave_ho_levels_lookup_g, GPSIG_HO_UNDO_G)(int C, int order, int M) {
-#if GPSIG_HO_UNDO_G == 16
-    if (C == 2) return pick_levels<16, 2>(order, M);
-    if (C == 4) return pick_levels<16, 4>(order, M);
-#elif GPSIG_HO_UNDO_G == 32
-    if (C == 2) return pick_levels<32, 2>(order, M);
-#else
-    if (C == 2) return pick_levels<64, 2>(order, M);
-    if (C == 4) return pick_levels<64, 4>(order, M);
-    if (C == 8) return pick_levels<64, 8>(order, M);
-#endif
-    return nullptr;
-}
+WaveHoLaunchFn HO_CAT(wave_ho_undo_lookup_g, GPSIG_HO_UNDO_G)(int C, int order, int M) { return undo_lookup_of<GPSIG_HO_UNDO_G>(C, order, M); }
+WaveHoLaunchFn HO_CAT(wave_ho_levels_lookup_g, GPSIG_HO_UNDO_G)(int C, int order, int M) { return levels_lookup_of<GPSIG_HO_UNDO_G>(C, order, M); }
 #endif
 }  // namespace gpsig

@@ -29,6 +29,8 @@
 #include <type_traits>
 #include <utility>
 
+#include "grad_plan.hpp"
+
 #include "grad_wave_kernel.hpp"
 
 namespace gpsig {
@@ -554,13 +556,7 @@ struct WaveHoUndo {
 #ifndef HO_UNDO_ATTR
 #define HO_UNDO_ATTR
 #endif
-inline size_t wave_ho_undo_lds(int G, int R1, int order, int M) {
-    int w = 0;
-    for (int j = 1; j < M; ++j) w += 1 + (((j + 1) < order ? (j + 1) : order) - 1);
-    return sizeof(double) * size_t(64 / G) * size_t(R1) * size_t(w);
-}
-
-// grid: ngroups / (64 / G) workgroups of one wavefront; dynamic LDS: wave_ho_undo_lds
+// grid: ngroups / (64 / G) workgroups of one wavefront; dynamic LDS: wave_ho_undo_lds (grad_plan.hpp)
 template <int G, int C, int MM, int O>
 __global__ void __launch_bounds__(64) HO_UNDO_ATTR seq_grad_wave_ho_undo_kernel(const WaveHoArgs A) {
     extern __shared__ double ho_rowtot[];

@@ -1,6 +1,7 @@
 // grad_wave_inst.hpp -- instantiation list of seq_grad_wave_kernel for one lattice mode (included by grad_wave_inst_*.hip)
 #pragma once
 #include "launchers.hpp"
+#include "grad_plan.hpp"
 #include "grad_wave_kernel.hpp"
 
 namespace gpsig {
@@ -11,16 +12,14 @@ hipError_t wave_launch(const WaveGradArgs& a, int nblocks, hipStream_t s) {
     return hipGetLastError();
 }
 
-// (G, C, DP): lanes per pair, columns per lane, padded feature count.  C * DP bounded by the register file.
-#define GPSIG_WAVE_SHAPES(X) \
-    X(16, 2, 4) X(16, 2, 8) X(16, 2, 16) X(16, 4, 4) X(16, 4, 8) X(16, 4, 16) \
-    X(64, 2, 4) X(64, 2, 8) X(64, 2, 16) X(64, 4, 4) X(64, 4, 8) X(64, 4, 16) X(64, 8, 4) X(64, 8, 8)
-
-// Level variants of the scratch-free kernels: num_levels 4 and 5 at compile time (LQ = 3, 4), otherwise LQ = 4 or 7 at run time.
+// The shapes (G, C, DP) are GPSIG_WAVE_SHAPES of grad_plan.hpp, which the planners read too.
+// Level variants of the scratch-free kernels (grad_w2_variant there): num_levels 4 and 5 at compile time (LQ = 3, 4), otherwise LQ = 4 or 7 at run time.
 #define GPSIG_W2_PICK(LAUNCH, G_, C_, D_)                                           \
-    if (G == G_ && C == C_ && DP == D_)                                             \
-        return LQ == 3 ? LAUNCH<G_, C_, D_, 3, MODE, true>                          \
-                       : (LQ == 4 ? LAUNCH<G_, C_, D_, 4, MODE, true> : (LQ < 3 ? LAUNCH<G_, C_, D_, 4, MODE, false> : LAUNCH<G_, C_, D_, 7, MODE, false>));
+    if (G == G_ && C == C_ && DP == D_) {                                           \
+        const GradLevelVariant v = grad_w2_variant(LQ);                             \
+        return v == GRAD_LV_CT3 ? LAUNCH<G_, C_, D_, 3, MODE, true>                 \
+                                : (v == GRAD_LV_CT4 ? LAUNCH<G_, C_, D_, 4, MODE, true> : (v == GRAD_LV_RT4 ? LAUNCH<G_, C_, D_, 4, MODE, false> : LAUNCH<G_, C_, D_, 7, MODE, false>)); \
+    }
 
 #ifdef GPSIG_INST_WAVE2
 template <int G, int C, int DP, int LQ, int MODE, bool MX>
@@ -59,7 +58,7 @@ struct LamUndoInst {
 template <int MODE>
 WaveLaunchFn wave_lookup_mode(int G, int C, int DP, int LQ) {
 #define X_W(G_, C_, D_)                                                              \
-    if (G == G_ && C == C_ && DP == D_) return LQ <= 4 ? wave_launch<G_, C_, D_, 4, MODE> : wave_launch<G_, C_, D_, 7, MODE>;
+    if (G == G_ && C == C_ && DP == D_) return grad_wave_variant(LQ) == GRAD_LV_RT4 ? wave_launch<G_, C_, D_, 4, MODE> : wave_launch<G_, C_, D_, 7, MODE>;
     GPSIG_WAVE_SHAPES(X_W)
 #undef X_W
     return nullptr;

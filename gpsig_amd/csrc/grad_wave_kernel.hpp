@@ -547,7 +547,7 @@ __global__ void __launch_bounds__(64, LAM_UNDO_WAVES) seq_lam_undo_kernel(const 
 #pragma unroll
                 for (int p = 0; p < LQ; ++p) rtv[p] = rt[a * LQ + p];
                 dmg.row(xn, false, kind, A.p0, A.p1, dm);
-                bw.step(dm, clev, rtv, sufin, svin, M, a == 0, ln == 0, lv);
+                bw.step(dm, clev, rtv, sufin, svin, M, a == 0, ln == 0, lv, a, C * ln);       // (exact zeros where a level has no chain yet)
                 if (have) {
 #pragma unroll
                     for (int c = 0; c < C; ++c)

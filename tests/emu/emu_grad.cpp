@@ -332,7 +332,7 @@ void wave_pair_undo(const double* X, const double* Y, int i, int j, int L1, int 
             for (int p = 0; p < LQ; ++p) { sufin[p] = snap[l][p]; svin[p] = snap[l][LQ + p]; rt[p] = rowtot[size_t(a) * LQ + p]; }
             load(X, i, L1, a, xn);
             dm[l].row(xn, false, kind, p0, p1, dmv);
-            bw[l].step(dmv, clev, rt, sufin, svin, M, a == 0, l == 0, lv);
+            bw[l].step(dmv, clev, rt, sufin, svin, M, a == 0, l == 0, lv, a, C * l);          // as seq_lam_undo_kernel
             for (int c = 0; c < C; ++c)
                 if (c < dm[l].nvalid) lam_out[size_t(a) * R2 + C * l + c] = lv[c];
         }
@@ -387,6 +387,8 @@ int emu_seq_grad_wave(const double* X, const double* Y, int N1, int N2, int L1, 
             if (Gg == 16 && Cc == 2) { if (DP == 4) { if (small) WP(16, 2, 4, 4); else WP(16, 2, 4, 7); } else { if (small) WP(16, 2, 8, 4); else WP(16, 2, 8, 7); } }
             else if (Gg == 16 && Cc == 4) { if (DP == 4) { if (small) WP(16, 4, 4, 4); else WP(16, 4, 4, 7); } else { if (small) WP(16, 4, 8, 4); else WP(16, 4, 8, 7); } }
             else if (Gg == 64 && Cc == 2) { if (DP == 4) { if (small) WP(64, 2, 4, 4); else WP(64, 2, 4, 7); } else { if (small) WP(64, 2, 8, 4); else WP(64, 2, 8, 7); } }
+            else if (Gg == 64 && Cc == 4) { if (DP == 4) { if (small) WP(64, 4, 4, 4); else WP(64, 4, 4, 7); } else { if (small) WP(64, 4, 8, 4); else WP(64, 4, 8, 7); } }
+            else if (Gg == 64 && Cc == 8) { if (DP == 4) { if (small) WP(64, 8, 4, 4); else WP(64, 8, 4, 7); } else { if (small) WP(64, 8, 8, 4); else WP(64, 8, 8, 7); } }
             else return -2;
 #undef WP
             std::vector<double> scr(size_t(M) * (R1 > 0 ? R1 : 0) * (R2 > 0 ? R2 : 0) + 8, 0.0);

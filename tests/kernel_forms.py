@@ -16,6 +16,7 @@ _G = "test_gpu_grad.py::"
 _W = "test_gpu_wide.py::"
 _F = "test_gpu_kernel_forms.py::"
 _L = "test_gpu_lowrank_spectral.py::"
+_I = "test_gpu_grad_instances.py::"
 
 OPTIONS = {
     "glds": {"default": 1, "values": [0, 1], "tests": [_P + "test_lds_dma_staging_and_generic_kernels_agree_bitwise"]},
@@ -25,7 +26,7 @@ OPTIONS = {
     "grad_scratch_mb": {"default": 4096, "exempt": "a memory budget, not a kernel form: chunked launches are covered by test_gpu_grad.py (test_seq_level_gradients_are_chunk_invariant)"},
     "grad_impl": {"default": 0, "values": [0, 1, 2, 3, 4], "tests": [_G + "test_wave_and_storage_gradient_kernels_agree", _G + "test_tensor_level_gradients",
                                                                      _G + "test_stationary_kernels_reverse_pass_in_one_launch", _G + "test_higher_order_reverse_pass_in_two_sweeps",
-                                                                     _F + "test_fused_reverse_kernel_edges"]},
+                                                                     _F + "test_fused_reverse_kernel_edges", _I + "test_every_compiled_sweep_instance_against_the_oracle"]},
     "grad_stash_mb": {"default": 4096, "values": [0, 4096], "tests": [_G + "test_forward_pass_keeps_what_its_reverse_pass_needs"]},
     "matern_fast": {"default": 1, "values": [0, 1], "tests": [_P + "test_matern_families_at_compile_time_in_the_sequence_gram", _F + "test_keep_reset_in_the_float64_pair_kernel"]},
     "grad_fused_piece": {"default": 0, "values": [0, 1, 3, 16, 17, 64], "tests": [_F + "test_grad_fused_piece"]},
@@ -46,13 +47,14 @@ OPTIONS = {
     "tvs_tile": {"default": -1, "values": [-1, 0, 1], "tests": [_G + "test_weighted_tensor_vs_sequence_sum", _P + "test_tile_kernel_for_many_tensors",
                                                                 _F + "test_threshold_tvs_tile_from_32_tensors"]},
     "wide": {"default": -1, "values": [-1, 0, 1], "tests": [_W + "test_wide_sequence_lattices_and_gradient", _G + "test_higher_order_reverse_pass_in_two_sweeps",
-                                                            _F + "test_threshold_wide_kzx_beyond_8_columns", _F + "test_threshold_wide_kzz_beyond_12_columns"]},
+                                                            _F + "test_threshold_wide_kzx_beyond_8_columns", _F + "test_threshold_wide_kzz_beyond_12_columns",
+                                                            _I + "test_every_compiled_sweep_instance_against_the_oracle"]},
     "wide_chunk_mb": {"default": 0, "values": [0, 1], "tests": [_W + "test_wide_tensor_vs_sequence_levels_and_gradient", _F + "test_wide_contract_forms_in_the_kzx_reverse_pass"]},
     "wide_contract": {"default": 1, "values": [0, 1, 2, 3], "tests": [_F + "test_wide_contract_forms_in_the_kzx_reverse_pass", _F + "test_wide_contract_forms_in_the_lattice_reverse_pass",
                                                                       _F + "test_wide_contract_strip_grid_stride"]},
     "wide_lat_waves": {"default": -1, "values": [-1, 0, 1], "tests": [_W + "test_wide_sequence_lattices_and_gradient", _F + "test_threshold_lat_waves_at_128_lattices"]},
     "wide_sym_fold": {"default": 1, "values": [0, 1], "tests": [_W + "test_wide_sequence_lattices_and_gradient"]},
-    "ho_g32": {"default": -1, "values": [-1, 0, 1], "tests": [_F + "test_ho_g32"]},
+    "ho_g32": {"default": -1, "values": [-1, 0, 1], "tests": [_F + "test_ho_g32", _I + "test_every_compiled_sweep_instance_against_the_oracle"]},
     "wide_few_cols": {"default": 0, "values": [0, 6], "tests": [_F + "test_threshold_few_rule"]},
     "tvs_grad_matern": {"default": 1, "values": [0, 1], "tests": [_F + "test_tvs_grad_matern"]},
     "wide_o1_sweeps": {"default": 1, "values": [0, 1, 2], "tests": [_W + "test_wide_sequence_lattices_and_gradient", _F + "test_threshold_wide_o1_sweeps_at_1024_lattices"]},
